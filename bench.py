@@ -14,7 +14,9 @@ The step runs as the reference's does (training=True): its Dropout layers (W:29-
 active, with counter-based masks (--dropout off gives the rates-0 configuration the loss-curve parity tests pin).
 ``--workload wav2vec2`` times BASELINE configs[3]'s model (Wav2Vec2-base pre-training step, 2 s clips) the same way.
 
-Every line carries, besides the contract's fields:
+A plain run sets up, warms up, times the K steps and prints the line.  ``--dump-outputs DIR`` then writes what the last
+timed step computed (``dump_outputs``).  ``--full`` adds to the line, after the timed steps:
+  exchange      (N > 1) rccl_ranks, exposed_exchange_ms, host_enqueue_ms per rank: ``exchange_diagnostics``
   roofline      the dominant kernel class (the MFMA GEMM, tmi_gemm): algorithmic FLOPs of
                 every tmi_gemm launch in a step / their device time measured with HIP events
                 recorded on the launch stream during an instrumented pass of the same steps
@@ -29,6 +31,7 @@ Every line carries, besides the contract's fields:
                 dropout rates 0): thread setting 1 = the physical cores of one socket this process may use,
                 setting 2 = 5 threads (the reference pod's CPU limit, sample_tfjobs/whisper-dist.yaml:36); the
                 CPU's per-step losses are compared with the GPU fp32 path on the same steps.
+(``--no-roofline`` / ``--no-cpu-baseline`` leave one of them out of a ``--full`` run.)
 """
 import argparse
 import json
@@ -47,6 +50,8 @@ GF_PER_SAMPLE_BY_SIZE = {"tiny": 141.3, "small": 449.1, "large": 8320.6}  # SURV
 W2V_GF_PER_SAMPLE = {"base": 83.43}                                        # SURVEY.md 8(d), 2 s clips
 POD_CPU_LIMIT = 5                # sample_tfjobs/whisper-dist.yaml:36
 CPU_TIMED_MIN = 3                # 1 warm-up + >= 3 timed steps per thread setting
+DUMP_PARAM_SAMPLES = 1 << 22     # --dump-outputs: parameters sampled (16 MiB of fp32)
+DUMP_SEED = 1234
 
 
 def log(msg):
@@ -400,6 +405,38 @@ def throughput(clip_seconds, per_gpu_batch, world, steps, dt):
     return clip_seconds * per_gpu_batch * world * steps / dt
 
 
+def dump_outputs(out_dir, model, last_loss):
+    """``--dump-outputs DIR``: what the last timed step gave its caller, for comparing two builds output for output.
+      loss.npy           float64 [1], the step's loss (summed over ranks, as the step returns it)
+      params_sample.npy  float32, the parameters the step's update left: a fixed, seeded sample of DUMP_PARAM_SAMPLES
+                         positions of the reference's variables (sorted by path, each flattened in row-major order), so
+                         it does not depend on how the arena stores them
+    Called right after the timed region, before anything else runs a step."""
+    import numpy as np
+    import torch
+    if hasattr(model, "finish_late"):
+        model.finish_late()  # a decoder-layer Adam slice the last pipelined step left on the second stream
+    torch.cuda.synchronize()
+    views = model.arena.ref_views(model.arena.p)
+    names = sorted(views)
+    starts = np.cumsum([0] + [views[n].numel() for n in names])
+    total = int(starts[-1])
+    if total > DUMP_PARAM_SAMPLES:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, size=DUMP_PARAM_SAMPLES))
+    else:
+        idx = np.arange(total)
+    parts = []
+    for i, n in enumerate(names):
+        lo, hi = np.searchsorted(idx, [starts[i], starts[i + 1]])
+        if hi > lo:
+            at = torch.from_numpy(idx[lo:hi] - starts[i]).to(model.arena.p.device)
+            parts.append(views[n].reshape(-1)[at].float().cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([last_loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "params_sample.npy"), np.concatenate(parts).astype(np.float32))
+    log(f"outputs of the last timed step written to {out_dir}: loss, {len(idx)} of {total} parameters")
+
+
 def self_launch(gpus, script=None, argv=None):
     """`python bench.py --gpus N` with no WORLD_SIZE in the environment: start the N ranks ourselves.
 
@@ -467,13 +504,22 @@ def main():
                     help="wire dtype of the gradient exchange (N > 1)")
     ap.add_argument("--exchange", choices=["allreduce", "rs_ag", "mesh"], default=os.environ.get("TMI_EXCHANGE", "allreduce"),
                     help="form of the gradient exchange (N > 1): dist.DataParallelStrategy")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the exchange diagnostics (N > 1), the roofline and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a fixed sample of the parameters it left as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--no-plan", action="store_true", help="issue every step from Python instead of replaying a launch plan (tethys_speech_amd/plan.py)")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of timed CPU work for the first thread setting")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        raise SystemExit(self_launch(args.gpus))
+        argv = sys.argv[1:]
+        if args.dump_outputs:  # the ranks run from the repository root
+            argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        raise SystemExit(self_launch(args.gpus, argv=argv))
     if args.dropout is None:
         args.dropout = "reference" if args.precision == "bf16" else "off"
 
@@ -612,9 +658,11 @@ def main():
                      "host_callbacks": [p_.callbacks for p_ in pl]}
         log(f"launch plan: {plan_note}")
     log(f"timed {args.steps} steps: {dt / args.steps * 1e3:.2f} ms/step, loss {last_loss:.4f}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last_loss)
 
     multi = None
-    if world > 1:
+    if args.full and world > 1:
         # the same ranks without the exchange, issued the same way as the timed steps: a launch plan of its own (the recorded
         # launch sequence differs), or the eager step with --no-plan
         def without_exchange(run):
@@ -629,7 +677,7 @@ def main():
         multi = exchange_diagnostics(without_exchange, args, strategy, dev, world, dt / args.steps * 1e3, host_ms)
 
     roof = classes = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roof, classes = measure_roofline(model, one_step, min(args.steps, 3), args.precision, tag)
 
     if rank == 0:
@@ -650,7 +698,7 @@ def main():
         if roof is not None:
             out["roofline"] = roof
             out["roofline_classes"] = classes
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("timing the restated reference CPU path (oracle) on the host cores")
             del model
             torch.cuda.empty_cache()

@@ -14,7 +14,7 @@ the compiler believes dead (an unused asm output) gets handed to something else 
 it copies or spills early holds stale data.  hipcc keeps this for its own loads; the asm-issued ones are checked here.
 
 usage: check_mfma_hazards.py [libtethys_mi.so]   (exit code 1 if a candidate is found)"""
-import os, re, subprocess, sys
+import os, re, subprocess, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "tethys-speech_amd", "libtethys_mi.so")
@@ -34,12 +34,10 @@ def regs(tok):
     return out
 
 
-def extract_bundles(path):
-    """device code objects embedded in the host library (llvm-objdump --offloading writes them next to its input: a copy)"""
+def extract_bundles(path, tmp):
+    """device code objects embedded in the host library (llvm-objdump --offloading writes them next to its input: a copy
+    in the empty directory ``tmp``)"""
     import shutil
-    tmp = "/tmp/_tmi_hazard"
-    shutil.rmtree(tmp, ignore_errors=True)
-    os.makedirs(tmp)
     cp = os.path.join(tmp, "lib.so")
     shutil.copy(path, cp)
     subprocess.run([OBJDUMP, "--offloading", cp], capture_output=True, text=True, cwd=tmp)
@@ -142,7 +140,11 @@ def scan_scalar_loads(asm_lines):
 
 
 def main():
-    objs = extract_bundles(lib)
+    with tempfile.TemporaryDirectory(prefix="tmi_hazard_") as tmp:
+        return check(extract_bundles(lib, tmp))
+
+
+def check(objs):
     if not objs:
         print("no gfx950 code object found in", lib)
         return 2

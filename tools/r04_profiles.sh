@@ -35,12 +35,12 @@ pmc() {  # tag -- bench args
 pmc whisper
 pmc wav2vec2_base --workload wav2vec2
 echo "pmc done"
-python3 bench.py > $O/bench_n1.json 2> $O/bench_n1.log
+python3 bench.py --full > $O/bench_n1.json 2> $O/bench_n1.log
 echo "bench default done"
-python3 bench.py --dropout off --no-cpu-baseline > $O/bench_n1_dropout_off.json 2> $O/bench_n1_dropout_off.log
-python3 bench.py --precision fp32 --steps 40 --no-cpu-baseline > $O/bench_n1_fp32.json 2> $O/bench_n1_fp32.log
-python3 bench.py --workload wav2vec2 > $O/bench_wav2vec2_n1.json 2> $O/bench_wav2vec2_n1.log
-python3 bench.py --workload whisper_single --batch_size 4 --steps 100 > $O/bench_whisper_single_n1.json 2> $O/bench_whisper_single_n1.log || true
+python3 bench.py --full --dropout off --no-cpu-baseline > $O/bench_n1_dropout_off.json 2> $O/bench_n1_dropout_off.log
+python3 bench.py --full --precision fp32 --steps 40 --no-cpu-baseline > $O/bench_n1_fp32.json 2> $O/bench_n1_fp32.log
+python3 bench.py --full --workload wav2vec2 > $O/bench_wav2vec2_n1.json 2> $O/bench_wav2vec2_n1.log
+python3 bench.py --full --workload whisper_single --batch_size 4 --steps 100 > $O/bench_whisper_single_n1.json 2> $O/bench_whisper_single_n1.log || true
 echo "bench lines done"
 python3 tools/host_step_time.py > $O/host_step_time.txt 2>&1 || true
 python3 tools/host_step_time.py wav2vec2 >> $O/host_step_time.txt 2>&1 || true

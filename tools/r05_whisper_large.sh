@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 O=gpurun_out/r5L; rm -rf $O; mkdir -p $O
-python3 bench.py --model_type large --steps 10 --warmup 5 --no-cpu-baseline > $O/bench_whisper_large_n1.json 2> $O/bench_whisper_large_n1.log || { tail -5 $O/bench_whisper_large_n1.log; exit 1; }
+python3 bench.py --full --model_type large --steps 10 --warmup 5 --no-cpu-baseline > $O/bench_whisper_large_n1.json 2> $O/bench_whisper_large_n1.log || { tail -5 $O/bench_whisper_large_n1.log; exit 1; }
 echo "bench done"
 D=$O/_s
 TMI_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats --output-format csv -d $D -- python3 bench.py --model_type large --steps 2 --warmup 4 --no-cpu-baseline --no-roofline > $O/serial.log 2>&1

@@ -4,8 +4,9 @@
 # the rate it prints means nothing (host-staged all-reduce of 591 MB per step, four processes time-slicing one device).
 cd $GRAFT_REPO_ROOT
 export TETHYS_ONE_DEVICE=1 TETHYS_DIST_BACKEND=gloo
+O=${BENCH_OUT:-bench_out}; mkdir -p $O
 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node ${1:-4} --master-addr 127.0.0.1 --master-port 29577 \
-  bench.py --gpus ${1:-4} --steps ${2:-2} --warmup ${3:-1} --no-cpu-baseline ${4:-} > gpurun_out/rehearse_multi_rank.json 2> gpurun_out/rehearse_multi_rank.log
+  bench.py --gpus ${1:-4} --steps ${2:-2} --warmup ${3:-1} --full --no-cpu-baseline ${4:-} > $O/rehearse_multi_rank.json 2> $O/rehearse_multi_rank.log
 echo "rc=$?"
-cat gpurun_out/rehearse_multi_rank.json | cut -c1-700
-grep -E "timed|Error|error" gpurun_out/rehearse_multi_rank.log | head -5
+cat $O/rehearse_multi_rank.json | cut -c1-700
+grep -E "timed|Error|error" $O/rehearse_multi_rank.log | head -5
