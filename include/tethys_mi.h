@@ -309,6 +309,26 @@ int tmi_linear_xent(const void* x, int64_t x_ld, const void* w, int64_t w_sk, in
 int tmi_sum_scale(const float* x, float* out, int64_t n, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Greedy decoding's next token (W:675 / W:697: argmax(lm_head(decoder_out)[:, -1, :]), with the final decoder LayerNorm of
+ * W:466 in front): for each of M hidden-state rows x[r * x_ld + k] (k < d; fp32 or bf16: x_dtype)
+ *   y    = gamma, beta given ? LayerNorm_eps(x[r, :]) (fp32 statistics, W:392) : x[r, :]
+ *   z[n] = sum_k y[k] * w[k * w_ld + n]        (w: the LM head in its stored [d, w_ld] layout, fp32 or bf16: w_dtype;
+ *                                              fp32 accumulation, in a fixed order: bit-reproducible)
+ *   ids[r * ids_ld] = argmax_{n < V} z[n]       (int32; the smallest n among equal maxima, as tf.argmax; -0 == +0;
+ *                                              the pad columns [V, w_ld) are never chosen)
+ *   eos_count[0] = #{r : ids[r * ids_ld] == eos_id}   (int32; eos_id < 0: 0; eos_count may be NULL)
+ * x_ld is an arbitrary row stride (the last position of each sample, read in place).  gamma and beta are both given or
+ * both NULL.  w must be 16-byte aligned, w_ld a multiple of 8 and >= V.  One launch: the weights are streamed once
+ * (for M <= 16; M rows in groups of 16 otherwise); the workgroups' candidates meet in `workspace` (>= 8 * (M + 1) bytes,
+ * 8-byte aligned, ZERO before the first call: the launch leaves it zero again, so one buffer serves every step on one
+ * stream; concurrent calls need one each).  d * min(M, 16) * 4 bytes of LDS must fit in 160 KiB (d <= 2544 at M >= 16).
+ */
+int tmi_lm_head_argmax(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                       const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, int32_t* ids,
+                       int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-tensor Adam over a flat fp32 arena (tf.keras.optimizers.Adam, W:901; V:1271-1275).
  *   g' = g * gscale                      (gscale: 1 for Whisper's SUM, 1/N for V:1231)
  *   m <- b1 m + (1-b1) g' ; v <- b2 v + (1-b2) g'^2

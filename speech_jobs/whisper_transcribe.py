@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Inference job: greedy transcription with a Whisper model (the reference's ``transcribe_audio`` / ``generate``,
+speech_jobs/whisper_dist.py W:962-986 / W:636-709, which its job scripts never call).
+
+Loads a checkpoint (``--resume_from``: a ``save_checkpoint`` or ``save_weights`` file; without one the model keeps its
+seeded initialisation), turns each ``--wav`` clip (16-bit PCM mono 16 kHz) or, without one, ``--batch_size`` copies of
+the reference's seeded 30 s dummy clip into log-mel features on the GPU, and decodes them greedily.  Prints one JSON line
+per clip, {"clip", "ids", "n_tokens"} (ids start with the decoder start token), then one timing line.  No tokenizer ships
+with the project, so the output is token ids.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Whisper greedy transcription (token ids)")
+    parser.add_argument("--model_type", default="small", choices=["tiny", "base", "small", "medium", "large"])
+    parser.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
+    parser.add_argument("--resume_from", default=None, help="checkpoint to load the weights from")
+    parser.add_argument("--wav", action="append", default=[], help="16-bit PCM mono 16 kHz .wav file (repeatable)")
+    parser.add_argument("--batch_size", type=int, default=1, help="number of dummy clips when no --wav is given")
+    parser.add_argument("--max_length", type=int, default=448, help="decoding steps at most (<= 448)")
+    args = parser.parse_args(argv)
+
+    import numpy as np
+    import torch
+    import tethys_speech_amd  # noqa: F401
+    from tethys_speech_amd import train, whisper
+    from tethys_speech_amd.frontend import LogMelFrontend
+
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)
+    device = f"cuda:{local_rank}"
+    model = whisper.create_whisper_model(args.model_type, device=device, precision=args.precision)
+    whisper.check_generate_args(model.config, args.max_length)
+    if args.resume_from:
+        train.load_weights(model, args.resume_from)
+    if args.wav:
+        clips = [(p, whisper.read_wav(p)) for p in args.wav]
+    else:
+        clips = [(f"dummy{i}", whisper.dummy_waveform()) for i in range(max(1, args.batch_size))]
+    fe = LogMelFrontend(device=device, n_mels=model.config.n_mels)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    n_tok = 0
+    # clips of one length are decoded as one batch (the dummy clips, or wav files of equal length)
+    groups = {}
+    for name, wav in clips:
+        groups.setdefault(len(wav), []).append((name, wav))
+    for items in groups.values():
+        wave = torch.from_numpy(np.stack([w for _, w in items])).to(device)
+        ids = model.generate(fe(wave), max_length=args.max_length).cpu()
+        for (name, _), row in zip(items, ids):
+            n_tok += row.numel() - 1
+            print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1)}), flush=True)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    print(json.dumps({"clips": len(clips), "seconds": round(dt, 4), "tokens": n_tok,
+                      "tokens_per_s": round(n_tok / dt, 1) if dt > 0 else None}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -133,9 +133,11 @@ SIGNATURES = {
     "tmi_segment_clip": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_vp]),
     "tmi_loss_combine": (c_i32, [c_vp, c_vp, c_f32, c_f32, c_vp, c_vp]),
     "tmi_debug_gemm_stamps": (c_i32, [c_vp]),
+    "tmi_lm_head_argmax": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp,
+                                   c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
 }
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 _lib = None
 
 

@@ -453,6 +453,17 @@ def xent_fwd_bwd(logits, ld, labels, row_loss, B, S, V, grad_scale, lm=None):
                                         row_loss.data_ptr(), B, S, V, grad_scale, dt(logits), stream()), "tmi_linear_xent")
 
 
+def lm_head_argmax(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma=None, beta=None, eps=1e-5, eos_id=-1,
+                   eos_count=None):
+    """ids[r * ids_ld] = argmax_{n < V} (LayerNorm(x[r]) . w)[n] for M rows of x (row stride x_ld), w the LM head in its
+    stored [d, w_ld] layout (fp32 arena or bf16 mirror); eos_count[0] = how many of them equal eos_id.  ``workspace``: an
+    int64 tensor of >= M + 1 elements, zero before the first call (tmi_lm_head_argmax leaves it zero)."""
+    with _probe("lm_head_argmax", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_argmax(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
+                                       V, ids.data_ptr(), ids_ld, eos_id, ptr(eos_count), workspace.data_ptr(),
+                                       workspace.numel() * workspace.element_size(), stream()), "tmi_lm_head_argmax")
+
+
 def sum_scale(x, out, n, scale):
     check(lib().tmi_sum_scale(x.data_ptr(), out.data_ptr(), n, scale, stream()), "tmi_sum_scale")
 

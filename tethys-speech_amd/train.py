@@ -365,6 +365,24 @@ def save_checkpoint(model, optimizer, path, dataset=None, step=None, background=
     _CKPT_THREADS.append(t)
 
 
+def load_weights(model, path):
+    """The parameters of a checkpoint, without an optimizer (inference: ``generate`` / ``transcribe_audio``): ``path`` is a
+    ``save_checkpoint`` file (flat arena; its layout must match the model) or a ``save_weights`` file (reference-keyed).
+    The bf16 mirror is re-derived; the model's training state (dropout step, optimizer moments) is left alone."""
+    ck = torch.load(path, map_location="cpu")
+    a = model.arena
+    if hasattr(model, "finish_late"):
+        model.finish_late()
+    if "p" in ck:
+        if ck.get("names") != a.names or ck.get("offsets") != a.offsets or ck.get("shapes") != a.shapes or \
+                ck["p"].numel() != a.p.numel():
+            raise ValueError("checkpoint layout does not match the model")
+        a.p.copy_(ck["p"])
+    else:
+        a.load_ref(ck)
+    model.refresh_shadows()
+
+
 def load_checkpoint(model, optimizer, path, dataset=None):
     """The restore path the reference lacks.  Returns the step index to continue from."""
     ck = torch.load(path, map_location="cpu")

@@ -166,7 +166,7 @@ class ParamArena(Arena):
 
 # ----------------------------------------------------------------------------- model
 class WhisperForConditionalGeneration(KernelBlocks):
-    """W:536-616 (training path only).  Holds parameters, bf16 shadows and all activation
+    """W:536-616: the training step, the forward-only pass and greedy generate.  Holds parameters, bf16 shadows and all activation
     workspaces; sized lazily for a batch size on first use."""
 
     def __init__(self, config: WhisperConfig, device="cuda:0", precision: str = "bf16", seed: int = 1234):
@@ -799,15 +799,372 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self._join_side()
         return ws["loss"]
 
-    def __call__(self, features, labels=None, training=True):
-        """Reference call surface (W:829): returns {"loss": ...}.  Gradients are a side effect."""
-        if not training or labels is None:
-            raise NotImplementedError("only the training path (labels given, training=True) is on the hot path")
-        return {"loss": self.forward_backward(features, labels)}
+    def __call__(self, features, decoder_input_ids=None, labels=None, training=None):
+        """Reference call surface (W:547-616).  ``training=True`` (the default when labels are given): the training step,
+        {"loss": ...} with the gradients as a side effect (W:829).  ``training=False``: the forward pass alone (no dropout,
+        no gradients, nothing of the training state touched) -> {"loss": None, "logits" [B, S, V], "last_hidden_state"
+        [B, S, d], "encoder_last_hidden_state" [B, T, d]}, in the model's compute dtype.  The decoder reads
+        ``decoder_input_ids`` [B, S] (their first column must be the start token: every sequence the reference feeds its
+        decoder starts with it, W:559-563 / W:663), else ``labels`` shifted right behind the start token (W:555-563), else
+        the start token alone."""
+        if training is None:
+            training = labels is not None
+        if training:
+            if labels is None or decoder_input_ids is not None:
+                raise ValueError("the training path takes labels (and forms the decoder input from them itself)")
+            return {"loss": self.forward_backward(features, labels)}
+        return self.forward_infer(features, decoder_input_ids=decoder_input_ids, labels=labels)
 
+    # -- inference (forward only): W:547-616 with training=False, greedy generate W:636-709 --------------------------
+    # Its own workspace set (``_inf``), never one of ``_ws_sets``: the per-layer activations training keeps for backward are
+    # not needed, so every layer of a stack shares one set of buffers, sized for the encoder's B*T rows or the decoder's
+    # B*max_target_positions rows, whichever is more; one attention scratch (softmax statistics, or the fp32 path's P) serves
+    # every attention call.  Swapped in as ``self.ws`` only for the duration of an inference call (the blocks read
+    # ``self.ws``); nothing else of the training state (``_ws_key``, the shape attributes, ``_drop_step``, the optimizer,
+    # recorded plans) is read or written, and no dropout site is passed (dropout is off even after enable_dropout).
+
+    def _infer_prepare(self, B: int, T_in: int) -> dict:
+        cfg = self.config
+        inf = self.__dict__.get("_inf")
+        if inf is not None and inf["key"] == (B, T_in):
+            return inf
+        self._inf = None  # (the previous set is released first)
+        T1, pl1, pr1 = same_pad(T_in, 3, 1)
+        T, pl2, pr2 = same_pad(T1, 3, 2)
+        if T > cfg.n_ctx:
+            raise ValueError("encoder length exceeds n_ctx")
+        d, ff, Smax = cfg.d_model, cfg.d_ff, cfg.max_target_positions
+        He, Hd = cfg.encoder_attention_heads, cfg.decoder_attention_heads
+        inf = {"key": (B, T_in), "T1": T1, "pl1": pl1, "pr1": pr1, "T": T, "pl2": pl2, "pr2": pr2,
+               "Tp0": T_in + pl1 + pr1, "Tp1": T1 + pl2 + pr2, "K1p": -(-3 * cfg.n_mels // 64) * 64}
+        saved, self.ws = self.ws, {}
+        try:
+            slack = 2  # (as in _prepare: zero rows behind the last conv window)
+            z = dict(zero=True)
+            self._buf("xp0", (B, inf["Tp0"] + slack, cfg.n_mels), **z)
+            self._buf("h1pad", (B, inf["Tp1"] + slack, d), **z)
+            if self.precision == "bf16" and inf["K1p"] != 3 * cfg.n_mels and inf["K1p"] - 3 * cfg.n_mels <= slack * cfg.n_mels:
+                self._buf("w1pad", (inf["K1p"], d), **z)
+            R, Rd = B * T, B * Smax
+            Rm = max(R, Rd)
+            for n, w in (("x", d), ("x_mid", d), ("x_mid2", d), ("xn", d), ("ctx", d), ("qc", d), ("qkv", 3 * d), ("g", ff)):
+                self._buf(n, (Rm, w))
+            self._buf("ln.mean", (Rm,), torch.float32)
+            self._buf("ln.rstd", (Rm,), torch.float32)
+            self._buf("enc_out", (R, d))
+            self._buf("kvc_all", (R, max(1, cfg.decoder_layers) * 2 * d))
+            if self.precision == "bf16":
+                n_att = B * max(He, Hd) * max(T, Smax) * 2
+            else:
+                n_att = max(B * He * T * T, B * Hd * Smax * max(Smax, T))
+            self._buf("att_flat", (n_att,), torch.float32)
+            self._buf("labels", (Rd,), torch.int32)
+            self._buf("argmax_ws", (B + 1,), torch.int64, zero=True)  # tmi_lm_head_argmax leaves it zero again
+            inf["ws"] = self.ws
+        finally:
+            self.ws = saved
+        self._inf = inf
+        return inf
+
+    def _infer_begin(self, inf):
+        """Enter an inference call: pin the stream, order it behind every parameter update that may still be running on
+        the second stream (the late Adam slices: their persistent events are waited for, ``_late_pending`` is left as it
+        is), and swap the inference workspace in."""
+        self.begin_step()
+        main = self._main or torch.cuda.current_stream(self.device)
+        for ev in self.__dict__.get("_late_done", {}).values():
+            main.wait_event(ev)  # (a wait on an event that has completed, or was never recorded, is free)
+        for st in getattr(self, "_sides", []):
+            main.wait_stream(st)
+        saved = self.ws
+        self.ws = inf["ws"]
+        return saved
+
+    def _infer_end(self, saved):
+        self.ws = saved
+        self.end_step()
+
+    def _att(self, key, B, H, Tq, Tk):
+        """The shared attention scratch as call ``key``'s statistics [B, H, Tq, 2] (bf16) or scores [B, H, Tq, Tk] (fp32)."""
+        flat = self.ws["att_flat"]
+        shape = (B, H, Tq, 2) if self.precision == "bf16" else (B, H, Tq, Tk)
+        self.ws[key] = flat[:int(np.prod(shape))].view(shape)
+        return key
+
+    def _encode_infer(self, features, inf):
+        """W:324-372 with training=False into ws["enc_out"] [B*T, d]: the training forward's blocks and kernels, the
+        pre-activations backward would need not saved."""
+        cfg, ws, a, d = self.config, self.ws, self.arena, self.config.d_model
+        B, Cn, T_in = features.shape
+        T, He = inf["T"], cfg.encoder_attention_heads
+        scal_e = (d // He) ** -0.5
+        R = B * T
+        xp0, h1pad = ws["xp0"], ws["h1pad"]
+        ops.feat_to_channels_last(features, xp0, B, Cn, T_in, inf["pl1"], inf["pr1"] + (xp0.shape[1] - inf["Tp0"]))
+        w1pad = ws.get("w1pad")
+        if w1pad is not None:
+            ops.copy(w1pad[:3 * Cn], self.W("encoder.conv1.kernel")[0])
+            ops.gemm(xp0, w1pad, h1pad, inf["T1"], d, inf["K1p"], Cn, 1, d, 1, ldc=d, nbatch=B, a_sb=xp0.stride(0),
+                     c_sb=h1pad.stride(0), c_off=inf["pl2"] * d, bias=a.param("encoder.conv1.bias"), act=1)
+        else:
+            self._gemm_xw(xp0, "encoder.conv1.kernel", h1pad, inf["T1"], d, 3 * Cn, Cn, ldc=d, nbatch=B,
+                          a_sb=xp0.stride(0), c_sb=h1pad.stride(0), c_off=inf["pl2"] * d,
+                          bias=a.param("encoder.conv1.bias"), act=1)
+        x, x_mid, xn, ctx, qkv, g = (ws[n][:R] for n in ("x", "x_mid", "xn", "ctx", "qkv", "g"))
+        self._gemm_xw(h1pad, "encoder.conv2.kernel", x, T, d, 3 * d, 2 * d, ldc=d, nbatch=B, a_sb=h1pad.stride(0),
+                      c_sb=T * d, bias=a.param("encoder.conv2.bias"), act=1, resid=self.pe_enc_t, r_ld=d, r_sb=0)
+        for i in range(cfg.encoder_layers):
+            p = f"encoder.layers.{i}"
+            self._ln_fwd(x, p + ".self_attn_layer_norm", xn, "ln")
+            self._dense_fwd(xn, p + ".self_attn.qkv.kernel", qkv, scale_cols=d, scale=scal_e)
+            self._attn_fwd(self._att("att", B, He, T, T), (qkv, 0), (qkv, d), (qkv, 2 * d), ctx, B, He, T, T, 0)
+            self._dense_fwd(ctx, p + ".self_attn.out_proj.kernel", x_mid, resid=x, r_ld=d)
+            self._ln_fwd(x_mid, p + ".final_layer_norm", xn, "ln")
+            self._dense_fwd(xn, p + ".feed_forward.fc1.kernel", g, act=1)
+            self._dense_fwd(g, p + ".feed_forward.fc2.kernel", x, resid=x_mid, r_ld=d)
+        self._ln_fwd(x, "encoder.layer_norm", ws["enc_out"], "ln")
+        return ws["enc_out"]
+
+    def _cross_kv_infer(self, enc_out):
+        """W:122-123 for every decoder layer at once: the cross-attention k|v, computed once per encoder output."""
+        if self.config.decoder_layers:
+            self._dense_fwd(enc_out, "decoder.cross_kv.kernel", self.ws["kvc_all"][:enc_out.shape[0]])
+
+    def _decode_infer(self, labels, B, S, T):
+        """W:394-466 (training=False) over S positions without the final LayerNorm: returns the residual stream
+        [B*S, d].  ``labels`` [B, S] int32: the decoder reads [start, labels[:, :-1]] (tmi_embed_fwd's shift)."""
+        cfg, ws, d = self.config, self.ws, self.config.d_model
+        Hd = cfg.decoder_attention_heads
+        scal_d = (d // Hd) ** -0.5
+        Rd = B * S
+        x, x_mid, x_mid2, xn, ctx, qc, qkv, g = (ws[n][:Rd] for n in ("x", "x_mid", "x_mid2", "xn", "ctx", "qc", "qkv", "g"))
+        kvc = ws["kvc_all"][:B * T]
+        ops.embed_fwd(labels, self.arena.param("decoder.embed_tokens.embeddings"), self.pe_dec, x, B, S, d,
+                      cfg.decoder_start_token_id)
+        for i in range(cfg.decoder_layers):
+            p = f"decoder.layers.{i}"
+            self._ln_fwd(x, p + ".self_attn_layer_norm", xn, "ln")
+            self._dense_fwd(xn, p + ".self_attn.qkv.kernel", qkv, scale_cols=d, scale=scal_d)
+            # the inverted mask of W:416-418 (mask_mode 1): each query sees the strictly later positions only
+            self._attn_fwd(self._att("att", B, Hd, S, S), (qkv, 0), (qkv, d), (qkv, 2 * d), ctx, B, Hd, S, S, 1)
+            self._dense_fwd(ctx, p + ".self_attn.out_proj.kernel", x_mid, resid=x, r_ld=d)
+            self._ln_fwd(x_mid, p + ".encoder_attn_layer_norm", xn, "ln")
+            self._dense_fwd(xn, p + ".encoder_attn.q_proj.kernel", qc, scale_cols=d, scale=scal_d)
+            self._attn_fwd(self._att("att", B, Hd, S, T), (qc, 0), (kvc, 2 * i * d), (kvc, (2 * i + 1) * d), ctx,
+                           B, Hd, S, T, 0)
+            self._dense_fwd(ctx, p + ".encoder_attn.out_proj.kernel", x_mid2, resid=x_mid, r_ld=d)
+            self._ln_fwd(x_mid2, p + ".final_layer_norm", xn, "ln")
+            self._dense_fwd(xn, p + ".feed_forward.fc1.kernel", g, act=1)
+            self._dense_fwd(g, p + ".feed_forward.fc2.kernel", x, resid=x_mid2, r_ld=d)
+        return x
+
+    def _check_features(self, features):
+        if features.dim() != 3 or features.shape[1] != self.config.n_mels:
+            raise ValueError(f"features must be [B, {self.config.n_mels}, T_in]")
+        if features.dtype != torch.float32:
+            raise TypeError("features must be float32")
+        if features.shape[0] < 1:
+            raise ValueError("empty batch")
+        return features.to(self.device).contiguous()
+
+    @torch.no_grad()
+    def forward_infer(self, features, decoder_input_ids=None, labels=None):
+        """The forward pass alone (W:547-616, training=False); see ``__call__``."""
+        cfg = self.config
+        features = self._check_features(features)
+        B = features.shape[0]
+        start = cfg.decoder_start_token_id
+        if decoder_input_ids is not None:
+            dec = torch.as_tensor(decoder_input_ids).to(device=self.device, dtype=torch.int32)
+            if dec.dim() != 2 or dec.shape[0] != B or dec.shape[1] < 1:
+                raise ValueError("decoder_input_ids must be [B, S]")
+            if not bool((dec[:, 0] == start).all()):
+                raise ValueError("decoder_input_ids must start with decoder_start_token_id")
+            S = dec.shape[1]
+            shifted = torch.cat([dec[:, 1:], dec[:, :1]], dim=1)  # (the last column is never read)
+        elif labels is not None:
+            shifted = torch.as_tensor(labels).to(device=self.device, dtype=torch.int32)
+            if shifted.dim() != 2 or shifted.shape[0] != B:
+                raise ValueError("labels must be [B, S]")
+            S = shifted.shape[1]
+        else:
+            S, shifted = 1, torch.zeros(B, 1, dtype=torch.int32, device=self.device)
+        if not 1 <= S <= cfg.max_target_positions:
+            raise ValueError("target length exceeds max_target_positions")
+        inf = self._infer_prepare(B, features.shape[2])
+        saved = self._infer_begin(inf)
+        try:
+            ws, d, T = self.ws, cfg.d_model, inf["T"]
+            lab = ws["labels"][:B * S].view(B, S)
+            lab.copy_(shifted)
+            enc_out = self._encode_infer(features, inf)
+            self._cross_kv_infer(enc_out)
+            h = self._decode_infer(lab, B, S, T)
+            out = torch.empty(B * S, d, dtype=self.dtype, device=self.device)
+            self._ln_fwd(h, "decoder.layer_norm", out, "ln")
+            Vp = self.arena.v_pad
+            logits = torch.empty(B * S, Vp, dtype=self.dtype, device=self.device)
+            self._gemm_xw(out, "lm_head.kernel", logits, B * S, Vp, d, d, ldc=Vp)  # W:579
+            result = {"loss": None,
+                      "logits": logits.view(B, S, Vp)[:, :, :cfg.vocab_size],
+                      "last_hidden_state": out.view(B, S, d),
+                      "encoder_last_hidden_state": enc_out.view(B, T, d).clone()}
+        finally:
+            self._infer_end(saved)
+        return result
+
+    @torch.no_grad()
+    def generate(self, input_features, max_length=None, min_length=None, num_beams=None, temperature=1.0, top_k=None,
+                 top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None):
+        """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.
+
+        As in the reference: the encoder runs once; every step runs the WHOLE decoder over the whole prefix (under the
+        inverted mask of W:416-418 appending a token changes every earlier position's state from layer 1 up, so there is
+        no valid KV cache) and appends argmax(lm_head(decoder_out)[:, -1, :]) to every row; the loop stops when every
+        row's token of the same step is EOS, or after ``max_length`` steps.  Temperature and top-k do not change an argmax;
+        the other options are accepted and ignored (W:643-648).  Fixed against the reference: the logits come from the LM
+        head (W:675 reads a key WhisperModel does not return), ``num_beams > 1`` raises instead of leaving ``next_tokens``
+        unbound, ``max_length`` above max_target_positions raises up front instead of overrunning the positional table
+        (W:383).  ``eos_token_id`` (not in the reference's signature): overrides config.eos_token_id; -1 disables the stop.
+
+        Per step: the embedding of [start, tokens so far] (tmi_embed_fwd), the decoder over the prefix, and
+        tmi_lm_head_argmax on the B last rows (final LayerNorm, LM head and argmax in one launch).  The EOS count of a step
+        is read one step late (``greedy_loop``), so the device never idles on the host's check."""
+        cfg = self.config
+        max_length = check_generate_args(cfg, max_length, num_beams, temperature)
+        features = self._check_features(input_features)
+        B = features.shape[0]
+        eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+        dev = self.device
+        ids = torch.empty(B, 1 + max_length, dtype=torch.int32, device=dev)
+        if max_length == 0:
+            ids.fill_(cfg.decoder_start_token_id)
+            return ids
+        inf = self._infer_prepare(B, features.shape[2])
+        counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
+        host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
+        events = [torch.cuda.Event(), torch.cuda.Event()]
+        saved = self._infer_begin(inf)
+        try:
+            ws, d, T = self.ws, cfg.d_model, inf["T"]
+            ids[:, 0] = cfg.decoder_start_token_id
+            enc_out = self._encode_infer(features, inf)
+            self._cross_kv_infer(enc_out)
+            lab_flat = ws["labels"]
+            wl, ldw = self.W("lm_head.kernel")
+            gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
+            main = self._main or torch.cuda.current_stream(dev)
+            L1 = 1 + max_length
+
+            def step(t):
+                """Decoding step t (1-based): the prefix is columns [0, t) of ids, the token lands in column t."""
+                lab = lab_flat[:B * t].view(B, t)
+                if t > 1:
+                    lab[:, :t - 1].copy_(ids[:, 1:t])  # (index relayout only: the embedding shift reads rows of stride t)
+                h = self._decode_infer(lab, B, t, T)
+                col = ids[:, t:]
+                ops.lm_head_argmax(h[t - 1:], t * d, wl, ldw, B, d, cfg.vocab_size, col, L1, ws["argmax_ws"], gamma=gamma,
+                                   beta=beta, eps=cfg.layer_norm_eps, eos_id=eos, eos_count=counts[t:])
+                host[t:t + 1].copy_(counts[t:t + 1], non_blocking=True)
+                events[t & 1].record(main)
+
+            def read_eos(t):
+                events[t & 1].synchronize()
+                return int(host[t])
+
+            n = greedy_loop(max_length, B, step, read_eos if eos >= 0 else None)
+        finally:
+            self._infer_end(saved)
+        torch.cuda.current_stream(dev).synchronize()
+        return ids[:, :1 + n].clone()
 
 def create_whisper_model(model_type: str = "small", device="cuda:0", precision: str = "bf16", seed: int = 1234,
                          **overrides) -> WhisperForConditionalGeneration:
     """W:852-890."""
     return WhisperForConditionalGeneration(make_config(model_type, **overrides), device=device,
                                            precision=precision, seed=seed)
+
+
+# ----------------------------------------------------------------------------- greedy decoding host logic
+def check_generate_args(cfg: WhisperConfig, max_length=None, num_beams=None, temperature=1.0) -> int:
+    """The arguments of ``generate`` (W:636-648) -> max_length.  Raises where the reference would fail later or silently:
+    ``num_beams > 1`` (W:696-698 leaves next_tokens unbound), ``max_length`` above max_target_positions (the prefix of the
+    last step would outrun the positional table, W:383), a temperature <= 0 (W:678 divides by it)."""
+    max_length = cfg.max_target_positions if max_length is None else int(max_length)
+    if max_length < 0 or max_length > cfg.max_target_positions:
+        raise ValueError(f"max_length must be in [0, {cfg.max_target_positions}]")
+    if num_beams is not None and int(num_beams) > 1:
+        raise ValueError("beam search is not implemented (the reference leaves it unimplemented too)")
+    if temperature is not None and not float(temperature) > 0.0:
+        raise ValueError("temperature must be > 0")
+    return max_length
+
+
+def greedy_loop(max_length: int, n_rows: int, step, read_eos=None, late: bool = True) -> int:
+    """Host side of greedy decoding: the number n of tokens to keep (the result is ids[:, :1 + n]).
+
+    ``step(t)`` queues decoding step t = 1 .. max_length (its token lands in column t); ``read_eos(t)`` waits for step t
+    and returns how many of the ``n_rows`` rows emitted EOS there (None: no stop check).  The loop ends after the first
+    step at which EVERY row's token is EOS (W:700-707: a row that emitted EOS earlier keeps decoding, only an all-EOS
+    step stops), or after ``max_length`` steps.  ``late``: step t + 1 is queued before step t's count is read, so the
+    device is never idle during the check; when step t stops the loop, the extra step's column is simply dropped - the
+    result is the same as with ``late=False``."""
+    pending = None
+    for t in range(1, max_length + 1):
+        if not late:
+            step(t)
+            if read_eos is not None and read_eos(t) == n_rows:
+                return t
+            continue
+        step(t)
+        if pending is not None and read_eos is not None and read_eos(pending) == n_rows:
+            return pending
+        pending = t
+    if late and pending is not None and read_eos is not None and read_eos(pending) == n_rows:
+        return pending
+    return max_length
+
+
+# ----------------------------------------------------------------------------- transcription (W:962-986)
+DUMMY_AUDIO_SEED = 0
+
+
+def read_wav(path: str) -> np.ndarray:
+    """16-bit PCM, mono, 16 kHz ``.wav`` -> float32 samples in [-1, 1) (stdlib ``wave``; anything else raises)."""
+    import wave
+    with wave.open(path, "rb") as f:
+        if f.getnchannels() != 1 or f.getsampwidth() != 2 or f.getframerate() != 16000:
+            raise ValueError(f"{path}: expected 16-bit PCM mono at 16 kHz, got {f.getnchannels()} channel(s), "
+                             f"{8 * f.getsampwidth()} bit, {f.getframerate()} Hz")
+        if f.getcomptype() != "NONE":
+            raise ValueError(f"{path}: compressed wav files are not supported")
+        raw = f.readframes(f.getnframes())
+    return (np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0)
+
+
+def dummy_waveform(seed: int = DUMMY_AUDIO_SEED) -> np.ndarray:
+    """W:971: 30 s of N(0, 1) samples at 16 kHz (seeded here; the reference draws it unseeded)."""
+    return np.random.RandomState(seed).randn(16000 * 30).astype(np.float32)
+
+
+def transcribe_audio(model, audio=None, tokenizer=None, max_length=448):
+    """W:962-986: waveform -> log-mel (frontend.LogMelFrontend, channels-first: the layout the encoder reads; the reference
+    feeds [frames, 80] un-transposed) -> ``model.generate`` -> ``tokenizer.decode(ids)``, or the ids
+    (int32 numpy array, start token first) without a tokenizer.  ``audio``: a waveform (1-D tensor or array, 16 kHz), a
+    ``.wav`` path, or None for the reference's 30 s dummy clip (seeded)."""
+    from .frontend import LogMelFrontend
+    if audio is None:
+        wav = dummy_waveform()
+    elif isinstance(audio, (str, os.PathLike)):
+        wav = read_wav(os.fspath(audio))
+    else:
+        wav = audio
+    wav = torch.as_tensor(wav).to(device=model.device, dtype=torch.float32).reshape(-1).contiguous()
+    fe = model.__dict__.get("_frontend")
+    if fe is None:
+        fe = model._frontend = LogMelFrontend(device=model.device, n_mels=model.config.n_mels)
+    feats = fe(wav)
+    ids = model.generate(feats, max_length=max_length)[0].cpu().numpy()
+    if tokenizer is not None:
+        return tokenizer.decode(ids)
+    return ids

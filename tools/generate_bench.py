@@ -1,0 +1,95 @@
+"""Greedy decoding, measured: Whisper small-ref, B = 8, features [8, 80, 3000], bf16, EOS disabled (eos_id -1) so that
+all 448 steps run.  Prints ONE JSON line: the encoder time (encoder + cross-attention k|v), the whole decode and its
+per-step mean, tokens / s, and tmi_lm_head_argmax alone at M = 8 (d 768 and 1280, the bf16 LM head [d, 51904]) in us and
+GB/s of weight stream (device time: launches captured in a graph and replayed) beside the per-call time from Python.
+bench.py measures training and stays as it is; this is the inference counterpart.
+
+usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+import tethys_speech_amd  # noqa: E402,F401
+from tethys_speech_amd import ops, whisper  # noqa: E402
+
+
+def timed_us(fn, iters=50, warm=5):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / iters
+
+
+def argmax_alone(dev, d, M=8, V=51865, Vp=51904):
+    g = torch.Generator(device=dev).manual_seed(d)
+    x = torch.randn(M, d, device=dev, generator=g).to(torch.bfloat16)
+    w = (torch.randn(d, Vp, device=dev, generator=g) * 0.03).to(torch.bfloat16)
+    gamma, beta = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+    ids = torch.empty(M, dtype=torch.int32, device=dev)
+    cnt = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+    call = lambda: ops.lm_head_argmax(x, d, w, Vp, M, d, V, ids, 1, ws, gamma=gamma, beta=beta, eos_id=2, eos_count=cnt)
+    eager = timed_us(call)  # per call from Python: host-bound (ctypes + wrapper) at this size
+    # device time: n back-to-back launches captured once and replayed (no host in between)
+    n = 20
+    call()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(n):
+            call()
+    us = timed_us(graph.replay, iters=10, warm=2) / n
+    return {"us": round(us, 2), "GBps": round(d * Vp * 2 / (us * 1e-6) / 1e9, 1), "us_eager_call": round(eager, 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=448)
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=2)
+    args = ap.parse_args()
+    dev = "cuda:0"
+    model = whisper.create_whisper_model("small", device=dev, precision="bf16")
+    B = args.batch
+    feats = torch.randn(B, 80, 3000, generator=torch.Generator().manual_seed(0))
+    feats_d = feats.to(dev)
+    # encoder alone (the first part of every generate call), through the same inference path
+    inf = model._infer_prepare(B, 3000)
+
+    def encode():
+        saved = model._infer_begin(inf)
+        try:
+            model._cross_kv_infer(model._encode_infer(feats_d, inf))
+        finally:
+            model._infer_end(saved)
+    enc_ms = timed_us(encode, iters=10, warm=2) / 1e3
+    model.generate(feats_d, max_length=4, eos_token_id=-1)  # warm-up: workspace, kernels
+    torch.cuda.synchronize()
+    best = None
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        ids = model.generate(feats_d, max_length=args.steps, eos_token_id=-1)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        best = dt if best is None else min(best, dt)
+    assert tuple(ids.shape) == (B, 1 + args.steps), ids.shape
+    decode_s = best - enc_ms / 1e3
+    out = {"workload": "whisper_small_generate", "batch": B, "steps": args.steps, "precision": "bf16",
+           "encoder_ms": round(enc_ms, 3), "generate_s": round(best, 4), "decode_s": round(decode_s, 4),
+           "per_step_ms": round(decode_s * 1e3 / args.steps, 3), "tokens_per_s": round(B * args.steps / best, 1),
+           "lm_head_argmax_M8": {"d768": argmax_alone(dev, 768), "d1280": argmax_alone(dev, 1280)}}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
