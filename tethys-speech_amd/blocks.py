@@ -147,10 +147,6 @@ class Arena:
                 v.zero_()
 
 
-_DEFER_WGRAD = os.environ.get("TMI_DEFER_WGRAD", "0") != "0"
-_DKV_ON_SIDE = os.environ.get("TMI_CROSS_DKV_SIDE", "1") != "0"
-
-
 class KernelBlocks:
     # ---- weight-gradient stream ------------------------------------------------------------
     # dW = xᵀ·dy and db = colsum(dy) feed nothing until the optimizer (or the all-reduce), so they run
@@ -175,19 +171,11 @@ class KernelBlocks:
             ops.set_stream(self._prev_override)
             self._main = None
 
-    # Number of weight-gradient streams ("lanes"; TMI_WGRAD_LANES).  Round 3 tried two - a layer's weight gradients are
-    # independent, so two side by side could each run with a smaller split-K (fewer workgroups, longer K loops, less slab
-    # traffic) - and measured it level with one (8.58 = 8.58 ms/step at a split cap of 4; smaller caps lose with either:
-    # the no-split kernel needs 1.36 us per K-tile, the per-CU staging rate, not the MFMA's 0.86).  One stays the default.
-    N_LANES = max(1, int(os.environ.get("TMI_WGRAD_LANES", "1")))
-
     def enable_wgrad_stream(self, on=True):
         on = on and self.device.type == "cuda"
-        self._sides = [torch.cuda.Stream(device=self.device) for _ in range(self.N_LANES)] if on else []
-        self._side = self._sides[0] if on else None           # lane 0: also the stream of the non-GEMM side work
-        self._side_handles = [st.cuda_stream for st in self._sides]
-        self._side_handle = self._side_handles[0] if on else None
-        self._side_reads = {}     # buffer address -> {lane: event recorded after the lane's last reader of it}
+        self._side = torch.cuda.Stream(device=self.device) if on else None
+        self._side_handle = self._side.cuda_stream if on else None
+        self._side_reads = {}     # buffer address -> event recorded after the side stream's last reader of it
         self._done_events = {}
         # events are reused round-robin: creating two per launch costs more host time than the
         # decoder-sized kernels take (re-recording an event other work already waited on is legal)
@@ -200,49 +188,34 @@ class KernelBlocks:
         self._ev_i = (self._ev_i + 1) % len(self._ev_ring)
         return ev
 
-    def _run_on_side(self, fn, dy, defer=False, ready=None, lane=0):
+    def _run_on_side(self, fn, dy):
         """Launch ``fn``'s kernels (readers of the finished buffer ``dy``, writers of gradients only)
-        on a weight-gradient stream (``lane``), or inline if there is none.  ``defer`` (TMI_DEFER_WGRAD=1): do not enqueue
-        yet - ``_flush_deferred`` does, at the point the caller picks (before a kernel the work should run beside)."""
+        on the weight-gradient stream, or inline if there is none."""
         if self._side is None:
             fn()
             return
-        lane = lane % len(self._sides)
-        if ready is None:
-            # a ring slot is only good for an event that is waited for at once; one that is parked (TMI_DEFER_WGRAD)
-            # could be re-recorded by a later launch before its waiter is enqueued, so it gets an event of its own
-            ready = torch.cuda.Event() if (defer and _DEFER_WGRAD) else self._event()
-            ready.record(self._main or torch.cuda.current_stream())  # dy is complete on the main stream here
-        if defer and _DEFER_WGRAD:
-            self.__dict__.setdefault("_deferred", []).append((fn, dy, ready, lane))
-            return
-        side = self._sides[lane]
-        side.wait_event(ready)
-        prev = ops.set_stream(self._side_handles[lane])
+        ready = self._event()
+        ready.record(self._main or torch.cuda.current_stream())  # dy is complete on the main stream here
+        self._side.wait_event(ready)
+        prev = ops.set_stream(self._side_handle)
         try:
             fn()
         finally:
             ops.set_stream(prev)
         # "done" events are STORED (``_side_reads``) and waited for arbitrarily later - decoder buffers two layers on,
-        # the early-decoder / kv_rest / embedding hand-offs - so they never come from the ring: one event per (buffer
-        # address, lane), re-recorded only by a later reader of the same buffer on the same stream, which supersedes it
+        # the early-decoder / kv_rest / embedding hand-offs - so they never come from the ring: one event per buffer
+        # address, re-recorded only by a later reader of the same buffer, which supersedes it
         key = dy.data_ptr()
-        done = self._done_events.get((key, lane))
+        done = self._done_events.get(key)
         if done is None:
-            done = self._done_events[(key, lane)] = torch.cuda.Event()
-        done.record(side)
-        self._side_reads.setdefault(key, {})[lane] = done
-
-    def _flush_deferred(self):
-        pend = self.__dict__.get("_deferred")
-        if pend:
-            self._deferred = []
-            for fn, dy, ready, lane in pend:
-                self._run_on_side(fn, dy, ready=ready, lane=lane)
+            done = self._done_events[key] = torch.cuda.Event()
+        done.record(self._side)
+        self._side_reads[key] = done
 
     def _pop_side_reads(self, tensor):
         """Events after which every queued side-stream reader of ``tensor`` has finished (and forget them)."""
-        return list(self._side_reads.pop(tensor.data_ptr(), {}).values())
+        ev = self._side_reads.pop(tensor.data_ptr(), None)
+        return [] if ev is None else [ev]
 
     def _wait_events(self, events):
         main = self._main or torch.cuda.current_stream()
@@ -250,12 +223,7 @@ class KernelBlocks:
             main.wait_event(ev)
 
     def _guard_write(self, *tensors):
-        if self._side is None:
-            return
-        pend = self.__dict__.get("_deferred")
-        if pend and any(t.data_ptr() == dy.data_ptr() for t in tensors for _, dy, _, _ in pend):
-            self._flush_deferred()  # a queued-but-not-enqueued reader of this buffer: enqueue it, then wait for it below
-        if not self._side_reads:
+        if self._side is None or not self._side_reads:
             return
         for t in tensors:
             self._wait_events(self._pop_side_reads(t))
@@ -307,16 +275,12 @@ class KernelBlocks:
 
     def gradient_streams(self):
         """Streams other than the compute stream on which gradient-producing kernels are queued."""
-        self._flush_deferred()
-        return list(self._sides) if self._side is not None else []
+        return [self._side] if self._side is not None else []
 
     def _join_side(self):
-        """Main stream waits for everything queued on the weight-gradient streams."""
-        self._flush_deferred()
+        """Main stream waits for everything queued on the weight-gradient stream."""
         if self._side is not None:
-            cur = torch.cuda.current_stream()
-            for st in self._sides:
-                cur.wait_stream(st)
+            torch.cuda.current_stream().wait_stream(self._side)
             self._side_reads.clear()
 
     def refresh_shadows(self):
@@ -420,7 +384,7 @@ class KernelBlocks:
                       bias=bias, **epi)
 
     def _dense_bwd(self, x2d, dy2d, wname, dx2d=None, accumulate_dx=False, aux_in=None, dgrad_on_side=False,
-                   dgrad_epi=None, bias_done=False, defer=False, wgrad=True, lane=0):
+                   dgrad_epi=None, bias_done=False, wgrad=True):
         """dW = xᵀ·dy, db = colsum(dy), optionally dx (=|+=) dy·Wᵀ (* gelu'(aux_in)).
         ``dgrad_on_side``: dx is not needed by the chain that follows (the caller joins the side stream
         before its consumer), so the dgrad goes to the weight-gradient stream too."""
@@ -446,7 +410,7 @@ class KernelBlocks:
             self._run_on_side(lambda: (weight_grads(), dgrad()), dy2d)
             return
         if wgrad:  # (False: the caller batches this layer's weight gradient with the other layers', _wgrad_batched)
-            self._run_on_side(weight_grads, dy2d, defer=defer, lane=lane)
+            self._run_on_side(weight_grads, dy2d)
         if dx2d is not None:
             self._guard_write(dx2d)
             dgrad()
@@ -465,7 +429,7 @@ class KernelBlocks:
         """``emit`` = (bias gradient tensor, masked-copy buffer or None, dropout site or None): the Dense layer below this
         LayerNorm takes dx (or its Dropout-masked copy) as dy; its bias gradient and the masked copy come out of this
         kernel (tmi_layernorm_bwd_emit) instead of a dropout pass and a column-sum pass over dx.  A buffer without
-        dropout (rate 0 or no site) receives a plain copy of dx: the snapshot a deferred weight gradient reads."""
+        dropout (rate 0 or no site) receives a plain copy of dx: the snapshot a batched weight gradient reads."""
         a = self.arena
         self._guard_write(dx2d)
         if emit is None:
@@ -561,7 +525,7 @@ class KernelBlocks:
         if self.precision == "bf16":
             def m(t, off, T):
                 return (t, off, T * t.stride(0), t.stride(0))
-            split = dkv_on_side and self._side is not None and _DKV_ON_SIDE
+            split = dkv_on_side and self._side is not None
             # (a pass on another stream reads delta later: its own buffer, not the one every attention backward shares)
             delta = self._buf(key + ".delta", (B, H, Tq), torch.float32) if split else self.ws["delta"]
 

@@ -492,51 +492,31 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
 
         # The gradient of the residual stream that a LayerNorm backward leaves in ``dres`` is the dy of the Dense layer below
         # it (attention out_proj under the FFN LayerNorm, the previous layer's output_dense under the attention LayerNorm):
-        # that layer's bias gradient and - with dropout - its masked copy come out of the LayerNorm kernel
-        # (tmi_layernorm_bwd_emit) instead of a dropout pass and a column-sum pass over dres.  TMI_LN_EMIT=0: separate kernels.
-        emit_on = os.environ.get("TMI_LN_EMIT", "1") != "0"
+        # that layer's bias gradient and its dy - dres, Dropout-masked with dropout - come out of the LayerNorm kernel
+        # (tmi_layernorm_bwd_emit) instead of a dropout pass and a column-sum pass over dres.
+        # Weight gradients of the encoder are batched over the layers.  Every Dense layer's dy is kept in a per-layer buffer:
+        # dqkv / dU are written there by the kernels that produce them, the residual-stream gradients (dyf for output_dense,
+        # dya for out_proj) are the second output of the LayerNorm backward above them.
         Lh = cfg.num_hidden_layers
-        # Weight gradients of the encoder: deferred and batched over the layers (TMI_WGRAD_BATCH=0: one launch per layer
-        # beside its dgrad, the round-2 form).  Every Dense layer's dy is kept in a per-layer buffer - dqkv / dU are written
-        # there by the kernels that produce them, the residual-stream gradients (dyf for output_dense, dya for out_proj) are
-        # the second output of the LayerNorm backward above them (its Dropout-masked copy, or a plain copy at rate 0).
-        batch = os.environ.get("TMI_WGRAD_BATCH", "1") != "0" and Lh > 1
 
         def emit(bias_name, buf, site):
-            return (a.grad(bias_name), ws[buf] if (drop or batch) else None, site) if emit_on else None
+            return (a.grad(bias_name), ws[buf], site)
 
-        def residual_dy(i, kind, site, have):
-            """The dy a Dense layer on the residual stream sees: ``dres`` itself, its masked copy (dropout), or - when the
-            weight gradient is deferred - a snapshot, since ``dres`` is rewritten by the next LayerNorm backward.
-            ``have``: the LayerNorm backward that produced ``dres`` already wrote the per-layer buffer."""
-            if not (drop or batch):
-                return dres
-            dy = ws[f"enc{i}.{kind}"]
-            if not have:
-                if drop:
-                    self._dropout(dres, dy, site)
-                else:
-                    self._guard_write(dy)
-                    ops.copy(dy, dres)
-            return dy
-
-        # The batched weight gradients go to the second stream in CHUNKS of layers (TMI_WGRAD_CHUNKS, default 4): a chunk
-        # starts as soon as the backward chain has left its layers - that chain is a string of decoder-sized kernels on a
-        # mostly idle chip - instead of everything queueing behind layer 0 and running into the conv-stack backward, whose
-        # own weight gradients share that stream (measured with those on it, ms/step: 1 chunk 4.74, 2: 4.75, 3: 4.71, 4: 4.70).
-        nchunk = max(1, min(Lh, int(os.environ.get("TMI_WGRAD_CHUNKS", "4")))) if batch else 1
+        # The batched weight gradients go to the second stream in 4 CHUNKS of layers: a chunk starts as soon as the backward
+        # chain has left its layers - that chain is a string of decoder-sized kernels on a mostly idle chip - instead of
+        # everything queueing behind layer 0 and running into the conv-stack backward, whose own weight gradients share that
+        # stream (measured with those on it, ms/step: 1 chunk 4.74, 2: 4.75, 3: 4.71, 4: 4.70).
+        nchunk = max(1, min(Lh, 4))
         cuts = sorted({(Lh * j) // nchunk for j in range(nchunk)})   # chunk j = layers [cuts[j], cuts[j + 1])
-        st = {n: ws[f"enc*.{n}"] for n in ("xn1", "ctx", "xn2", "g", "dqkv", "dya", "dU", "dyf")} if batch else None
+        st = {n: ws[f"enc*.{n}"] for n in ("xn1", "ctx", "xn2", "g", "dqkv", "dya", "dU", "dyf")}
         lay = "encoder.layers.{}"
 
         def encoder_weight_grads(lo, hi):
-            # the bias gradients the LayerNorm backward did not emit: every layer's with TMI_LN_EMIT=0, the top layer's
-            # output_dense otherwise (its dres came from the projection head)
-            self._wgrad_batched(st["g"], st["dyf"], lay + ".feed_forward.output_dense.kernel", Lh, bias=not emit_on, lo=lo, hi=hi)
-            if emit_on and hi == Lh:
+            self._wgrad_batched(st["g"], st["dyf"], lay + ".feed_forward.output_dense.kernel", Lh, bias=False, lo=lo, hi=hi)
+            if hi == Lh:  # (the one bias gradient the LayerNorm backward did not emit: the top layer's dres came from the head)
                 ops.bias_grad(st["dyf"][Lh - 1], a.grad(lay.format(Lh - 1) + ".feed_forward.output_dense.bias"))
             self._wgrad_batched(st["xn2"], st["dU"], lay + ".feed_forward.intermediate_dense.kernel", Lh, lo=lo, hi=hi)
-            self._wgrad_batched(st["ctx"], st["dya"], lay + ".attention.out_proj.kernel", Lh, bias=not emit_on, lo=lo, hi=hi)
+            self._wgrad_batched(st["ctx"], st["dya"], lay + ".attention.out_proj.kernel", Lh, bias=False, lo=lo, hi=hi)
             # the q / k / v blocks are three [H, H] kernels side by side in the arena: one launch per block over the layers
             gq0 = a.grad(lay.format(lo) + ".attention.qkv3.kernel")
             lstride = self._layer_stride(lay + ".attention.qkv3.kernel", Lh)
@@ -550,38 +530,33 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         for i in reversed(range(Lh)):
             p, kk = f"encoder.layers.{i}", f"enc{i}."
             dU, dt_, dctx, dqkv = ws[kk + "dU"], ws["dtmp"], ws["dctx"], ws[kk + "dqkv"]
-            top = i == Lh - 1  # (the top layer's dres comes from the projection head's dgrad, not from a LayerNorm)
-            dy = residual_dy(i, "dyf", SITE_FFN_OUT + i, emit_on and not top)  # the branch sees the masked gradient
+            if i == Lh - 1:
+                # the top layer's dres comes from the projection head's dgrad, not from a LayerNorm: its dy (the masked
+                # gradient with dropout) is written here
+                if drop:
+                    self._dropout(dres, ws[kk + "dyf"], SITE_FFN_OUT + i)
+                else:
+                    self._guard_write(ws[kk + "dyf"])
+                    ops.copy(ws[kk + "dyf"], dres)
             # d u = gelu'(u) * mask/keep * d g: both factors are epilogue terms of the dgrad (elementwise factors commute)
-            self._dense_bwd(ws[kk + "g"], dy, p + ".feed_forward.output_dense.kernel", dU, aux_in=ws[kk + "u"],
-                            dgrad_epi=self._drop_epi(SITE_FFN_MID + i, p=pa), bias_done=emit_on and not top, wgrad=not batch)
-            self._dense_bwd(ws[kk + "xn2"], dU, p + ".feed_forward.intermediate_dense.kernel", dt_, wgrad=not batch)
+            self._dense_bwd(ws[kk + "g"], ws[kk + "dyf"], p + ".feed_forward.output_dense.kernel", dU, aux_in=ws[kk + "u"],
+                            dgrad_epi=self._drop_epi(SITE_FFN_MID + i, p=pa), wgrad=False)
+            self._dense_bwd(ws[kk + "xn2"], dU, p + ".feed_forward.intermediate_dense.kernel", dt_, wgrad=False)
             self._ln_bwd(dt_, ws[kk + "x_mid"], p + ".feed_forward_layer_norm", dres, kk + "ln2", True,
                          emit=emit(p + ".attention.out_proj.bias", kk + "dya", SITE_ATTN_OUT + i))
-            dy = residual_dy(i, "dya", SITE_ATTN_OUT + i, emit_on)
-            self._dense_bwd(ws[kk + "ctx"], dy, p + ".attention.out_proj.kernel", dctx, bias_done=emit_on, wgrad=not batch)
+            self._dense_bwd(ws[kk + "ctx"], ws[kk + "dya"], p + ".attention.out_proj.kernel", dctx, wgrad=False)
             qkv = ws[kk + "qkv"]
             self._attn_bwd(kk + ("stats" if self.precision == "bf16" else "P"), (qkv, 0), (qkv, H), (qkv, 2 * H),
                            ws[kk + "ctx"], dctx, (dqkv, 0), (dqkv, H), (dqkv, 2 * H), B, Hh, T, T, 0, score_scale=sscale,
                            q_prescaled=False, site=SITE_ATTN + i)
-            # three separate kernels: wgrad / bias grad batched over the blocks, dgrad summed over them
+            # the dgrad of the three q / k / v blocks, summed over them in one launch
             wq, _ = self.W(p + ".attention.qkv3.kernel")
-            if not batch:
-                gq = a.grad(p + ".attention.qkv3.kernel")
-                xn1 = ws[kk + "xn1"]
-                gqb = a.grad(p + ".attention.qkv3.bias").view(3 * H)
-
-                def qkv_weight_grads(xn1=xn1, gq=gq, gqb=gqb, dqkv=dqkv):
-                    ops.gemm(xn1, dqkv, gq, H, H, R, 1, H, 3 * H, 1, H, nbatch=3, b_sb=H, c_sb=H * H, splitk=0)
-                    ops.bias_grad(dqkv, gqb)
-
-                self._run_on_side(qkv_weight_grads, dqkv)
             self._guard_write(dt_)
             ops.gemm(dqkv, wq, dt_, R, H, H, 3 * H, 1, 1, H, H, kbatch=3, a_skb=H, b_skb=H * H)
             self._ln_bwd(dt_, ws[kk + "x_in"], p + ".attention_layer_norm", dres, kk + "ln1", True,
                          emit=emit(f"encoder.layers.{i - 1}.feed_forward.output_dense.bias", f"enc{i - 1}.dyf",
                                    SITE_FFN_OUT + i - 1) if i > 0 else None)
-            if batch and i in cuts:
+            if i in cuts:
                 # every dy of layers [i, next cut) is final (this layer's dqkv was the last to be written); the rest of the
                 # step runs beside this chunk: the layers below, then the feature-projection / pos-conv / conv-stack backward
                 lo, hi = i, ([c for c in cuts if c > i] + [Lh])[0]
@@ -598,16 +573,8 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         gwp = a.grad("feature_extractor.pos_conv_embed.kernel")
         # (weight gradients of the positional conv and of the conv stack feed nothing on the chain: second stream.  Their
         # operands - the packed / padded forward inputs and the per-layer dy buffers - are not rewritten before the join)
-        conv_side = os.environ.get("TMI_CONV_WGRAD_SIDE", "1") != "0"
-
-        def off_chain(fn, dy):
-            if conv_side:
-                self._run_on_side(fn, dy)
-            else:
-                fn()
-
-        off_chain(lambda: ops.gemm(ws["xg"], ws["dyg"], gwp, k * Cg, Cg, Mw, 1, Cg, Cg, 1, C, nbatch=Gn, a_sb=B * self.Tpp * Cg,
-                                   b_sb=B * self.Tpp * Cg, c_sb=Cg, splitk=0), ws["dyg"])
+        self._run_on_side(lambda: ops.gemm(ws["xg"], ws["dyg"], gwp, k * Cg, Cg, Mw, 1, Cg, Cg, 1, C, nbatch=Gn,
+                                           a_sb=B * self.Tpp * Cg, b_sb=B * self.Tpp * Cg, c_sb=Cg, splitk=0), ws["dyg"])
         ops.group_pack(dhp, ws["dyg2"], B, T, C, Gn, self.Tpp2, k - 1)
         Mw2 = B * self.Tpp2 - (k - 1)
         ops.gemm(ws["dyg2"], self.pos_wb, ws["dxg2"], Mw2, Cg, k * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
@@ -639,9 +606,9 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             wname = f"feature_extractor.conv_layers.{i}.conv.kernel"
             xin = ws[f"in{i}"]
             gw = a.grad(wname).view(kc * cin, c)
-            off_chain(lambda xin=xin, dup=dup, gw=gw, kc=kc, cin=cin, c=c, Ti=Ti, s=s:
-                      ops.gemm(xin, dup, gw, kc * cin, c, Ti, 1, s * cin, c, 1, c, kbatch=B, a_skb=xin.stride(0),
-                               b_skb=dup.stride(0), b_off=c, splitk=0), dup)
+            self._run_on_side(lambda xin=xin, dup=dup, gw=gw, kc=kc, cin=cin, c=c, Ti=Ti, s=s:
+                              ops.gemm(xin, dup, gw, kc * cin, c, Ti, 1, s * cin, c, 1, c, kbatch=B, a_skb=xin.stride(0),
+                                       b_skb=dup.stride(0), b_off=c, splitk=0), dup)
             if i == 0:
                 continue
             if s != 2 or kc not in (2, 3):

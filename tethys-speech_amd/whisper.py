@@ -34,9 +34,7 @@ from .blocks import Arena, KernelBlocks, _round_up
 # dropout site ids (seed = f(base, step, site), KernelBlocks._site_seed; restated in oracle/dropout.py)
 SITE_ENC_STEM, SITE_DEC_EMBED = 1, 2
 SITE_ENC_ATTN, SITE_ENC_FFN, SITE_DEC_SELF, SITE_DEC_CROSS, SITE_DEC_FFN = 100, 200, 300, 400, 500
-
-
-_XENT_EXACT = os.environ.get("TMI_XENT_EXACT_TARGET", "1") != "0"
+_STEM_SLACK = 2  # rows of zero slack behind the padded stem inputs, so the padded-K tail reads of the last window stay in bounds
 
 
 @dataclass
@@ -202,11 +200,32 @@ class WhisperForConditionalGeneration(KernelBlocks):
         # weight / bias gradients on a second stream beside the dgrad chain (blocks.KernelBlocks)
         self.enable_wgrad_stream(os.environ.get("TMI_WGRAD_STREAM", "1") != "0")
 
-    # -- weights ---------------------------------------------------------------------
-
-
-
     # -- workspaces --------------------------------------------------------------------
+    def _stem_geometry(self, T_in: int) -> dict:
+        """TF "SAME" geometry of the conv stem (W:329-339) for ``T_in`` frames: conv1 (stride 1) gives T1 rows from the
+        padded input of Tp0 rows, conv2 (stride 2) the encoder length T from Tp1.  Shared by training and inference."""
+        cfg = self.config
+        T1, pl1, pr1 = same_pad(T_in, 3, 1)
+        T, pl2, pr2 = same_pad(T1, 3, 2)
+        if T > cfg.n_ctx:
+            raise ValueError("encoder length exceeds n_ctx")
+        # conv1's reduction length 3*n_mels (240) is not a multiple of the GEMM's 64-deep K tile: the bf16
+        # path multiplies against a copy of the kernel padded with zero rows, so the tile-aligned kernels
+        # apply; the extra A columns are the next frames of xp0 (finite, inside the slack) times zero
+        K1p = -(-3 * cfg.n_mels // 64) * 64
+        w1pad = self.precision == "bf16" and K1p != 3 * cfg.n_mels and K1p - 3 * cfg.n_mels <= _STEM_SLACK * cfg.n_mels
+        return {"T1": T1, "pl1": pl1, "pr1": pr1, "T": T, "pl2": pl2, "pr2": pr2, "Tp0": T_in + pl1 + pr1,
+                "Tp1": T1 + pl2 + pr2, "K1p": K1p, "w1pad": w1pad}
+
+    def _stem_bufs(self, B: int, geo: dict):
+        """The stem's inputs: the padded features, conv1's padded output, the padded conv1 kernel (bf16)."""
+        d, z = self.config.d_model, dict(zero=True)
+        self._buf("xp0", (B, geo["Tp0"] + _STEM_SLACK, self.config.n_mels), **z)
+        self._buf("h1pad", (B, geo["Tp1"] + _STEM_SLACK, d), **z)
+        if geo["w1pad"]:
+            self._buf("w1pad", (geo["K1p"], d), **z)
+        else:
+            self.ws.pop("w1pad", None)
 
     def _prepare(self, B: int, T_in: int, S: int):
         key = (B, T_in, S)
@@ -222,30 +241,18 @@ class WhisperForConditionalGeneration(KernelBlocks):
         cfg = self.config
         if S > cfg.max_target_positions:
             raise ValueError("target length exceeds max_target_positions")
-        self.T1, self.pl1, self.pr1 = same_pad(T_in, 3, 1)
-        self.T, self.pl2, self.pr2 = same_pad(self.T1, 3, 2)
-        if self.T > cfg.n_ctx:
-            raise ValueError("encoder length exceeds n_ctx")
+        geo = self._geo = self._stem_geometry(T_in)
+        # (the shape attributes model.T, model.T1, ...: tests, tools and bench read them)
+        self.T1, self.pl1, self.pr1, self.T, self.pl2, self.pr2, self.Tp0, self.Tp1, self.K1p = (
+            geo[n] for n in ("T1", "pl1", "pr1", "T", "pl2", "pr2", "Tp0", "Tp1", "K1p"))
         d, ff = cfg.d_model, cfg.d_ff
-        self.Tp0 = T_in + self.pl1 + self.pr1
-        self.Tp1 = self.T1 + self.pl2 + self.pr2
-        slack = 2  # rows of zero slack so the padded-K tail reads of the last window stay in bounds
         f32 = torch.float32
         z = dict(zero=True)
-        self._buf("xp0", (B, self.Tp0 + slack, cfg.n_mels), **z)
-        self._buf("h1pad", (B, self.Tp1 + slack, d), **z)
-        self._buf("u1pad", (B, self.Tp1 + slack, d), **z)
-        self._buf("dh1pad", (B, self.Tp1 + slack, d), **z)
+        self._stem_bufs(B, geo)
+        self._buf("u1pad", (B, self.Tp1 + _STEM_SLACK, d), **z)
+        self._buf("dh1pad", (B, self.Tp1 + _STEM_SLACK, d), **z)
         self._buf("u2", (B, self.T, d))
         self._buf("du2pad", (B, self.T + 1, d), **z)
-        # conv1's reduction length 3*n_mels (240) is not a multiple of the GEMM's 64-deep K tile: the bf16
-        # path multiplies against a copy of the kernel padded with zero rows, so the tile-aligned kernels
-        # apply; the extra A columns are the next frames of xp0 (finite, inside the slack) times zero
-        self.K1p = -(-3 * cfg.n_mels // 64) * 64
-        if self.precision == "bf16" and self.K1p != 3 * cfg.n_mels and self.K1p - 3 * cfg.n_mels <= slack * cfg.n_mels:
-            self._buf("w1pad", (self.K1p, d), **z)
-        else:
-            self.ws.pop("w1pad", None)
         R, Rd = B * self.T, B * S
         # decoder: the operands of the six weight gradients per layer live at a constant layer stride (one allocation per
         # kind) - the saved activations xn1 / ctx / xn2 / ctxc / xn3 / g and the gradients dqkv / dyos / dqc / dyoc / dU /
@@ -323,13 +330,88 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 self._buf(f"dec{i}.Pc", (B, Hd, S, self.T), f32)
             self._buf("dP", (B, max(He, Hd), max(self.T, S), self.T), f32)
 
-    # -- building blocks -----------------------------------------------------------------
+    # -- forward blocks, shared by the training step and the forward-only pass ---------------------------------------
+    # Each takes a map of its buffers: training passes the layer's own workspace entries (kept for backward), inference
+    # buffers every layer shares, without the GELU pre-activation ``u`` (None).  ``sites``: the dropout sites apply (the
+    # training step; inference runs without dropout even after enable_dropout).  Buffer-map keys: activations x_in, xn1,
+    # qkv, ctx, x_mid, xn2, g, u (encoder layer, decoder self block; qc for the cross-attention query), ctxc, x_mid2, xn3
+    # (decoder cross block), x_out (the next layer's input), kvc (every decoder layer's cross-attention k|v); the names of
+    # the LayerNorm statistics ln1 / ln2 / ln3 and of the attention scratch att / attc.
 
+    def _stem(self, features, geo, x, u1pad=None, u2=None):
+        """W:329-339: conv1 + GELU into ws["h1pad"] (its pad rows stay zero), conv2 + GELU + positional encoding into
+        ``x`` [B*T, d].  ``u1pad`` / ``u2``: where training keeps the pre-activations for backward."""
+        ws, a, d = self.ws, self.arena, self.config.d_model
+        B, Cn, T_in = features.shape
+        xp0, h1pad, w1pad = ws["xp0"], ws["h1pad"], ws.get("w1pad")
+        ops.feat_to_channels_last(features, xp0, B, Cn, T_in, geo["pl1"], geo["pr1"] + (xp0.shape[1] - geo["Tp0"]))
+        conv1_out = dict(ldc=d, nbatch=B, a_sb=xp0.stride(0), c_sb=h1pad.stride(0), c_off=geo["pl2"] * d,
+                         bias=a.param("encoder.conv1.bias"), act=1, aux_out=u1pad)
+        if w1pad is not None:
+            ops.copy(w1pad[:3 * Cn], self.W("encoder.conv1.kernel")[0])
+            ops.gemm(xp0, w1pad, h1pad, geo["T1"], d, geo["K1p"], Cn, 1, d, 1, **conv1_out)
+        else:
+            self._gemm_xw(xp0, "encoder.conv1.kernel", h1pad, geo["T1"], d, 3 * Cn, Cn, **conv1_out)
+        T = geo["T"]
+        self._gemm_xw(h1pad, "encoder.conv2.kernel", x, T, d, 3 * d, 2 * d, ldc=d, nbatch=B, a_sb=h1pad.stride(0),
+                      c_sb=T * d, bias=a.param("encoder.conv2.bias"), act=1, aux_out=u2, resid=self.pe_enc_t,
+                      r_ld=d, r_sb=0)
 
+    def _enc_layer(self, i, b, B, T, sites):
+        """W:218-236: encoder layer i, b["x_in"] -> b["x_out"]."""
+        cfg, d = self.config, self.config.d_model
+        p, He = f"encoder.layers.{i}", cfg.encoder_attention_heads
+        self._ln_fwd(b["x_in"], p + ".self_attn_layer_norm", b["xn1"], b["ln1"])
+        self._dense_fwd(b["xn1"], p + ".self_attn.qkv.kernel", b["qkv"], scale_cols=d, scale=(d // He) ** -0.5)
+        qkv = b["qkv"]
+        self._attn_fwd(b["att"], (qkv, 0), (qkv, d), (qkv, 2 * d), b["ctx"], B, He, T, T, 0,
+                       site=SITE_ENC_ATTN + i if sites else None)
+        self._dense_fwd(b["ctx"], p + ".self_attn.out_proj.kernel", b["x_mid"], resid=b["x_in"], r_ld=d)
+        self._ln_fwd(b["x_mid"], p + ".final_layer_norm", b["xn2"], b["ln2"])
+        self._dense_fwd(b["xn2"], p + ".feed_forward.fc1.kernel", b["g"], act=1, aux_out=b["u"])
+        # W:205: x_mid + Dropout(fc2(g)): the mask is a term of the GEMM epilogue (before the residual add)
+        self._dense_fwd(b["g"], p + ".feed_forward.fc2.kernel", b["x_out"], resid=b["x_mid"], r_ld=d,
+                        **(self._drop_epi(SITE_ENC_FFN + i) if sites else {}))
 
+    def _dec_self_block(self, i, b, B, S, sites):
+        """Decoder layer i (W:394-466) up to the cross-attention query: needs nothing from the encoder."""
+        cfg, d = self.config, self.config.d_model
+        p, Hd = f"decoder.layers.{i}", cfg.decoder_attention_heads
+        scal = (d // Hd) ** -0.5
+        self._ln_fwd(b["x_in"], p + ".self_attn_layer_norm", b["xn1"], b["ln1"])
+        self._dense_fwd(b["xn1"], p + ".self_attn.qkv.kernel", b["qkv"], scale_cols=d, scale=scal)
+        qkv = b["qkv"]
+        # the inverted mask of W:416-418 (mask_mode 1): each query sees the strictly later positions only
+        self._attn_fwd(b["att"], (qkv, 0), (qkv, d), (qkv, 2 * d), b["ctx"], B, Hd, S, S, 1,
+                       site=SITE_DEC_SELF + i if sites else None)
+        self._dense_fwd(b["ctx"], p + ".self_attn.out_proj.kernel", b["x_mid"], resid=b["x_in"], r_ld=d)
+        # cross attention (W:278-290): k/v projections of the encoder output in every layer
+        self._ln_fwd(b["x_mid"], p + ".encoder_attn_layer_norm", b["xn2"], b["ln2"])
+        self._dense_fwd(b["xn2"], p + ".encoder_attn.q_proj.kernel", b["qc"], scale_cols=d, scale=scal)
 
-    # attention: q/k/v given as (tensor2d, column offset); rows are (b, t) with Tq / Tk per batch
+    def _dec_cross_ffn(self, i, b, B, S, T, sites):
+        """Decoder layer i from its cross-attention on: b["x_mid"] -> b["x_out"]."""
+        cfg, d = self.config, self.config.d_model
+        p, Hd, kvc = f"decoder.layers.{i}", cfg.decoder_attention_heads, b["kvc"]
+        self._attn_fwd(b["attc"], (b["qc"], 0), (kvc, 2 * i * d), (kvc, (2 * i + 1) * d), b["ctxc"], B, Hd, S, T, 0,
+                       site=SITE_DEC_CROSS + i if sites else None)
+        self._dense_fwd(b["ctxc"], p + ".encoder_attn.out_proj.kernel", b["x_mid2"], resid=b["x_mid"], r_ld=d)
+        self._ln_fwd(b["x_mid2"], p + ".final_layer_norm", b["xn3"], b["ln3"])
+        self._dense_fwd(b["xn3"], p + ".feed_forward.fc1.kernel", b["g"], act=1, aux_out=b["u"])
+        self._dense_fwd(b["g"], p + ".feed_forward.fc2.kernel", b["x_out"], resid=b["x_mid2"], r_ld=d,
+                        **(self._drop_epi(SITE_DEC_FFN + i) if sites else {}))
 
+    def _train_bufs(self, side, i, L):
+        """Training's buffer map of layer i of ``side`` ("enc" / "dec", L layers): the layer's own workspace entries."""
+        ws, k = self.ws, f"{side}{i}."
+        att = ("stats", "statsc") if self.precision == "bf16" else ("P", "Pc")
+        b = {n: ws[k + n] for n in ("x_in", "xn1", "qkv", "ctx", "x_mid", "xn2", "g", "u")}
+        b.update(ln1=k + "ln1", ln2=k + "ln2", att=k + att[0],
+                 x_out=ws[f"{side}{i + 1}.x_in"] if i + 1 < L else ws[f"{side}_x"])
+        if side == "dec":
+            b.update({n: ws[k + n] for n in ("qc", "ctxc", "x_mid2", "xn3")})
+            b.update(ln3=k + "ln3", attc=k + att[1], kvc=ws["kvc_all"])
+        return b
 
     def embedding_tables(self):
         """(arena offset, rows, row length) of the tf.keras.layers.Embedding tables (W:382): rows that never see a
@@ -415,9 +497,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if features.dtype != torch.float32 or labels.dtype != torch.int32:
             raise TypeError("features must be float32 and labels int32")
         self._prepare(B, T_in, S)
-        ws, a, d, ff = self.ws, self.arena, cfg.d_model, cfg.d_ff
-        T, He, Hd = self.T, cfg.encoder_attention_heads, cfg.decoder_attention_heads
-        scal_e, scal_d = (d // He) ** -0.5, (d // Hd) ** -0.5
+        ws, a, d = self.ws, self.arena, cfg.d_model
+        T, Hd = self.T, cfg.decoder_attention_heads
         if not getattr(a, "g_clean", False):
             self._wait_late()  # (a pending late Adam slice reads the gradients this fill would overwrite)
             ops.fill_zero(a.g)  # (an optimizer step with zero_grad leaves the arena clean: no fill pass)
@@ -429,7 +510,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
             """Everything stored at or after parameter ``name`` now has its final gradient."""
             if name != next(expected, None):
                 raise RuntimeError(f"backward reported {name} out of the order grad_ready_names() promises")
-            self._flush_deferred()
             lo = a.offsets[name]
             if grad_ready is not None and lo < done[0]:
                 # (a consumer that acts on the range at once must first order itself after the
@@ -438,88 +518,31 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 done[0] = lo
 
         drop = self._drop_p > 0.0
-        # The decoder's embedding and layer 0 up to its cross-attention query depend on the labels only: a chain of
-        # ~10 decoder-sized kernels that would otherwise sit, alone on the chip, between the encoder and the decoder.
-        # They run on the second stream beside the encoder's forward.
-        # decoder pieces (W:394-466); ids = [start, labels[:, :-1]] (W:559-563) inside the embedding kernel
-        kvc = ws["kvc_all"]
-        Ld = cfg.decoder_layers
+        Le, Ld = cfg.encoder_layers, cfg.decoder_layers
+        dec_bufs = [self._train_bufs("dec", i, Ld) for i in range(Ld)]
 
         def dec_embed():
+            """ids = [start, labels[:, :-1]] (W:559-563) inside the embedding kernel."""
             y = ws["dec0.x_in"] if Ld else ws["dec_x"]
             ops.embed_fwd(labels, a.param("decoder.embed_tokens.embeddings"), self.pe_dec, y, B, S, d,
                           cfg.decoder_start_token_id)
             if drop:
                 self._dropout(y, y, SITE_DEC_EMBED)  # W:411
 
-        def dec_self_block(i):
-            """Layer i up to the cross-attention query: needs nothing from the encoder."""
-            p, k = f"decoder.layers.{i}", f"dec{i}."
-            x_in = ws[k + "x_in"]
-            self._ln_fwd(x_in, p + ".self_attn_layer_norm", ws[k + "xn1"], k + "ln1")
-            self._dense_fwd(ws[k + "xn1"], p + ".self_attn.qkv.kernel", ws[k + "qkv"], scale_cols=d, scale=scal_d)
-            qkv = ws[k + "qkv"]
-            self._attn_fwd(k + ("stats" if self.precision == "bf16" else "P"), (qkv, 0), (qkv, d), (qkv, 2 * d),
-                           ws[k + "ctx"], B, Hd, S, S, 1, site=SITE_DEC_SELF + i)
-            self._dense_fwd(ws[k + "ctx"], p + ".self_attn.out_proj.kernel", ws[k + "x_mid"], resid=x_in, r_ld=d)
-            # cross attention (W:278-290): k/v projections of the encoder output in every layer
-            self._ln_fwd(ws[k + "x_mid"], p + ".encoder_attn_layer_norm", ws[k + "xn2"], k + "ln2")
-            self._dense_fwd(ws[k + "xn2"], p + ".encoder_attn.q_proj.kernel", ws[k + "qc"], scale_cols=d, scale=scal_d)
-
-        def dec_cross_ffn(i):
-            p, k = f"decoder.layers.{i}", f"dec{i}."
-            self._attn_fwd(k + ("statsc" if self.precision == "bf16" else "Pc"), (ws[k + "qc"], 0),
-                           (kvc, 2 * i * d), (kvc, (2 * i + 1) * d), ws[k + "ctxc"], B, Hd, S, T, 0, site=SITE_DEC_CROSS + i)
-            self._dense_fwd(ws[k + "ctxc"], p + ".encoder_attn.out_proj.kernel", ws[k + "x_mid2"],
-                            resid=ws[k + "x_mid"], r_ld=d)
-            self._ln_fwd(ws[k + "x_mid2"], p + ".final_layer_norm", ws[k + "xn3"], k + "ln3")
-            self._dense_fwd(ws[k + "xn3"], p + ".feed_forward.fc1.kernel", ws[k + "g"], act=1, aux_out=ws[k + "u"])
-            nxt = ws[f"dec{i + 1}.x_in"] if i + 1 < Ld else ws["dec_x"]
-            self._dense_fwd(ws[k + "g"], p + ".feed_forward.fc2.kernel", nxt, resid=ws[k + "x_mid2"], r_ld=d,
-                            **self._drop_epi(SITE_DEC_FFN + i))
-
-        early_dec = self._side is not None and Ld > 0 and self._main is not None and os.environ.get("TMI_DEC_EARLY", "1") != "0"
-        early_ev = None
+        # The decoder's embedding and layer 0 up to its cross-attention query depend on the labels only: a chain of
+        # ~10 decoder-sized kernels that would otherwise sit, alone on the chip, between the encoder and the decoder.
+        # They run on the second stream beside the encoder's forward.
+        early_dec = self._side is not None and Ld > 0 and self._main is not None
         if early_dec:
-            self._run_on_side(lambda: (dec_embed(), dec_self_block(0)), labels)
+            self._run_on_side(lambda: (dec_embed(), self._dec_self_block(0, dec_bufs[0], B, S, True)), labels)
             early_ev = self._pop_side_reads(labels)
-        # ---- encoder stem (W:329-339)
-        xp0, h1pad, u1pad = ws["xp0"], ws["h1pad"], ws["u1pad"]
-        ops.feat_to_channels_last(features, xp0, B, Cn, T_in, self.pl1, self.pr1 + (xp0.shape[1] - self.Tp0))
-        w1pad = ws.get("w1pad")
-        if w1pad is not None:
-            ops.copy(w1pad[:3 * Cn], self.W("encoder.conv1.kernel")[0])
-            ops.gemm(xp0, w1pad, h1pad, self.T1, d, self.K1p, Cn, 1, d, 1, ldc=d, nbatch=B,
-                     a_sb=xp0.stride(0), c_sb=h1pad.stride(0), c_off=self.pl2 * d,
-                     bias=a.param("encoder.conv1.bias"), act=1, aux_out=u1pad)
-        else:
-            self._gemm_xw(xp0, "encoder.conv1.kernel", h1pad, self.T1, d, 3 * Cn, Cn, ldc=d, nbatch=B,
-                          a_sb=xp0.stride(0), c_sb=h1pad.stride(0), c_off=self.pl2 * d,
-                          bias=a.param("encoder.conv1.bias"), act=1, aux_out=u1pad)
-        w2, ld2 = self.W("encoder.conv2.kernel")
-        x = ws["enc0.x_in"] if cfg.encoder_layers else ws["enc_x"]
-        self._gemm_xw(h1pad, "encoder.conv2.kernel", x, T, d, 3 * d, 2 * d, ldc=d, nbatch=B, a_sb=h1pad.stride(0),
-                      c_sb=T * d, bias=a.param("encoder.conv2.bias"), act=1, aux_out=ws["u2"], resid=self.pe_enc_t,
-                      r_ld=d, r_sb=0)
-
+        # ---- encoder stem (W:329-339) and layers (W:218-236)
+        x = ws["enc0.x_in"] if Le else ws["enc_x"]
+        self._stem(features, self._geo, x, u1pad=ws["u1pad"], u2=ws["u2"])
         if drop:
             self._dropout(x, x, SITE_ENC_STEM)  # W:342
-        # ---- encoder layers (W:218-236)
-        for i in range(cfg.encoder_layers):
-            p, k = f"encoder.layers.{i}", f"enc{i}."
-            x_in = ws[k + "x_in"]
-            self._ln_fwd(x_in, p + ".self_attn_layer_norm", ws[k + "xn1"], k + "ln1")
-            self._dense_fwd(ws[k + "xn1"], p + ".self_attn.qkv.kernel", ws[k + "qkv"], scale_cols=d, scale=scal_e)
-            qkv = ws[k + "qkv"]
-            self._attn_fwd(k + ("stats" if self.precision == "bf16" else "P"), (qkv, 0), (qkv, d), (qkv, 2 * d),
-                           ws[k + "ctx"], B, He, T, T, 0, site=SITE_ENC_ATTN + i)
-            self._dense_fwd(ws[k + "ctx"], p + ".self_attn.out_proj.kernel", ws[k + "x_mid"], resid=x_in, r_ld=d)
-            self._ln_fwd(ws[k + "x_mid"], p + ".final_layer_norm", ws[k + "xn2"], k + "ln2")
-            self._dense_fwd(ws[k + "xn2"], p + ".feed_forward.fc1.kernel", ws[k + "g"], act=1, aux_out=ws[k + "u"])
-            nxt = ws[f"enc{i + 1}.x_in"] if i + 1 < cfg.encoder_layers else ws["enc_x"]
-            # W:205: x_mid + Dropout(fc2(g)): the mask is a term of the GEMM epilogue (before the residual add)
-            self._dense_fwd(ws[k + "g"], p + ".feed_forward.fc2.kernel", nxt, resid=ws[k + "x_mid"], r_ld=d,
-                            **self._drop_epi(SITE_ENC_FFN + i))
+        for i in range(Le):
+            self._enc_layer(i, self._train_bufs("enc", i, Le), B, T, True)
         self._ln_fwd(ws["enc_x"], "encoder.layer_norm", ws["enc_out"], "enc_ln")
         enc_out = ws["enc_out"]
 
@@ -527,6 +550,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self._wait_late()  # the previous step's late Adam slices, if they were left running (train.ADAM_LATE)
         if not early_dec:
             dec_embed()
+        kvc, kv_rest = ws["kvc_all"], None
         if Ld:
             if self._side is not None and Ld > 1:
                 # W:122-123 for all layers: layer 0's k/v now (its cross-attention is next), the other layers' as ONE
@@ -537,15 +561,14 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 kv_rest = self._pop_side_reads(enc_out)
             else:
                 self._dense_fwd(enc_out, "decoder.cross_kv.kernel", kvc)
-                kv_rest = None
         for i in range(Ld):
             if not (early_dec and i == 0):
-                dec_self_block(i)
-            elif early_ev is not None:
+                self._dec_self_block(i, dec_bufs[i], B, S, True)
+            else:
                 self._wait_events(early_ev)  # layer 0's self-attention block ran beside the encoder
             if i == 1 and kv_rest is not None:
                 self._wait_events(kv_rest)
-            dec_cross_ffn(i)
+            self._dec_cross_ffn(i, dec_bufs[i], B, S, T, True)
         self._ln_fwd(ws["dec_x"], "decoder.layer_norm", ws["dec_out"], "dec_ln")
 
         # ---- LM head + shifted cross-entropy (W:579-600); logits become dlogits in place
@@ -555,10 +578,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
         Vp = self.ldl  # pad columns of the stored kernel are zero: their logits are 0 and ignored by xent
         self._gemm_xw(ws["dec_out"], "lm_head.kernel", logits, B * S, Vp, d, d, ldc=Vp)
         gs = loss_scale / (B * (S - 1))
-        # (tmi_linear_xent: the loss's target logit in fp32 from the LM head's own operands - bf16 logits have lost its low bits;
-        # TMI_XENT_EXACT_TARGET=0: the plain cross-entropy of the stored logits)
-        lm = (ws["dec_out"], d, wl, ldw, 1, d) if _XENT_EXACT else None
-        ops.xent_fwd_bwd(logits, self.ldl, labels, ws["row_loss"], B, S, V, gs, lm=lm)
+        # (tmi_linear_xent: the loss's target logit in fp32 from the LM head's own operands - bf16 logits have lost its low bits)
+        ops.xent_fwd_bwd(logits, self.ldl, labels, ws["row_loss"], B, S, V, gs, lm=(ws["dec_out"], d, wl, ldw, 1, d))
         ops.sum_scale(ws["row_loss"], ws["loss"], B * S, 1.0 / (B * (S - 1)))
 
         # ================= backward =================
@@ -588,132 +609,75 @@ class WhisperForConditionalGeneration(KernelBlocks):
             self._run_on_side(lambda: early_update(lm_lo, a.numel), ws["row_loss"])
         # Column sums (bias gradients) and Dropout-masked copies of the residual-stream gradient come out of the LayerNorm
         # backward that produces it (tmi_layernorm_bwd_emit): ffn_emit(side, i) = what layer i's fc2 needs of the dres
-        # handed down to it - its bias gradient and, with dropout, dres under the mask of W:205 in one of two
-        # alternating buffers (a layer's weight gradient on the second stream may still be reading the other one)
-        emit_on = os.environ.get("TMI_LN_EMIT", "1") != "0"
-
-        Ld = cfg.decoder_layers
-        # Decoder weight gradients deferred and batched over the layers (TMI_WGRAD_BATCH=0: one launch per layer, the round-2
-        # form): 24 launches of 13-26 us on B*S = 800 rows become 6 with L times the tiles (KernelBlocks._wgrad_batched).
-        batchd = os.environ.get("TMI_WGRAD_BATCH", "1") != "0" and Ld > 1
-
+        # handed down to it - its bias gradient and its dy: in the decoder, dres (under the mask of W:205 with dropout) in
+        # the layer's own buffer, which the batched weight gradient reads after the loop; in the encoder, with dropout,
+        # the masked dres in one of two alternating buffers (a layer's weight gradient on the second stream may still be
+        # reading the other one)
         def ffn_emit(side, i, rows):
-            if not emit_on or i < 0:
+            if i < 0:
                 return None
-            pre = f"{'encoder' if side == 'enc' else 'decoder'}.layers.{i}.feed_forward.fc2.bias"
-            site = (SITE_ENC_FFN if side == "enc" else SITE_DEC_FFN) + i
-            if side == "dec" and batchd:  # the per-layer buffer: masked copy (dropout) or snapshot (rate 0)
-                return (a.grad(pre), ws[f"dec{i}.dyf"], site)
-            return (a.grad(pre), ws[f"dyd{i & 1}"][:rows] if drop else None, site)
-
-        def bias_emit(name, snapshot=None):
-            """``snapshot``: per-layer buffer that receives a copy of the emitted dres (a deferred weight gradient's dy)."""
-            return (a.grad(name), snapshot, None) if emit_on else None
-
-        def snap(buf, have):
-            """dres for a deferred reader: the LayerNorm backward wrote ``buf`` (``have``) or it is copied now."""
-            if not have:
-                self._guard_write(buf)
-                ops.copy(buf, dres)
-            return buf
+            if side == "dec":
+                return (a.grad(f"decoder.layers.{i}.feed_forward.fc2.bias"), ws[f"dec{i}.dyf"], SITE_DEC_FFN + i)
+            return (a.grad(f"encoder.layers.{i}.feed_forward.fc2.bias"), ws[f"dyd{i & 1}"][:rows] if drop else None,
+                    SITE_ENC_FFN + i)
 
         self._ln_bwd(dtmp, ws["dec_x"], "decoder.layer_norm", dres, "dec_ln", False, emit=ffn_emit("dec", Ld - 1, B * S))
         ready("decoder.layer_norm.gamma")
 
+        # Decoder weight gradients are batched over the layers after the loop: 24 launches of 13-26 us on B*S = 800 rows
+        # become 6 with L times the tiles (KernelBlocks._wgrad_batched).  Every Dense layer's dy is kept in a per-layer
+        # buffer: dU / dqc / dqkv are written there by the kernels that produce them, the residual-stream gradients (dyf,
+        # dyoc, dyos) are the second output of the LayerNorm backward above them.
         d_enc, dkv = ws["d_enc_out"], ws["dkv_all"]
-        # (opt-in: measured slower on MI355X, 9.41 -> 9.73 ms/step - four K = 12000 weight gradients with their own
-        # split-K reductions cost more than the one fused GEMM saves by leaving the critical path)
-        kv_per_layer = (self._side is not None and cfg.decoder_layers > 1 and self._main is not None and
-                        os.environ.get("TMI_KV_PER_LAYER", "0") != "0")
-        if cfg.decoder_layers:
-            Lkv = cfg.decoder_layers * 2 * d
-            gkv = a.grad("decoder.cross_kv.kernel").view(d, Lkv)
-            gkvb = a.grad("decoder.cross_kv.bias")
-            wkv, ldkv = self.W("decoder.cross_kv.kernel")
-        for i in reversed(range(cfg.decoder_layers)):
+        Rd = B * S
+        dt_, dctx = ws["dtmp"][:Rd], ws["dctx"][:Rd]
+        for i in reversed(range(Ld)):
             p, k = f"decoder.layers.{i}", f"dec{i}."
-            Rd = B * S
-            dt_, dctx = ws["dtmp"][:Rd], ws["dctx"][:Rd]
-            dU = ws[k + "dU"] if batchd else ws["dU"][:Rd]
-            dqkv = ws[k + "dqkv"] if batchd else ws["dqkv"][:Rd]
-            wg = not batchd
             # FFN (with dropout the branch sees the masked gradient: the same mask, regenerated)
-            dy = dres
-            if batchd:
-                dy = ws[k + "dyf"]
-                if not emit_on:
-                    if drop:
-                        self._dropout(dres, dy, SITE_DEC_FFN + i)
-                    else:
-                        snap(dy, False)
-            elif drop:
-                dy = ws[f"dyd{i & 1}"][:Rd]
-                if not emit_on:
-                    self._dropout(dres, dy, SITE_DEC_FFN + i)
-            self._dense_bwd(ws[k + "g"], dy, p + ".feed_forward.fc2.kernel", dU, aux_in=ws[k + "u"], bias_done=emit_on, wgrad=wg)
-            self._dense_bwd(ws[k + "xn3"], dU, p + ".feed_forward.fc1.kernel", dt_, wgrad=wg)
+            self._dense_bwd(ws[k + "g"], ws[k + "dyf"], p + ".feed_forward.fc2.kernel", ws[k + "dU"], aux_in=ws[k + "u"],
+                            wgrad=False)
+            self._dense_bwd(ws[k + "xn3"], ws[k + "dU"], p + ".feed_forward.fc1.kernel", dt_, wgrad=False)
             self._ln_bwd(dt_, ws[k + "x_mid2"], p + ".final_layer_norm", dres, k + "ln3", True,
-                         emit=bias_emit(p + ".encoder_attn.out_proj.bias", ws[k + "dyoc"] if batchd else None))
+                         emit=(a.grad(p + ".encoder_attn.out_proj.bias"), ws[k + "dyoc"], None))
             # cross attention: dK / dV feed only the shared k/v projections' backward after the loop, so their pass runs on the
             # second stream (its dO lives in a buffer of its own: the chain rewrites ws["dctx"] two kernels later)
             dctxc = ws[f"dctxc{i & 1}"][:Rd]
-            dyoc = snap(ws[k + "dyoc"], emit_on) if batchd else dres
-            self._dense_bwd(ws[k + "ctxc"], dyoc, p + ".encoder_attn.out_proj.kernel", dctxc, bias_done=emit_on, wgrad=wg)
-            dqc = ws[k + "dqc"] if batchd else ws["dtmp"][:Rd]
+            self._dense_bwd(ws[k + "ctxc"], ws[k + "dyoc"], p + ".encoder_attn.out_proj.kernel", dctxc, wgrad=False)
+            dqc = ws[k + "dqc"]
             self._attn_bwd(k + ("statsc" if self.precision == "bf16" else "Pc"), (ws[k + "qc"], 0),
                            (kvc, 2 * i * d), (kvc, (2 * i + 1) * d), ws[k + "ctxc"], dctxc, (dqc, 0),
                            (dkv, 2 * i * d), (dkv, (2 * i + 1) * d), B, Hd, S, T, 0, site=SITE_DEC_CROSS + i,
-                           dkv_on_side=not kv_per_layer)
-            if kv_per_layer:
-                # this layer's dk / dv are final: its share of the cross-attention k/v projections' backward (weight
-                # and bias gradient, and d enc_out += dkv_i . Wkv_i^T) goes to the second stream now, under the chain of
-                # decoder-sized kernels that follows, instead of one K = L*2d GEMM alone on the chip after the loop
-                def kv_backward(i=i):
-                    lo = 2 * i * d
-                    ops.gemm(enc_out, dkv, gkv, d, 2 * d, B * T, 1, enc_out.stride(0), dkv.stride(0), 1, Lkv, splitk=0,
-                             b_off=lo, c_off=lo)
-                    ops.bias_grad(dkv[:, lo:lo + 2 * d], gkvb[lo:lo + 2 * d])
-                    ops.gemm(dkv, wkv, d_enc, B * T, d, 2 * d, dkv.stride(0), 1, 1, ldkv, d_enc.stride(0),
-                             accumulate=(i != cfg.decoder_layers - 1), a_off=lo, b_off=lo)
-                self._run_on_side(kv_backward, dkv[:, 2 * i * d:])
-            dxn2 = ws["dctx"][:Rd]
-            self._dense_bwd(ws[k + "xn2"], dqc, p + ".encoder_attn.q_proj.kernel", dxn2, wgrad=wg)
-            self._ln_bwd(dxn2, ws[k + "x_mid"], p + ".encoder_attn_layer_norm", dres, k + "ln2", True,
-                         emit=bias_emit(p + ".self_attn.out_proj.bias", ws[k + "dyos"] if batchd else None))
+                           dkv_on_side=True)
+            self._dense_bwd(ws[k + "xn2"], dqc, p + ".encoder_attn.q_proj.kernel", dctx, wgrad=False)
+            self._ln_bwd(dctx, ws[k + "x_mid"], p + ".encoder_attn_layer_norm", dres, k + "ln2", True,
+                         emit=(a.grad(p + ".self_attn.out_proj.bias"), ws[k + "dyos"], None))
             # self attention
-            dyos = snap(ws[k + "dyos"], emit_on) if batchd else dres
-            self._dense_bwd(ws[k + "ctx"], dyos, p + ".self_attn.out_proj.kernel", dctx, bias_done=emit_on, wgrad=wg)
-            qkv = ws[k + "qkv"]
+            self._dense_bwd(ws[k + "ctx"], ws[k + "dyos"], p + ".self_attn.out_proj.kernel", dctx, wgrad=False)
+            qkv, dqkv = ws[k + "qkv"], ws[k + "dqkv"]
             self._attn_bwd(k + ("stats" if self.precision == "bf16" else "P"), (qkv, 0), (qkv, d), (qkv, 2 * d),
                            ws[k + "ctx"], dctx, (dqkv, 0), (dqkv, d), (dqkv, 2 * d), B, Hd, S, S, 1, site=SITE_DEC_SELF + i)
-            self._dense_bwd(ws[k + "xn1"], dqkv, p + ".self_attn.qkv.kernel", dt_, wgrad=wg)
+            self._dense_bwd(ws[k + "xn1"], dqkv, p + ".self_attn.qkv.kernel", dt_, wgrad=False)
             self._ln_bwd(dt_, ws[k + "x_in"], p + ".self_attn_layer_norm", dres, k + "ln1", True, emit=ffn_emit("dec", i - 1, Rd))
-            if not batchd:
-                ready(p + ".self_attn_layer_norm.gamma")
-        if cfg.decoder_layers:
-            if kv_per_layer:
-                self._wait_events(self._pop_side_reads(dkv))  # d_enc is complete after layer 0's share
-            else:
-                # every layer's dk / dv is in place (their passes ran on the second stream: join it): one weight gradient, one
-                # bias gradient and one dgrad (K = L*2d) for the cross-attention k/v projections of all layers
-                self._join_side()
-                self._dense_bwd(enc_out, dkv, "decoder.cross_kv.kernel", d_enc)
-            if batchd:
-                st = {n: ws[f"dec*.{n}"] for n in ("xn1", "ctx", "xn2", "ctxc", "xn3", "g", "dqkv", "dyos", "dqc", "dyoc", "dU", "dyf")}
-                lay = "decoder.layers.{}"
+        if Ld:
+            # every layer's dk / dv is in place (their passes ran on the second stream: join it): one weight gradient, one
+            # bias gradient and one dgrad (K = L*2d) for the cross-attention k/v projections of all layers
+            self._join_side()
+            self._dense_bwd(enc_out, dkv, "decoder.cross_kv.kernel", d_enc)
+            st = {n: ws[f"dec*.{n}"] for n in ("xn1", "ctx", "xn2", "ctxc", "xn3", "g", "dqkv", "dyos", "dqc", "dyoc", "dU", "dyf")}
+            lay = "decoder.layers.{}"
 
-                def decoder_weight_grads():
-                    nb = not emit_on  # the biases of the residual-stream layers come out of the LayerNorm backward otherwise
-                    self._wgrad_batched(st["g"], st["dyf"], lay + ".feed_forward.fc2.kernel", Ld, bias=nb)
-                    self._wgrad_batched(st["xn3"], st["dU"], lay + ".feed_forward.fc1.kernel", Ld)
-                    self._wgrad_batched(st["ctxc"], st["dyoc"], lay + ".encoder_attn.out_proj.kernel", Ld, bias=nb)
-                    self._wgrad_batched(st["xn2"], st["dqc"], lay + ".encoder_attn.q_proj.kernel", Ld)
-                    self._wgrad_batched(st["ctx"], st["dyos"], lay + ".self_attn.out_proj.kernel", Ld, bias=nb)
-                    self._wgrad_batched(st["xn1"], st["dqkv"], lay + ".self_attn.qkv.kernel", Ld)
-                # on the second stream, under the start of the encoder's backward
-                self._run_on_side(decoder_weight_grads, st["dqkv"])
-                for i in reversed(range(Ld)):
-                    ready(f"decoder.layers.{i}.self_attn_layer_norm.gamma")
+            def decoder_weight_grads():
+                # (the biases of the residual-stream layers came out of the LayerNorm backward)
+                self._wgrad_batched(st["g"], st["dyf"], lay + ".feed_forward.fc2.kernel", Ld, bias=False)
+                self._wgrad_batched(st["xn3"], st["dU"], lay + ".feed_forward.fc1.kernel", Ld)
+                self._wgrad_batched(st["ctxc"], st["dyoc"], lay + ".encoder_attn.out_proj.kernel", Ld, bias=False)
+                self._wgrad_batched(st["xn2"], st["dqc"], lay + ".encoder_attn.q_proj.kernel", Ld)
+                self._wgrad_batched(st["ctx"], st["dyos"], lay + ".self_attn.out_proj.kernel", Ld, bias=False)
+                self._wgrad_batched(st["xn1"], st["dqkv"], lay + ".self_attn.qkv.kernel", Ld)
+            # on the second stream, under the start of the encoder's backward
+            self._run_on_side(decoder_weight_grads, st["dqkv"])
+            for i in reversed(range(Ld)):
+                ready(f"decoder.layers.{i}.self_attn_layer_norm.gamma")
             ready("decoder.cross_kv.kernel")
         # the embedding's backward (mask of W:411, scatter of the rows) feeds nothing on the chain: second stream
         gemb, dres_dec = a.grad("decoder.embed_tokens.embeddings"), dres
@@ -730,41 +694,31 @@ class WhisperForConditionalGeneration(KernelBlocks):
 
         # ---- encoder backward
         dres = ws["dres_enc"]
-        if cfg.decoder_layers == 0:
+        if Ld == 0:
             ops.fill_zero(d_enc)
-        R = B * T
-        self._ln_bwd(d_enc, ws["enc_x"], "encoder.layer_norm", dres, "enc_ln", False,
-                     emit=ffn_emit("enc", cfg.encoder_layers - 1, R))
+        R, He = B * T, cfg.encoder_attention_heads
+        self._ln_bwd(d_enc, ws["enc_x"], "encoder.layer_norm", dres, "enc_ln", False, emit=ffn_emit("enc", Le - 1, R))
         ready("encoder.layer_norm.gamma")
-        for i in reversed(range(cfg.encoder_layers)):
+        dU, dt_, dctx, dqkv = ws["dU"][:R], ws["dtmp"][:R], ws["dctx"][:R], ws["dqkv"][:R]
+        for i in reversed(range(Le)):
             p, k = f"encoder.layers.{i}", f"enc{i}."
-            dU, dt_, dctx, dqkv = ws["dU"][:R], ws["dtmp"][:R], ws["dctx"][:R], ws["dqkv"][:R]
-            dy = dres
-            if drop:
-                dy = ws[f"dyd{i & 1}"][:R]
-                if not emit_on:
-                    self._dropout(dres, dy, SITE_ENC_FFN + i)
-            # (TMI_DEFER_WGRAD=1: the two FFN weight gradients are enqueued when the attention backward starts - MFMA-bound work
-            # beside the VALU-bound attention kernels instead of beside the FFN dgrads)
-            # (the four weight gradients of a layer alternate between the two weight-gradient streams: KernelBlocks.N_LANES)
-            self._dense_bwd(ws[k + "g"], dy, p + ".feed_forward.fc2.kernel", dU, aux_in=ws[k + "u"], bias_done=emit_on,
-                            defer=dy is not dres, lane=0)
-            self._dense_bwd(ws[k + "xn2"], dU, p + ".feed_forward.fc1.kernel", dt_, defer=True, lane=1)
+            dy = ws[f"dyd{i & 1}"][:R] if drop else dres
+            self._dense_bwd(ws[k + "g"], dy, p + ".feed_forward.fc2.kernel", dU, aux_in=ws[k + "u"], bias_done=True)
+            self._dense_bwd(ws[k + "xn2"], dU, p + ".feed_forward.fc1.kernel", dt_)
             self._ln_bwd(dt_, ws[k + "x_mid"], p + ".final_layer_norm", dres, k + "ln2", True,
-                         emit=bias_emit(p + ".self_attn.out_proj.bias"))
-            self._dense_bwd(ws[k + "ctx"], dres, p + ".self_attn.out_proj.kernel", dctx, bias_done=emit_on, lane=0)
+                         emit=(a.grad(p + ".self_attn.out_proj.bias"), None, None))
+            self._dense_bwd(ws[k + "ctx"], dres, p + ".self_attn.out_proj.kernel", dctx, bias_done=True)
             qkv = ws[k + "qkv"]
-            self._flush_deferred()
             self._attn_bwd(k + ("stats" if self.precision == "bf16" else "P"), (qkv, 0), (qkv, d), (qkv, 2 * d),
                            ws[k + "ctx"], dctx, (dqkv, 0), (dqkv, d), (dqkv, 2 * d), B, He, T, T, 0, site=SITE_ENC_ATTN + i)
-            self._dense_bwd(ws[k + "xn1"], dqkv, p + ".self_attn.qkv.kernel", dt_, lane=1)
+            self._dense_bwd(ws[k + "xn1"], dqkv, p + ".self_attn.qkv.kernel", dt_)
             self._ln_bwd(dt_, ws[k + "x_in"], p + ".self_attn_layer_norm", dres, k + "ln1", True, emit=ffn_emit("enc", i - 1, R))
             ready(p + ".self_attn_layer_norm.gamma")
 
         # ---- stem backward: x0 = gelu(u2) + PE ; u2 = conv2(h1) ; h1 = gelu(u1) ; u1 = conv1(x)
         if drop:
             self._dropout(dres, dres, SITE_ENC_STEM)
-        du2pad, dh1pad = ws["du2pad"], ws["dh1pad"]
+        xp0, h1pad, u1pad, du2pad, dh1pad = ws["xp0"], ws["h1pad"], ws["u1pad"], ws["du2pad"], ws["dh1pad"]
         du2 = du2pad[:, 1:]  # row 0 of every batch stays zero (the "t-1" term of the first output)
         # one launch over the B per-sample spans (du2 skips the zero row 0 of every sample)
         ops.gelu_bwd_batched(dres, ws["u2"], du2, T * d, B, T * d, T * d, du2pad.stride(0))
@@ -777,10 +731,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
                      b_skb=du2pad.stride(0), b_off=d, splitk=0)
         # conv2's weight gradient (88 us + its split-K reduce) feeds nothing on the chain: beside the two dgrad launches
         # below (du2pad and h1pad are not rewritten before the join)
-        if os.environ.get("TMI_CONV_WGRAD_SIDE", "1") != "0":
-            self._run_on_side(conv2_weight_grads, du2pad)
-        else:
-            conv2_weight_grads()
+        self._run_on_side(conv2_weight_grads, du2pad)
+        w2, ld2 = self.W("encoder.conv2.kernel")
         sd = du2pad.stride(0)
         # even padded rows u = 2j: dY[j]·W0ᵀ + dY[j-1]·W2ᵀ  (kbatch walks the two kernel taps)
         ops.gemm(du2pad, w2, dh1pad, T, d, d, d, 1, 1, ld2, 2 * d, nbatch=B, a_sb=sd, c_sb=dh1pad.stride(0),
@@ -829,22 +781,13 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if inf is not None and inf["key"] == (B, T_in):
             return inf
         self._inf = None  # (the previous set is released first)
-        T1, pl1, pr1 = same_pad(T_in, 3, 1)
-        T, pl2, pr2 = same_pad(T1, 3, 2)
-        if T > cfg.n_ctx:
-            raise ValueError("encoder length exceeds n_ctx")
-        d, ff, Smax = cfg.d_model, cfg.d_ff, cfg.max_target_positions
+        geo = self._stem_geometry(T_in)
+        T, d, ff, Smax = geo["T"], cfg.d_model, cfg.d_ff, cfg.max_target_positions
         He, Hd = cfg.encoder_attention_heads, cfg.decoder_attention_heads
-        inf = {"key": (B, T_in), "T1": T1, "pl1": pl1, "pr1": pr1, "T": T, "pl2": pl2, "pr2": pr2,
-               "Tp0": T_in + pl1 + pr1, "Tp1": T1 + pl2 + pr2, "K1p": -(-3 * cfg.n_mels // 64) * 64}
+        inf = dict(geo, key=(B, T_in))
         saved, self.ws = self.ws, {}
         try:
-            slack = 2  # (as in _prepare: zero rows behind the last conv window)
-            z = dict(zero=True)
-            self._buf("xp0", (B, inf["Tp0"] + slack, cfg.n_mels), **z)
-            self._buf("h1pad", (B, inf["Tp1"] + slack, d), **z)
-            if self.precision == "bf16" and inf["K1p"] != 3 * cfg.n_mels and inf["K1p"] - 3 * cfg.n_mels <= slack * cfg.n_mels:
-                self._buf("w1pad", (inf["K1p"], d), **z)
+            self._stem_bufs(B, geo)
             R, Rd = B * T, B * Smax
             Rm = max(R, Rd)
             for n, w in (("x", d), ("x_mid", d), ("x_mid2", d), ("xn", d), ("ctx", d), ("qc", d), ("qkv", 3 * d), ("g", ff)):
@@ -874,8 +817,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
         main = self._main or torch.cuda.current_stream(self.device)
         for ev in self.__dict__.get("_late_done", {}).values():
             main.wait_event(ev)  # (a wait on an event that has completed, or was never recorded, is free)
-        for st in getattr(self, "_sides", []):
-            main.wait_stream(st)
+        if self._side is not None:
+            main.wait_stream(self._side)
         saved = self.ws
         self.ws = inf["ws"]
         return saved
@@ -891,39 +834,25 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self.ws[key] = flat[:int(np.prod(shape))].view(shape)
         return key
 
+    def _infer_bufs(self, rows):
+        """Inference's buffer map: every layer of a stack works in the same shared buffers, ``rows`` rows of each; one
+        LayerNorm-statistics buffer, no GELU pre-activation, each layer's output overwrites its input."""
+        x, x_mid, x_mid2, xn, ctx, qc, qkv, g = (self.ws[n][:rows] for n in ("x", "x_mid", "x_mid2", "xn", "ctx", "qc", "qkv", "g"))
+        return {"x_in": x, "xn1": xn, "qkv": qkv, "ctx": ctx, "x_mid": x_mid, "xn2": xn, "g": g, "u": None, "qc": qc,
+                "ctxc": ctx, "x_mid2": x_mid2, "xn3": xn, "x_out": x, "ln1": "ln", "ln2": "ln", "ln3": "ln"}
+
     def _encode_infer(self, features, inf):
-        """W:324-372 with training=False into ws["enc_out"] [B*T, d]: the training forward's blocks and kernels, the
-        pre-activations backward would need not saved."""
-        cfg, ws, a, d = self.config, self.ws, self.arena, self.config.d_model
-        B, Cn, T_in = features.shape
-        T, He = inf["T"], cfg.encoder_attention_heads
-        scal_e = (d // He) ** -0.5
-        R = B * T
-        xp0, h1pad = ws["xp0"], ws["h1pad"]
-        ops.feat_to_channels_last(features, xp0, B, Cn, T_in, inf["pl1"], inf["pr1"] + (xp0.shape[1] - inf["Tp0"]))
-        w1pad = ws.get("w1pad")
-        if w1pad is not None:
-            ops.copy(w1pad[:3 * Cn], self.W("encoder.conv1.kernel")[0])
-            ops.gemm(xp0, w1pad, h1pad, inf["T1"], d, inf["K1p"], Cn, 1, d, 1, ldc=d, nbatch=B, a_sb=xp0.stride(0),
-                     c_sb=h1pad.stride(0), c_off=inf["pl2"] * d, bias=a.param("encoder.conv1.bias"), act=1)
-        else:
-            self._gemm_xw(xp0, "encoder.conv1.kernel", h1pad, inf["T1"], d, 3 * Cn, Cn, ldc=d, nbatch=B,
-                          a_sb=xp0.stride(0), c_sb=h1pad.stride(0), c_off=inf["pl2"] * d,
-                          bias=a.param("encoder.conv1.bias"), act=1)
-        x, x_mid, xn, ctx, qkv, g = (ws[n][:R] for n in ("x", "x_mid", "xn", "ctx", "qkv", "g"))
-        self._gemm_xw(h1pad, "encoder.conv2.kernel", x, T, d, 3 * d, 2 * d, ldc=d, nbatch=B, a_sb=h1pad.stride(0),
-                      c_sb=T * d, bias=a.param("encoder.conv2.bias"), act=1, resid=self.pe_enc_t, r_ld=d, r_sb=0)
+        """W:324-372 with training=False into ws["enc_out"] [B*T, d]: the training forward's blocks, the pre-activations
+        backward would need not saved."""
+        cfg = self.config
+        B, T = features.shape[0], inf["T"]
+        b = self._infer_bufs(B * T)
+        b["att"] = self._att("att", B, cfg.encoder_attention_heads, T, T)
+        self._stem(features, inf, b["x_in"])
         for i in range(cfg.encoder_layers):
-            p = f"encoder.layers.{i}"
-            self._ln_fwd(x, p + ".self_attn_layer_norm", xn, "ln")
-            self._dense_fwd(xn, p + ".self_attn.qkv.kernel", qkv, scale_cols=d, scale=scal_e)
-            self._attn_fwd(self._att("att", B, He, T, T), (qkv, 0), (qkv, d), (qkv, 2 * d), ctx, B, He, T, T, 0)
-            self._dense_fwd(ctx, p + ".self_attn.out_proj.kernel", x_mid, resid=x, r_ld=d)
-            self._ln_fwd(x_mid, p + ".final_layer_norm", xn, "ln")
-            self._dense_fwd(xn, p + ".feed_forward.fc1.kernel", g, act=1)
-            self._dense_fwd(g, p + ".feed_forward.fc2.kernel", x, resid=x_mid, r_ld=d)
-        self._ln_fwd(x, "encoder.layer_norm", ws["enc_out"], "ln")
-        return ws["enc_out"]
+            self._enc_layer(i, b, B, T, False)
+        self._ln_fwd(b["x_in"], "encoder.layer_norm", self.ws["enc_out"], "ln")
+        return self.ws["enc_out"]
 
     def _cross_kv_infer(self, enc_out):
         """W:122-123 for every decoder layer at once: the cross-attention k|v, computed once per encoder output."""
@@ -933,30 +862,16 @@ class WhisperForConditionalGeneration(KernelBlocks):
     def _decode_infer(self, labels, B, S, T):
         """W:394-466 (training=False) over S positions without the final LayerNorm: returns the residual stream
         [B*S, d].  ``labels`` [B, S] int32: the decoder reads [start, labels[:, :-1]] (tmi_embed_fwd's shift)."""
-        cfg, ws, d = self.config, self.ws, self.config.d_model
+        cfg = self.config
         Hd = cfg.decoder_attention_heads
-        scal_d = (d // Hd) ** -0.5
-        Rd = B * S
-        x, x_mid, x_mid2, xn, ctx, qc, qkv, g = (ws[n][:Rd] for n in ("x", "x_mid", "x_mid2", "xn", "ctx", "qc", "qkv", "g"))
-        kvc = ws["kvc_all"][:B * T]
-        ops.embed_fwd(labels, self.arena.param("decoder.embed_tokens.embeddings"), self.pe_dec, x, B, S, d,
+        b = self._infer_bufs(B * S)
+        b.update(att=self._att("att", B, Hd, S, S), attc=self._att("attc", B, Hd, S, T), kvc=self.ws["kvc_all"][:B * T])
+        ops.embed_fwd(labels, self.arena.param("decoder.embed_tokens.embeddings"), self.pe_dec, b["x_in"], B, S, cfg.d_model,
                       cfg.decoder_start_token_id)
         for i in range(cfg.decoder_layers):
-            p = f"decoder.layers.{i}"
-            self._ln_fwd(x, p + ".self_attn_layer_norm", xn, "ln")
-            self._dense_fwd(xn, p + ".self_attn.qkv.kernel", qkv, scale_cols=d, scale=scal_d)
-            # the inverted mask of W:416-418 (mask_mode 1): each query sees the strictly later positions only
-            self._attn_fwd(self._att("att", B, Hd, S, S), (qkv, 0), (qkv, d), (qkv, 2 * d), ctx, B, Hd, S, S, 1)
-            self._dense_fwd(ctx, p + ".self_attn.out_proj.kernel", x_mid, resid=x, r_ld=d)
-            self._ln_fwd(x_mid, p + ".encoder_attn_layer_norm", xn, "ln")
-            self._dense_fwd(xn, p + ".encoder_attn.q_proj.kernel", qc, scale_cols=d, scale=scal_d)
-            self._attn_fwd(self._att("att", B, Hd, S, T), (qc, 0), (kvc, 2 * i * d), (kvc, (2 * i + 1) * d), ctx,
-                           B, Hd, S, T, 0)
-            self._dense_fwd(ctx, p + ".encoder_attn.out_proj.kernel", x_mid2, resid=x_mid, r_ld=d)
-            self._ln_fwd(x_mid2, p + ".final_layer_norm", xn, "ln")
-            self._dense_fwd(xn, p + ".feed_forward.fc1.kernel", g, act=1)
-            self._dense_fwd(g, p + ".feed_forward.fc2.kernel", x, resid=x_mid2, r_ld=d)
-        return x
+            self._dec_self_block(i, b, B, S, False)
+            self._dec_cross_ffn(i, b, B, S, T, False)
+        return b["x_in"]
 
     def _check_features(self, features):
         if features.dim() != 3 or features.shape[1] != self.config.n_mels:
