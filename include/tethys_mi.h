@@ -329,6 +329,45 @@ int tmi_lm_head_argmax(const void* x, int64_t x_ld, int32_t x_dtype, const float
                        void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Beam search's next candidates (whisper.py generate, num_beams > 1): tmi_lm_head_argmax's LayerNorm and LM head, then
+ * per row r of the M rows
+ *   s[n] = z[n] * inv_temperature                     (n < V; the pad columns [V, w_ld) are never chosen)
+ *   lse[r] = log sum_{n < V} exp(s[n])               (fp32; the per-workgroup (max, sum) partials are folded in a fixed
+ *                                                     order, not in arrival order: bit-reproducible; lse may be NULL)
+ *   ids[r * N + j], logprobs[r * N + j], j < N       (the N largest s, ordered by s desc then column asc - ties go to the
+ *                                                     smaller column, -0 == +0; logprobs = s - lse[r], fp32)
+ * 1 <= N <= 16, N <= V <= 65536; inv_temperature finite and > 0.  x, gamma/beta and w as for tmi_lm_head_argmax (the
+ * weights are streamed once per 16 rows, the logits never reach memory).  `workspace`: >= 8 * M * (1 + ceil(V / 128) *
+ * (N + 1)) bytes, 8-byte aligned, ZERO before the first call; the last workgroup of each 16-row tile leaves its part zero again,
+ * so one buffer serves every step on one stream (concurrent calls need one each).  LDS: max(d * MT, 4 * MT * 128, 2048)
+ * floats, MT = M rounded up to a power of two, at most 16, must fit in 160 KiB - 256 bytes (d <= 2544 at M > 8).
+ */
+int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                     const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, float inv_temperature,
+                     int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * One step of beam search's bookkeeping (the rule of whisper.py generate / INTEGRATION.md), one workgroup per batch item
+ * b of B; row r = b * K + k is beam k (1 <= K <= 8).  Step t (finalize = 0; 2K <= N <= 16):
+ *   candidates (k, cand_ids[r * N + j], sums[r] + cand_lp[r * N + j]) (fp32 add), ranked by score desc then (k, id) asc;
+ *   the first 2K are walked: EOS (eos_id >= 0) at rank < K offers cur[r, :t] + [EOS] (length t, score / len_pow) to the
+ *   pool, at rank >= K is skipped; any other becomes the next live beam n: nxt[b*K + n, :t+1] = cur[parent, :t] + [id],
+ *   sums[b*K + n] = score.  The pool (pool_ids [B, K, ld], pool_scores / pool_len [B, K], pool_cnt [B]) stays sorted by
+ *   score desc then insertion; it admits while not full, then replaces its last entry only on a strictly greater score.
+ *   done[b] = 1 and done_count[0] += 1 once the pool is full and early_stopping or pool_scores[b, K-1] >= (best new live
+ *   sum) / len_pow.  An item that is done is frozen: only nxt[r, :t] = cur[r, :t] is written.
+ * finalize = 1: every item not done offers its K live beams cur[r, :t+1] (length t, score sums[r] / len_pow) in order
+ *   k = 0..K-1; cand_ids, cand_lp and nxt are not read.
+ * len_pow = t ** length_penalty (fp32, finite, > 0) is the caller's, so that a host restatement rounds identically; the
+ * divisions are correctly rounded.  1 <= t < ld.
+ */
+int tmi_beam_step(const int32_t* cand_ids, const float* cand_lp, int64_t N, int64_t B, int64_t K, float* sums,
+                  const int32_t* cur, int32_t* nxt, int64_t ld, int64_t t, int32_t eos_id, float len_pow,
+                  int32_t early_stopping, int32_t* pool_ids, float* pool_scores, int32_t* pool_len, int32_t* pool_cnt,
+                  int32_t* done, int32_t* done_count, int32_t finalize, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-tensor Adam over a flat fp32 arena (tf.keras.optimizers.Adam, W:901; V:1271-1275).
  *   g' = g * gscale                      (gscale: 1 for Whisper's SUM, 1/N for V:1231)
  *   m <- b1 m + (1-b1) g' ; v <- b2 v + (1-b2) g'^2

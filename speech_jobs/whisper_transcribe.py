@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Inference job: greedy transcription with a Whisper model (the reference's ``transcribe_audio`` / ``generate``,
+"""Inference job: greedy or beam-search transcription with a Whisper model (the reference's ``transcribe_audio`` / ``generate``,
 speech_jobs/whisper_dist.py W:962-986 / W:636-709, which its job scripts never call).
 
 Loads a checkpoint (``--resume_from``: a ``save_checkpoint`` or ``save_weights`` file; without one the model keeps its
 seeded initialisation), turns each ``--wav`` clip (16-bit PCM mono 16 kHz) or, without one, ``--batch_size`` copies of
-the reference's seeded 30 s dummy clip into log-mel features on the GPU, and decodes them greedily.  Prints one JSON line
-per clip, {"clip", "ids", "n_tokens"} (ids start with the decoder start token), then one timing line.  No tokenizer ships
+the reference's seeded 30 s dummy clip into log-mel features on the GPU, and decodes them greedily or, with
+``--num_beams`` > 1, by beam search.  Prints one JSON line per returned sequence, {"clip", "ids", "n_tokens"} (ids start
+with the decoder start token; beam search adds "rank" and "score"), then one timing line.  No tokenizer ships
 with the project, so the output is token ids.
 """
 import argparse
@@ -20,13 +21,16 @@ if ROOT not in sys.path:
 
 
 def main(argv=None):
-    parser = argparse.ArgumentParser(description="Whisper greedy transcription (token ids)")
+    parser = argparse.ArgumentParser(description="Whisper transcription, greedy or beam search (token ids)")
     parser.add_argument("--model_type", default="small", choices=["tiny", "base", "small", "medium", "large"])
     parser.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
     parser.add_argument("--resume_from", default=None, help="checkpoint to load the weights from")
     parser.add_argument("--wav", action="append", default=[], help="16-bit PCM mono 16 kHz .wav file (repeatable)")
     parser.add_argument("--batch_size", type=int, default=1, help="number of dummy clips when no --wav is given")
     parser.add_argument("--max_length", type=int, default=448, help="decoding steps at most (<= 448)")
+    parser.add_argument("--num_beams", type=int, default=1, help="1: greedy; 2 to 8: beam search")
+    parser.add_argument("--length_penalty", type=float, default=1.0, help="beam search: score = sum log p / length ** this")
+    parser.add_argument("--num_return_sequences", type=int, default=1, help="beam search: hypotheses per clip (<= num_beams)")
     args = parser.parse_args(argv)
 
     import numpy as np
@@ -39,7 +43,12 @@ def main(argv=None):
     torch.cuda.set_device(local_rank)
     device = f"cuda:{local_rank}"
     model = whisper.create_whisper_model(args.model_type, device=device, precision=args.precision)
-    whisper.check_generate_args(model.config, args.max_length)
+    beam = args.num_beams > 1
+    if beam:
+        whisper.check_beam_args(model.config, args.max_length, args.num_beams, 1.0, args.length_penalty,
+                                args.num_return_sequences)
+    else:
+        whisper.check_generate_args(model.config, args.max_length)
     if args.resume_from:
         train.load_weights(model, args.resume_from)
     if args.wav:
@@ -56,10 +65,21 @@ def main(argv=None):
         groups.setdefault(len(wav), []).append((name, wav))
     for items in groups.values():
         wave = torch.from_numpy(np.stack([w for _, w in items])).to(device)
-        ids = model.generate(fe(wave), max_length=args.max_length).cpu()
-        for (name, _), row in zip(items, ids):
-            n_tok += row.numel() - 1
-            print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1)}), flush=True)
+        if not beam:
+            ids = model.generate(fe(wave), max_length=args.max_length).cpu()
+            for (name, _), row in zip(items, ids):
+                n_tok += row.numel() - 1
+                print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1)}), flush=True)
+            continue
+        R = args.num_return_sequences
+        out = model.generate(fe(wave), max_length=args.max_length, num_beams=args.num_beams,
+                             length_penalty=args.length_penalty, num_return_sequences=R, return_dict_in_generate=True)
+        seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
+        for i, row in enumerate(seqs):
+            n = int(lens[i])
+            n_tok += n
+            print(json.dumps({"clip": items[i // R][0], "rank": i % R, "ids": row[:1 + n].tolist(), "n_tokens": n,
+                              "score": float(scores[i])}), flush=True)
     torch.cuda.synchronize()
     dt = time.time() - t0
     print(json.dumps({"clips": len(clips), "seconds": round(dt, 4), "tokens": n_tok,

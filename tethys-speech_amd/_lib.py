@@ -135,9 +135,13 @@ SIGNATURES = {
     "tmi_debug_gemm_stamps": (c_i32, [c_vp]),
     "tmi_lm_head_argmax": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp,
                                    c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
+    "tmi_lm_head_topk": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32,
+                                 c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "tmi_beam_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32, c_vp,
+                              c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
 }
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 _lib = None
 
 

@@ -70,17 +70,14 @@ __device__ __forceinline__ void am_fma_row(float (&acc)[MT][8], const float* __r
   }
 }
 
-// grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128) floats
+// The shared body of the LM-head kernels: rows [row0, row0 + rows) of workgroup (blockIdx.x, blockIdx.y) times the
+// workgroup's 128 columns of the head, left in LDS as the four waves' partials red[(wave * MT + m) * 128 + column]
+// (fold them as ((red0 + red1) + red2) + red3).  Ends with every thread past a barrier.
 template <typename TW, int MT>
-__global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
-    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
-    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, int32_t* __restrict__ ids, int64_t ids_ld,
-    int eos_id, int32_t* __restrict__ eos_count, uint64_t* __restrict__ slots, uint32_t* __restrict__ counter) {
-  extern __shared__ __attribute__((aligned(16))) float am_lds[];
-  __shared__ int am_last, am_eos;
+__device__ __forceinline__ void am_head_tile(float* am_lds, const void* __restrict__ xv, int64_t x_ld, int x_bf16,
+                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                             const TW* __restrict__ w, int64_t w_ld, int d, int V, int row0, int rows) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int row0 = blockIdx.y * MT;
-  const int rows = min(MT, M - row0);
 
   // ---- prologue: rows [row0, row0 + rows) normalised (or copied) into LDS as xs[k * MT + m], fp32
   float* xs = am_lds;
@@ -176,6 +173,21 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
       for (int c = 0; c < 8; ++c) red[(wave * MT + m) * AM_COLS + cg * 8 + c] = acc[m][c];
   }
   __syncthreads();
+}
+
+// grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128) floats
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, int32_t* __restrict__ ids, int64_t ids_ld,
+    int eos_id, int32_t* __restrict__ eos_count, uint64_t* __restrict__ slots, uint32_t* __restrict__ counter) {
+  extern __shared__ __attribute__((aligned(16))) float am_lds[];
+  __shared__ int am_last, am_eos;
+  const int tid = threadIdx.x;
+  const int row0 = blockIdx.y * MT;
+  const int rows = min(MT, M - row0);
+  am_head_tile<TW, MT>(am_lds, xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, d, V, row0, rows);
+  const float* red = am_lds;
 
   // ---- per row: best key over the workgroup's 128 columns (16 lanes of 8 columns), one atomic max per row
   {
@@ -266,6 +278,237 @@ int am_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int
   return TMI_ERR_INVALID;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Beam search's LM head: tmi_lm_head_topk.  The argmax kernel's body (am_head_tile) with a top-N epilogue: per row, the
+// logsumexp of s = z * inv_temperature over the V real columns and the N largest s (ties: smaller column first), written
+// as log-probabilities s - logsumexp.
+//
+// Per workgroup and row: (max, sum exp(s - max)) over its 128 columns (16 lanes, a fixed butterfly) and its N best keys
+// (the argmax kernel's 64-bit keys, extracted in N rounds of a 16-lane max), both stored in the row's slots for this
+// workgroup - plain stores, nothing depends on the arrival order.  The last workgroup of a row tile (one completion
+// counter per tile) then works one wave per row: it folds the (max, sum) slots in a fixed order (lane w takes slots w,
+// w + 64, ... in order, then a butterfly that pairs the lower lane first), takes tau = the N-th largest of the
+// workgroups' best keys (N rounds of a wave max over the lists' heads held in registers), gathers the listed keys >= tau
+// into LDS - they can only come from the N workgroups whose best key is >= tau, so there are at most N * N <= 256 - ranks
+// them (rank = how many gathered keys are larger), writes the N best and puts every slot back to zero.
+constexpr int TK_CAP = 256;    // gathered keys per row: N * N at most
+constexpr int TK_HEADS = 8;    // list heads per lane: ceil(V / 128) <= 512
+
+__device__ __forceinline__ float tk_unorder(uint32_t u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+
+// (max, sum exp(x - max)) pairs: b folded into a
+__device__ __forceinline__ void tk_fold(float& am, float& as, float bm, float bs) {
+  if (bm == -INFINITY) return;
+  if (bm > am) {
+    as = as * expf(am - bm) + bs;
+    am = bm;
+  } else {
+    as = as + bs * expf(bm - am);
+  }
+}
+
+__device__ __forceinline__ uint64_t tk_wave_max(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const uint64_t other = __shfl_xor(v, o, 64);
+    v = other > v ? other : v;
+  }
+  return v;
+}
+
+// grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128, 4 * TK_CAP * 2) floats
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_topk_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float inv_t, int N, int32_t* __restrict__ out_ids,
+    float* __restrict__ out_lp, float* __restrict__ out_lse, uint32_t* __restrict__ counters, float2* __restrict__ part,
+    uint64_t* __restrict__ keys) {
+  extern __shared__ __attribute__((aligned(16))) float am_lds[];
+  __shared__ int tk_last;
+  __shared__ int tk_n[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.y * MT;
+  const int rows = min(MT, M - row0);
+  const int nwg = gridDim.x;
+  am_head_tile<TW, MT>(am_lds, xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, d, V, row0, rows);
+  const float* red = am_lds;
+
+  // ---- per row (16 lanes of 8 columns): the (max, sum) partial and the workgroup's N best keys
+  {
+    const int m = tid >> 4, g = tid & 15;
+    if (m < rows) {
+      const int r = row0 + m;
+      const int c0 = blockIdx.x * AM_COLS + g * 8;
+      float s[8];
+      uint64_t k8[8];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int o = m * AM_COLS + g * 8 + c;
+        const float z = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
+        s[c] = z * inv_t;
+        const bool ok = c0 + c < V;
+        k8[c] = ok ? (((uint64_t)am_order(s[c]) << 32) | (uint64_t)(~(uint32_t)(c0 + c))) : 0;
+        if (ok) mx = fmaxf(mx, s[c]);
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) se += (c0 + c < V) ? expf(s[c] - mx) : 0.f;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) se += __shfl_xor(se, o, 64);  // (xor pairs: both lanes add the same two values)
+      if (g == 0) part[(int64_t)r * nwg + blockIdx.x] = make_float2(mx, se);
+
+      // N rounds: the best remaining key of the 128 columns goes to lane `round` (0 once the columns run out)
+      uint64_t mine = 0;
+      for (int round = 0; round < N; ++round) {
+        uint64_t best = 0;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) best = k8[c] > best ? k8[c] : best;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+          const uint64_t other = __shfl_xor(best, o, 64);
+          best = other > best ? other : best;
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c) k8[c] = k8[c] == best ? 0 : k8[c];
+        if (round == g) mine = best;
+      }
+      if (g < N) keys[((int64_t)r * nwg + blockIdx.x) * N + g] = mine;
+    }
+  }
+
+  // ---- completion: the last workgroup of the row tile publishes and cleans up
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t prev = __hip_atomic_fetch_add(counters + blockIdx.y, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    tk_last = prev == (uint32_t)nwg - 1;
+  }
+  __syncthreads();
+  if (!tk_last) return;
+  __threadfence();
+  uint64_t* lk = reinterpret_cast<uint64_t*>(am_lds) + wave * TK_CAP;  // this wave's gathered keys
+  for (int m = wave; m < rows; m += 4) {
+    const int r = row0 + m;
+    uint64_t* list = keys + (int64_t)r * nwg * N;
+    uint64_t head[TK_HEADS];
+#pragma unroll
+    for (int i = 0; i < TK_HEADS; ++i) {
+      const int wg = lane + 64 * i;
+      head[i] = wg < nwg ? list[(int64_t)wg * N] : 0;
+    }
+    // logsumexp: fixed order, whatever the arrival order was
+    float am = -INFINITY, as = 0.f;
+    for (int wg = lane; wg < nwg; wg += 64) {
+      float2* p = part + (int64_t)r * nwg + wg;
+      const float2 v = *p;
+      tk_fold(am, as, v.x, v.y);
+      *p = make_float2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
+      if (lane & o) {  // the lower lane's pair first, in both lanes
+        float lm = om, ls = os;
+        tk_fold(lm, ls, am, as);
+        am = lm, as = ls;
+      } else {
+        tk_fold(am, as, om, os);
+      }
+    }
+    const float lse = am + logf(as);
+    if (out_lse && lane == 0) out_lse[r] = lse;
+
+    // tau: the N-th largest head (0 when fewer than N workgroups: then every listed key is gathered)
+    uint64_t tau = 0;
+    {
+      uint64_t h[TK_HEADS];
+#pragma unroll
+      for (int i = 0; i < TK_HEADS; ++i) h[i] = head[i];
+      for (int round = 0; round < N; ++round) {
+        uint64_t best = 0;
+#pragma unroll
+        for (int i = 0; i < TK_HEADS; ++i) best = h[i] > best ? h[i] : best;
+        best = tk_wave_max(best);
+#pragma unroll
+        for (int i = 0; i < TK_HEADS; ++i) h[i] = h[i] == best ? 0 : h[i];
+        tau = best;
+      }
+    }
+    // gather the keys >= tau of the (at most N) lists whose head is >= tau
+    if (lane == 0) tk_n[wave] = 0;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#pragma unroll
+    for (int i = 0; i < TK_HEADS; ++i) {
+      const int wg = lane + 64 * i;
+      if (head[i] != 0 && head[i] >= tau) {
+        for (int j = 0; j < N; ++j) {
+          const uint64_t key = list[(int64_t)wg * N + j];
+          if (key == 0 || key < tau) break;  // (a list is sorted)
+          lk[atomicAdd(&tk_n[wave], 1)] = key;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    const int c = tk_n[wave];
+    for (int j = lane; j < c; j += 64) {
+      const uint64_t key = lk[j];
+      int rank = 0;
+      for (int i = 0; i < c; ++i) rank += lk[i] > key;
+      if (rank < N) {
+        out_ids[(int64_t)r * N + rank] = (int32_t)(~(uint32_t)key);
+        out_lp[(int64_t)r * N + rank] = tk_unorder((uint32_t)(key >> 32)) - lse;
+      }
+    }
+    for (int64_t j = lane; j < (int64_t)nwg * N; j += 64) list[j] = 0;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (lk and tk_n are reused by the wave's next row)
+  }
+  __syncthreads();
+  if (tid == 0) __hip_atomic_store(counters + blockIdx.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <typename TW, int MT>
+int tk_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
+              const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, float inv_t, int N,
+              int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys) {
+  auto kern = lm_head_topk_kernel<TW, MT>;
+  static size_t opted = 65536;  // (as am_launch)
+  if (lds > opted) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess) {
+      (void)hipGetLastError();
+      tmi_set_error("tmi_lm_head_topk: the LDS size could not be granted");
+      return TMI_ERR_LAUNCH;
+    }
+    opted = lds;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
+                     reinterpret_cast<const TW*>(w), w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse, counters, part, keys);
+  return tmi_check_launch("tmi_lm_head_topk");
+}
+
+template <typename TW>
+int tk_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
+                const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, float inv_t, int N,
+                int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys) {
+#define TK_CASE(n)                                                                                                     \
+  case n:                                                                                                              \
+    return tk_launch<TW, n>(grid, lds, s, x, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, inv_t, N, out_ids,      \
+                            out_lp, out_lse, counters, part, keys);
+  switch (MT) {
+    TK_CASE(1) TK_CASE(2) TK_CASE(4) TK_CASE(8) TK_CASE(16)
+  }
+#undef TK_CASE
+  return TMI_ERR_INVALID;
+}
+
 inline bool am_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -313,4 +556,56 @@ static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype,
                                eos_id, eos_count, slots, counter);
   return am_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V, ids, ids_ld,
                             eos_id, eos_count, slots, counter);
+}
+
+static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                 float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                 float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
+                                 void* workspace, int64_t workspace_bytes, void* stream);
+extern "C" int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  if (tmi_plan_recording())
+    tmi_plan_push([=]() -> int {
+      return tmi_lm_head_topk(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N, ids,
+                              logprobs, lse, workspace, workspace_bytes, stream);
+    });
+  tmi_plan_enter();
+  const int rc_ = tmi_lm_head_topk_impl(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N,
+                                        ids, logprobs, lse, workspace, workspace_bytes, stream);
+  tmi_plan_leave();
+  return rc_;
+}
+static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                 float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                 float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
+  const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
+  int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
+  if (lds_floats < 4 * TK_CAP * 2) lds_floats = 4 * TK_CAP * 2;
+  const int64_t nwg = (V + AM_COLS - 1) / AM_COLS;
+  const bool sizes_ok = M >= 1 && M <= (int64_t)16 * 65535 && d >= 1 && V >= 1 && nwg <= 64 * TK_HEADS && N >= 1 &&
+                        N <= 16 && N <= V;
+  if (!x || !w || !ids || !logprobs || !workspace || !dt_ok || !sizes_ok || w_ld < V || (w_ld & 7) || !am_al16(w) ||
+      x_ld < d || (gamma == nullptr) != (beta == nullptr) || !(inv_temperature > 0.f && inv_temperature < INFINITY) ||
+      workspace_bytes < 8 * M * (1 + nwg * (N + 1)) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+      lds_floats * 4 > 160 * 1024 - 256) {
+    tmi_set_error("tmi_lm_head_topk: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(workspace);
+  uint32_t* counters = reinterpret_cast<uint32_t*>(base);  // (one per row tile; 8 * M bytes reserved)
+  float2* part = reinterpret_cast<float2*>(base + 8 * M);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(base + 8 * M + 8 * M * nwg);
+  const dim3 grid((unsigned)nwg, (unsigned)((M + MT - 1) / MT));
+  const size_t lds = (size_t)lds_floats * 4;
+  const int xb = x_dtype == TMI_BF16;
+  if (w_dtype == TMI_BF16)
+    return tk_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
+                               inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys);
+  return tk_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
+                            inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys);
 }

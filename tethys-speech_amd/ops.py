@@ -464,6 +464,36 @@ def lm_head_argmax(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma=None
                                        workspace.numel() * workspace.element_size(), stream()), "tmi_lm_head_argmax")
 
 
+def lm_head_topk_workspace_elems(M, V, N):
+    """int64 elements of tmi_lm_head_topk's workspace: 8 * M * (1 + ceil(V / 128) * (N + 1)) bytes."""
+    return M * (1 + (V + 127) // 128 * (N + 1))
+
+
+def lm_head_topk(x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma=None, beta=None, eps=1e-5,
+                 temperature=1.0, lse=None):
+    """Per row r of M rows of x (row stride x_ld): s = (LayerNorm(x[r]) . w)[:V] / temperature; ids[r, :N] the N largest
+    columns of s (ties: the smaller column first), logprobs[r, :N] their s - logsumexp(s) (fp32), lse[r] the logsumexp.
+    ``ids`` int32 and ``logprobs`` fp32 are contiguous [M, N].  ``workspace``: an int64 tensor of at least
+    ``lm_head_topk_workspace_elems(M, V, N)`` elements, zero before the first call (tmi_lm_head_topk leaves it zero)."""
+    with _probe("lm_head_topk", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_topk(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
+                                     V, 1.0 / float(temperature), N, ids.data_ptr(), logprobs.data_ptr(), ptr(lse),
+                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(), stream()),
+              "tmi_lm_head_topk")
+
+
+def beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping, pool_ids, pool_scores,
+              pool_len, pool_cnt, done, done_count, finalize=False):
+    """One step of beam search's bookkeeping on the device (tmi_beam_step; the rule is whisper.generate's): candidates
+    [B*K, N] -> the next prefix rows ``nxt`` [B*K, ld], the running ``sums``, the pool [B, K(, ld)], the done flags and
+    ``done_count``.  ``len_pow`` = t ** length_penalty as an fp32 value.  ``finalize``: offer the live beams of the items
+    not done (prefix rows ``cur`` of length t) to their pools instead; the candidates and ``nxt`` are not read."""
+    check(lib().tmi_beam_step(ptr(cand_ids), ptr(cand_lp), N, B, K, sums.data_ptr(), cur.data_ptr(), ptr(nxt), ld, t, eos_id,
+                              len_pow, 1 if early_stopping else 0, pool_ids.data_ptr(), pool_scores.data_ptr(),
+                              pool_len.data_ptr(), pool_cnt.data_ptr(), done.data_ptr(), done_count.data_ptr(),
+                              1 if finalize else 0, stream()), "tmi_beam_step")
+
+
 def sum_scale(x, out, n, scale):
     check(lib().tmi_sum_scale(x.data_ptr(), out.data_ptr(), n, scale, stream()), "tmi_sum_scale")
 

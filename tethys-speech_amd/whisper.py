@@ -15,6 +15,29 @@ Dropout (W:29-30) is off by default (parity mode: TF's RNG stream cannot be repr
 dropout has no parity definition against the reference).  ``enable_dropout`` turns on the
 reference's training-mode sites (W:160, W:205, W:342, W:411) on the bf16 path with counter-based masks
 (tmi_dropout / the fused attention kernels); the oracle fed the same masks is the checker.
+
+Beam search (``generate(num_beams=K)``, 2 <= K <= 8; the reference leaves it a ``pass`` at W:696-698).  Row r = b*K + k
+is beam k of batch item b.  Step t (1-based) reads prefix columns [0, t) and writes column t.  lp_r(v) =
+log_softmax(z_r / temperature)[v] over the V real columns (temperature as at W:678; top_k, top_p, min_length and
+repetition_penalty are accepted and ignored, as in greedy).
+  Start: running sums s_{b,0} = 0, s_{b,k>0} = -inf; every beam holds [decoder_start_token_id].
+  Per step, for each item not done: the candidates (k, v, s_k + lp_k(v)) ordered by score desc, then k*V + v asc; the
+    first 2K are kept (each row's top 2K of lp_k suffices).  Walk the ranks j = 0 .. 2K-1: an EOS candidate at j < K is
+    offered to the pool (the parent prefix + EOS, length t, score s / t**length_penalty), at j >= K it is skipped; any
+    other candidate becomes the next live beam, in rank order, until K are live (there are always K: each beam has one
+    EOS column).
+  Pool: at most K hypotheses per item, ordered by score desc then insertion asc; admitted while not full, then one
+    replaces the last entry only with a strictly greater score.
+  Done: the pool is full and either early_stopping, or its worst score >= max(new live sums) / t**length_penalty (the
+    early_stopping=False heuristic).  A done item is frozen: later steps change none of its state, its live rows keep
+    valid ids (so a step queued after the stop is harmless).
+  Stop: at the first step where every item is done (read one step late, as greedy), or after max_length steps.
+  Finalize: every item not done offers its live beams, k = 0 .. K-1, to its pool (length n, score s_k / n**length_penalty).
+  Output: the best num_return_sequences R of each item, int32 [B*R, 1 + n_out] (start token first, pad_token_id after
+    the hypothesis, n_out the longest returned length); return_dict_in_generate: {"sequences", "sequences_scores" fp32
+    [B*R], "lengths"}.  eos_token_id = -1: no hypothesis ends early.
+The t**length_penalty factors are rounded to fp32 once, on the host; the kernels' only arithmetic on scores is one fp32
+add per candidate and correctly rounded divisions.
 """
 from __future__ import annotations
 
@@ -775,34 +798,38 @@ class WhisperForConditionalGeneration(KernelBlocks):
     # ``self.ws``); nothing else of the training state (``_ws_key``, the shape attributes, ``_drop_step``, the optimizer,
     # recorded plans) is read or written, and no dropout site is passed (dropout is off even after enable_dropout).
 
-    def _infer_prepare(self, B: int, T_in: int) -> dict:
+    def _infer_prepare(self, B: int, T_in: int, K: int = 1) -> dict:
+        """The inference workspace for B encoder rows and B * K decoder rows (K beams per item; K = 1: greedy)."""
         cfg = self.config
         inf = self.__dict__.get("_inf")
-        if inf is not None and inf["key"] == (B, T_in):
+        if inf is not None and inf["key"] == (B, T_in, K):
             return inf
         self._inf = None  # (the previous set is released first)
         geo = self._stem_geometry(T_in)
         T, d, ff, Smax = geo["T"], cfg.d_model, cfg.d_ff, cfg.max_target_positions
         He, Hd = cfg.encoder_attention_heads, cfg.decoder_attention_heads
-        inf = dict(geo, key=(B, T_in))
+        inf = dict(geo, key=(B, T_in, K))
         saved, self.ws = self.ws, {}
         try:
             self._stem_bufs(B, geo)
-            R, Rd = B * T, B * Smax
+            BK = B * K
+            R, Rd = B * T, BK * Smax
             Rm = max(R, Rd)
             for n, w in (("x", d), ("x_mid", d), ("x_mid2", d), ("xn", d), ("ctx", d), ("qc", d), ("qkv", 3 * d), ("g", ff)):
                 self._buf(n, (Rm, w))
             self._buf("ln.mean", (Rm,), torch.float32)
             self._buf("ln.rstd", (Rm,), torch.float32)
             self._buf("enc_out", (R, d))
-            self._buf("kvc_all", (R, max(1, cfg.decoder_layers) * 2 * d))
+            self._buf("kvc_all", (BK * T, max(1, cfg.decoder_layers) * 2 * d))  # (k|v of item b in rows of b * K .. + K)
             if self.precision == "bf16":
-                n_att = B * max(He, Hd) * max(T, Smax) * 2
+                n_att = BK * max(He, Hd) * max(T, Smax) * 2
             else:
-                n_att = max(B * He * T * T, B * Hd * Smax * max(Smax, T))
+                n_att = max(B * He * T * T, BK * Hd * Smax * max(Smax, T))
             self._buf("att_flat", (n_att,), torch.float32)
             self._buf("labels", (Rd,), torch.int32)
             self._buf("argmax_ws", (B + 1,), torch.int64, zero=True)  # tmi_lm_head_argmax leaves it zero again
+            if K > 1:  # tmi_lm_head_topk's, N = 2K candidates per row; left zero again too
+                self._buf("topk_ws", (ops.lm_head_topk_workspace_elems(BK, cfg.vocab_size, 2 * K),), torch.int64, zero=True)
             inf["ws"] = self.ws
         finally:
             self.ws = saved
@@ -930,22 +957,31 @@ class WhisperForConditionalGeneration(KernelBlocks):
 
     @torch.no_grad()
     def generate(self, input_features, max_length=None, min_length=None, num_beams=None, temperature=1.0, top_k=None,
-                 top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None):
-        """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.
+                 top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None, length_penalty=1.0,
+                 early_stopping=False, num_return_sequences=1, return_dict_in_generate=False):
+        """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.  ``num_beams`` of 2 to
+        8: beam search (``_generate_beam``; the reference accepts num_beams at W:637 and leaves it as a ``pass`` at
+        W:696-698); None or 1: the greedy path below, unchanged.
 
         As in the reference: the encoder runs once; every step runs the WHOLE decoder over the whole prefix (under the
         inverted mask of W:416-418 appending a token changes every earlier position's state from layer 1 up, so there is
         no valid KV cache) and appends argmax(lm_head(decoder_out)[:, -1, :]) to every row; the loop stops when every
         row's token of the same step is EOS, or after ``max_length`` steps.  Temperature and top-k do not change an argmax;
         the other options are accepted and ignored (W:643-648).  Fixed against the reference: the logits come from the LM
-        head (W:675 reads a key WhisperModel does not return), ``num_beams > 1`` raises instead of leaving ``next_tokens``
-        unbound, ``max_length`` above max_target_positions raises up front instead of overrunning the positional table
-        (W:383).  ``eos_token_id`` (not in the reference's signature): overrides config.eos_token_id; -1 disables the stop.
+        head (W:675 reads a key WhisperModel does not return), ``max_length`` above max_target_positions raises up front
+        instead of overrunning the positional table (W:383).  ``eos_token_id`` (not in the reference's signature):
+        overrides config.eos_token_id; -1 disables the stop.
 
         Per step: the embedding of [start, tokens so far] (tmi_embed_fwd), the decoder over the prefix, and
         tmi_lm_head_argmax on the B last rows (final LayerNorm, LM head and argmax in one launch).  The EOS count of a step
         is read one step late (``greedy_loop``), so the device never idles on the host's check."""
         cfg = self.config
+        if num_beams is not None and int(num_beams) > 1:  # (ahead of check_generate_args: it still raises for num_beams > 1)
+            max_length = check_beam_args(cfg, max_length, num_beams, temperature, length_penalty, num_return_sequences)
+            eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+            return self._generate_beam(input_features, max_length, int(num_beams), float(temperature), eos,
+                                       float(length_penalty), bool(early_stopping), int(num_return_sequences),
+                                       bool(return_dict_in_generate))
         max_length = check_generate_args(cfg, max_length, num_beams, temperature)
         features = self._check_features(input_features)
         B = features.shape[0]
@@ -993,6 +1029,82 @@ class WhisperForConditionalGeneration(KernelBlocks):
         torch.cuda.current_stream(dev).synchronize()
         return ids[:, :1 + n].clone()
 
+    def _generate_beam(self, features, max_length, K, temperature, eos, length_penalty, early_stopping, R, return_dict):
+        """Beam search; the rule is the module docstring's "Beam search".  The encoder and the cross-attention k|v run once
+        on the B items, the k|v rows are then repeated for the K beams of each item; every step runs the decoder over the
+        B*K prefixes, tmi_lm_head_topk (N = 2K candidates per row: final LayerNorm, LM head, log-softmax and top-N in one
+        launch) and tmi_beam_step (one workgroup per item: the walk, the pool, the next prefixes in a second buffer, the
+        done flags and count).  The done count is read one step late (``greedy_loop``); the only other host work is
+        queueing.  Finalize (the live beams of the items not done, offered to the pools) is a mode of tmi_beam_step."""
+        cfg = self.config
+        features = self._check_features(features)
+        B, dev = features.shape[0], self.device
+        BK, N, L1, V = B * K, 2 * K, 1 + max_length, cfg.vocab_size
+        start, pad = cfg.decoder_start_token_id, cfg.pad_token_id
+        if max_length == 0:
+            seq = torch.full((B * R, 1), start, dtype=torch.int32, device=dev)
+            zeros = torch.zeros(B * R, device=dev)
+            return {"sequences": seq, "sequences_scores": zeros, "lengths": zeros.int()} if return_dict else seq
+        inf = self._infer_prepare(B, features.shape[2], K)
+        i32 = dict(dtype=torch.int32, device=dev)
+        prefix = torch.full((2, BK, L1), start, **i32)  # double-buffered prefixes; every entry a valid token id
+        sums = torch.zeros(B, K, device=dev)
+        sums[:, 1:] = float("-inf")
+        sums = sums.view(BK)
+        pool_ids = torch.full((B, K, L1), pad, **i32)
+        pool_scores = torch.zeros(B, K, device=dev)
+        pool_len = torch.zeros(B, K, **i32)
+        pool_cnt, done, n_done = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(1, **i32)
+        cand_ids, cand_lp = torch.empty(BK, N, **i32), torch.empty(BK, N, device=dev)
+        host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
+        events = [torch.cuda.Event(), torch.cuda.Event()]
+        len_pow = lambda n: float(np.float32(float(n) ** length_penalty))  # noqa: E731
+        saved = self._infer_begin(inf)
+        try:
+            ws, d, T = self.ws, cfg.d_model, inf["T"]
+            enc_out = self._encode_infer(features, inf)
+            self._cross_kv_infer(enc_out)
+            if cfg.decoder_layers:  # item b's k|v rows [b*T, (b+1)*T) -> the row blocks of b*K .. b*K + K - 1, from the back
+                kv = ws["kvc_all"].view(BK, T, -1)
+                for b in range(B - 1, -1, -1):
+                    kv[b * K + (1 if b == 0 else 0):(b + 1) * K].copy_(kv[b:b + 1].expand(K - (1 if b == 0 else 0), -1, -1))
+            lab_flat = ws["labels"]
+            wl, ldw = self.W("lm_head.kernel")
+            gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
+            main = self._main or torch.cuda.current_stream(dev)
+
+            def step(t):
+                cur, nxt = prefix[t & 1], prefix[(t + 1) & 1]
+                lab = lab_flat[:BK * t].view(BK, t)
+                if t > 1:
+                    lab[:, :t - 1].copy_(cur[:, 1:t])
+                h = self._decode_infer(lab, BK, t, T)
+                ops.lm_head_topk(h[t - 1:], t * d, wl, ldw, BK, d, V, N, cand_ids, cand_lp, ws["topk_ws"], gamma=gamma,
+                                 beta=beta, eps=cfg.layer_norm_eps, temperature=temperature)
+                ops.beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, L1, t, eos, len_pow(t), early_stopping, pool_ids,
+                              pool_scores, pool_len, pool_cnt, done, n_done)
+                host[t:t + 1].copy_(n_done, non_blocking=True)
+                events[t & 1].record(main)
+
+            def read_done(t):
+                events[t & 1].synchronize()
+                return int(host[t])
+
+            n = greedy_loop(max_length, B, step, read_done if eos >= 0 else None)
+            ops.beam_step(None, None, N, B, K, sums, prefix[(n + 1) & 1], None, L1, n, eos, len_pow(n), early_stopping,
+                          pool_ids, pool_scores, pool_len, pool_cnt, done, n_done, finalize=True)
+        finally:
+            self._infer_end(saved)
+        lengths = pool_len[:, :R].reshape(B * R)
+        n_out = int(lengths.max())
+        seq = pool_ids[:, :R, :1 + n_out].reshape(B * R, 1 + n_out)
+        seq = torch.where(torch.arange(1 + n_out, device=dev)[None, :] > lengths[:, None], pad, seq)
+        if return_dict:
+            return {"sequences": seq, "sequences_scores": pool_scores[:, :R].reshape(B * R).clone(),
+                    "lengths": lengths.clone()}
+        return seq
+
+
 def create_whisper_model(model_type: str = "small", device="cuda:0", precision: str = "bf16", seed: int = 1234,
                          **overrides) -> WhisperForConditionalGeneration:
     """W:852-890."""
@@ -1012,6 +1124,30 @@ def check_generate_args(cfg: WhisperConfig, max_length=None, num_beams=None, tem
         raise ValueError("beam search is not implemented (the reference leaves it unimplemented too)")
     if temperature is not None and not float(temperature) > 0.0:
         raise ValueError("temperature must be > 0")
+    return max_length
+
+
+def check_beam_args(cfg: WhisperConfig, max_length=None, num_beams=2, temperature=1.0, length_penalty=1.0,
+                    num_return_sequences=1) -> int:
+    """The arguments of beam search -> max_length: 2 <= num_beams <= 8 (tmi_lm_head_topk keeps 2K <= 16 candidates a
+    row), 1 <= num_return_sequences <= num_beams, generate's max_length and temperature bounds, and a finite
+    length_penalty whose n ** length_penalty is a finite, nonzero fp32 value for every length n <= max_length (the
+    scores are divided by it), so that a bad value fails here and not after the encoder has run."""
+    K = int(num_beams)
+    if not 2 <= K <= 8:
+        raise ValueError("num_beams must be in [2, 8] for beam search (1 or None: greedy)")
+    if not 1 <= int(num_return_sequences) <= K:
+        raise ValueError("num_return_sequences must be in [1, num_beams]")
+    max_length = check_generate_args(cfg, max_length, None, temperature)
+    lp = float(length_penalty)
+    if not math.isfinite(lp):
+        raise ValueError("length_penalty must be finite")
+    try:  # (n ** lp is monotone in n: its extremes are at n = 1, which gives 1, and at n = max_length)
+        edge = float(max(1, max_length)) ** lp
+    except OverflowError:
+        edge = math.inf
+    if not 0.0 < edge < float(np.finfo(np.float32).max) or np.float32(edge) == 0:
+        raise ValueError(f"length_penalty {lp}: max_length ** length_penalty is not a finite, nonzero fp32 value")
     return max_length
 
 
@@ -1062,11 +1198,12 @@ def dummy_waveform(seed: int = DUMMY_AUDIO_SEED) -> np.ndarray:
     return np.random.RandomState(seed).randn(16000 * 30).astype(np.float32)
 
 
-def transcribe_audio(model, audio=None, tokenizer=None, max_length=448):
+def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beams=1, length_penalty=1.0):
     """W:962-986: waveform -> log-mel (frontend.LogMelFrontend, channels-first: the layout the encoder reads; the reference
     feeds [frames, 80] un-transposed) -> ``model.generate`` -> ``tokenizer.decode(ids)``, or the ids
     (int32 numpy array, start token first) without a tokenizer.  ``audio``: a waveform (1-D tensor or array, 16 kHz), a
-    ``.wav`` path, or None for the reference's 30 s dummy clip (seeded)."""
+    ``.wav`` path, or None for the reference's 30 s dummy clip (seeded).  ``num_beams`` > 1: beam search (the best
+    hypothesis), with ``length_penalty``."""
     from .frontend import LogMelFrontend
     if audio is None:
         wav = dummy_waveform()
@@ -1079,7 +1216,11 @@ def transcribe_audio(model, audio=None, tokenizer=None, max_length=448):
     if fe is None:
         fe = model._frontend = LogMelFrontend(device=model.device, n_mels=model.config.n_mels)
     feats = fe(wav)
-    ids = model.generate(feats, max_length=max_length)[0].cpu().numpy()
+    if num_beams is not None and int(num_beams) > 1:
+        ids = model.generate(feats, max_length=max_length, num_beams=num_beams, length_penalty=length_penalty)
+    else:
+        ids = model.generate(feats, max_length=max_length)
+    ids = ids[0].cpu().numpy()
     if tokenizer is not None:
         return tokenizer.decode(ids)
     return ids

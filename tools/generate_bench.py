@@ -4,7 +4,10 @@ per-step mean, tokens / s, and tmi_lm_head_argmax alone at M = 8 (d 768 and 1280
 GB/s of weight stream (device time: launches captured in a graph and replayed) beside the per-call time from Python.
 bench.py measures training and stays as it is; this is the inference counterpart.
 
-usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2]"""
+--num_beams K > 1: beam search (B*K decoder rows, EOS disabled so that all steps run), and tmi_lm_head_topk (N = 2K)
+against tmi_lm_head_argmax at equal M (8 and 40, d 768 and 1280), both measured in this run, with their time ratio.
+
+usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2] [--num_beams 1]"""
 import argparse
 import json
 import os
@@ -30,15 +33,23 @@ def timed_us(fn, iters=50, warm=5):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
-def argmax_alone(dev, d, M=8, V=51865, Vp=51904):
+def argmax_alone(dev, d, M=8, V=51865, Vp=51904, topk_n=0):
+    """tmi_lm_head_argmax (topk_n = 0) or tmi_lm_head_topk with N = topk_n, alone on M rows."""
     g = torch.Generator(device=dev).manual_seed(d)
     x = torch.randn(M, d, device=dev, generator=g).to(torch.bfloat16)
     w = (torch.randn(d, Vp, device=dev, generator=g) * 0.03).to(torch.bfloat16)
     gamma, beta = torch.ones(d, device=dev), torch.zeros(d, device=dev)
-    ids = torch.empty(M, dtype=torch.int32, device=dev)
-    cnt = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.zeros(M + 1, dtype=torch.int64, device=dev)
-    call = lambda: ops.lm_head_argmax(x, d, w, Vp, M, d, V, ids, 1, ws, gamma=gamma, beta=beta, eos_id=2, eos_count=cnt)
+    if topk_n:
+        ids = torch.empty(M, topk_n, dtype=torch.int32, device=dev)
+        lp = torch.empty(M, topk_n, device=dev)
+        ws = torch.zeros(ops.lm_head_topk_workspace_elems(M, V, topk_n), dtype=torch.int64, device=dev)
+        call = lambda: ops.lm_head_topk(x, d, w, Vp, M, d, V, topk_n, ids, lp, ws, gamma=gamma, beta=beta)  # noqa: E731
+    else:
+        ids = torch.empty(M, dtype=torch.int32, device=dev)
+        cnt = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+        call = lambda: ops.lm_head_argmax(x, d, w, Vp, M, d, V, ids, 1, ws, gamma=gamma, beta=beta, eos_id=2,  # noqa: E731
+                                          eos_count=cnt)
     eager = timed_us(call)  # per call from Python: host-bound (ctypes + wrapper) at this size
     # device time: n back-to-back launches captured once and replayed (no host in between)
     n = 20
@@ -57,14 +68,17 @@ def main():
     ap.add_argument("--steps", type=int, default=448)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--num_beams", type=int, default=1)
     args = ap.parse_args()
+    K = args.num_beams
+    beam = dict(num_beams=K) if K > 1 else {}
     dev = "cuda:0"
     model = whisper.create_whisper_model("small", device=dev, precision="bf16")
     B = args.batch
     feats = torch.randn(B, 80, 3000, generator=torch.Generator().manual_seed(0))
     feats_d = feats.to(dev)
     # encoder alone (the first part of every generate call), through the same inference path
-    inf = model._infer_prepare(B, 3000)
+    inf = model._infer_prepare(B, 3000, K)
 
     def encode():
         saved = model._infer_begin(inf)
@@ -73,21 +87,31 @@ def main():
         finally:
             model._infer_end(saved)
     enc_ms = timed_us(encode, iters=10, warm=2) / 1e3
-    model.generate(feats_d, max_length=4, eos_token_id=-1)  # warm-up: workspace, kernels
+    model.generate(feats_d, max_length=4, eos_token_id=-1, **beam)  # warm-up: workspace, kernels
     torch.cuda.synchronize()
     best = None
     for _ in range(args.reps):
         t0 = time.perf_counter()
-        ids = model.generate(feats_d, max_length=args.steps, eos_token_id=-1)
+        ids = model.generate(feats_d, max_length=args.steps, eos_token_id=-1, **beam)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         best = dt if best is None else min(best, dt)
     assert tuple(ids.shape) == (B, 1 + args.steps), ids.shape
     decode_s = best - enc_ms / 1e3
-    out = {"workload": "whisper_small_generate", "batch": B, "steps": args.steps, "precision": "bf16",
-           "encoder_ms": round(enc_ms, 3), "generate_s": round(best, 4), "decode_s": round(decode_s, 4),
-           "per_step_ms": round(decode_s * 1e3 / args.steps, 3), "tokens_per_s": round(B * args.steps / best, 1),
-           "lm_head_argmax_M8": {"d768": argmax_alone(dev, 768), "d1280": argmax_alone(dev, 1280)}}
+    out = {"workload": "whisper_small_generate" + ("_beam" if K > 1 else ""), "batch": B, "steps": args.steps,
+           "precision": "bf16", "encoder_ms": round(enc_ms, 3), "generate_s": round(best, 4), "decode_s": round(decode_s, 4),
+           "per_step_ms": round(decode_s * 1e3 / args.steps, 3), "tokens_per_s": round(B * args.steps / best, 1)}
+    if K > 1:
+        out["num_beams"] = K
+        out["decoder_rows"] = B * K
+        head = {}
+        for M in (8, 40):
+            for d in (768, 1280):
+                am, tk = argmax_alone(dev, d, M), argmax_alone(dev, d, M, topk_n=2 * K)
+                head[f"M{M}_d{d}"] = {"argmax": am, f"topk_N{2 * K}": tk, "topk_over_argmax": round(tk["us"] / am["us"], 3)}
+        out["lm_head_topk_vs_argmax"] = head
+    else:
+        out["lm_head_argmax_M8"] = {"d768": argmax_alone(dev, 768), "d1280": argmax_alone(dev, 1280)}
     print(json.dumps(out), flush=True)
 
 
