@@ -132,7 +132,6 @@ SIGNATURES = {
     "tmi_segment_sumsq_chunks": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "tmi_segment_clip": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_vp]),
     "tmi_loss_combine": (c_i32, [c_vp, c_vp, c_f32, c_f32, c_vp, c_vp]),
-    "tmi_debug_gemm_stamps": (c_i32, [c_vp]),
     "tmi_lm_head_argmax": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp,
                                    c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "tmi_lm_head_topk": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32,
@@ -141,7 +140,7 @@ SIGNATURES = {
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
 }
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 _lib = None
 
 

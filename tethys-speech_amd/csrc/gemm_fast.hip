@@ -1,19 +1,24 @@
-// Fast bf16 GEMM path of tmi_gemm (gfx950).  One kernel template covers the three layouts
-// that carry the step's FLOPs; each operand is independently
+// Fast GEMM path of tmi_gemm (gfx950).  The bf16 kernels cover the three layouts that carry the step's FLOPs; each
+// operand is independently
 //   KC  k-contiguous rows   (A[m][k] / Bt[n][k]):  LDS image [128 rows][8 x 16 B], fragments by
 //       ds_read_b128, swizzle phys_chunk = chunk ^ ((row >> 1) & 7)
 //   KS  k-strided           (A[k][m] / B[k][n]):   LDS image [64 k][16 x 16 B], fragments by
 //       ds_read_b64_tr_b16 (hardware transpose of a 4(k) x 16(col) block), swizzle
 //       phys_chunk = chunk ^ ((k & 3) << 2)
 // forward X·W = (KC, KS) straight from the natural Keras [in,out] kernel; dgrad dY·Wᵀ = (KC, KC);
-// wgrad Xᵀ·dY = (KS, KS).  Two tile configurations (MFMA 32x32x16 bf16, BK = 64): 256x256 per
-// 512-thread workgroup, 8 waves as 2x4, each wave 128x64 (128 accumulator registers) — twice
-// the MFMA work per staged byte and per LDS-DMA instruction issued — and 128x128 per 256-thread
-// workgroup (waves 2x2 of 64x64, two workgroups per CU) for narrow / small problems.  Tiles are
-// staged global -> LDS directly (global_load_lds_dwordx4), double-buffered: the next K-tile's
-// DMA is in flight under the current tile's MFMAs, one barrier per K-tile.
-// The LDS image is lane-linear as the DMA requires; the swizzle is applied to the per-lane
-// SOURCE address and again on the read.
+// wgrad Xᵀ·dY = (KS, KS).  MFMA 32x32x16 bf16, K-tiles of 64.  The kernels this file ships:
+//   gemm_fast_kernel, 2-stage tiles: 128x128 (256 threads, 32x64 per wave, two workgroups per CU) and 256x256 (1024
+//       threads, 64x64 per wave, one workgroup per CU): the next K-tile's DMA is in flight under the current tile's
+//       MFMAs, one barrier per K-tile;
+//   gemm_fast_kernel, the 64x64 family for grids that cannot fill the chip with 128x128 tiles: two waves of 32x64;
+//       four waves of 32x32 with a 2- or 4-stage ring; two K-groups of four waves with 4- or 2-stage rings (see the
+//       Tile structs);
+//   gemm_p8_kernel, the eight-phase kernel: 256x256 or 192x256 per 512-thread workgroup, counted waits, one workgroup per
+//       tile or persistent (256 workgroups walk the tiles, the K-tile ring runs on from one tile into the next);
+//   gemm_f32_kernel, fp32 operands (the parity mode): 128x128, the bf16 staging on 32-float K slabs;
+//   splitk_reduce_kernel: sums the workspace slabs of a split-K launch into C.
+// Tiles are staged global -> LDS directly (global_load_lds_dwordx4).  The LDS image is lane-linear as the DMA
+// requires; the swizzle is applied to the per-lane SOURCE address and again on the read.
 // Epilogue: accumulators go through LDS (fp32, per-wave 64x64) and leave as whole 16-byte
 // row segments — bias/scale/accumulate/GELU/GELU'/residual are applied on 8-column chunks
 // with 16-byte loads and stores (a 2-byte-per-lane store tail is store-issue-bound).
@@ -45,15 +50,6 @@ __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
                : "memory");
 }
 
-// Diagnostic switches of the kernels below (in-kernel stamps, "skip the epilogue / the stores" ablations, TMI_GEMM_DBG): the
-// shipped library compiles them out - TMI_DBG(P) is the constant 0 and every `if (TMI_DBG(P) & ...)` folds away; a build with
-// make EXPERIMENTS=1 (-DTMI_GEMM_EXPERIMENTS) reads the field (tools/p8_stamps.py, tools/gemm_epi_probe.py need that build).
-#ifdef TMI_GEMM_EXPERIMENTS
-#define TMI_DBG(P) ((P).dbg)
-#else
-#define TMI_DBG(P) 0
-#endif
-
 struct FastParams {
   tmi_gemm_desc d;
   int tiles_m, tiles_n, ktiles;
@@ -63,7 +59,6 @@ struct FastParams {
   int wide;          // epilogue may use 16-byte accesses on C / aux / resid
   int64_t a_cols_rd; // KS operands: readable column count (multiple of 8)
   int64_t b_cols_rd;
-  int dbg;           // TMI_GEMM_DBG (diagnostics only; read through TMI_DBG: a constant 0 unless built with -DTMI_GEMM_EXPERIMENTS)
   uint32_t drop_thr, drop_key;  // epilogue dropout (desc.dropout_p): threshold (0 = off) and stream key
   float drop_scale;
   int64_t split_c_stride;  // != 0: split s stores (no atomics) to C + s * split_c_stride (workspace slabs)
@@ -78,8 +73,7 @@ struct FastParams {
 constexpr int EPI_GENERIC = 0, EPI_SIMPLE = 1 /* bias, scale, GELU + saved pre-activation */, EPI_AUXIN = 2 /* x GELU'(aux_in) */,
               EPI_RESID = 3 /* bias, [saved pre-activation, GELU,] dropout, + residual */, EPI_ACC = 4 /* C += */;
 inline int epi_class(const tmi_gemm_desc& d, bool wide) {
-  static const int off = [] { const char* e = getenv("TMI_GEMM_LEAN_EPI"); return e && atoi(e) == 0; }();
-  if (off || !wide || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15 || d.bias_sb % 4))) return EPI_GENERIC;
+  if (!wide || (d.bias && (reinterpret_cast<uintptr_t>(d.bias) & 15 || d.bias_sb % 4))) return EPI_GENERIC;
   const bool drop = d.dropout_p > 0.f;
   if (d.accumulate) return (!d.aux_in && !d.resid && !d.act && !d.aux_out && !drop && d.scale_cols <= 0) ? EPI_ACC : EPI_GENERIC;
   if (d.aux_in) return (!d.resid && !d.act && !d.aux_out && !drop && d.scale_cols <= 0) ? EPI_AUXIN : EPI_GENERIC;
@@ -93,13 +87,11 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
-// ---- KC staging: ROWS rows x 64 k (128 B per row); wave-instruction j covers rows 8j..8j+7
-// EM(src, i, j): what to do with wave-instruction j (the i-th of this wave) whose lane reads 16 B
-// at src: either issue the LDS-DMA to lds + j*1024 or load it into a register for a later
-// ds_write_b128 to lds + j*1024 + lane*16 (the same lane-linear image).
-template <int ROWS, int NW, typename EM>
+// ---- KC staging: ROWS rows x 64 k (128 B per row); wave-instruction j covers rows 8j..8j+7 and lands, by LDS-DMA, at
+// lds + j*1024 (each lane reads 16 B)
+template <int ROWS, int NW>
 __device__ __forceinline__ void stage_kc(const bf16_t* base, int64_t s_row, int64_t row0, int64_t nrows,
-                                         int64_t k0, int wave, int lane, EM em) {
+                                         int64_t k0, int wave, int lane, char* lds) {
   constexpr int PER = ROWS / 8 / NW;
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
@@ -108,7 +100,7 @@ __device__ __forceinline__ void stage_kc(const bf16_t* base, int64_t s_row, int6
     const int c = (lane & 7) ^ ((r >> 1) & 7);
     int64_t grow = row0 + r;
     grow = grow < nrows ? grow : nrows - 1;
-    em(base + grow * s_row + k0 + c * 8, i, j);
+    glds16(base + grow * s_row + k0 + c * 8, lds + j * 1024);
   }
 }
 
@@ -116,9 +108,9 @@ __device__ __forceinline__ void stage_kc(const bf16_t* base, int64_t s_row, int6
 // wave-instruction j covers k-rows 4(j%16)..+3 of sub-image j/16
 // (COLS == 64: one [64 k-rows][64 cols] image, 128 B per row; wave-instruction j covers k-rows
 //  8j..8j+7, swizzle phys = chunk ^ (((k >> 1) & 1) << 2) — conflict-free for the transposed reads)
-template <int COLS, int NW, typename EM>
+template <int COLS, int NW>
 __device__ __forceinline__ void stage_ks(const bf16_t* base, int64_t s_k, int64_t col0, int64_t ncols_rd,
-                                         int64_t k0, int64_t kend, int wave, int lane, EM em) {
+                                         int64_t k0, int64_t kend, int wave, int lane, char* lds) {
   if constexpr (COLS == 64) {
     constexpr int PER64 = 8 / NW;
 #pragma unroll
@@ -130,7 +122,7 @@ __device__ __forceinline__ void stage_ks(const bf16_t* base, int64_t s_k, int64_
       gk = gk < kend ? gk : kend - 1;
       int64_t gc = col0 + c * 8;
       gc = gc + 8 <= ncols_rd ? gc : ncols_rd - 8;
-      em(base + gk * s_k + gc, i, j);
+      glds16(base + gk * s_k + gc, lds + j * 1024);
     }
     return;
   }
@@ -145,7 +137,7 @@ __device__ __forceinline__ void stage_ks(const bf16_t* base, int64_t s_k, int64_
     gk = gk < kend ? gk : kend - 1;
     int64_t gc = col0 + sub * 128 + c * 8;
     gc = gc + 8 <= ncols_rd ? gc : ncols_rd - 8;
-    em(base + gk * s_k + gc, i, j);
+    glds16(base + gk * s_k + gc, lds + j * 1024);
   }
 }
 
@@ -277,15 +269,6 @@ template <> struct Vec8<bf16_t> {
   }
 };
 
-__device__ unsigned long long g_gemm_stamps[8];  // diagnostics (ABL == 8): cycles per loop phase, block 0 wave 0
-
-__device__ __forceinline__ unsigned long long stamp() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-__device__ unsigned long long g_epi_stamps[8];   // diagnostics (TMI_GEMM_DBG & 32): inside wide_epilogue, block 8 wave 0, first piece
-
 // Staging image of one 32x64 fp32 piece: 32 rows of 256 B; the 16-byte chunk c (four columns) of row r lives at
 // r * 256 + ((c ^ (r & 7)) << 4).  Conflict-free both ways: the accumulator layout writes one chunk per lane with eight
 // consecutive rows per ds_write_b128 lane group (the XOR spreads them over the 32 banks), the row-major read-back
@@ -389,9 +372,6 @@ __device__ __forceinline__ void wide_epilogue(const FastParams& P, const f32x16&
                                               int64_t mw, int64_t nw, int64_t bz, int lane, bool atomic) {
   asm volatile("" : "+v"(lane));  // (opaque: see lean_rows)
   const tmi_gemm_desc& d = P.d;
-  const bool st = (TMI_DBG(P) & 32) && blockIdx.x == 8 && threadIdx.x < 64;
-  unsigned long long e0 = 0, e1 = 0, e2 = 0, e3 = 0;
-  if (st) e0 = stamp();
   {
     const int m = lane & 31, h = lane >> 5, sw = m & 7;
     char* Er = E + m * 256;
@@ -401,16 +381,11 @@ __device__ __forceinline__ void wide_epilogue(const FastParams& P, const f32x16&
       *reinterpret_cast<f32x4*>(Er + (((8 + 2 * q + h) ^ sw) << 4)) = f32x4{a1[4 * q], a1[4 * q + 1], a1[4 * q + 2], a1[4 * q + 3]};
     }
   }
-  if (st) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); e1 = stamp(); }
-  if (P.epi != EPI_GENERIC && !atomic && mw + 32 <= d.M && nw + 64 <= d.N && !(TMI_DBG(P) & 8)) {  // (uniform over the wave)
+  if (P.epi != EPI_GENERIC && !atomic && mw + 32 <= d.M && nw + 64 <= d.N) {  // (uniform over the wave)
     if (P.epi == EPI_SIMPLE) lean_rows<TC, EPI_SIMPLE, AHEAD>(P, E, mw, nw, bz, lane);
     else if (P.epi == EPI_AUXIN) lean_rows<TC, EPI_AUXIN, AHEAD>(P, E, mw, nw, bz, lane);
     else if (P.epi == EPI_RESID) lean_rows<TC, EPI_RESID, AHEAD>(P, E, mw, nw, bz, lane);
     else lean_rows<TC, EPI_ACC, AHEAD>(P, E, mw, nw, bz, lane);
-    if (st) {
-      e3 = stamp();
-      if (lane == 0 && g_epi_stamps[7] == 0) { g_epi_stamps[0] = e1 - e0; g_epi_stamps[1] = 0; g_epi_stamps[2] = e3 - e1; g_epi_stamps[7] = 1; }
-    }
     return;
   }
   TC* C = reinterpret_cast<TC*>(d.C) + bz * d.c_sb + (int64_t)blockIdx.y * P.split_c_stride;
@@ -440,7 +415,6 @@ __device__ __forceinline__ void wide_epilogue(const FastParams& P, const f32x16&
   // this lane's two chunks of row 8 p + rsub: (row & 7) == rsub for every pass, so the passes differ by an immediate
   const char* Elo = E + rsub * 256 + (((2 * chunk) ^ rsub) << 4);
   const char* Ehi = E + rsub * 256 + (((2 * chunk + 1) ^ rsub) << 4);
-  if (st) e2 = stamp();
   if (full) {  // (edge pieces and launches outside the lean classes: one pass at a time, every feature tested)
 #pragma unroll 1
     for (int p = 0; p < 4; ++p) {
@@ -459,7 +433,7 @@ __device__ __forceinline__ void wide_epilogue(const FastParams& P, const f32x16&
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] += t[i];
       }
-      if (aux_out && !(TMI_DBG(P) & 8)) Vec8<TC>::store(aux_out + idx, v);
+      if (aux_out) Vec8<TC>::store(aux_out + idx, v);
       if (d.act == 1) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] = gelu_fwd_t<TC>(v[i]);
@@ -475,12 +449,7 @@ __device__ __forceinline__ void wide_epilogue(const FastParams& P, const f32x16&
 #pragma unroll
         for (int i = 0; i < 8; ++i) v[i] += t[i];
       }
-      if (TMI_DBG(P) & 8) { asm volatile("" ::"v"(v[0]), "v"(v[3]), "v"(v[7])); continue; }  // diagnostics: everything but the store
       Vec8<TC>::store(C + idx, v);
-    }
-    if (st) {
-      e3 = stamp();
-      if (lane == 0 && g_epi_stamps[7] == 0) { g_epi_stamps[0] = e1 - e0; g_epi_stamps[1] = e2 - e1; g_epi_stamps[2] = e3 - e2; g_epi_stamps[7] = 1; }
     }
     return;
   }
@@ -603,61 +572,40 @@ __device__ __forceinline__ void wide_epilogue32(const FastParams& P, const f32x1
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// CFG 0: 128x128 tile, 4 waves (2x2) of 64x64, 2 stages (64 KiB, two workgroups per CU)
-// CFG 1: 256x256 tile, 8 waves (2x4) of 128x64, 2 stages (128 KiB, one workgroup per CU): twice
-//        the MFMA work per staged byte and per LDS-DMA instruction a wave has to issue
-// SPEC (wave specialisation): the workgroup carries as many LOADER waves as consumer waves; the
-//        loaders only issue the LDS-DMA of the next K-tile, the consumers only read fragments
-//        and issue MFMAs, so no wave serialises ~100-cycle DMA issues with its MFMA stream
-// CFG 2: CFG 0's tile with 4 loader + 4 consumer waves
-// CFG 3: 256x128 tile, 4 consumer waves (2x2) of 128x64 + 4 loader waves (one of each per SIMD)
-template <int CFG> struct Cfg;
-template <> struct Cfg<0> { static constexpr int BM = 128, BN = 128, WM = 64, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-template <> struct Cfg<1> { static constexpr int BM = 256, BN = 256, WM = 128, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-template <> struct Cfg<2> { static constexpr int BM = 128, BN = 128, WM = 64, WN = 64, NSTAGE = 2; static constexpr bool SPEC = true; };
-template <> struct Cfg<3> { static constexpr int BM = 256, BN = 128, WM = 128, WN = 64, NSTAGE = 2; static constexpr bool SPEC = true; };
-// CFG 4 / 5: the same tiles with twice the waves (32x64 resp. 64x64 per wave): half the LDS-DMA
-// instructions per wave per K-tile, so their ~100-cycle issue cost stops dominating each wave's loop
-template <> struct Cfg<4> { static constexpr int BM = 128, BN = 128, WM = 32, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-template <> struct Cfg<5> { static constexpr int BM = 256, BN = 256, WM = 64, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-// CFG 6: 64x64 tile, 2 waves of 32x64 (32 KiB of LDS: several workgroups per CU).  For problems
+// Tile configurations of gemm_fast_kernel: BM x BN per workgroup, WM x WN per wave, NSTAGE LDS stages per K-group, KG
+// K-groups of (BM / WM) * (BN / WN) waves.
+// The 2-stage 128x128 and 256x256 tiles with 32x64 resp. 64x64 per wave (eight resp. sixteen waves): half the LDS-DMA
+// instructions per wave per K-tile of the 64x64 / 128x64-per-wave forms they replaced, so the ~100-cycle issue cost of
+// those instructions stops dominating each wave's loop.  256x256 (128 KiB, one workgroup per CU) does twice the MFMA
+// work per staged byte of 128x128 (64 KiB, two workgroups per CU).
+struct Tile128x128 { static constexpr int BM = 128, BN = 128, WM = 32, WN = 64, NSTAGE = 2, KG = 1; };
+struct Tile256x256 { static constexpr int BM = 256, BN = 256, WM = 64, WN = 64, NSTAGE = 2, KG = 1; };
+// 64x64 tile, 2 waves of 32x64 (32 KiB of LDS: several workgroups per CU).  For problems
 // with few 128x128 tiles (decoder / Wav2Vec2 encoder, M = B*100): a CU stages operands at
 // ~45 GB/s whatever the tile, so the time of such a GEMM is (BM + BN) * K * 2 B per workgroup
 // over that rate — smaller tiles on more CUs finish sooner.
-template <> struct Cfg<6> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-// CFG 7 / 8 / 9: tiles of CFG 4 / 5 / 6 with REGISTER staging (global_load_dwordx4 -> VGPR ->
-// ds_write_b128 into the same image): an LDS-DMA wave-instruction occupies the CU's memory
-// pipeline for ~55 cycles per KiB (measured with in-kernel stamps), which bounds a 128x128 tile
-// at ~0.8 PF/s; plain 16-byte loads issue several times faster
-template <> struct Cfg<7> { static constexpr int BM = 128, BN = 128, WM = 32, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-template <> struct Cfg<8> { static constexpr int BM = 256, BN = 256, WM = 64, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-template <> struct Cfg<9> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 64, NSTAGE = 2; static constexpr bool SPEC = false; };
-// CFG 10: CFG 6 with a 4-stage ring and counted vmcnt.  Only when the grid is at most one workgroup
-// per CU (64 KiB of LDS each: co-resident 2-stage workgroups hide latency better when there are
-// enough of them — M800 N3072 K3072: 40 us on CFG 6, 61 us on CFG 10) and K is long (M800 N768 K3072
-// with a k-strided B: 36 -> 30 us).
-template <> struct Cfg<10> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 64, NSTAGE = 4; static constexpr bool SPEC = false; };
-// CFG 11: the 64x64 tile on FOUR waves of 32x32 (all four SIMDs of the CU, half the fragment-read + MFMA
-// chain per K-tile per wave): for grids of at most ~one workgroup per CU, where the K loop of CFG 6 is a
-// latency chain on two SIMDs.  Never split (its epilogue has no atomic form).
-template <> struct Cfg<11> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 2; static constexpr bool SPEC = false; };
-// CFG 12: CFG 11 with the 4-stage ring of CFG 10
-template <> struct Cfg<12> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 4; static constexpr bool SPEC = false; };
-// CFG 13: CFG 12's tile with the K loop dealt over KG = 2 groups of four waves INSIDE the workgroup (group g multiplies
+struct Tile64Waves2 { static constexpr int BM = 64, BN = 64, WM = 32, WN = 64, NSTAGE = 2, KG = 1; };
+// The 64x64 tile on FOUR waves of 32x32 (all four SIMDs of the CU, half the fragment-read + MFMA chain per K-tile per
+// wave): for grids of at most ~one workgroup per CU, where the K loop of Tile64Waves2 is a latency chain on two SIMDs.
+// Never split (its epilogue has no atomic form).
+struct Tile64Waves4 { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 2, KG = 1; };
+// The same with a 4-stage ring and counted vmcnt.  Only when the grid is at most one workgroup per CU (64 KiB of LDS
+// each: co-resident 2-stage workgroups hide latency better when there are enough of them) and K is long.
+struct Tile64Waves4Ring4 { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 4, KG = 1; };
+// Tile64Waves4Ring4 with the K loop dealt over KG = 2 groups of four waves INSIDE the workgroup (group g multiplies
 // K-tiles g, g + KG, ...; each group has its own 4-stage LDS-DMA ring, 128 KiB in all; the partial accumulators meet in
-// LDS before the epilogue).  On grids of at most one workgroup per CU the K loop of CFG 12 is a dependent chain per K-tile
-// and wave (barrier -> DMA issue -> fragment reads -> four dependent MFMAs: ~0.4 us per 64-deep K-tile whatever feeds LDS:
-// an 8-stage DMA ring and a ring of registers filled by plain global loads with counted waits both measured level with the
-// 4-stage DMA ring); a second wave per SIMD on OTHER K-tiles overlaps those chains (0.24 us per K-tile; a third group adds
-// nothing: that is the CU's fill rate), and with the weights arriving from HBM, as they do in the step, the two rings'
-// six K-tiles in flight matter more still (M 800, N 768, K 768, cold weights: 13.5 us on CFG 11, 9.4 on CFG 12, 8.9 here).
-// K % 64 == 0 only (no tail zeroing).
-template <> struct Cfg<13> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 4; static constexpr bool SPEC = false; };
-// CFG 14: CFG 13's two K-groups on 2-stage rings (64 KiB: TWO workgroups per CU) - for 64x64 grids of more than one workgroup
-// per CU, where CFG 13's 128 KiB would run a second, nearly empty round (Whisper-large's decoder: [800, 1280] = 260 tiles).
-template <> struct Cfg<14> { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 2; static constexpr bool SPEC = false; };
-template <int CFG> constexpr int kKG = (CFG == 13 || CFG == 14) ? 2 : 1;
-template <int CFG> constexpr bool kRegStage = CFG >= 7 && CFG <= 9;
+// LDS before the epilogue).  On grids of at most one workgroup per CU the K loop of Tile64Waves4Ring4 is a dependent chain
+// per K-tile and wave (barrier -> DMA issue -> fragment reads -> four dependent MFMAs: ~0.4 us per 64-deep K-tile whatever
+// feeds LDS: an 8-stage DMA ring and a ring of registers filled by plain global loads with counted waits both measured
+// level with the 4-stage DMA ring); a second wave per SIMD on OTHER K-tiles overlaps those chains (0.24 us per K-tile; a
+// third group adds nothing: that is the CU's fill rate), and with the weights arriving from HBM, as they do in the step,
+// the two rings' six K-tiles in flight matter more still (M 800, N 768, K 768, cold weights: 13.5 us on Tile64Waves4,
+// 9.4 on Tile64Waves4Ring4, 8.9 here).  K % 64 == 0 only (no tail zeroing).
+struct Tile64KGroups2Ring4 { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 4, KG = 2; };
+// The two K-groups on 2-stage rings (64 KiB: TWO workgroups per CU) - for 64x64 grids of more than one workgroup per CU,
+// where the 128 KiB of Tile64KGroups2Ring4 would run a second, nearly empty round (Whisper-large's decoder: [800, 1280] =
+// 260 tiles).
+struct Tile64KGroups2Ring2 { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 2, KG = 2; };
 
 // Split-K through the workspace: every split runs the ordinary (non-atomic) epilogue into its own
 // fp32 slab [nbatch][M][N] of the caller's workspace, and splitk_reduce_kernel, launched right
@@ -699,12 +647,9 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
-// ABL (diagnostics, compile-time so the production loop is untouched): 2 = no MFMA/fragment reads,
-// 4 = no staging after the prologue
-template <typename TC, bool A_KS, bool B_KS, int CFG, int ABL = 0>
-__global__ __launch_bounds__((Cfg<CFG>::BM / Cfg<CFG>::WM) * (Cfg<CFG>::BN / Cfg<CFG>::WN) * (Cfg<CFG>::SPEC ? 128 : 64) * kKG<CFG>)
+template <typename TC, bool A_KS, bool B_KS, typename K>
+__global__ __launch_bounds__((K::BM / K::WM) * (K::BN / K::WN) * 64 * K::KG)
 void gemm_fast_kernel(const FastParams P) {
-  using K = Cfg<CFG>;
   constexpr int BM = K::BM, BN = K::BN, NSTAGE = K::NSTAGE;
   constexpr int WCOLS = BN / K::WN;           // waves along N
   constexpr int NW = (BM / K::WM) * WCOLS;
@@ -728,15 +673,12 @@ void gemm_fast_kernel(const FastParams P) {
   const int64_t m0 = (int64_t)tm * BM, n0 = (int64_t)tn * BN;
   const int64_t bz = blockIdx.z;
   const int lane = threadIdx.x & 63;
-  constexpr int KG = kKG<CFG>;                // K-groups of NW waves (CFG 13 / 14)
-  static_assert(KG == 1 || !K::SPEC, "K-groups and loader waves do not combine");
+  constexpr int KG = K::KG;                   // K-groups of NW waves
   const int wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const bool loader = K::SPEC && wave_all >= NW;       // wave-uniform role
-  const bool consumer = !K::SPEC || wave_all < NW || KG > 1;
   const int kgroup = KG > 1 ? wave_all / NW : 0;
-  const int wave = KG > 1 ? wave_all - kgroup * NW : (loader ? wave_all - NW : wave_all);  // index within its role / group
+  const int wave = KG > 1 ? wave_all - kgroup * NW : wave_all;  // index within its group
   const int wr = wave / WCOLS, wc = wave % WCOLS;
-  constexpr int NTHREADS = NW * (K::SPEC ? 128 : 64);
+  constexpr int NTHREADS = NW * 64;
 
   const int total_it = (int)d.kbatch * P.ktiles;
   const int nsplit = P.xsplit ? P.xsplit : (int)gridDim.y;
@@ -756,31 +698,13 @@ void gemm_fast_kernel(const FastParams P) {
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   constexpr int PA = BM / 8 / NW, PB = BN / 8 / NW;  // wave-instructions per wave per tile
-  u32x4 ra[PA], rb[PB];                               // register staging only
-  auto walk = [&](int it, auto emA, auto emB) {
+  auto stage = [&](int it, char* As) {  // LDS-DMA of K-tile `it` into the stage at As
+    char* Bs = As + A_BYTES;
     const int kb = it / P.ktiles, kt = it - kb * P.ktiles;
-    if constexpr (A_KS) stage_ks<BM, NW>(Abase + kb * d.a_skb, d.a_sk, m0, P.a_cols_rd, (int64_t)kt * 64, d.K, wave, lane, emA);
-    else stage_kc<BM, NW>(Abase + kb * d.a_skb, d.a_sm, m0, d.M, (int64_t)kt * 64, wave, lane, emA);
-    if constexpr (B_KS) stage_ks<BN, NW>(Bbase + kb * d.b_skb, d.b_sk, n0, P.b_cols_rd, (int64_t)kt * 64, d.K, wave, lane, emB);
-    else stage_kc<BN, NW>(Bbase + kb * d.b_skb, d.b_sn, n0, d.N, (int64_t)kt * 64, wave, lane, emB);
-  };
-  auto stage = [&](int it, int buf) {  // LDS-DMA
-    char* As = smem + buf * STAGE;
-    char* Bs = As + A_BYTES;
-    walk(it, [&](const bf16_t* src, int, int j) { glds16(src, As + j * 1024); },
-         [&](const bf16_t* src, int, int j) { glds16(src, Bs + j * 1024); });
-  };
-  auto fetch = [&](int it) {           // register staging, part 1: loads in flight
-    walk(it, [&](const bf16_t* src, int i, int) { ra[i] = *reinterpret_cast<const u32x4*>(src); },
-         [&](const bf16_t* src, int i, int) { rb[i] = *reinterpret_cast<const u32x4*>(src); });
-  };
-  auto commit = [&](int buf) {         // part 2: the same lane-linear image the DMA would write
-    char* As = smem + buf * STAGE;
-    char* Bs = As + A_BYTES;
-#pragma unroll
-    for (int i = 0; i < PA; ++i) *reinterpret_cast<u32x4*>(As + (PA * wave + i) * 1024 + lane * 16) = ra[i];
-#pragma unroll
-    for (int i = 0; i < PB; ++i) *reinterpret_cast<u32x4*>(Bs + (PB * wave + i) * 1024 + lane * 16) = rb[i];
+    if constexpr (A_KS) stage_ks<BM, NW>(Abase + kb * d.a_skb, d.a_sk, m0, P.a_cols_rd, (int64_t)kt * 64, d.K, wave, lane, As);
+    else stage_kc<BM, NW>(Abase + kb * d.a_skb, d.a_sm, m0, d.M, (int64_t)kt * 64, wave, lane, As);
+    if constexpr (B_KS) stage_ks<BN, NW>(Bbase + kb * d.b_skb, d.b_sk, n0, P.b_cols_rd, (int64_t)kt * 64, d.K, wave, lane, Bs);
+    else stage_kc<BN, NW>(Bbase + kb * d.b_skb, d.b_sn, n0, d.N, (int64_t)kt * 64, wave, lane, Bs);
   };
   // K tail (K % 64 != 0, host allows it only in (KS, KS)): rows k >= K of a KS image were loaded
   // from a clamped row; zero them so they contribute nothing
@@ -807,52 +731,7 @@ void gemm_fast_kernel(const FastParams P) {
     }
   };
 
-  const bool stager = !K::SPEC || loader;
-  if constexpr (ABL == 8) {  // stamped copy of the loop: where do an iteration's cycles go?
-    unsigned long long acc_t[5] = {0, 0, 0, 0, 0};
-    if (nt > 0) {
-      stage(it0, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      int buf = 0;
-      for (int t = 0; t < nt; ++t) {
-        const unsigned long long t0 = stamp();
-        if (t + 1 < nt) stage(it0 + t + 1, buf ^ 1);
-        const unsigned long long t1 = stamp();
-        const char* As = smem + buf * STAGE;
-        mma_tile<A_KS, B_KS, MI, NI, BM == 64, BN == 64>(As, As + A_BYTES, wr * K::WM, wc * K::WN, lane, acc);
-        asm volatile("s_nop 0" ::"v"(acc[0][0][0]));
-        const unsigned long long t2 = stamp();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t3 = stamp();
-        __syncthreads();
-        const unsigned long long t4 = stamp();
-        acc_t[0] += t1 - t0; acc_t[1] += t2 - t1; acc_t[2] += t3 - t2; acc_t[3] += t4 - t3; acc_t[4] += 1;
-        buf ^= 1;
-      }
-    }
-    if (blockIdx.x == 8 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0)
-      for (int i = 0; i < 5; ++i) g_gemm_stamps[i] = acc_t[i];
-    wide_epilogue<TC>(P, acc[0][0], acc[0][1], smem + wave * 8192, m0 + wr * K::WM, n0 + wc * K::WN, bz, lane, false);
-    return;
-  }
-  if constexpr (kRegStage<CFG>) {
-    if (nt > 0) {
-      fetch(it0);
-      commit(0);
-      __syncthreads();
-      int buf = 0;
-      for (int t = 0; t < nt; ++t) {
-        if (t + 1 < nt) fetch(it0 + t + 1);   // global loads fly under this tile's MFMAs
-        zero_tail(it0 + t, buf);
-        const char* As = smem + buf * STAGE;
-        mma_tile<A_KS, B_KS, MI, NI, BM == 64, BN == 64>(As, As + A_BYTES, wr * K::WM, wc * K::WN, lane, acc);
-        if (t + 1 < nt) commit(buf ^ 1);      // nobody reads the other buffer during this iteration
-        __syncthreads();
-        buf ^= 1;
-      }
-    }
-  } else if constexpr ((NSTAGE > 2 || kKG<CFG> > 1) && !K::SPEC && ABL == 0) {
+  if constexpr (NSTAGE > 2 || KG > 1) {
     // Deep ring for latency-bound problems (one small workgroup per CU, nothing else to hide the
     // DMA round trip behind): tiles t+1 .. t+NSTAGE-1 are in flight while tile t is multiplied.
     // Counted wait: each wave issues LPT LDS-DMA instructions per tile, in tile order, so
@@ -867,20 +746,14 @@ void gemm_fast_kernel(const FastParams P) {
       static_assert((NSTAGE - 2) * LPT <= 63, "vmcnt is a 6-bit counter");
       const int last = it0 + nt - 1;
       char* ring = smem + kgroup * (NSTAGE * STAGE);
-      auto gstage = [&](int it, int buf) {
-        char* As = ring + buf * STAGE;
-        char* Bs = As + A_BYTES;
-        walk(it, [&](const bf16_t* src, int, int j) { glds16(src, As + j * 1024); },
-             [&](const bf16_t* src, int, int j) { glds16(src, Bs + j * 1024); });
-      };
 #pragma unroll
-      for (int s_ = 0; s_ < NSTAGE - 1; ++s_) gstage(min(it0 + kgroup + KG * s_, last), s_);
+      for (int s_ = 0; s_ < NSTAGE - 1; ++s_) stage(min(it0 + kgroup + KG * s_, last), ring + s_ * STAGE);
       int slot = 0, fill = NSTAGE - 1;
       const int trips = (nt + KG - 1) / KG;
       for (int t = 0; t < trips; ++t) {
         wait_vmcnt<(NSTAGE - 2) * LPT>();
         __syncthreads();
-        gstage(min(it0 + kgroup + KG * (t + NSTAGE - 1), last), fill);
+        stage(min(it0 + kgroup + KG * (t + NSTAGE - 1), last), ring + fill * STAGE);
         if constexpr (KG == 1) zero_tail(it0 + t, slot);
         const char* As = ring + slot * STAGE;
         if (KG == 1 || kgroup + KG * t < nt)
@@ -910,28 +783,20 @@ void gemm_fast_kernel(const FastParams P) {
         for (int e = 0; e < 16; ++e) acc[0][0][e] += src[e * 64 + lane];
       }
     }
-  } else
-  if (nt > 0) {
-    if (stager) stage(it0, 0);
+  } else if (nt > 0) {
+    stage(it0, smem);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int buf = 0;
     for (int t = 0; t < nt; ++t) {
-      if (ABL != 4 && stager && t + 1 < nt) stage(it0 + t + 1, buf ^ 1);   // next tile's DMA flies under this tile's MFMAs
+      if (t + 1 < nt) stage(it0 + t + 1, smem + (buf ^ 1) * STAGE);   // next tile's DMA flies under this tile's MFMAs
       zero_tail(it0 + t, buf);
-      if (ABL != 2 && consumer) {
-        const char* As = smem + buf * STAGE;
-        mma_tile<A_KS, B_KS, MI, NI, BM == 64, BN == 64>(As, As + A_BYTES, wr * K::WM, wc * K::WN, lane, acc);
-      }
+      const char* As = smem + buf * STAGE;
+      mma_tile<A_KS, B_KS, MI, NI, BM == 64, BN == 64>(As, As + A_BYTES, wr * K::WM, wc * K::WN, lane, acc);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       buf ^= 1;
     }
-  }
-  if (!consumer) return;
-  if (TMI_DBG(P) & 1) {
-    if (acc[0][0][0] + acc[MI - 1][NI - 1][5] == 123.456f) reinterpret_cast<float*>(d.C)[0] = 0.f;  // keep acc live
-    return;
   }
   if constexpr (NI == 1) {  // 32x32 per wave: the 32-column epilogue, 4 KiB of staging per wave
     char* E32 = smem + wave * 4096;
@@ -1007,7 +872,7 @@ __device__ __forceinline__ void p8_barrier() {
 // the Q11 / Q10 phases issue 4 MFMAs instead of 8, A^1 is an 8 KiB half-tile staged with ONE LDS-DMA per lane, so the
 // counted waits are vmcnt(7) / vmcnt(5)).  For outputs whose 256-row tiling leaves CUs idle or a round mostly empty
 // (M = 12000, N = 768: 141 tiles on 256 CUs -> 189 tiles of 3/4 the work).  k-contiguous A only.
-template <typename TC, bool A_KS, bool B_KS, int BM = 256, bool PERSIST = false, int ABL = 0>
+template <typename TC, bool A_KS, bool B_KS, int BM = 256, bool PERSIST = false>
 __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
   static_assert(BM == 256 || (BM == 192 && !A_KS), "192-row tiles: k-contiguous A only");
   constexpr int WR = BM / 2;          // rows per wave row
@@ -1120,9 +985,7 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
   // PERSIST: the staging of a tile's last two K-tile steps already fetches the NEXT tile's first K-tiles (the ring never
   // drains between tiles); ``stage_next`` says the offsets above belong to the next tile
   bool has_next = false, stage_next = false;
-  bool in_loop = false;  // (ABL == 4, diagnostics: the loop's stages are skipped, the prologue's are not)
   auto stage = [&](int buf, int kind, int t) {  // kind: 0 A^0, 1 A^1, 2 B^0, 3 B^1; t: tile within the split
-    if (ABL == 4 && in_loop) return;
     if (PERSIST && stage_next) t -= nt;   // (the offsets were switched to the next tile: its K-tile 0 or 1; nt >= 2)
     else t = t < nt ? t : nt - 1;
     const int kt = kt0 + t;
@@ -1167,7 +1030,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
   // only the peeled last K-tile does.
   auto readA = [&](int bufoff, int a, int t, auto lastk_tag) {
     constexpr bool LASTK = decltype(lastk_tag)::value;
-    if constexpr (ABL == 2) return;
     if constexpr (A_KS) {
       const char* img = smem + bufoff + a * P8_HALF;
 #pragma unroll
@@ -1197,7 +1059,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
     }
   };
   auto readB = [&](int bufoff, int b, bf16x8 (&br)[4]) {
-    if constexpr (ABL == 2) return;
     if constexpr (B_KS) {
       const char* img = smem + bufoff + (2 + b) * P8_HALF;
 #pragma unroll
@@ -1210,7 +1071,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
   };
 #define P8_MMA(A_, B_, BR_)                                                                               \
   do {                                                                                                    \
-    if constexpr (ABL == 2) break;                                                                        \
     __builtin_amdgcn_s_setprio(1);                                                                        \
     _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) _Pragma("unroll") for (int mi = 0; mi < ((A_) == 0 ? 2 : MI1); ++mi) \
         acc[2 * (A_) + mi][B_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(BR_[kk], ar[mi][kk], acc[2 * (A_) + mi][B_], 0, 0, 0); \
@@ -1296,16 +1156,12 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
         char* E = wave < 4 ? smem + last * P8_BUF + (1 + 2 * (wave >> 1)) * P8_HALF + (wave & 1) * 8192
                            : smem + 2 * P8_BUF + (wave - 4) * 8192;
         const int64_t mw0 = m0 + wr * WR, nw0 = n0 + wc * 64;
-        if (TMI_DBG(P) & 1) {
-          if (acc[0][0][0] + acc[NMI - 1][1][5] == 123.456f) reinterpret_cast<float*>(d.C)[0] = 0.f;
-        } else {
-          // (written out: LLVM's pragma-unroll threshold declines four copies of the fp32 epilogue, and a rolled loop
-          // indexes acc dynamically - 576 B of scratch per lane in the weight-gradient kernels)
-          wide_epilogue<TC, 2>(P, acc[0][0], acc[0][1], E, mw0, nw0, bz, lane, false);
-          wide_epilogue<TC, 2>(P, acc[1][0], acc[1][1], E, mw0 + 32, nw0, bz, lane, false);
-          wide_epilogue<TC, 2>(P, acc[2][0], acc[2][1], E, mw0 + 64, nw0, bz, lane, false);
-          if constexpr (NMI == 4) wide_epilogue<TC, 2>(P, acc[NMI - 1][0], acc[NMI - 1][1], E, mw0 + 96, nw0, bz, lane, false);
-        }
+        // (written out: LLVM's pragma-unroll threshold declines four copies of the fp32 epilogue, and a rolled loop
+        // indexes acc dynamically - 576 B of scratch per lane in the weight-gradient kernels)
+        wide_epilogue<TC, 2>(P, acc[0][0], acc[0][1], E, mw0, nw0, bz, lane, false);
+        wide_epilogue<TC, 2>(P, acc[1][0], acc[1][1], E, mw0 + 32, nw0, bz, lane, false);
+        wide_epilogue<TC, 2>(P, acc[2][0], acc[2][1], E, mw0 + 64, nw0, bz, lane, false);
+        if constexpr (NMI == 4) wide_epilogue<TC, 2>(P, acc[NMI - 1][0], acc[NMI - 1][1], E, mw0 + 96, nw0, bz, lane, false);
       }
       if (!has_next) break;
       slot = nslot;
@@ -1317,9 +1173,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing (unread) stages
     return;
   } else {
-  const bool stamping = (TMI_DBG(P) & 16) && blockIdx.x == 8 && blockIdx.y == 0 && wave == 0;  // diagnostics: where a tile's cycles go
-  unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
-  if (stamping) ts[0] = stamp();
   if (nt > 0) {  // (uniform over the workgroup)
     // ---- prologue: tile 0 whole, the first-read half of tile 1
     stage(0, 2, 0);
@@ -1331,27 +1184,19 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     p8_barrier();
     if (wr == 1) p8_barrier();  // this group runs one barrier behind
-    if (stamping) ts[1] = stamp();
 
     // one K-tile per iteration
-    in_loop = true;
     if constexpr (A_KS && B_KS) {  // (the only layout with a K tail: its last K-tile is peeled)
       for (int t = 0; t < nt - 1; ++t) P8_KTILE(t & 1, t, (void)0);
       P8_KTILE_L((nt - 1) & 1, nt - 1, (void)0, std::true_type);
     } else {
       for (int t = 0; t < nt; ++t) P8_KTILE(t & 1, t, (void)0);
     }
-    if (stamping) ts[2] = stamp();
     if (wr == 0) p8_barrier();  // rejoin the other group
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // trailing (unread) stages must land before LDS is reused
     p8_barrier();
-    if (stamping) ts[3] = stamp();
   }
 
-  if (TMI_DBG(P) & 1) {  // diagnostics: no epilogue (keep the accumulators live)
-    if (acc[0][0][0] + acc[NMI - 1][1][5] == 123.456f) reinterpret_cast<float*>(d.C)[0] = 0.f;
-    return;
-  }
   char* E = smem + wave * 8192;
   {
     const int64_t mw0 = m0 + wr * WR, nw0 = n0 + wc * 64;  // (written out: see the persistent form)
@@ -1365,13 +1210,6 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
     wide_epilogue<TC, 2>(Q, acc[2][0], acc[2][1], E, mw0 + 64, nw0, bz, lane, false);
     if constexpr (NMI == 4) wide_epilogue<TC, 2>(Q, acc[NMI - 1][0], acc[NMI - 1][1], E, mw0 + 96, nw0, bz, lane, false);
   }
-  if (stamping) {
-    ts[4] = stamp();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ts[5] = stamp();
-    if (lane == 0)
-      for (int i = 0; i < 5; ++i) g_gemm_stamps[i] = ts[i + 1] - ts[i];
-  }
   }
 #undef P8_KTILE
 #undef P8_KTILE_L
@@ -1379,7 +1217,8 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(const FastParams P) {
 }
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline int64_t rup8(int64_t x) { return (x + 7) / 8 * 8; }
+inline int64_t rup(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
+inline int64_t rup8(int64_t x) { return rup(x, 8); }
 
 // split-K through workspace slabs: run `launch` on a copy of P whose C is the workspace, then reduce
 template <typename F>
@@ -1401,8 +1240,7 @@ int launch_with_slabs(const FastParams& P, int splitk, hipStream_t stream, F&& l
   const int vec_ok = d.N % 4 == 0 && d.ldc % 4 == 0 && d.c_sb % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0;
   const int64_t n = d.nbatch * d.M * d.N;
   int64_t blocks = (n / 4 + 255) / 256;
-  static const int64_t rcap = [] { const char* e = getenv("TMI_REDUCE_BLOCKS"); return e ? atoll(e) : 2048ll; }();
-  if (blocks > rcap) blocks = rcap;
+  if (blocks > 2048) blocks = 2048;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
                      reinterpret_cast<const float*>(d.workspace), splitk, Q.split_c_stride, C, d.M, d.N, d.ldc, d.c_sb,
@@ -1416,82 +1254,87 @@ int launch_with_slabs(const FastParams& P, int splitk, hipStream_t stream, F&& l
 // weights (M = 12000: A is the stream, the weights stay in L2); the LM head (M = 800, N = 51904: 80 MB of weights,
 // 1.2 MB of activations) and its weight gradient want the opposite, or every row-tile re-fetches each weight panel.
 inline int walk_along_m(const tmi_gemm_desc& d, int xm, int xn) {
-  static const int force = [] { const char* e = getenv("TMI_GEMM_WALK_M"); return e ? atoi(e) : -1; }();
-  if (force >= 0) return force;
   const double a_share = (double)d.M * (double)d.K * (double)d.kbatch * 2.0 / xm;  // bytes of A one XCD touches
   const double b_share = (double)d.N * (double)d.K * (double)d.kbatch * 2.0 / xn;
   return b_share > 3.0 * 1048576.0 && a_share < b_share;
 }
 
-template <typename TC, bool A_KS, bool B_KS, int CFG>
-int launch_cfg(const tmi_gemm_desc& d, hipStream_t stream) {
-  using K = Cfg<CFG>;
-  constexpr int NW = (K::BM / K::WM) * (K::BN / K::WN);
-  constexpr int LDS_BYTES = kKG<CFG> * K::NSTAGE * (K::BM + K::BN) * 128;
-  static_assert(LDS_BYTES >= NW * (K::WN == 32 ? 4096 : 8192), "epilogue staging must fit the ring");
+// XCD partition of the tile grid: `groups` XCDs (8: the whole chip; 8 / S: the XCDs that serve one of S K ranges) as xn
+// column groups x (groups / xn) row groups.  Never pay for the aimed xn with padding: among the splits take the one with
+// the fewest (padded) workgroups, nearest to the aim on ties (aim = 1: the first minimum).
+inline void xcd_partition(FastParams& P, int groups, int aim) {
+  int xn = aim;
+  int64_t best = -1;
+  int best_dist = 0;
+  for (int cand = 1; cand <= groups; cand *= 2) {
+    const int64_t padded = (int64_t)((P.tiles_m + groups / cand - 1) / (groups / cand)) * ((P.tiles_n + cand - 1) / cand);
+    int dist = 0;
+    for (int v = cand; v < aim; v *= 2) ++dist;
+    for (int v = aim; v < cand; v *= 2) ++dist;
+    if (best < 0 || padded < best || (padded == best && dist < best_dist)) {
+      best = padded;
+      best_dist = dist;
+      xn = cand;
+    }
+  }
+  P.xn = xn;
+  P.xm = groups / xn;
+  P.ptm = (P.tiles_m + P.xm - 1) / P.xm;
+  P.ptn = (P.tiles_n + P.xn - 1) / P.xn;
+}
+
+// The part of FastParams every launch shares: BM x BN tiles, K-tiles of BK elements, operands of in_bytes and results of
+// out_bytes per element; the whole-chip XCD partition and the walk order.
+inline FastParams fast_params(const tmi_gemm_desc& d, int BM, int BN, int BK, int in_bytes, int out_bytes) {
   FastParams P;
   P.d = d;
-  P.tiles_m = (int)((d.M + K::BM - 1) / K::BM);
-  P.tiles_n = (int)((d.N + K::BN - 1) / K::BN);
-  P.ktiles = (int)((d.K + 63) / 64);
-  P.a_cols_rd = rup8(d.M);
-  P.b_cols_rd = rup8(d.N);
-  const int vecC = 16 / (int)sizeof(TC);
+  P.tiles_m = (int)((d.M + BM - 1) / BM);
+  P.tiles_n = (int)((d.N + BN - 1) / BN);
+  P.ktiles = (int)((d.K + BK - 1) / BK);
+  P.a_cols_rd = rup(d.M, 16 / in_bytes);
+  P.b_cols_rd = rup(d.N, 16 / in_bytes);
+  const int vecC = 16 / out_bytes;
   P.wide = al16(d.C) && d.ldc % vecC == 0 && d.c_sb % vecC == 0 && (!d.aux_out || al16(d.aux_out)) &&
            (!d.aux_in || al16(d.aux_in)) && (!d.resid || (al16(d.resid) && d.r_ld % vecC == 0 && d.r_sb % vecC == 0));
   P.epi = epi_class(d, P.wide != 0);
-  static const int dbg = [] { const char* e = getenv("TMI_GEMM_DBG"); return e ? atoi(e) : 0; }();
-  P.dbg = dbg;
   P.split_c_stride = 0;
   P.xsplit = 0;
   P.slots = 0;
   P.drop_thr = tmi_drop_thr(d.dropout_p);
   P.drop_key = tmi_stream_key(d.dropout_seed, 0u);
   P.drop_scale = tmi_keep_scale(P.drop_thr);
+  // aim for one XCD's share of B (K x N / xn elements) <= ~2 MiB
+  int aim = 1;
+  while (aim < 8 && (double)d.K * (double)d.kbatch * ((double)d.N / aim) * (double)in_bytes > 2.0 * 1048576.0 && P.tiles_n >= 2 * aim) aim *= 2;
+  xcd_partition(P, 8, aim);
+  P.walk_m = walk_along_m(d, P.xm, P.xn);
+  return P;
+}
+
+// Split-K over XCD groups: with the split on blockIdx.y every XCD serves all S K-ranges, each with its own panels; dealt
+// over groups of 8 / S XCDs instead, an XCD's L2 holds ONE K-range and (tiles / (8 / S)) tiles that share its row and
+// column panels (fc weight gradient, S = 4: 15 -> 9 panel fetches from beyond L2 per 18 tiles).  The walk order stays
+// the whole-chip partition's.
+inline bool xsplit_over_groups(FastParams& P, int splitk) {
+  if (P.d.nbatch != 1 || (splitk != 2 && splitk != 4 && splitk != 8)) return false;
+  P.xsplit = splitk;
+  xcd_partition(P, 8 / splitk, 1);
+  return true;
+}
+
+template <typename TC, bool A_KS, bool B_KS, typename K>
+int launch_cfg(const tmi_gemm_desc& d, hipStream_t stream) {
+  constexpr int NW = (K::BM / K::WM) * (K::BN / K::WN);
+  constexpr int LDS_BYTES = K::KG * K::NSTAGE * (K::BM + K::BN) * 128;
+  static_assert(LDS_BYTES >= NW * (K::WN == 32 ? 4096 : 8192), "epilogue staging must fit the ring");
+  FastParams P = fast_params(d, K::BM, K::BN, 64, 2, (int)sizeof(TC));
   bool ws_split = false;
-  auto kern = gemm_fast_kernel<TC, A_KS, B_KS, CFG>;
-#ifdef TMI_GEMM_EXPERIMENTS
-  if constexpr (sizeof(TC) == 2 && !A_KS && !B_KS && (CFG < 2 || CFG == 4 || CFG == 6)) {  // ablation builds exist for the bf16-out KC-A kernels only
-    if ((dbg & 6) == 2) kern = gemm_fast_kernel<TC, A_KS, B_KS, CFG, 2>;
-    if ((dbg & 6) == 4) kern = gemm_fast_kernel<TC, A_KS, B_KS, CFG, 4>;
-    if (dbg == 8) kern = gemm_fast_kernel<TC, A_KS, B_KS, CFG, 8>;
-    if (dbg & 14) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-  }
-#endif
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_fast_kernel<TC, A_KS, B_KS, CFG>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+  auto kern = gemm_fast_kernel<TC, A_KS, B_KS, K>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
   if (attr != hipSuccess) {
     tmi_set_error("tmi_gemm(fast): cannot raise the dynamic LDS limit");
     return TMI_ERR_LAUNCH;
   }
-  // XCD partition: xn column groups x (8 / xn) row groups, one per XCD.  Aim for one XCD's share of
-  // B (K x N/xn bf16) <= ~2 MiB, but never pay for it with padding: among the four splits take the one
-  // with the fewest (padded) workgroups, nearest to the aimed one on ties.
-  static const int force_xn = [] { const char* e = getenv("TMI_GEMM_XN"); return e ? atoi(e) : 0; }();
-  int aim = 1;
-  while (aim < 8 && (double)d.K * (double)d.kbatch * ((double)d.N / aim) * 2.0 > 2.0 * 1048576.0 && P.tiles_n >= 2 * aim) aim *= 2;
-  int xn = aim;
-  {
-    int64_t best = -1;
-    int best_dist = 0;
-    for (int cand = 1; cand <= 8; cand *= 2) {
-      const int64_t padded = (int64_t)((P.tiles_m + 8 / cand - 1) / (8 / cand)) * ((P.tiles_n + cand - 1) / cand);
-      int dist = 0;
-      for (int v = cand; v < aim; v *= 2) ++dist;
-      for (int v = aim; v < cand; v *= 2) ++dist;
-      if (best < 0 || padded < best || (padded == best && dist < best_dist)) {
-        best = padded;
-        best_dist = dist;
-        xn = cand;
-      }
-    }
-  }
-  if (force_xn) xn = force_xn;
-  P.xn = xn;
-  P.xm = 8 / xn;
-  P.ptm = (P.tiles_m + P.xm - 1) / P.xm;
-  P.ptn = (P.tiles_n + P.xn - 1) / P.xn;
-  P.walk_m = walk_along_m(d, P.xm, P.xn);
   int splitk = d.splitk > 1 ? d.splitk : 1;
   if (d.splitk == 0 && d.out_dtype == TMI_F32 && !d.bias && !d.accumulate && !d.act && !d.aux_out && !d.aux_in &&
       !d.resid && d.scale_cols <= 0) {
@@ -1502,21 +1345,19 @@ int launch_cfg(const tmi_gemm_desc& d, hipStream_t stream) {
     // the total atomic traffic bounded by what the K loop can amortise (160 KB per K-tile + 3 MB).
     const int64_t wgs = (int64_t)8 * P.ptm * P.ptn * d.nbatch;
     const int64_t its = (int64_t)d.kbatch * P.ktiles;
-    const int64_t slots = (CFG == 1 || CFG == 3 || CFG == 5 || CFG == 8) ? 256 : 512;
+    const int64_t slots = K::BM == 256 ? 256 : 512;
     const int64_t out_bytes = d.M * d.N * d.nbatch * 4;
     int64_t want = slots / wgs;
     if (want > its / 4) want = its / 4;
     // with a workspace the reduction is plain stores + one streaming reduce pass; the fp32-atomic
     // fallback pays ~2 us per MB per split, so it is bounded by what the K loop amortises
     const int64_t slab_bytes = out_bytes;  // one fp32 [nbatch][M][N] slab per split
-    static const int no_ws = [] { const char* e = getenv("TMI_GEMM_NO_WS"); return e ? atoi(e) : 0; }();
-    static const int ws_cap = [] { const char* e = getenv("TMI_GEMM_WS_MAXSPLIT"); return e ? atoi(e) : 8; }();
     // (measured, tools/wgrad_bench.py: slabs + reduce launch match or beat atomics for long reductions,
     // lose to them below ~64 K-tiles where the extra launch shows)
-    bool use_ws = !no_ws && sizeof(TC) == 4 && its >= 64 && d.workspace && (reinterpret_cast<uintptr_t>(d.workspace) & 15) == 0 &&
-                  2 * slab_bytes <= d.workspace_bytes;
+    const bool use_ws = sizeof(TC) == 4 && its >= 64 && d.workspace && (reinterpret_cast<uintptr_t>(d.workspace) & 15) == 0 &&
+                        2 * slab_bytes <= d.workspace_bytes;
     if (use_ws) {
-      if (want > ws_cap) want = ws_cap;
+      if (want > 8) want = 8;
       if (want > d.workspace_bytes / slab_bytes) want = d.workspace_bytes / slab_bytes;
     } else {
       if (want > 5) want = 5;
@@ -1526,9 +1367,6 @@ int launch_cfg(const tmi_gemm_desc& d, hipStream_t stream) {
       // on the arrival order; three or more do - ADVICE r4)
       if (tmi_deterministic() && want > 2) want = 2;
     }
-    static const int force_split = [] { const char* e = getenv("TMI_GEMM_SPLIT"); return e ? atoi(e) : 0; }();
-    if (force_split > 0) want = force_split < its ? force_split : its;
-    if (use_ws && want * slab_bytes > d.workspace_bytes) use_ws = false;
     if (use_ws && want > 1) ws_split = true;
     splitk = want < 1 ? 1 : (int)want;
   }
@@ -1536,27 +1374,13 @@ int launch_cfg(const tmi_gemm_desc& d, hipStream_t stream) {
     splitk = 1;
     ws_split = false;
   }
-  static const int xsplit_on = [] { const char* e = getenv("TMI_GEMM_XSPLIT"); return e ? atoi(e) : 1; }();
-  if (xsplit_on && d.nbatch == 1 && (splitk == 2 || splitk == 4 || splitk == 8)) {  // split-K over XCD groups: see launch_p8
-    const int groups = 8 / splitk;
-    int bxn = 1;
-    int64_t bpad = -1;
-    for (int cand = 1; cand <= groups; cand *= 2) {
-      const int64_t padded = (int64_t)((P.tiles_m + groups / cand - 1) / (groups / cand)) * ((P.tiles_n + cand - 1) / cand);
-      if (bpad < 0 || padded < bpad) { bpad = padded; bxn = cand; }
-    }
-    P.xsplit = splitk;
-    P.xn = bxn;
-    P.xm = groups / bxn;
-    P.ptm = (P.tiles_m + P.xm - 1) / P.xm;
-    P.ptn = (P.tiles_n + P.xn - 1) / P.xn;
-    splitk = 1;  // (grid.y)
-  }
+  const int nsplit = splitk;
+  if (xsplit_over_groups(P, splitk)) splitk = 1;  // (grid.y)
   dim3 grid((unsigned)(8 * P.ptm * P.ptn), (unsigned)splitk, (unsigned)d.nbatch);
-  if (ws_split) return launch_with_slabs(P, P.xsplit ? P.xsplit : splitk, stream, [&](const FastParams& Q) {
-    hipLaunchKernelGGL(kern, grid, dim3(NW * (K::SPEC ? 128 : 64) * kKG<CFG>), LDS_BYTES, stream, Q);
+  if (ws_split) return launch_with_slabs(P, nsplit, stream, [&](const FastParams& Q) {
+    hipLaunchKernelGGL(kern, grid, dim3(NW * 64 * K::KG), LDS_BYTES, stream, Q);
   });
-  hipLaunchKernelGGL(kern, grid, dim3(NW * (K::SPEC ? 128 : 64) * kKG<CFG>), LDS_BYTES, stream, P);
+  hipLaunchKernelGGL(kern, grid, dim3(NW * 64 * K::KG), LDS_BYTES, stream, P);
   return tmi_check_launch("tmi_gemm(fast)");
 }
 
@@ -1574,52 +1398,13 @@ inline bool p8_eligible(const tmi_gemm_desc& d, bool a_ks, bool b_ks) {
 
 template <typename TC, bool A_KS, bool B_KS, int BM = 256>
 int launch_p8(const tmi_gemm_desc& d, hipStream_t stream) {
-  FastParams P;
-  P.d = d;
-  P.tiles_m = (int)((d.M + BM - 1) / BM);
-  P.tiles_n = (int)((d.N + 255) / 256);
-  P.ktiles = (int)((d.K + 63) / 64);
-  P.a_cols_rd = rup8(d.M);
-  P.b_cols_rd = rup8(d.N);
-  const int vecC = 16 / (int)sizeof(TC);
-  P.wide = al16(d.C) && d.ldc % vecC == 0 && d.c_sb % vecC == 0 && (!d.aux_out || al16(d.aux_out)) &&
-           (!d.aux_in || al16(d.aux_in)) && (!d.resid || (al16(d.resid) && d.r_ld % vecC == 0 && d.r_sb % vecC == 0));
-  P.epi = epi_class(d, P.wide != 0);
-  static const int dbg8 = [] { const char* e = getenv("TMI_GEMM_DBG"); return e ? atoi(e) : 0; }();
-  P.dbg = dbg8;
-  P.split_c_stride = 0;
-  P.xsplit = 0;
-  P.drop_thr = tmi_drop_thr(d.dropout_p);
-  P.drop_key = tmi_stream_key(d.dropout_seed, 0u);
-  P.drop_scale = tmi_keep_scale(P.drop_thr);
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_p8_kernel<TC, A_KS, B_KS, BM>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P8_BUF);
+  FastParams P = fast_params(d, BM, 256, 64, 2, (int)sizeof(TC));
+  auto kern = gemm_p8_kernel<TC, A_KS, B_KS, BM>;
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P8_BUF);
   if (attr != hipSuccess) {
     tmi_set_error("tmi_gemm(p8): cannot raise the dynamic LDS limit");
     return TMI_ERR_LAUNCH;
   }
-  // XCD partition with the fewest padded workgroups (see launch_cfg)
-  int aim = 1;
-  while (aim < 8 && (double)d.K * ((double)d.N / aim) * 2.0 > 2.0 * 1048576.0 && P.tiles_n >= 2 * aim) aim *= 2;
-  int xn = aim;
-  int64_t best = -1;
-  int best_dist = 0;
-  for (int cand = 1; cand <= 8; cand *= 2) {
-    const int64_t padded = (int64_t)((P.tiles_m + 8 / cand - 1) / (8 / cand)) * ((P.tiles_n + cand - 1) / cand);
-    int dist = 0;
-    for (int v = cand; v < aim; v *= 2) ++dist;
-    for (int v = aim; v < cand; v *= 2) ++dist;
-    if (best < 0 || padded < best || (padded == best && dist < best_dist)) {
-      best = padded;
-      best_dist = dist;
-      xn = cand;
-    }
-  }
-  P.xn = xn;
-  P.xm = 8 / xn;
-  P.ptm = (P.tiles_m + P.xm - 1) / P.xm;
-  P.ptn = (P.tiles_n + P.xn - 1) / P.xn;
-  P.walk_m = walk_along_m(d, P.xm, P.xn);
   // split-K (library-chosen only, fp32 output, workspace slabs only): fill the 256 CUs, >= 6 K-tiles per split
   int splitk = 1;
   if constexpr (sizeof(TC) == 4) {
@@ -1629,17 +1414,15 @@ int launch_p8(const tmi_gemm_desc& d, hipStream_t stream) {
       const int64_t wgs = (int64_t)8 * P.ptm * P.ptn * d.nbatch;
       // (cap 4, round 3: measured in the step - the weight gradients run beside the dgrad chain, where a split costs slab
       // traffic and CUs the other stream could use: 8.82 -> 8.74 ms/step against a cap of 8; 2 and 1 lose)
-      static const int cap = [] { const char* e = getenv("TMI_GEMM_P8_MAXSPLIT"); return e ? atoi(e) : 4; }();
       int64_t want = 256 / wgs;
       if (want > P.ktiles / 6) want = P.ktiles / 6;
-      if (want > cap) want = cap;
+      if (want > 4) want = 4;
       // (round 4) a very deep reduction onto a handful of tiles (>= 32 K-tiles per split left): as many splits as fill the
-      // chip, a power of two so that they can be dealt over the XCDs (below)
-      static const int deep = [] { const char* e = getenv("TMI_GEMM_P8_DEEPSPLIT"); return e ? atoi(e) : 32; }();
+      // chip, at most 32, a power of two so that they can be dealt over the XCDs (below)
       const int64_t tiles = (int64_t)P.tiles_m * P.tiles_n;
-      if (d.nbatch == 1 && deep > cap && tiles <= 32) {
+      if (d.nbatch == 1 && tiles <= 32) {
         int64_t w2 = 1;
-        while (w2 * 2 <= deep && w2 * 2 * tiles <= 256 && P.ktiles / (w2 * 2) >= 32) w2 *= 2;
+        while (w2 * 2 <= 32 && w2 * 2 * tiles <= 256 && P.ktiles / (w2 * 2) >= 32) w2 *= 2;
         if (w2 > want) want = w2;
       }
       if (want > d.workspace_bytes / slab_bytes) want = d.workspace_bytes / slab_bytes;
@@ -1649,10 +1432,9 @@ int launch_p8(const tmi_gemm_desc& d, hipStream_t stream) {
   P.slots = 8 * P.ptm * P.ptn;
   // More tiles than CUs (bf16-output forward / dgrad launches of two or three rounds): the persistent form - 256 workgroups
   // walk the slots, the K-tile ring runs on from one tile into the next (no prologue after the first tile) and the epilogue
-  // is staged outside the ring.  TMI_GEMM_P8_PERSIST=0 restores one workgroup per tile.
+  // is staged outside the ring.
   if constexpr (!(A_KS && B_KS)) {
-    static const int persist = [] { const char* e = getenv("TMI_GEMM_P8_PERSIST"); return e ? atoi(e) : 1; }();
-    if (persist && splitk == 1 && d.nbatch == 1 && P.slots > 256 && P.ktiles >= 2) {
+    if (splitk == 1 && d.nbatch == 1 && P.slots > 256 && P.ktiles >= 2) {
       constexpr int LDS_P = 2 * P8_BUF + 32768;
       static const hipError_t attr_p = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_p8_kernel<TC, A_KS, B_KS, BM, true>),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_P);
@@ -1662,185 +1444,128 @@ int launch_p8(const tmi_gemm_desc& d, hipStream_t stream) {
       }
     }
   }
-  // Split-K over XCD groups (round 4): with the split on blockIdx.y every XCD serves all S K-ranges, each with its own
-  // panels; dealt over groups of 8 / S XCDs instead, an XCD's L2 holds ONE K-range and (tiles / (8 / S)) tiles that share its
-  // row and column panels (fc weight gradient, S = 4: 15 -> 9 panel fetches from beyond L2 per 18 tiles).
-  static const int xsplit_on = [] { const char* e = getenv("TMI_GEMM_XSPLIT"); return e ? atoi(e) : 1; }();
-  if (xsplit_on && d.nbatch == 1 && (splitk == 16 || splitk == 32)) {  // splitk / 8 K ranges per XCD, each with all the tiles
+  dim3 grid((unsigned)(8 * P.ptm * P.ptn), (unsigned)splitk, (unsigned)d.nbatch);
+  if (d.nbatch == 1 && (splitk == 16 || splitk == 32)) {  // splitk / 8 K ranges per XCD, each with all the tiles (see the kernel)
     P.xsplit = splitk;
     P.xn = P.xm = 1;
     P.ptm = P.tiles_m;
     P.ptn = P.tiles_n;
     P.slots = 8 * P.ptm * P.ptn * (splitk / 8);
-    dim3 gridx((unsigned)P.slots, 1u, 1u);
-    return launch_with_slabs(P, splitk, stream, [&](const FastParams& Q) {
-      hipLaunchKernelGGL((gemm_p8_kernel<TC, A_KS, B_KS, BM>), gridx, dim3(512), 2 * P8_BUF, stream, Q);
-    });
-  }
-  if (xsplit_on && d.nbatch == 1 && (splitk == 2 || splitk == 4 || splitk == 8)) {
-    const int groups = 8 / splitk;  // XCDs per split: 4, 2 or 1
-    int bxn = 1;
-    int64_t bpad = -1;
-    for (int cand = 1; cand <= groups; cand *= 2) {
-      const int64_t padded = (int64_t)((P.tiles_m + groups / cand - 1) / (groups / cand)) * ((P.tiles_n + cand - 1) / cand);
-      if (bpad < 0 || padded < bpad) { bpad = padded; bxn = cand; }
-    }
-    P.xsplit = splitk;
-    P.xn = bxn;
-    P.xm = groups / bxn;
-    P.ptm = (P.tiles_m + P.xm - 1) / P.xm;
-    P.ptn = (P.tiles_n + P.xn - 1) / P.xn;
+    grid = dim3((unsigned)P.slots, 1u, 1u);
+  } else if (xsplit_over_groups(P, splitk)) {
     P.slots = 8 * P.ptm * P.ptn;
-    dim3 gridx((unsigned)(8 * P.ptm * P.ptn), 1u, 1u);
-    return launch_with_slabs(P, splitk, stream, [&](const FastParams& Q) {
-      hipLaunchKernelGGL((gemm_p8_kernel<TC, A_KS, B_KS, BM>), gridx, dim3(512), 2 * P8_BUF, stream, Q);
-    });
+    grid = dim3((unsigned)P.slots, 1u, 1u);
   }
-  dim3 grid((unsigned)(8 * P.ptm * P.ptn), (unsigned)splitk, (unsigned)d.nbatch);
-#ifdef TMI_GEMM_EXPERIMENTS
-  if constexpr (sizeof(TC) == 2 && !A_KS && !B_KS && BM == 192) {  // diagnostics: TMI_GEMM_DBG & 6 = 2 no MFMA / reads, 4 no staging in the loop
-    if ((dbg8 & 6) && splitk == 1) {
-      auto kern = (dbg8 & 6) == 2 ? gemm_p8_kernel<TC, A_KS, B_KS, BM, false, 2> : gemm_p8_kernel<TC, A_KS, B_KS, BM, false, 4>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * P8_BUF);
-      hipLaunchKernelGGL(kern, grid, dim3(512), 2 * P8_BUF, stream, P);
-      return tmi_check_launch("tmi_gemm(p8 ablation)");
-    }
-  }
-#endif
   if (splitk > 1) return launch_with_slabs(P, splitk, stream, [&](const FastParams& Q) {
-    hipLaunchKernelGGL((gemm_p8_kernel<TC, A_KS, B_KS, BM>), grid, dim3(512), 2 * P8_BUF, stream, Q);
+    hipLaunchKernelGGL(kern, grid, dim3(512), 2 * P8_BUF, stream, Q);
   });
-  hipLaunchKernelGGL((gemm_p8_kernel<TC, A_KS, B_KS, BM>), grid, dim3(512), 2 * P8_BUF, stream, P);
+  hipLaunchKernelGGL(kern, grid, dim3(512), 2 * P8_BUF, stream, P);
   return tmi_check_launch("tmi_gemm(p8)");
 }
 
+// TMI_GEMM_CFG=n, the one diagnostic switch of this file: force a shipped kernel where it can run (tools/ and the recorded
+// results in profiles/ are keyed by these values; any other value, the numbers of retired configurations included,
+// leaves the choice to the rules below, without the eight-phase rules):
+//    4  Tile128x128            5  Tile256x256             6  Tile64Waves2
+//   10  eight-phase, 256 rows 14  eight-phase, 192 rows (k-contiguous A)
+//   12  Tile64Waves4          13  Tile64Waves4Ring4
+//   15  Tile64KGroups2Ring4   16  Tile64KGroups2Ring2    (K % 64 == 0)
+// (10 and 12-16 only without a caller-chosen split-K.)
 template <typename TC, bool A_KS, bool B_KS>
 int launch_fast(const tmi_gemm_desc& d, hipStream_t stream) {
   static const int force = [] { const char* e = getenv("TMI_GEMM_CFG"); return e ? atoi(e) : -1; }();
-  // Measured on MI355X (tools/gemm_bench.py): the 256x256 tile wins for bf16-output GEMMs with a
-  // long reduction (K >= 1536: its unoverlapped epilogue is amortised) or whose tile count fills
-  // whole rounds of the 256 CUs; weight gradients (split-K, atomic epilogue) and small problems
-  // run better on the 128x128 tile with two workgroups per CU.
-  const int64_t big_tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256) * d.nbatch;
-  const double round_eff = (double)big_tiles / (double)(((big_tiles + 255) / 256) * 256);
-  const bool wgrad_like = d.splitk == 0 && d.out_dtype == TMI_F32;
-  bool big = d.out_dtype == TMI_BF16 && d.M >= 2048 && d.N >= 512 && (d.K * d.kbatch >= 1536 || round_eff >= 0.8);
   if constexpr (!A_KS || B_KS) {  // (k-strided A with k-contiguous B is not instantiated)
     if (force == 10 && p8_eligible(d, A_KS, B_KS) && d.splitk <= 1) return launch_p8<TC, A_KS, B_KS>(d, stream);
   }
   if constexpr (!A_KS) {
     if (force == 14 && p8_eligible(d, false, B_KS) && d.splitk <= 1) return launch_p8<TC, false, B_KS, 192>(d, stream);
   }
-  // too few 128x128 tiles to occupy the chip (and not a split-K weight gradient): 64x64 tiles
+  if (force == 4) return launch_cfg<TC, A_KS, B_KS, Tile128x128>(d, stream);
+  if (force == 5) return launch_cfg<TC, A_KS, B_KS, Tile256x256>(d, stream);
+  if (force == 6) return launch_cfg<TC, A_KS, B_KS, Tile64Waves2>(d, stream);
+  if (force == 12 && d.splitk <= 1) return launch_cfg<TC, A_KS, B_KS, Tile64Waves4>(d, stream);
+  if (force == 13 && d.splitk <= 1) return launch_cfg<TC, A_KS, B_KS, Tile64Waves4Ring4>(d, stream);
+  if (force == 15 && d.splitk <= 1 && d.K % 64 == 0) return launch_cfg<TC, A_KS, B_KS, Tile64KGroups2Ring4>(d, stream);
+  if (force == 16 && d.splitk <= 1 && d.K % 64 == 0) return launch_cfg<TC, A_KS, B_KS, Tile64KGroups2Ring2>(d, stream);
+
+  const int64_t big_tiles = ((d.M + 255) / 256) * ((d.N + 255) / 256) * d.nbatch;
+  const bool wgrad_like = d.splitk == 0 && d.out_dtype == TMI_F32;
+  // 1. Too few 128x128 tiles to occupy the chip (and not a split-K weight gradient): 64x64 tiles.
   const int64_t mid_tiles = ((d.M + 127) / 128) * ((d.N + 127) / 128) * d.nbatch;
-  const bool small = !wgrad_like && mid_tiles < 200 && d.M >= 64 && d.N >= 64;
-  // (configurations 0-3 and 7-10 are round-1/2 experiments no rule picks: built only with -DTMI_GEMM_EXPERIMENTS - they were
-  // 60 % of this file's compile time)
-#ifdef TMI_GEMM_EXPERIMENTS
-  if (force == 0) return launch_cfg<TC, A_KS, B_KS, 0>(d, stream);
-  if (force == 1) return launch_cfg<TC, A_KS, B_KS, 1>(d, stream);
-  if (force == 2) return launch_cfg<TC, A_KS, B_KS, 2>(d, stream);
-  if (force == 3) return launch_cfg<TC, A_KS, B_KS, 3>(d, stream);
-  if (force == 7) return launch_cfg<TC, A_KS, B_KS, 7>(d, stream);
-  if (force == 8) return launch_cfg<TC, A_KS, B_KS, 8>(d, stream);
-  if (force == 9) return launch_cfg<TC, A_KS, B_KS, 9>(d, stream);
-  if (force == 11) return launch_cfg<TC, A_KS, B_KS, 10>(d, stream);
-#endif
-  if (force == 4) return launch_cfg<TC, A_KS, B_KS, 4>(d, stream);
-  if (force == 5) return launch_cfg<TC, A_KS, B_KS, 5>(d, stream);
-  if (force == 6) return launch_cfg<TC, A_KS, B_KS, 6>(d, stream);
-  if (force == 12 && d.splitk <= 1) return launch_cfg<TC, A_KS, B_KS, 11>(d, stream);
-  if (force == 13 && d.splitk <= 1) return launch_cfg<TC, A_KS, B_KS, 12>(d, stream);
-  if (force == 15 && d.splitk <= 1 && d.K % 64 == 0) return launch_cfg<TC, A_KS, B_KS, 13>(d, stream);
-  if (force == 16 && d.splitk <= 1 && d.K % 64 == 0) return launch_cfg<TC, A_KS, B_KS, 14>(d, stream);
-  if (small) {
+  if (!wgrad_like && mid_tiles < 200 && d.M >= 64 && d.N >= 64) {
     // measured (tools/gemm_small.py, M = 800): four waves of 32x32 beat two of 32x64 wherever the grid is
     // at most one workgroup per CU (N 768, K 768: 12.3 -> 9.1 us) and tie elsewhere; the 4-stage ring adds
     // to that for long K on such grids (N 768, K 3072: 27.4 -> 21.4 us) and loses co-residency on larger ones
     const int64_t tiles64 = ((d.M + 63) / 64) * ((d.N + 63) / 64) * d.nbatch;
-    if (d.splitk <= 1) {
-      // at most one workgroup per CU: two K-groups of four waves overlap each other's per-K-tile chains
-      // (tools/gemm_small2.py, M 800 N 768: K 3072 22.9 -> 17.4 us, K 768 9.2 -> 8.7 us; a third group adds nothing)
-      static const int no_kg = [] { const char* e = getenv("TMI_GEMM_NO_KGROUPS"); return e ? atoi(e) : 0; }();
-      if (!no_kg && tiles64 <= 256 && d.K % 64 == 0 && d.K * d.kbatch >= 512) return launch_cfg<TC, A_KS, B_KS, 13>(d, stream);
-      // more than one workgroup per CU, up to two: the K-groups on 2-stage rings (Whisper-large's decoder, [800, 1280]:
-      // K 1280 16.0 -> 14.8 us, K 5120 50.6 -> 41.1 us; tools/gemm_large_dec_probe.py.  TMI_GEMM_KG2=0: CFG 11)
-      static const int kg2 = [] { const char* e = getenv("TMI_GEMM_KG2"); return e ? atoi(e) : 1024; }();
-      if (!no_kg && kg2 > 0 && tiles64 > 256 && tiles64 <= 512 && d.K % 64 == 0 && d.K * d.kbatch >= kg2)
-        return launch_cfg<TC, A_KS, B_KS, 14>(d, stream);
-      if (tiles64 <= 256 && d.K * d.kbatch >= 1536) return launch_cfg<TC, A_KS, B_KS, 12>(d, stream);
-      return launch_cfg<TC, A_KS, B_KS, 11>(d, stream);
-    }
-    return launch_cfg<TC, A_KS, B_KS, 6>(d, stream);
+    if (d.splitk > 1) return launch_cfg<TC, A_KS, B_KS, Tile64Waves2>(d, stream);  // (the four-wave tiles have no atomic epilogue)
+    // at most one workgroup per CU: two K-groups of four waves overlap each other's per-K-tile chains
+    // (tools/gemm_small2.py, M 800 N 768: K 3072 22.9 -> 17.4 us, K 768 9.2 -> 8.7 us; a third group adds nothing)
+    if (tiles64 <= 256 && d.K % 64 == 0 && d.K * d.kbatch >= 512) return launch_cfg<TC, A_KS, B_KS, Tile64KGroups2Ring4>(d, stream);
+    // more than one workgroup per CU, up to two: the K-groups on 2-stage rings (Whisper-large's decoder, [800, 1280]:
+    // K 1280 16.0 -> 14.8 us, K 5120 50.6 -> 41.1 us; tools/gemm_large_dec_probe.py)
+    if (tiles64 > 256 && tiles64 <= 512 && d.K % 64 == 0 && d.K * d.kbatch >= 1024)
+      return launch_cfg<TC, A_KS, B_KS, Tile64KGroups2Ring2>(d, stream);
+    if (tiles64 <= 256 && d.K * d.kbatch >= 1536) return launch_cfg<TC, A_KS, B_KS, Tile64Waves4Ring4>(d, stream);
+    return launch_cfg<TC, A_KS, B_KS, Tile64Waves4>(d, stream);
   }
-  // fp32 results of a very deep reduction onto few tiles (the LM head's dgrad: [800, 768] from K = 51904, 134 us on the 128x128
-  // kernel with 8 atomic splits): eight-phase kernel, 16 / 32 slab splits dealt two / four per XCD (launch_p8)
+  // 2. fp32 results of a very deep reduction onto few tiles (the LM head's dgrad: [800, 768] from K = 51904, 134 us on the
+  // 128x128 kernel with 8 atomic splits): eight-phase kernel, 16 / 32 slab splits dealt two / four per XCD (launch_p8)
   if constexpr (!A_KS && sizeof(TC) == 4) {
-    static const int deep_on = [] { const char* e = getenv("TMI_GEMM_P8_DEEP"); return e ? atoi(e) : 1; }();
     const int64_t t192 = ((d.M + 191) / 192) * ((d.N + 255) / 256), t256 = ((d.M + 255) / 256) * ((d.N + 255) / 256);
-    if (deep_on && force < 0 && wgrad_like && d.workspace && p8_eligible(d, false, B_KS) && d.nbatch == 1 && d.K >= 16384 &&
+    if (force < 0 && wgrad_like && d.workspace && p8_eligible(d, false, B_KS) && d.nbatch == 1 && d.K >= 16384 &&
         d.M >= 512 && d.N >= 256 && t256 <= 32 && 16 * d.M * d.N * 4 <= d.workspace_bytes) {
       if (t192 <= 32 && (d.M + 191) / 192 * 192 < (d.M + 255) / 256 * 256) return launch_p8<TC, false, B_KS, 192>(d, stream);
       return launch_p8<TC, false, B_KS>(d, stream);
     }
   }
-  // weight gradients with a large output and a long reduction: eight-phase kernel, split-K through
+  // 3. Weight gradients with a large output and a long reduction: eight-phase kernel, split-K through
   // workspace slabs (-13 % against the 128x128 kernel with atomics; smaller outputs lose)
   if constexpr (A_KS && B_KS && sizeof(TC) == 4) {
-    static const int no_p8w = [] { const char* e = getenv("TMI_GEMM_NO_P8"); return e ? atoi(e) : 0; }();
     // (round 4: the LM head's weight gradient - [768, 51904] from K = 800, 609 tiles - 140 -> 110 us: with two and a half
     // rounds of tiles the short reduction's prologue and epilogue overlap other tiles' loops)
-    static const int wide_on = [] { const char* e = getenv("TMI_GEMM_P8_WIDE"); return e ? atoi(e) : 1; }();
-    const bool wide_out = wide_on && big_tiles >= 512;
-    if (!no_p8w && force < 0 && wgrad_like && d.workspace && p8_eligible(d, true, true) && d.M * d.N >= 768 * 2304 &&
+    const bool wide_out = big_tiles >= 512;
+    if (force < 0 && wgrad_like && d.workspace && p8_eligible(d, true, true) && d.M * d.N >= 768 * 2304 &&
         (d.K >= 4096 || (wide_out && d.K >= 512)) && d.nbatch == 1 &&
         (2 * d.M * d.N * 4 <= d.workspace_bytes || big_tiles >= 192))  // (>= 192 tiles: no split, no slabs)
       return launch_p8<TC, true, true>(d, stream);
   }
-  // Eight-phase 256x256 kernel (measured, tools/gemm_p8_check.py, tools/gemm_rule_probe.py): +20 % on long
-  // reductions, ahead or level from K = 1024 (d_model 1024 / 1280 layers); with a k-strided B and K = 768
-  // its un-overlapped epilogue (one workgroup per CU) loses to the two co-resident 128x128 workgroups, so
-  // those stay where they were.
+  // 4. Eight-phase kernel for bf16-style launches with k-contiguous A (measured, tools/gemm_p8_check.py,
+  // tools/gemm_rule_probe.py): +20 % on long reductions, ahead or level from K = 1024 (d_model 1024 / 1280 layers).
   if constexpr (!A_KS) {
-    static const int no_p8 = [] { const char* e = getenv("TMI_GEMM_NO_P8"); return e ? atoi(e) : 0; }();
     const bool light_epi = !d.aux_in && !d.aux_out && !d.act && d.N <= 1024;
-    // (round 4: batched launches count their batches - the conv2 forward is 8 x [1500, 768] x K 2304 and ran 148 us on the
-    // 2-stage 256x256 kernel)
-    static const int p8_all = [] { const char* e = getenv("TMI_GEMM_P8_ALL"); return e ? atoi(e) : 0; }();  // (off: level or +0.04 ms in the step, profiles/r04_step_ab_p8_all.txt)
-    // (round 4: the LM head's forward, [800, 51904] from K = 768 - 812 tiles walked by the persistent form: 127 -> 111 us)
-    static const int wide_on = [] { const char* e = getenv("TMI_GEMM_P8_WIDE"); return e ? atoi(e) : 1; }();
-    // (round 4: batched launches count their batches - the conv2 forward is 8 x [1500, 768] x K 2304; TMI_GEMM_P8_BATCHED=0: the 128x128 kernel)
-    static const int p8_batched = [] { const char* e = getenv("TMI_GEMM_P8_BATCHED"); return e ? atoi(e) : 1; }();
-    // (>= 160 of its 192-row tiles: Wav2Vec2's conv3, 8 x [1600, 512] x K 1536 = 144 tiles, runs 38 us on the 128x128 kernel and 46 here)
+    // Rows: M >= 2048; or batched launches that count their batches (round 4: the conv2 forward is 8 x [1500, 768] x
+    // K 2304 and ran 148 us on the 2-stage 256x256 kernel) when they fill >= 160 of the 192-row tiles (Wav2Vec2's conv3,
+    // 8 x [1600, 512] x K 1536 = 144 tiles, runs 38 us on the 128x128 kernel and 46 here); or very wide outputs (round 4:
+    // the LM head's forward, [800, 51904] from K = 768 - 812 tiles walked by the persistent form: 127 -> 111 us).
+    // (Taking every M >= 1024 launch with M * nbatch >= 4096 measured level or +0.04 ms in the step:
+    // profiles/r04_step_ab_p8_all.txt.)
     const bool fills = ((d.M + 191) / 192) * ((d.N + 255) / 256) * d.nbatch >= 160;
-    const bool m_ok = d.M >= 2048 || ((p8_all || (p8_batched && d.K >= 1024 && fills)) && d.M >= 1024 && d.M * d.nbatch >= 4096) ||
-                      (wide_on && d.M >= 512 && big_tiles >= 512);
-    if (!no_p8 && force < 0 && !wgrad_like && d.splitk <= 1 && p8_eligible(d, false, B_KS) && m_ok && d.N >= 256) {
+    const bool m_ok = d.M >= 2048 || (d.K >= 1024 && fills && d.M >= 1024 && d.M * d.nbatch >= 4096) || (d.M >= 512 && big_tiles >= 512);
+    if (force < 0 && !wgrad_like && d.splitk <= 1 && p8_eligible(d, false, B_KS) && m_ok && d.N >= 256) {
       if (d.M < 1024) return launch_p8<TC, false, B_KS>(d, stream);  // (the LM head's forward: 256-row tiles measured ahead of 192)
       // 192-row tiles when they need fewer CU-rounds of work: cost = rounds of 256 workgroups x tile rows
-      static const int no192 = [] { const char* e = getenv("TMI_GEMM_NO_P8_192"); return e ? atoi(e) : 0; }();
-      // (round 4: on by default - with the lean epilogue the 192-row tile beats the two co-resident 128x128 workgroups in the step
-      // as well: fc1 forward + GELU + saved pre-activation 115 -> 95 us, fc2 dgrad + GELU' 113 -> 97 us, step 8.22 -> 8.16 ms)
-      static const int short192 = [] { const char* e = getenv("TMI_GEMM_P8_192_SHORTK"); return e ? atoi(e) : 1; }();
+      // (the 192-row loop does ~10 % less per cycle - two of its four phases issue half the MFMAs - so it has to save more
+      // than that).  Whatever K (round 4): with the lean epilogue the 192-row tile beats the two co-resident 128x128
+      // workgroups in the step as well: fc1 forward + GELU + saved pre-activation 115 -> 95 us, fc2 dgrad + GELU' 113 -> 97 us,
+      // step 8.22 -> 8.16 ms.
       const int64_t tn = (d.N + 255) / 256;
       const int64_t t256 = ((d.M + 255) / 256) * tn * d.nbatch, t192 = ((d.M + 191) / 192) * tn * d.nbatch;
       const int64_t c256 = ((t256 + 255) / 256) * 256, c192 = ((t192 + 255) / 256) * 192;
-      // (the 192-row loop does ~10 % less per cycle - two of its four phases issue half the MFMAs - so it has to save more than that)
-      const bool win192 = !no192 && c192 * 100 <= c256 * 85;
-      // (round 4, TMI_GEMM_P8_ALL=1: short K too - with the lean epilogue the eight-phase kernel wins there as well: qkv forward
-      // 12000 x 2304 x 768 65.8 us on the 2-stage 256x256 kernel in the step, 56 us here)
-      const bool long_k = p8_all || d.K >= 1024 || (!B_KS && light_epi);
-      // short K with heavy epilogues / k-strided weights (TMI_GEMM_P8_192_SHORTK=1, off): alone and with a plain epilogue the
-      // 192-row tile wins there too (fc1 forward 12000 x 3072 x 768: 100.6 -> 80.3 us), but with the real GELU + aux epilogues
-      // in the step the one-workgroup-per-CU kernel loses to two co-resident 128x128 workgroups: 9.06 -> 9.29 ms/step
-      // (=2: only the forward fc1 shape - GELU + saved pre-activation, no aux_in - which runs alone on the chip: the forward
-      // pass has no second stream beside it, so what counts there is the launch's own latency)
-      const bool fwd_only = short192 == 2 && d.act == 1 && !d.aux_in;
-      if (win192 && (long_k || short192 == 1 || fwd_only)) return launch_p8<TC, false, B_KS, 192>(d, stream);
-      if (long_k) return launch_p8<TC, false, B_KS>(d, stream);
+      if (c192 * 100 <= c256 * 85) return launch_p8<TC, false, B_KS, 192>(d, stream);
+      // 256-row tiles from K = 1024, or with k-contiguous weights and a light epilogue; with a k-strided B and K = 768 the
+      // un-overlapped epilogue (one workgroup per CU) loses to the two co-resident 128x128 workgroups, so those stay
+      // where they were.  (Short K too measured 65.8 -> 56 us alone for the qkv forward 12000 x 2304 x 768 and level in
+      // the step: profiles/r04_step_ab_p8_all.txt.)
+      if (d.K >= 1024 || (!B_KS && light_epi)) return launch_p8<TC, false, B_KS>(d, stream);
     }
   }
-  return big ? launch_cfg<TC, A_KS, B_KS, 5>(d, stream) : launch_cfg<TC, A_KS, B_KS, 4>(d, stream);
+  // 5. The 2-stage tiles.  Measured on MI355X (tools/gemm_bench.py): the 256x256 tile wins for bf16-output GEMMs with a
+  // long reduction (K >= 1536: its unoverlapped epilogue is amortised) or whose tile count fills
+  // whole rounds of the 256 CUs; weight gradients (split-K, atomic epilogue) and small problems
+  // run better on the 128x128 tile with two workgroups per CU.
+  const double round_eff = (double)big_tiles / (double)(((big_tiles + 255) / 256) * 256);
+  const bool big = d.out_dtype == TMI_BF16 && d.M >= 2048 && d.N >= 512 && (d.K * d.kbatch >= 1536 || round_eff >= 0.8);
+  return big ? launch_cfg<TC, A_KS, B_KS, Tile256x256>(d, stream) : launch_cfg<TC, A_KS, B_KS, Tile128x128>(d, stream);
 }
 
 template <bool A_KS, bool B_KS>
@@ -2019,52 +1744,13 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const FastParams P) {
 
 template <bool A_KS, bool B_KS>
 int launch_f32(const tmi_gemm_desc& d, hipStream_t stream) {
-  FastParams P;
-  P.d = d;
-  P.tiles_m = (int)((d.M + 127) / 128);
-  P.tiles_n = (int)((d.N + 127) / 128);
-  P.ktiles = (int)((d.K + 31) / 32);
-  P.a_cols_rd = (d.M + 3) / 4 * 4;
-  P.b_cols_rd = (d.N + 3) / 4 * 4;
-  P.wide = al16(d.C) && d.ldc % 4 == 0 && d.c_sb % 4 == 0 && (!d.aux_out || al16(d.aux_out)) &&
-           (!d.aux_in || al16(d.aux_in)) && (!d.resid || (al16(d.resid) && d.r_ld % 4 == 0 && d.r_sb % 4 == 0));
-  P.epi = epi_class(d, P.wide != 0);
-  static const int dbg = [] { const char* e = getenv("TMI_GEMM_DBG"); return e ? atoi(e) : 0; }();
-  P.dbg = dbg;
-  P.split_c_stride = 0;
-  P.xsplit = 0;
-  P.slots = 0;
-  P.drop_thr = tmi_drop_thr(d.dropout_p);
-  P.drop_key = tmi_stream_key(d.dropout_seed, 0u);
-  P.drop_scale = tmi_keep_scale(P.drop_thr);
+  FastParams P = fast_params(d, 128, 128, 32, 4, 4);  // (an fp32 operand share is twice the bf16 one)
   auto kern = gemm_f32_kernel<float, A_KS, B_KS>;
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
   if (attr != hipSuccess) {
     tmi_set_error("tmi_gemm(f32): cannot raise the dynamic LDS limit");
     return TMI_ERR_LAUNCH;
   }
-  // XCD partition with the fewest padded workgroups (see launch_cfg); an fp32 operand share is twice the bf16 one
-  int aim = 1;
-  while (aim < 8 && (double)d.K * (double)d.kbatch * ((double)d.N / aim) * 4.0 > 2.0 * 1048576.0 && P.tiles_n >= 2 * aim) aim *= 2;
-  int xn = aim;
-  int64_t best = -1;
-  int best_dist = 0;
-  for (int cand = 1; cand <= 8; cand *= 2) {
-    const int64_t padded = (int64_t)((P.tiles_m + 8 / cand - 1) / (8 / cand)) * ((P.tiles_n + cand - 1) / cand);
-    int dist = 0;
-    for (int v = cand; v < aim; v *= 2) ++dist;
-    for (int v = aim; v < cand; v *= 2) ++dist;
-    if (best < 0 || padded < best || (padded == best && dist < best_dist)) {
-      best = padded;
-      best_dist = dist;
-      xn = cand;
-    }
-  }
-  P.xn = xn;
-  P.xm = 8 / xn;
-  P.ptm = (P.tiles_m + P.xm - 1) / P.xm;
-  P.ptn = (P.tiles_n + P.xn - 1) / P.xn;
-  P.walk_m = walk_along_m(d, P.xm, P.xn);
   // split-K (library-chosen, weight-gradient shapes): through workspace slabs when there is a workspace, fp32 atomics else
   int splitk = d.splitk > 1 ? d.splitk : 1;
   bool ws_split = false;
@@ -2093,23 +1779,10 @@ int launch_f32(const tmi_gemm_desc& d, hipStream_t stream) {
 
 }  // namespace
 
-// diagnostics: copies the ABL == 8 phase counters (host-synchronous)
-extern "C" int tmi_debug_gemm_stamps(unsigned long long* out5) {
-  static const int epi = [] { const char* e = getenv("TMI_GEMM_DBG"); return e ? (atoi(e) & 32) : 0; }();
-  if (epi) {  // (TMI_GEMM_DBG & 32: the stamps inside wide_epilogue instead; reading them re-arms the probe)
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}, got[8];
-    if (hipMemcpyFromSymbol(got, HIP_SYMBOL(g_epi_stamps), sizeof(got)) != hipSuccess) return -2;
-    for (int i = 0; i < 5; ++i) out5[i] = got[i];
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_epi_stamps), z, sizeof(z)) == hipSuccess ? 0 : -2;
-  }
-  return hipMemcpyFromSymbol(out5, HIP_SYMBOL(g_gemm_stamps), 5 * sizeof(unsigned long long)) == hipSuccess ? 0 : -2;
-}
-
 // Returns 1 and sets *rc if the fast path took the GEMM, 0 if the generic kernel must run.
 int tmi_gemm_fast_try(const tmi_gemm_desc& d, hipStream_t stream, int* rc) {
   if (d.in_dtype == TMI_F32) {  // the parity mode's GEMMs: fp32 in, fp32 out, whole 32-float slabs, 16-byte aligned operands
-    static const int off = [] { const char* e = getenv("TMI_GEMM_F32_FAST"); return e && atoi(e) == 0; }();
-    if (off || d.out_dtype != TMI_F32 || d.K % 4 != 0 || d.K < 32 || !al16(d.A) || !al16(d.B) || d.a_sb % 4 || d.b_sb % 4 || d.a_skb % 4 ||
+    if (d.out_dtype != TMI_F32 || d.K % 4 != 0 || d.K < 32 || !al16(d.A) || !al16(d.B) || d.a_sb % 4 || d.b_sb % 4 || d.a_skb % 4 ||
         d.b_skb % 4 || d.a_sb2 % 4 || d.b_sb2 % 4 || d.M < 32 || d.N < 32 || (d.K % 32 != 0 && d.kbatch > 1 && d.splitk != 1))
       return 0;
     const bool a_kc = d.a_sk == 1 && d.a_sm % 4 == 0, b_kc = d.b_sk == 1 && d.b_sn % 4 == 0;

@@ -1,4 +1,4 @@
-# tools/gemm_epi_probe.py once per library setting (the switches are read once per process), two rounds.
+# tools/gemm_epi_probe.py once per library setting (TMI_GEMM_CFG=n is read once per process), two rounds.
 # Usage on the GPU box: bash tools/gemm_epi_ab.sh "SETTING A" "SETTING B" ...   ("default" = no variables)
 cd $GRAFT_REPO_ROOT
 for round in 1 2; do

@@ -1,7 +1,7 @@
 """The step's multi-round GEMMs (more tiles than CUs) WITH the epilogues they carry in the step: fc1 forward = bias + GELU +
 saved pre-activation, fc2 dgrad = GELU' of the saved pre-activation, qkv forward = bias + q scale, LM head; plain forms beside
-them.  Prints time per launch and the max error against torch (fp32 reference of the same bf16 operands).  Environment
-switches of the library are read once per process: run once per setting (tools/gemm_epi_ab.sh)."""
+them.  Prints time per launch and the max error against torch (fp32 reference of the same bf16 operands).  TMI_GEMM_CFG
+is read once per process: run once per setting (tools/gemm_epi_ab.sh)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,6 +1,6 @@
 """How the un-overlapped epilogue of the eight-phase kernel scales with the number of busy CUs: one tile per workgroup, N = 3072,
-K = 768, M chosen for 48 / 96 / 192 / 252 tiles (one round) and the step's 12000 (three rounds).  Run with and without
-TMI_GEMM_DBG=1 (no epilogue); TMI_GEMM_CFG=14 forces the 192 x 256 tile."""
+K = 768, M chosen for 48 / 96 / 192 / 252 tiles (one round) and the step's 12000 (three rounds).  TMI_GEMM_CFG=14 forces the
+192 x 256 tile.  (The recorded runs without the epilogue, profiles/r04_p8_ablations.txt, used a diagnostic build that is gone.)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

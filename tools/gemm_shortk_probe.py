@@ -1,6 +1,6 @@
 """Short-K (768), k-strided-weight forward launches that stay on the two-stage 256x256 kernel (CFG 5): the fused qkv projection
 [12000, 2304] and the decoder's cross k|v projection of all layers [12000, 6144], with their bias (+ q scale) epilogues.
-Library switches are read once per process: run once per setting (TMI_GEMM_P8_ALL=1, TMI_GEMM_CFG=10 / 14)."""
+TMI_GEMM_CFG is read once per process: run once per setting (default, TMI_GEMM_CFG=10 / 14 for the eight-phase kernel)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

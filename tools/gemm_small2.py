@@ -54,7 +54,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
         assert e1 < 1e-2 and e2 < 1e-2
     sys.exit(0)
 res = {}
-cfgs = ["", "12", "13", "15", "11", "6", "4"]
+cfgs = ["", "12", "13", "15", "6", "4"]
 for c in cfgs:
     env = dict(os.environ)
     if c:
@@ -69,6 +69,6 @@ for c in cfgs:
         print("cfg", c, "failed:", p.stderr[-300:])
     elif c in ("15",):
         print(p.stderr.strip())
-print(f"{'shape':36s} " + " ".join(f"{(c or 'auto'):>7s}" for c in cfgs) + "   (us; cfg 12 = 64x64 4 waves, 13 = + 4-stage ring, 15 = K-groups 2x4 waves, 4 = 128x128, 11 = 2 waves ring, 6 = 2 waves)")
+print(f"{'shape':36s} " + " ".join(f"{(c or 'auto'):>7s}" for c in cfgs) + "   (us; cfg 12 = 64x64 4 waves, 13 = + 4-stage ring, 15 = K-groups 2x4 waves, 4 = 128x128, 6 = 2 waves)")
 for k, v in res.items():
     print(f"{k:36s} " + " ".join(f"{v.get(c or 'auto', float('nan')):7.1f}" for c in cfgs))
