@@ -162,25 +162,6 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(
 static int tmi_beam_step_impl(const int32_t* cand_ids, const float* cand_lp, int64_t N, int64_t B, int64_t K, float* sums,
                               const int32_t* cur, int32_t* nxt, int64_t ld, int64_t t, int32_t eos_id, float len_pow,
                               int32_t early_stopping, int32_t* pool_ids, float* pool_scores, int32_t* pool_len,
-                              int32_t* pool_cnt, int32_t* done, int32_t* done_count, int32_t finalize, void* stream);
-extern "C" int tmi_beam_step(const int32_t* cand_ids, const float* cand_lp, int64_t N, int64_t B, int64_t K, float* sums,
-                             const int32_t* cur, int32_t* nxt, int64_t ld, int64_t t, int32_t eos_id, float len_pow,
-                             int32_t early_stopping, int32_t* pool_ids, float* pool_scores, int32_t* pool_len,
-                             int32_t* pool_cnt, int32_t* done, int32_t* done_count, int32_t finalize, void* stream) {
-  if (tmi_plan_recording())
-    tmi_plan_push([=]() -> int {
-      return tmi_beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping, pool_ids,
-                           pool_scores, pool_len, pool_cnt, done, done_count, finalize, stream);
-    });
-  tmi_plan_enter();
-  const int rc_ = tmi_beam_step_impl(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping,
-                                     pool_ids, pool_scores, pool_len, pool_cnt, done, done_count, finalize, stream);
-  tmi_plan_leave();
-  return rc_;
-}
-static int tmi_beam_step_impl(const int32_t* cand_ids, const float* cand_lp, int64_t N, int64_t B, int64_t K, float* sums,
-                              const int32_t* cur, int32_t* nxt, int64_t ld, int64_t t, int32_t eos_id, float len_pow,
-                              int32_t early_stopping, int32_t* pool_ids, float* pool_scores, int32_t* pool_len,
                               int32_t* pool_cnt, int32_t* done, int32_t* done_count, int32_t finalize, void* stream) {
   const bool step_ok = finalize ? true : (cand_ids && cand_lp && nxt && N >= 2 * K && N <= 16);
   if (!step_ok || !sums || !cur || !pool_ids || !pool_scores || !pool_len || !pool_cnt || !done || !done_count ||
@@ -193,4 +174,11 @@ static int tmi_beam_step_impl(const int32_t* cand_ids, const float* cand_lp, int
                      cand_ids, cand_lp, (int)N, (int)K, sums, cur, nxt, ld, (int)t, eos_id, len_pow, early_stopping,
                      pool_ids, pool_scores, pool_len, pool_cnt, done, done_count, finalize);
   return tmi_check_launch("tmi_beam_step");
+}
+extern "C" int tmi_beam_step(const int32_t* cand_ids, const float* cand_lp, int64_t N, int64_t B, int64_t K, float* sums,
+                             const int32_t* cur, int32_t* nxt, int64_t ld, int64_t t, int32_t eos_id, float len_pow,
+                             int32_t early_stopping, int32_t* pool_ids, float* pool_scores, int32_t* pool_len,
+                             int32_t* pool_cnt, int32_t* done, int32_t* done_count, int32_t finalize, void* stream) {
+  return tmi_plan_run<tmi_beam_step_impl>(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping,
+                                          pool_ids, pool_scores, pool_len, pool_cnt, done, done_count, finalize, stream);
 }

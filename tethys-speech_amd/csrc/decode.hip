@@ -516,25 +516,6 @@ inline bool am_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15
 static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                    float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
                                    int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
-                                   int64_t workspace_bytes, void* stream);
-extern "C" int tmi_lm_head_argmax(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                  int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
-                                  int64_t workspace_bytes, void* stream) {
-  if (tmi_plan_recording())
-    tmi_plan_push([=]() -> int {
-      return tmi_lm_head_argmax(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids, ids_ld, eos_id, eos_count,
-                                workspace, workspace_bytes, stream);
-    });
-  tmi_plan_enter();
-  const int rc_ = tmi_lm_head_argmax_impl(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids, ids_ld, eos_id,
-                                          eos_count, workspace, workspace_bytes, stream);
-  tmi_plan_leave();
-  return rc_;
-}
-static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                   int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
                                    int64_t workspace_bytes, void* stream) {
   const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
   const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
@@ -557,26 +538,14 @@ static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype,
   return am_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V, ids, ids_ld,
                             eos_id, eos_count, slots, counter);
 }
-
-static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                 float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                 float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
-                                 void* workspace, int64_t workspace_bytes, void* stream);
-extern "C" int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-  if (tmi_plan_recording())
-    tmi_plan_push([=]() -> int {
-      return tmi_lm_head_topk(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N, ids,
-                              logprobs, lse, workspace, workspace_bytes, stream);
-    });
-  tmi_plan_enter();
-  const int rc_ = tmi_lm_head_topk_impl(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N,
-                                        ids, logprobs, lse, workspace, workspace_bytes, stream);
-  tmi_plan_leave();
-  return rc_;
+extern "C" int tmi_lm_head_argmax(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                  int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  return tmi_plan_run<tmi_lm_head_argmax_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids, ids_ld,
+                                               eos_id, eos_count, workspace, workspace_bytes, stream);
 }
+
 static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
                                  float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
@@ -608,4 +577,11 @@ static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, c
                                inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys);
   return tk_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
                             inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys);
+}
+extern "C" int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return tmi_plan_run<tmi_lm_head_topk_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N,
+                                             ids, logprobs, lse, workspace, workspace_bytes, stream);
 }

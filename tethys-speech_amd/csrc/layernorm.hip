@@ -449,24 +449,20 @@ static int ln_fwd_launch(const void* x, const float* gamma, const float* beta, v
   return tmi_check_launch("tmi_layernorm_fwd");
 }
 
+static int tmi_layernorm_fwd_impl(const void* x, const float* gamma, const float* beta, void* y, float* mean,
+                                  float* rstd, int64_t rows, int64_t C, float eps, int32_t dtype, void* stream) {
+  return ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, C, eps, 0.f, 0, dtype, stream);
+}
 extern "C" int tmi_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                  float* rstd, int64_t rows, int64_t C, float eps, int32_t dtype, void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, C, eps, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, C, eps, 0.f, 0, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
+  return tmi_plan_run<tmi_layernorm_fwd_impl>(x, gamma, beta, y, mean, rstd, rows, C, eps, dtype, stream);
 }
 
 extern "C" int tmi_layernorm_dropout_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                                          int64_t rows, int64_t C, float eps, float dropout_p, uint64_t dropout_seed, int32_t dtype,
                                          void* stream) {
-  if (tmi_plan_recording())
-    tmi_plan_push([=]() -> int { return tmi_layernorm_dropout_fwd(x, gamma, beta, y, mean, rstd, rows, C, eps, dropout_p, dropout_seed + tmi_plan_seed_delta(), dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = ln_fwd_launch(x, gamma, beta, y, mean, rstd, rows, C, eps, dropout_p, dropout_seed, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
+  return tmi_plan_run<ln_fwd_launch>(x, gamma, beta, y, mean, rstd, rows, C, eps, dropout_p, tmi_plan_seed{dropout_seed}, dtype,
+                                     stream);  // (the launcher has this entry point's own parameter list)
 }
 
 static int64_t ln_bwd_blocks(int64_t rows) {
@@ -547,52 +543,32 @@ static int ln_bwd_launch(const void* dy, const void* x, const float* gamma, cons
 
 static int tmi_layernorm_bwd_impl(const void* dy, const void* x, const float* gamma, const float* mean,
                                  const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
-                                 int32_t accumulate_dx, float* workspace, int64_t workspace_bytes, int32_t dtype, void* stream);
-extern "C" int tmi_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
-                                 const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
-                                 int32_t accumulate_dx, float* workspace, int64_t workspace_bytes, int32_t dtype, void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, workspace, workspace_bytes, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = tmi_layernorm_bwd_impl(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, workspace, workspace_bytes, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
-}
-static int tmi_layernorm_bwd_impl(const void* dy, const void* x, const float* gamma, const float* mean,
-                                 const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
                                  int32_t accumulate_dx, float* workspace, int64_t workspace_bytes, int32_t dtype, void* stream) {
   return ln_bwd_launch(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, nullptr, nullptr, 0.f, 0, dtype, stream,
                        "tmi_layernorm_bwd", workspace, workspace_bytes);
 }
+extern "C" int tmi_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
+                                 const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
+                                 int32_t accumulate_dx, float* workspace, int64_t workspace_bytes, int32_t dtype, void* stream) {
+  return tmi_plan_run<tmi_layernorm_bwd_impl>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, workspace,
+                                              workspace_bytes, dtype, stream);
+}
 
+static int tmi_layernorm_dropout_bwd_impl(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
+                                          void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C, int32_t accumulate_dx,
+                                          float dropout_p, uint64_t dropout_seed, float* workspace, int64_t workspace_bytes,
+                                          int32_t dtype, void* stream) {
+  return ln_bwd_launch(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, nullptr, nullptr, 0.f, 0, dtype,
+                       stream, "tmi_layernorm_dropout_bwd", workspace, workspace_bytes, dropout_p, dropout_seed);
+}
 extern "C" int tmi_layernorm_dropout_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
                                          void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C, int32_t accumulate_dx,
                                          float dropout_p, uint64_t dropout_seed, float* workspace, int64_t workspace_bytes,
                                          int32_t dtype, void* stream) {
-  if (tmi_plan_recording())
-    tmi_plan_push([=]() -> int { return tmi_layernorm_dropout_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, dropout_p, dropout_seed + tmi_plan_seed_delta(), workspace, workspace_bytes, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = ln_bwd_launch(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, nullptr, nullptr, 0.f, 0, dtype,
-                                stream, "tmi_layernorm_dropout_bwd", workspace, workspace_bytes, dropout_p, dropout_seed);
-  tmi_plan_leave();
-  return rc_;
+  return tmi_plan_run<tmi_layernorm_dropout_bwd_impl>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, dropout_p,
+                                                      tmi_plan_seed{dropout_seed}, workspace, workspace_bytes, dtype, stream);
 }
 
-static int tmi_layernorm_bwd_emit_impl(const void* dy, const void* x, const float* gamma, const float* mean,
-                                      const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
-                                      int32_t accumulate_dx, float* colsum, void* masked, float dropout_p,
-                                      uint64_t dropout_seed, float* workspace, int64_t workspace_bytes, int32_t dtype,
-                                      void* stream);
-extern "C" int tmi_layernorm_bwd_emit(const void* dy, const void* x, const float* gamma, const float* mean,
-                                      const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
-                                      int32_t accumulate_dx, float* colsum, void* masked, float dropout_p,
-                                      uint64_t dropout_seed, float* workspace, int64_t workspace_bytes, int32_t dtype,
-                                      void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_layernorm_bwd_emit(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, colsum, masked, dropout_p, dropout_seed + tmi_plan_seed_delta(), workspace, workspace_bytes, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = tmi_layernorm_bwd_emit_impl(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, colsum, masked, dropout_p, dropout_seed, workspace, workspace_bytes, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
-}
 static int tmi_layernorm_bwd_emit_impl(const void* dy, const void* x, const float* gamma, const float* mean,
                                       const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
                                       int32_t accumulate_dx, float* colsum, void* masked, float dropout_p,
@@ -605,17 +581,16 @@ static int tmi_layernorm_bwd_emit_impl(const void* dy, const void* x, const floa
   return ln_bwd_launch(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, colsum, masked, dropout_p, dropout_seed,
                        dtype, stream, "tmi_layernorm_bwd_emit", workspace, workspace_bytes);
 }
-
-static int tmi_colsum_batched_impl(const void* dy, int64_t ld, int64_t dy_sb, float* out, int64_t out_sb, int64_t rows, int64_t N,
-                                  int64_t nbatch, int32_t dtype, void* stream);
-extern "C" int tmi_colsum_batched(const void* dy, int64_t ld, int64_t dy_sb, float* out, int64_t out_sb, int64_t rows, int64_t N,
-                                  int64_t nbatch, int32_t dtype, void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_colsum_batched(dy, ld, dy_sb, out, out_sb, rows, N, nbatch, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = tmi_colsum_batched_impl(dy, ld, dy_sb, out, out_sb, rows, N, nbatch, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
+extern "C" int tmi_layernorm_bwd_emit(const void* dy, const void* x, const float* gamma, const float* mean,
+                                      const float* rstd, void* dx, float* dgamma, float* dbeta, int64_t rows, int64_t C,
+                                      int32_t accumulate_dx, float* colsum, void* masked, float dropout_p,
+                                      uint64_t dropout_seed, float* workspace, int64_t workspace_bytes, int32_t dtype,
+                                      void* stream) {
+  return tmi_plan_run<tmi_layernorm_bwd_emit_impl>(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, rows, C, accumulate_dx, colsum,
+                                                   masked, dropout_p, tmi_plan_seed{dropout_seed}, workspace, workspace_bytes,
+                                                   dtype, stream);
 }
+
 static int tmi_colsum_batched_impl(const void* dy, int64_t ld, int64_t dy_sb, float* out, int64_t out_sb, int64_t rows, int64_t N,
                                   int64_t nbatch, int32_t dtype, void* stream) {
   const int vec = dtype == TMI_BF16 ? 8 : 4;
@@ -640,32 +615,20 @@ static int tmi_colsum_batched_impl(const void* dy, int64_t ld, int64_t dy_sb, fl
     return TMI_ERR_UNSUPPORTED;
   return tmi_check_launch("tmi_colsum");
 }
-
-static int tmi_colsum_impl(const void* dy, int64_t ld, float* out, int64_t rows, int64_t N, int32_t dtype,
-                          void* stream);
-extern "C" int tmi_colsum(const void* dy, int64_t ld, float* out, int64_t rows, int64_t N, int32_t dtype,
-                          void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_colsum(dy, ld, out, rows, N, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = tmi_colsum_impl(dy, ld, out, rows, N, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
+extern "C" int tmi_colsum_batched(const void* dy, int64_t ld, int64_t dy_sb, float* out, int64_t out_sb, int64_t rows, int64_t N,
+                                  int64_t nbatch, int32_t dtype, void* stream) {
+  return tmi_plan_run<tmi_colsum_batched_impl>(dy, ld, dy_sb, out, out_sb, rows, N, nbatch, dtype, stream);
 }
+
 static int tmi_colsum_impl(const void* dy, int64_t ld, float* out, int64_t rows, int64_t N, int32_t dtype,
                           void* stream) {
   return tmi_colsum_batched(dy, ld, 0, out, 0, rows, N, 1, dtype, stream);
 }
-
-static int tmi_gelu_bwd_batched_impl(const void* dy, const void* u, void* dx, int64_t n, int64_t nbatch, int64_t dy_sb,
-                                    int64_t u_sb, int64_t dx_sb, int32_t dtype, void* stream);
-extern "C" int tmi_gelu_bwd_batched(const void* dy, const void* u, void* dx, int64_t n, int64_t nbatch, int64_t dy_sb,
-                                    int64_t u_sb, int64_t dx_sb, int32_t dtype, void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_gelu_bwd_batched(dy, u, dx, n, nbatch, dy_sb, u_sb, dx_sb, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = tmi_gelu_bwd_batched_impl(dy, u, dx, n, nbatch, dy_sb, u_sb, dx_sb, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
+extern "C" int tmi_colsum(const void* dy, int64_t ld, float* out, int64_t rows, int64_t N, int32_t dtype,
+                          void* stream) {
+  return tmi_plan_run<tmi_colsum_impl>(dy, ld, out, rows, N, dtype, stream);
 }
+
 static int tmi_gelu_bwd_batched_impl(const void* dy, const void* u, void* dx, int64_t n, int64_t nbatch, int64_t dy_sb,
                                     int64_t u_sb, int64_t dx_sb, int32_t dtype, void* stream) {
   const int vec = dtype == TMI_BF16 ? 8 : 4;
@@ -690,15 +653,14 @@ static int tmi_gelu_bwd_batched_impl(const void* dy, const void* u, void* dx, in
     return TMI_ERR_UNSUPPORTED;
   return tmi_check_launch("tmi_gelu_bwd");
 }
-
-static int tmi_gelu_bwd_impl(const void* dy, const void* u, void* dx, int64_t n, int32_t dtype, void* stream);
-extern "C" int tmi_gelu_bwd(const void* dy, const void* u, void* dx, int64_t n, int32_t dtype, void* stream) {
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_gelu_bwd(dy, u, dx, n, dtype, stream); });
-  tmi_plan_enter();
-  const int rc_ = tmi_gelu_bwd_impl(dy, u, dx, n, dtype, stream);
-  tmi_plan_leave();
-  return rc_;
+extern "C" int tmi_gelu_bwd_batched(const void* dy, const void* u, void* dx, int64_t n, int64_t nbatch, int64_t dy_sb,
+                                    int64_t u_sb, int64_t dx_sb, int32_t dtype, void* stream) {
+  return tmi_plan_run<tmi_gelu_bwd_batched_impl>(dy, u, dx, n, nbatch, dy_sb, u_sb, dx_sb, dtype, stream);
 }
+
 static int tmi_gelu_bwd_impl(const void* dy, const void* u, void* dx, int64_t n, int32_t dtype, void* stream) {
   return tmi_gelu_bwd_batched(dy, u, dx, n, 1, 0, 0, 0, dtype, stream);
+}
+extern "C" int tmi_gelu_bwd(const void* dy, const void* u, void* dx, int64_t n, int32_t dtype, void* stream) {
+  return tmi_plan_run<tmi_gelu_bwd_impl>(dy, u, dx, n, dtype, stream);
 }

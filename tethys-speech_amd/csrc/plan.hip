@@ -6,13 +6,14 @@
 // 5-100 us kernels; issuing each from Python costs 9-25 us of host time per launch (ctypes + descriptor marshalling), so
 // the decoder-sized chains wait for the host.  hipGraph is not the answer on ROCm 7.2 (a replay of the ~430-node graph
 // costs the host as much as the eager launches, tools/graph_check.py), so the plan is the library's own: while a plan is
-// recording, every launching entry point appends a closure of ITSELF with its arguments copied by value (descriptors
-// included) and then runs as usual, so the recorded step is a real step; a replay walks the closures - the same entry
-// points, the same argument checks, the same dispatch rules, one hipLaunchKernel each, no Python.
+// recording, every launching entry point appends a closure of its implementation with its arguments copied by value
+// (descriptors included) and then runs as usual (tmi_plan_run in tmi_common.h), so the recorded step is a real step; a
+// replay walks the closures - the same implementations, the same argument checks, the same dispatch rules, one
+// hipLaunchKernel each, no Python.
 //
 // What changes from step to step is patched at replay time, not re-recorded:
 //   - dropout seeds: every site seed is base + step * K + site * K' (blocks.KernelBlocks._site_seed), so a replay adds
-//     `seed_delta` = (step_now - step_recorded) * K to every recorded seed (tmi_plan_seed_delta(), read by the closures);
+//     `seed_delta` = (step_now - step_recorded) * K to every recorded seed (tmi_plan_seed_delta(), read by the closures only);
 //   - the Adam step number: `step_delta` is added to the recorded `step` argument of tmi_adam_step*.
 // Events and cross-stream waits of the step (the weight-gradient stream, the early / late Adam slices) are recorded
 // through tmi_plan_note_event_record / tmi_plan_note_stream_wait (the host code's own event objects: the handles stay
@@ -131,34 +132,41 @@ extern "C" int tmi_plan_replay(tmi_plan* p, uint64_t seed_delta, int64_t step_de
 
 // Fill / copy as entry points of their own, so that the handful of memsets and copies a step makes between its kernels
 // are part of the plan (torch's fill_ / copy_ would run while recording and silently be missing from every replay).
+// These three check their arguments first and record second: a rejected fill or copy is not part of the plan.
+static int memset_impl(void* dst, int32_t value, int64_t bytes, void* stream) {
+  if (bytes == 0) return TMI_OK;
+  return hipMemsetAsync(dst, value, (size_t)bytes, reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? TMI_OK : TMI_ERR_LAUNCH;
+}
 extern "C" int tmi_memset_async(void* dst, int32_t value, int64_t bytes, void* stream) {
   if (!dst || bytes < 0) {
     tmi_set_error("tmi_memset_async: bad argument");
     return TMI_ERR_INVALID;
   }
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_memset_async(dst, value, bytes, stream); });
-  if (bytes == 0) return TMI_OK;
-  return hipMemsetAsync(dst, value, (size_t)bytes, reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? TMI_OK : TMI_ERR_LAUNCH;
+  return tmi_plan_run<memset_impl>(dst, value, bytes, stream);
 }
 
+static int memset2d_impl(void* dst, int64_t pitch_bytes, int32_t value, int64_t width_bytes, int64_t rows, void* stream) {
+  if (width_bytes == 0 || rows == 0) return TMI_OK;
+  return hipMemset2DAsync(dst, (size_t)pitch_bytes, value, (size_t)width_bytes, (size_t)rows, reinterpret_cast<hipStream_t>(stream)) == hipSuccess
+             ? TMI_OK : TMI_ERR_LAUNCH;
+}
 extern "C" int tmi_memset2d_async(void* dst, int64_t pitch_bytes, int32_t value, int64_t width_bytes, int64_t rows, void* stream) {
   if (!dst || width_bytes < 0 || rows < 0 || pitch_bytes < width_bytes) {
     tmi_set_error("tmi_memset2d_async: bad argument");
     return TMI_ERR_INVALID;
   }
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_memset2d_async(dst, pitch_bytes, value, width_bytes, rows, stream); });
-  if (width_bytes == 0 || rows == 0) return TMI_OK;
-  return hipMemset2DAsync(dst, (size_t)pitch_bytes, value, (size_t)width_bytes, (size_t)rows, reinterpret_cast<hipStream_t>(stream)) == hipSuccess
-             ? TMI_OK : TMI_ERR_LAUNCH;
+  return tmi_plan_run<memset2d_impl>(dst, pitch_bytes, value, width_bytes, rows, stream);
 }
 
+static int memcpy_impl(void* dst, const void* src, int64_t bytes, void* stream) {
+  if (bytes == 0) return TMI_OK;
+  return hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? TMI_OK
+                                                                                                                              : TMI_ERR_LAUNCH;
+}
 extern "C" int tmi_memcpy_async(void* dst, const void* src, int64_t bytes, void* stream) {
   if (!dst || !src || bytes < 0) {
     tmi_set_error("tmi_memcpy_async: bad argument");
     return TMI_ERR_INVALID;
   }
-  if (tmi_plan_recording()) tmi_plan_push([=]() -> int { return tmi_memcpy_async(dst, src, bytes, stream); });
-  if (bytes == 0) return TMI_OK;
-  return hipMemcpyAsync(dst, src, (size_t)bytes, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(stream)) == hipSuccess ? TMI_OK
-                                                                                                                              : TMI_ERR_LAUNCH;
+  return tmi_plan_run<memcpy_impl>(dst, src, bytes, stream);
 }

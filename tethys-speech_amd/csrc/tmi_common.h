@@ -20,15 +20,62 @@ void tmi_set_error(const char* msg);
 int tmi_check_launch(const char* what);
 int tmi_deterministic();  // runtime.hip: tmi_set_deterministic
 
-// Launch plans (plan.hip).  Every launching entry point is a thin wrapper around its `_impl`: while this thread records a
-// plan (and is not already inside another entry point) the wrapper appends a closure that calls the entry point again
-// with the same arguments - copied by value, per-step ones (dropout seeds, the Adam step) offset by the replay's deltas.
+// Launch plans (plan.hip).  To make a new entry point recordable:
+//   1. write its body as `static int tmi_foo_impl(<the entry point's parameters>)`, above the entry point;
+//   2. make the entry point the one statement `return tmi_plan_run<tmi_foo_impl>(<its parameters>);`
+//      (tmi_plan_run_desc<tmi_foo_impl>(desc, stream) when it takes a descriptor with dropout_p / dropout_seed);
+//   3. wrap what changes from step to step at that call: tmi_plan_seed{dropout_seed}, tmi_plan_step{step}.
+// While this thread records a plan (and is not already inside another entry point: a nested entry point is part of its
+// caller's closure) tmi_plan_run appends a closure of the implementation with the arguments copied by value, BEFORE the
+// implementation looks at them, so a rejected call is recorded too and its replay returns the same error.  A tagged
+// argument is the plain value in the direct call - also one made from a callback node in the middle of a replay - and
+// value + the replay's delta in the closure only.  Off the record the helper is two counter updates around the call.
 bool tmi_plan_recording();
 void tmi_plan_push(std::function<int()> fn);
 void tmi_plan_enter();
 void tmi_plan_leave();
 uint64_t tmi_plan_seed_delta();
 int64_t tmi_plan_step_delta();
+
+struct tmi_plan_seed { uint64_t v; };  // a dropout seed
+struct tmi_plan_step { int32_t v; };   // an Adam step number
+template <typename T> inline T tmi_plan_direct(T a) { return a; }
+inline uint64_t tmi_plan_direct(tmi_plan_seed s) { return s.v; }
+inline int32_t tmi_plan_direct(tmi_plan_step s) { return s.v; }
+template <typename T> inline T tmi_plan_replayed(T a) { return a; }
+inline uint64_t tmi_plan_replayed(tmi_plan_seed s) { return s.v + tmi_plan_seed_delta(); }
+inline int32_t tmi_plan_replayed(tmi_plan_step s) { return (int32_t)(s.v + tmi_plan_step_delta()); }
+
+struct tmi_plan_scope {  // inside an entry point
+  tmi_plan_scope() { tmi_plan_enter(); }
+  ~tmi_plan_scope() { tmi_plan_leave(); }
+  tmi_plan_scope(const tmi_plan_scope&) = delete;
+  tmi_plan_scope& operator=(const tmi_plan_scope&) = delete;
+};
+
+template <auto impl, typename... A> inline int tmi_plan_run(A... a) {
+  if (tmi_plan_recording())
+    tmi_plan_push([=]() -> int {
+      tmi_plan_scope in;
+      return impl(tmi_plan_replayed(a)...);
+    });
+  tmi_plan_scope in;
+  return impl(tmi_plan_direct(a)...);
+}
+
+// The descriptor form (tmi_gemm, tmi_attn_fwd, tmi_attn_bwd): the closure holds a copy of the descriptor, and a replay
+// moves its dropout_seed only where the call draws a mask.  A null descriptor is rejected by the implementation, unrecorded.
+template <auto impl, typename D> inline int tmi_plan_run_desc(const D* dp, void* stream) {
+  if (tmi_plan_recording() && dp)
+    tmi_plan_push([c = *dp, stream]() -> int {
+      D d = c;
+      if (d.dropout_p > 0.f) d.dropout_seed += tmi_plan_seed_delta();
+      tmi_plan_scope in;
+      return impl(&d, stream);
+    });
+  tmi_plan_scope in;
+  return impl(dp, stream);
+}
 
 template <typename T> struct tmi_type;
 template <> struct tmi_type<float> { static constexpr int id = TMI_F32; };
