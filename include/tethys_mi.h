@@ -348,6 +348,38 @@ int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, const float* 
                      void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Sampled decoding's next token (whisper.py generate, do_sample): tmi_lm_head_argmax's LayerNorm and LM head, then per
+ * row r of the M rows
+ *   s[n]  = z[n] / temperature  (n < V),  s[suppress_id] = -inf    (suppress_id -1: none)
+ *   lse   = log sum_n exp(s[n])                                    (tmi_lm_head_topk's fixed-order fold)
+ *   rk    = the dropout generator's row key of (stream key of seed and stream 0, row r), csrc/tmi_common.h;
+ *   bits(c) = mix32(rk.a ^ mix32(c ^ rk.b))                        (mix32: the "lowbias32" finaliser)
+ *   u(c)  = ((bits(c) >> 8) + 0.5) * 2^-24                          (never 0 or 1)
+ * top_k == 0 (top_p must be 1): Gumbel-max over the vocabulary,
+ *   token = argmax_n (s[n] - log(-log(u(n))))                      (fp32; ties: the smaller column)
+ * 1 <= top_k <= 64: candidates c_0 .. c_{k-1} = the k largest z (ties: the smaller column first; every column that can
+ *   be drawn when there are fewer than top_k), p_i = exp(s[c_i] - lse), P_j = p_0 + .. + p_j (fp32, in index order),
+ *   m = the smallest m >= 1 with P_{m-1} >= top_p * P_{k-1} (top_p == 1: m = k),
+ *   token = c_j for the smallest j < m with P_j > u(0xFFFFFFFF) * P_{m-1}, else c_{m-1}.
+ *   top_k == 1 is exactly tmi_lm_head_argmax's token.  Ranking on z instead of s is deliberate: s = z / temperature
+ *   is monotone in z, so the two orders differ only where two different z round to one fp32 s, and there the larger z
+ *   goes first (not the smaller column): the finer order, and the one that makes top_k == 1 greedy at every temperature.
+ * A row in which no column can be drawn (V == 1 and that column suppressed) writes pad_id and logprob 0.
+ * ids[r * ids_ld] = token, logprob[r] = s[token] - lse (the unfiltered tempered distribution; logprob may be NULL).
+ * finished[M] (int32, in and out): a row with finished[r] != 0 writes pad_id and logprob 0; a row that draws eos_id sets
+ * finished[r] = 1.  n_finished[0] = the number of nonzero finished[] after the call.  The result does not depend on the
+ * order in which workgroups finish.  temperature finite and > 0; 0 < top_p <= 1; V <= 65536; x, gamma/beta, w and the
+ * LDS bound as for tmi_lm_head_topk.  `workspace`: >= tmi_lm_head_sample_workspace_bytes(M, V, top_k) bytes (-1 for
+ * sizes the kernel refuses), 8-byte aligned, ZERO before the first call and left zero by every call.
+ */
+int64_t tmi_lm_head_sample_workspace_bytes(int64_t M, int64_t V, int64_t top_k);
+int tmi_lm_head_sample(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                       const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, float temperature,
+                       int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id, int32_t eos_id, int32_t pad_id,
+                       int32_t* finished, int32_t* ids, int64_t ids_ld, float* logprob, int32_t* n_finished,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * One step of beam search's bookkeeping (the rule of whisper.py generate / INTEGRATION.md), one workgroup per batch item
  * b of B; row r = b * K + k is beam k (1 <= K <= 8).  Step t (finalize = 0; 2K <= N <= 16):
  *   candidates (k, cand_ids[r * N + j], sums[r] + cand_lp[r * N + j]) (fp32 add), ranked by score desc then (k, id) asc;

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Inference job: greedy or beam-search transcription with a Whisper model (the reference's ``transcribe_audio`` / ``generate``,
+"""Inference job: greedy, beam-search or sampled transcription with a Whisper model (the reference's ``transcribe_audio`` / ``generate``,
 speech_jobs/whisper_dist.py W:962-986 / W:636-709, which its job scripts never call).
 
 Loads a checkpoint (``--resume_from``: a ``save_checkpoint`` or ``save_weights`` file; without one the model keeps its
 seeded initialisation), turns each ``--wav`` clip (16-bit PCM mono 16 kHz) or, without one, ``--batch_size`` copies of
 the reference's seeded 30 s dummy clip into log-mel features on the GPU, and decodes them greedily or, with
-``--num_beams`` > 1, by beam search.  Prints one JSON line per returned sequence, {"clip", "ids", "n_tokens"} (ids start
+``--num_beams`` > 1, by beam search, or with ``--do_sample`` by seeded sampling (``--temperature --top_k --top_p
+--min_length --seed``; adds "logprob", the sum of the tokens' log-probabilities).  Prints one JSON line per returned sequence, {"clip", "ids", "n_tokens"} (ids start
 with the decoder start token; beam search adds "rank" and "score"), then one timing line.  No tokenizer ships
 with the project, so the output is token ids.
 """
@@ -31,7 +32,15 @@ def main(argv=None):
     parser.add_argument("--num_beams", type=int, default=1, help="1: greedy; 2 to 8: beam search")
     parser.add_argument("--length_penalty", type=float, default=1.0, help="beam search: score = sum log p / length ** this")
     parser.add_argument("--num_return_sequences", type=int, default=1, help="beam search: hypotheses per clip (<= num_beams)")
+    parser.add_argument("--do_sample", action="store_true", help="sampled decoding (not with --num_beams > 1)")
+    parser.add_argument("--temperature", type=float, default=1.0, help="sampling: the logits are divided by this")
+    parser.add_argument("--top_k", type=int, default=50, help="sampling: keep the k largest (0: no filter; at most 64)")
+    parser.add_argument("--top_p", type=float, default=1.0, help="sampling: nucleus mass within the top_k, in (0, 1]")
+    parser.add_argument("--min_length", type=int, default=0, help="sampling: no end-of-text in the first this many tokens")
+    parser.add_argument("--seed", type=int, default=0, help="sampling: the seed (a seeded run repeats)")
     args = parser.parse_args(argv)
+    if args.do_sample and args.num_beams > 1:
+        parser.error("--do_sample does not go with --num_beams > 1")
 
     import numpy as np
     import torch
@@ -44,7 +53,12 @@ def main(argv=None):
     device = f"cuda:{local_rank}"
     model = whisper.create_whisper_model(args.model_type, device=device, precision=args.precision)
     beam = args.num_beams > 1
-    if beam:
+    sample = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                  min_length=args.min_length, seed=args.seed) if args.do_sample else None
+    if sample:
+        whisper.check_sample_args(model.config, args.max_length, args.num_beams, args.temperature, args.top_k, args.top_p,
+                                  args.min_length)
+    elif beam:
         whisper.check_beam_args(model.config, args.max_length, args.num_beams, 1.0, args.length_penalty,
                                 args.num_return_sequences)
     else:
@@ -65,6 +79,14 @@ def main(argv=None):
         groups.setdefault(len(wav), []).append((name, wav))
     for items in groups.values():
         wave = torch.from_numpy(np.stack([w for _, w in items])).to(device)
+        if sample:
+            out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample)
+            seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
+            for (name, _), row, sc, n in zip(items, seqs, scores, lens):
+                n_tok += int(n)
+                print(json.dumps({"clip": name, "ids": row[:1 + int(n)].tolist(), "n_tokens": int(n), "logprob": float(sc)}),
+                      flush=True)
+            continue
         if not beam:
             ids = model.generate(fe(wave), max_length=args.max_length).cpu()
             for (name, _), row in zip(items, ids):

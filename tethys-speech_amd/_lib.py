@@ -136,11 +136,15 @@ SIGNATURES = {
                                    c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "tmi_lm_head_topk": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32,
                                  c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "tmi_lm_head_sample_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "tmi_lm_head_sample": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32,
+                                   c_i64, c_f32, C.c_uint64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
+                                   c_vp]),
     "tmi_beam_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
 }
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 _lib = None
 
 

@@ -509,6 +509,325 @@ int tk_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int
   return TMI_ERR_INVALID;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Sampled decoding's LM head: tmi_lm_head_sample.  The same body again (am_head_tile) with a choice rule on top; the rule
+// is include/tethys_mi.h's.  The keys carry z, not z / temperature: dividing by a positive temperature keeps the order and
+// can only merge neighbours, so ranking on z is the finer order - and top_k = 1 is the argmax kernel's token at every
+// temperature.
+//
+// top_k >= 1.  Per workgroup and row: the (max, sum) partial of s = z / temperature and the top_k best keys of its 128
+// columns (the top-k kernel's rounds; lane g keeps rounds g, g + 16, g + 32, g + 48), plain stores into the row's slots.
+// The last workgroup of a row tile works one wave per row: the logsumexp fold of the top-k kernel; tau = the top_k-th
+// largest list head by a radix select over the heads in registers (64 ballots of 8 compares: no cross-lane traffic);
+// the at most top_k lists whose head is >= tau - no other list can hold one of the top_k keys - get one lane each; a
+// top_k-round tournament over those lanes' heads (a wave max per round; the winner's lane pops its list, which it holds
+// four keys at a time) leaves candidate j in lane j, so nothing like the top-k kernel's N * N gather exists at 64.
+// Then p_j = exp(s_j - lse), the running sums in index order (through LDS: lane j adds p_0 .. p_j itself, one order for
+// every lane), the nucleus size and the inverse-CDF draw as two ballots.
+//
+// top_k == 0 (Gumbel-max over the whole vocabulary).  Per workgroup and row: the (max, sum) partial, and the best key of
+// s + g over its columns together with that column's unperturbed s (list slots 0 and 1).  The last workgroup takes the
+// largest key - a max, so the arrival order cannot matter - and writes s - lse of its column.
+//
+// The last workgroup of the LAST tile to finish (a second counter) counts the finished rows.
+constexpr int SM_MAXK = 64;
+
+__device__ __forceinline__ uint64_t sm_key(float z, int col) {
+  return ((uint64_t)am_order(z) << 32) | (uint64_t)(~(uint32_t)col);
+}
+
+// -log(u) of the uniform u = (n + 0.5) * 2^-24, n < 2^24.  u has 25 significant bits from n = 2^23 on, where fp32 would
+// round it (n = 2^24 - 1 to 1.0: an infinite Gumbel); there 1 - u = (2^24 - 1 - n + 0.5) * 2^-24 is exact instead.
+__device__ __forceinline__ float sm_neglog_u(uint32_t n) {
+  if (n < (1u << 23)) return -logf(((float)n + 0.5f) * 0x1p-24f);
+  return -log1pf(-(((float)(0xFFFFFFu - n) + 0.5f) * 0x1p-24f));
+}
+
+// grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128, 512) floats
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_sample_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float temperature, int top_k, float top_p,
+    uint32_t stream_key, int suppress_id, int eos_id, int pad_id, int32_t* __restrict__ finished, int32_t* __restrict__ ids,
+    int64_t ids_ld, float* __restrict__ out_lp, int32_t* __restrict__ n_finished, uint32_t* __restrict__ counters,
+    float2* __restrict__ part, uint64_t* __restrict__ keys) {
+  extern __shared__ __attribute__((aligned(16))) float am_lds[];
+  __shared__ int sm_last, sm_count;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.y * MT;
+  const int rows = min(MT, M - row0);
+  const int nwg = gridDim.x;
+  const int KL = top_k > 0 ? top_k : 2;  // list slots per (row, workgroup)
+  am_head_tile<TW, MT>(am_lds, xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, d, V, row0, rows);
+  const float* red = am_lds;
+
+  // ---- per row (16 lanes of 8 columns): the (max, sum) partial and the workgroup's list
+  {
+    const int m = tid >> 4, g = tid & 15;
+    if (m < rows) {
+      const int r = row0 + m;
+      const int c0 = blockIdx.x * AM_COLS + g * 8;
+      float s[8];
+      uint64_t k8[8];
+      bool ok[8];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int o = m * AM_COLS + g * 8 + c;
+        const float z = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
+        s[c] = __fdiv_rn(z, temperature);
+        ok[c] = c0 + c < V && c0 + c != suppress_id;
+        k8[c] = ok[c] ? sm_key(z, c0 + c) : 0;
+        if (ok[c]) mx = fmaxf(mx, s[c]);
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) se += (ok[c] && mx > -INFINITY) ? expf(s[c] - mx) : 0.f;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) se += __shfl_xor(se, o, 64);  // (xor pairs: both lanes add the same two values)
+      if (g == 0) part[(int64_t)r * nwg + blockIdx.x] = make_float2(mx, se);
+      uint64_t* list = keys + ((int64_t)r * nwg + blockIdx.x) * KL;
+
+      if (top_k > 0) {
+        // top_k rounds: the best remaining key goes to lane round % 16, slot round / 16 (0 once the columns run out)
+        uint64_t mine[SM_MAXK / 16] = {0, 0, 0, 0};
+        bool more = true;
+#pragma unroll
+        for (int q = 0; q < SM_MAXK / 16; ++q) {
+          for (int rr = 0; rr < 16 && more && q * 16 + rr < top_k; ++rr) {
+            uint64_t best = 0;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) best = k8[c] > best ? k8[c] : best;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) {
+              const uint64_t other = __shfl_xor(best, o, 64);
+              best = other > best ? other : best;
+            }
+#pragma unroll
+            for (int c = 0; c < 8; ++c) k8[c] = k8[c] == best ? 0 : k8[c];
+            if (rr == g) mine[q] = best;
+            more = best != 0;  // (the same in all 16 lanes)
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < SM_MAXK / 16; ++q)
+          if (q * 16 + g < top_k) list[q * 16 + g] = mine[q];
+      } else {
+        const tmi_rowkey rk = tmi_row_key(stream_key, (uint32_t)r);
+        uint64_t best = 0;
+        float best_s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+          if (!ok[c]) continue;
+          const float gum = -logf(sm_neglog_u(tmi_sample_bits(rk, (uint32_t)(c0 + c)) >> 8));
+          const uint64_t key = sm_key(s[c] + gum, c0 + c);
+          if (key > best) best = key, best_s = s[c];
+        }
+        uint64_t all = best;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+          const uint64_t other = __shfl_xor(all, o, 64);
+          all = other > all ? other : all;
+        }
+        if (all != 0 && all == best) {  // (keys are distinct: one lane)
+          list[0] = best;
+          list[1] = (uint64_t)__float_as_uint(best_s);
+        }
+      }
+    }
+  }
+
+  // ---- completion: the last workgroup of the row tile publishes and cleans up
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t prev = __hip_atomic_fetch_add(counters + blockIdx.y, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    sm_last = prev == (uint32_t)nwg - 1;
+  }
+  __syncthreads();
+  if (!sm_last) return;
+  __threadfence();
+  int* sl = reinterpret_cast<int*>(am_lds) + wave * 128;  // this wave's live lists ...
+  float* pl = am_lds + wave * 128 + 64;                   // ... and its candidates' probabilities
+  for (int m = wave; m < rows; m += 4) {
+    const int r = row0 + m;
+    uint64_t* list = keys + (int64_t)r * nwg * KL;
+    uint64_t head[TK_HEADS];
+#pragma unroll
+    for (int i = 0; i < TK_HEADS; ++i) {
+      const int wg = lane + 64 * i;
+      head[i] = wg < nwg ? list[(int64_t)wg * KL] : 0;
+    }
+    // logsumexp: fixed order, whatever the arrival order was (the top-k kernel's fold)
+    float am = -INFINITY, as = 0.f;
+    for (int wg = lane; wg < nwg; wg += 64) {
+      float2* p = part + (int64_t)r * nwg + wg;
+      const float2 v = *p;
+      tk_fold(am, as, v.x, v.y);
+      *p = make_float2(0.f, 0.f);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
+      if (lane & o) {  // the lower lane's pair first, in both lanes
+        float lm = om, ls = os;
+        tk_fold(lm, ls, am, as);
+        am = lm, as = ls;
+      } else {
+        tk_fold(am, as, om, os);
+      }
+    }
+    const float lse = am + logf(as);
+    const bool was_finished = finished[r] != 0;
+    int token = pad_id;
+    float lp = 0.f;
+
+    if (was_finished) {
+      // (nothing to choose; the slots are still cleaned below)
+    } else if (top_k == 0) {
+      uint64_t best = 0;
+#pragma unroll
+      for (int i = 0; i < TK_HEADS; ++i) best = head[i] > best ? head[i] : best;
+      const uint64_t all = tk_wave_max(best);
+      float s_tok = 0.f;
+#pragma unroll
+      for (int i = 0; i < TK_HEADS; ++i)
+        if (all != 0 && head[i] == all) s_tok = __uint_as_float((uint32_t)list[(int64_t)(lane + 64 * i) * KL + 1]);
+      s_tok = wave_sum(s_tok);  // (one lane holds it, the others 0)
+      if (all != 0) {  // (0: no column can be drawn - V == 1 and it is suppressed - and the row writes pad, as below)
+        token = (int32_t)(~(uint32_t)all);
+        lp = s_tok - lse;
+      }
+    } else {
+      // tau: the top_k-th largest head (0 when fewer lists than that have a key)
+      uint64_t tau = 0;
+      for (int b = 63; b >= 0; --b) {
+        const uint64_t cand = tau | ((uint64_t)1 << b);
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < TK_HEADS; ++i) cnt += __popcll(__ballot(head[i] >= cand));
+        if (cnt >= top_k) tau = cand;
+      }
+      // one lane per live list (at most top_k <= 64 of them)
+      int nlive = 0;
+#pragma unroll
+      for (int i = 0; i < TK_HEADS; ++i) {
+        const bool live = head[i] != 0 && head[i] >= tau;
+        const uint64_t mask = __ballot(live);
+        if (live) sl[nlive + __popcll(mask & (((uint64_t)1 << lane) - 1))] = lane + 64 * i;
+        nlive += __popcll(mask);
+      }
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      const uint64_t* mylist = list + (int64_t)(lane < nlive ? sl[lane] : 0) * KL;
+      uint64_t h0 = 0, h1 = 0, h2 = 0, h3 = 0;
+      int pos = 0, have = 0;
+      auto refill = [&]() {
+        h0 = pos < KL ? mylist[pos] : 0;
+        h1 = pos + 1 < KL ? mylist[pos + 1] : 0;
+        h2 = pos + 2 < KL ? mylist[pos + 2] : 0;
+        h3 = pos + 3 < KL ? mylist[pos + 3] : 0;
+        pos += 4, have = 4;
+      };
+      if (lane < nlive) refill();
+      uint64_t cand = 0;
+      int kc = 0;  // candidates found: top_k, or every column that can be drawn when there are fewer
+      for (; kc < top_k; ++kc) {
+        const uint64_t best = tk_wave_max(h0);
+        if (best == 0) break;
+        if (lane == kc) cand = best;
+        if (h0 == best) {
+          h0 = h1, h1 = h2, h2 = h3, h3 = 0;
+          if (--have == 0 && pos < KL) refill();
+        }
+      }
+      // p_j = exp(s_j - lse), the running sums P_j in index order, the nucleus and the draw
+      const float s_me = __fdiv_rn(tk_unorder((uint32_t)(cand >> 32)), temperature);
+      pl[lane] = lane < kc ? expf(s_me - lse) : 0.f;
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      float P = 0.f;
+      for (int j = 0; j < kc; ++j) P += j <= lane ? pl[j] : 0.f;
+      const float p_all = __shfl(P, kc > 0 ? kc - 1 : 0, 64);
+      int mnuc = kc;
+      if (top_p < 1.f) {
+        const uint64_t in = __ballot(lane < kc && P >= top_p * p_all);
+        if (in) mnuc = __ffsll((unsigned long long)in);
+      }
+      const tmi_rowkey rk = tmi_row_key(stream_key, (uint32_t)r);
+      const float u = ((float)(tmi_sample_bits(rk, 0xFFFFFFFFu) >> 8) + 0.5f) * 0x1p-24f;
+      const float thr = u * __shfl(P, mnuc > 0 ? mnuc - 1 : 0, 64);
+      const uint64_t hit = __ballot(lane < mnuc && P > thr);
+      const int j = hit ? __ffsll((unsigned long long)hit) - 1 : (mnuc > 0 ? mnuc - 1 : 0);
+      if (kc > 0) {  // (kc == 0: no column can be drawn - V == 1 and it is suppressed - and the row writes pad)
+        token = (int32_t)(~(uint32_t)__shfl(cand, j, 64));
+        lp = __shfl(s_me, j, 64) - lse;
+      }
+    }
+    if (lane == 0) {
+      ids[(int64_t)r * ids_ld] = token;
+      if (out_lp) out_lp[r] = lp;
+      if (!was_finished && token == eos_id) finished[r] = 1;
+    }
+    for (int64_t j = lane; j < (int64_t)nwg * KL; j += 64) list[j] = 0;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // (sl and pl are reused by the wave's next row)
+  }
+
+  // ---- the last tile to finish counts the finished rows
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    __hip_atomic_store(counters + blockIdx.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint32_t prev = __hip_atomic_fetch_add(counters + M, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    sm_last = prev == gridDim.y - 1;
+    sm_count = 0;
+  }
+  __syncthreads();
+  if (!sm_last) return;
+  __threadfence();
+  int n = 0;
+  for (int r = tid; r < M; r += AM_THREADS)
+    n += __hip_atomic_load(finished + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+  if (n) atomicAdd(&sm_count, n);
+  __syncthreads();
+  if (tid == 0) {
+    if (n_finished) n_finished[0] = sm_count;
+    __hip_atomic_store(counters + M, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+template <typename TW, int MT, typename... A>
+int sm_launch(dim3 grid, size_t lds, hipStream_t s, A... a) {
+  auto kern = lm_head_sample_kernel<TW, MT>;
+  static size_t opted = 65536;  // (as am_launch)
+  if (lds > opted) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess) {
+      (void)hipGetLastError();
+      tmi_set_error("tmi_lm_head_sample: the LDS size could not be granted");
+      return TMI_ERR_LAUNCH;
+    }
+    opted = lds;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, a...);
+  return tmi_check_launch("tmi_lm_head_sample");
+}
+
+template <typename TW, typename... A>
+int sm_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, A... a) {
+  switch (MT) {
+    case 1: return sm_launch<TW, 1>(grid, lds, s, a...);
+    case 2: return sm_launch<TW, 2>(grid, lds, s, a...);
+    case 4: return sm_launch<TW, 4>(grid, lds, s, a...);
+    case 8: return sm_launch<TW, 8>(grid, lds, s, a...);
+    case 16: return sm_launch<TW, 16>(grid, lds, s, a...);
+  }
+  return TMI_ERR_INVALID;
+}
+
 inline bool am_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
@@ -584,4 +903,59 @@ extern "C" int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, co
                                 int64_t workspace_bytes, void* stream) {
   return tmi_plan_run<tmi_lm_head_topk_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N,
                                              ids, logprobs, lse, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t tmi_lm_head_sample_workspace_bytes(int64_t M, int64_t V, int64_t top_k) {
+  if (M < 1 || V < 1 || top_k < 0 || top_k > SM_MAXK) return -1;
+  const int64_t nwg = (V + AM_COLS - 1) / AM_COLS;
+  return 8 * M * (1 + nwg * (1 + (top_k > 0 ? top_k : 2))) + 8;
+}
+
+static int tmi_lm_head_sample_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                   float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id,
+                                   int32_t eos_id, int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld,
+                                   float* logprob, int32_t* n_finished, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
+  const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
+  int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
+  if (lds_floats < 512) lds_floats = 512;
+  const int64_t nwg = (V + AM_COLS - 1) / AM_COLS;
+  const bool sizes_ok = M >= 1 && M <= (int64_t)16 * 65535 && d >= 1 && V >= 1 && nwg <= 64 * TK_HEADS;
+  const bool rule_ok = temperature > 0.f && temperature < INFINITY && top_k >= 0 && top_k <= SM_MAXK && top_p > 0.f &&
+                       top_p <= 1.f && (top_k > 0 || top_p == 1.f);
+  if (!x || !w || !ids || !finished || !n_finished || !workspace || !dt_ok || !sizes_ok || !rule_ok || w_ld < V ||
+      (w_ld & 7) || !am_al16(w) || x_ld < d || ids_ld < 1 || (gamma == nullptr) != (beta == nullptr) ||
+      workspace_bytes < tmi_lm_head_sample_workspace_bytes(M, V, top_k) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+      lds_floats * 4 > 160 * 1024 - 256) {
+    tmi_set_error("tmi_lm_head_sample: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(workspace);
+  uint32_t* counters = reinterpret_cast<uint32_t*>(base);  // (one per row tile, then the tiles' own at [M]; 8 * M + 8 bytes)
+  float2* part = reinterpret_cast<float2*>(base + 8 * M + 8);
+  uint64_t* keys = reinterpret_cast<uint64_t*>(base + 8 * M + 8 + 8 * M * nwg);
+  const dim3 grid((unsigned)nwg, (unsigned)((M + MT - 1) / MT));
+  const size_t lds = (size_t)lds_floats * 4;
+  const int xb = x_dtype == TMI_BF16;
+  const uint32_t skey = tmi_stream_key(seed, 0);
+  if (w_dtype == TMI_BF16)
+    return sm_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const bf16_t*>(w), w_ld,
+                               (int)M, (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id,
+                               (int)pad_id, finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
+  return sm_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const float*>(w), w_ld, (int)M,
+                            (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id, (int)pad_id,
+                            finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
+}
+extern "C" int tmi_lm_head_sample(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                  float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id,
+                                  int32_t eos_id, int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld,
+                                  float* logprob, int32_t* n_finished, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+  return tmi_plan_run<tmi_lm_head_sample_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, temperature,
+                                               top_k, top_p, seed, suppress_id, eos_id, pad_id, finished, ids, ids_ld,
+                                               logprob, n_finished, workspace, workspace_bytes, stream);
 }

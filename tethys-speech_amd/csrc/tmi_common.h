@@ -174,6 +174,12 @@ __host__ __device__ __forceinline__ float tmi_keep_scale(uint32_t thr) { return 
 __host__ __device__ __forceinline__ uint32_t tmi_stream_key(uint64_t seed, uint32_t stream_id) {
   return tmi_mix32((uint32_t)seed ^ tmi_mix32((uint32_t)(seed >> 32) + stream_id));
 }
+// 32 draw bits for counter `c` of the row with key `rk` (tmi_lm_head_sample: c = the column, or 0xFFFFFFFF for the row's one
+// inverse-CDF draw).  Two full avalanches: the draws are compared across all columns of a row, where the mul24 pair hash's
+// 2^17-column limit would not do.  A uniform is u = ((bits >> 8) + 0.5) * 2^-24, never 0 or 1.
+__host__ __device__ __forceinline__ uint32_t tmi_sample_bits(tmi_rowkey rk, uint32_t c) {
+  return tmi_mix32(rk.a ^ tmi_mix32(c ^ rk.b));
+}
 // keep decision of element (row, col) of a stream
 __host__ __device__ __forceinline__ bool tmi_keep(uint32_t stream_key, uint32_t row, uint32_t col, uint32_t thr) {
   const uint32_t h = tmi_pair_hash(tmi_row_key(stream_key, row), col >> 1);

@@ -482,6 +482,29 @@ def lm_head_topk(x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma=N
               "tmi_lm_head_topk")
 
 
+def lm_head_sample_workspace_elems(M, V, top_k):
+    """int64 elements of tmi_lm_head_sample's workspace (tmi_lm_head_sample_workspace_bytes / 8)."""
+    n = lib().tmi_lm_head_sample_workspace_bytes(M, V, top_k)
+    if n < 0:
+        raise ValueError(f"tmi_lm_head_sample takes no M {M}, V {V}, top_k {top_k}")
+    return n // 8
+
+
+def lm_head_sample(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace, temperature=1.0, top_k=50,
+                   top_p=1.0, seed=0, suppress_id=-1, eos_id=-1, pad_id=0, logprob=None, gamma=None, beta=None, eps=1e-5):
+    """One sampled token per row of M rows of x (row stride x_ld): ids[r * ids_ld] drawn from softmax((LayerNorm(x[r]) . w)
+    [:V] / temperature) cut to its ``top_k`` largest columns and their ``top_p`` nucleus (top_k 0: the whole vocabulary,
+    Gumbel-max), logprob[r] = its log-probability under the uncut distribution; the rule is include/tethys_mi.h's.
+    ``finished`` int32 [M] in and out, ``n_finished`` int32 [1]; ``workspace``: an int64 tensor of at least
+    ``lm_head_sample_workspace_elems(M, V, top_k)`` elements, zero before the first call (left zero by every call)."""
+    with _probe("lm_head_sample", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_sample(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
+                                       V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       suppress_id, eos_id, pad_id, finished.data_ptr(), ids.data_ptr(), ids_ld,
+                                       ptr(logprob), n_finished.data_ptr(), workspace.data_ptr(),
+                                       workspace.numel() * workspace.element_size(), stream()), "tmi_lm_head_sample")
+
+
 def beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping, pool_ids, pool_scores,
               pool_len, pool_cnt, done, done_count, finalize=False):
     """One step of beam search's bookkeeping on the device (tmi_beam_step; the rule is whisper.generate's): candidates

@@ -836,6 +836,14 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self._inf = inf
         return inf
 
+    def _sample_workspace(self, inf, B: int, top_k: int):
+        """tmi_lm_head_sample's workspace for B rows and this top_k, added to the inference set ``inf`` on the sampled path
+        only (nothing else of the set depends on the mode); zero before the first call, left zero by every call."""
+        need = ops.lm_head_sample_workspace_elems(B, self.config.vocab_size, top_k)
+        have = inf["ws"].get("sample_ws")
+        if have is None or have.numel() < need:
+            inf["ws"]["sample_ws"] = torch.zeros(need, dtype=torch.int64, device=self.device)
+
     def _infer_begin(self, inf):
         """Enter an inference call: pin the stream, order it behind every parameter update that may still be running on
         the second stream (the late Adam slices: their persistent events are waited for, ``_late_pending`` is left as it
@@ -958,7 +966,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
     @torch.no_grad()
     def generate(self, input_features, max_length=None, min_length=None, num_beams=None, temperature=1.0, top_k=None,
                  top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None, length_penalty=1.0,
-                 early_stopping=False, num_return_sequences=1, return_dict_in_generate=False):
+                 early_stopping=False, num_return_sequences=1, return_dict_in_generate=False, do_sample=False, seed=0):
         """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.  ``num_beams`` of 2 to
         8: beam search (``_generate_beam``; the reference accepts num_beams at W:637 and leaves it as a ``pass`` at
         W:696-698); None or 1: the greedy path below, unchanged.
@@ -970,12 +978,18 @@ class WhisperForConditionalGeneration(KernelBlocks):
         the other options are accepted and ignored (W:643-648).  Fixed against the reference: the logits come from the LM
         head (W:675 reads a key WhisperModel does not return), ``max_length`` above max_target_positions raises up front
         instead of overrunning the positional table (W:383).  ``eos_token_id`` (not in the reference's signature):
-        overrides config.eos_token_id; -1 disables the stop.
+        overrides config.eos_token_id; -1 disables the stop.  ``do_sample=True``: sampled decoding (``_generate_sample``),
+        the one mode in which temperature, top_k, top_p and min_length take effect; False: nothing below changes.
 
         Per step: the embedding of [start, tokens so far] (tmi_embed_fwd), the decoder over the prefix, and
         tmi_lm_head_argmax on the B last rows (final LayerNorm, LM head and argmax in one launch).  The EOS count of a step
         is read one step late (``greedy_loop``), so the device never idles on the host's check."""
         cfg = self.config
+        if do_sample:
+            max_length, top_k, top_p, min_length = sample_args(cfg, max_length, num_beams, temperature, top_k, top_p, min_length)
+            eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+            return self._generate_sample(input_features, max_length, float(temperature), top_k, top_p, min_length, eos,
+                                         int(seed), bool(return_dict_in_generate))
         if num_beams is not None and int(num_beams) > 1:  # (ahead of check_generate_args: it still raises for num_beams > 1)
             max_length = check_beam_args(cfg, max_length, num_beams, temperature, length_penalty, num_return_sequences)
             eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
@@ -1028,6 +1042,73 @@ class WhisperForConditionalGeneration(KernelBlocks):
             self._infer_end(saved)
         torch.cuda.current_stream(dev).synchronize()
         return ids[:, :1 + n].clone()
+
+    def _generate_sample(self, features, max_length, temperature, top_k, top_p, min_length, eos, seed, return_dict):
+        """Sampled decoding: the greedy loop with tmi_lm_head_sample as the choice rule (include/tethys_mi.h states it:
+        top_k >= 1 keeps the top_k largest scores and their top_p nucleus and draws by inverse CDF, top_k == 0 draws from
+        the whole vocabulary by Gumbel-max).  Step t (1-based) draws with the seed (seed + t * 0x9E3779B97F4A7C15) mod
+        2^64, row b with row key b, so a seeded call repeats; EOS is suppressed while t <= min_length.  A row that draws
+        EOS is finished: its later columns are pad_token_id (which it also feeds its own decoder; the rows of a batch do
+        not see each other) and their log-probabilities 0.  The loop stops once every row is finished (the count is read
+        one step late) or after max_length steps.  -> ids [B, 1 + n], or with ``return_dict`` {"sequences",
+        "token_logprobs" [B, n] (log-softmax of logits / temperature at the token: the uncut distribution),
+        "sequences_scores" [B] (their sum up to and including the row's EOS), "lengths" [B] (tokens up to and including
+        EOS)}."""
+        cfg = self.config
+        features = self._check_features(features)
+        B, dev = features.shape[0], self.device
+        start, pad, V = cfg.decoder_start_token_id, cfg.pad_token_id, cfg.vocab_size
+        ids = torch.empty(B, 1 + max_length, dtype=torch.int32, device=dev)
+        ids[:, 0] = start
+        lps = torch.zeros(1 + max_length, B, device=dev)  # (a step's log-probabilities are one contiguous row)
+        n = 0
+        if max_length > 0:
+            inf = self._infer_prepare(B, features.shape[2])
+            self._sample_workspace(inf, B, top_k)
+            finished = torch.zeros(B, dtype=torch.int32, device=dev)
+            counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
+            host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
+            events = [torch.cuda.Event(), torch.cuda.Event()]
+            saved = self._infer_begin(inf)
+            try:
+                ws, d, T = self.ws, cfg.d_model, inf["T"]
+                enc_out = self._encode_infer(features, inf)
+                self._cross_kv_infer(enc_out)
+                lab_flat = ws["labels"]
+                wl, ldw = self.W("lm_head.kernel")
+                gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
+                main = self._main or torch.cuda.current_stream(dev)
+                L1 = 1 + max_length
+
+                def step(t):
+                    lab = lab_flat[:B * t].view(B, t)
+                    if t > 1:
+                        lab[:, :t - 1].copy_(ids[:, 1:t])
+                    h = self._decode_infer(lab, B, t, T)
+                    ops.lm_head_sample(h[t - 1:], t * d, wl, ldw, B, d, V, ids[:, t:], L1, finished, counts[t:],
+                                       ws["sample_ws"], temperature=temperature, top_k=top_k, top_p=top_p,
+                                       seed=sample_step_seed(seed, t), suppress_id=eos if t <= min_length else -1,
+                                       eos_id=eos, pad_id=pad, logprob=lps[t], gamma=gamma, beta=beta,
+                                       eps=cfg.layer_norm_eps)
+                    host[t:t + 1].copy_(counts[t:t + 1], non_blocking=True)
+                    events[t & 1].record(main)
+
+                def read_finished(t):
+                    events[t & 1].synchronize()
+                    return int(host[t])
+
+                n = greedy_loop(max_length, B, step, read_finished if eos >= 0 else None)
+            finally:
+                self._infer_end(saved)
+            torch.cuda.current_stream(dev).synchronize()
+        seq = ids[:, :1 + n].clone()
+        if not return_dict:
+            return seq
+        tok_lp = lps[1:1 + n].t().contiguous()
+        is_eos = (seq[:, 1:] == eos) if eos >= 0 else torch.zeros(B, n, dtype=torch.bool, device=dev)
+        first = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1, n) if n else torch.zeros(B, dtype=torch.int64, device=dev)
+        return {"sequences": seq, "token_logprobs": tok_lp, "sequences_scores": tok_lp.sum(dim=1),
+                "lengths": first.to(torch.int32)}
 
     def _generate_beam(self, features, max_length, K, temperature, eos, length_penalty, early_stopping, R, return_dict):
         """Beam search; the rule is the module docstring's "Beam search".  The encoder and the cross-attention k|v run once
@@ -1151,6 +1232,45 @@ def check_beam_args(cfg: WhisperConfig, max_length=None, num_beams=2, temperatur
     return max_length
 
 
+SAMPLE_MAX_TOP_K = 64  # tmi_lm_head_sample's
+
+
+def check_sample_args(cfg: WhisperConfig, max_length=None, num_beams=None, temperature=1.0, top_k=None, top_p=None,
+                      min_length=None) -> int:
+    """The arguments of sampled decoding (``generate(do_sample=True)``) -> max_length; the bounds are ``sample_args``'."""
+    return sample_args(cfg, max_length, num_beams, temperature, top_k, top_p, min_length)[0]
+
+
+def sample_args(cfg: WhisperConfig, max_length=None, num_beams=None, temperature=1.0, top_k=None, top_p=None,
+                min_length=None):
+    """The arguments of sampled decoding, checked -> (max_length, top_k, top_p, min_length) with the defaults filled in.
+    num_beams None or 1; temperature > 0; top_k None -> 50 (W:646), 0 = no
+    filter, at most 64; top_p None -> 1.0, in (0, 1], and < 1 only with a top_k filter (the nucleus is cut out of the
+    top_k candidates; one over the whole vocabulary is not built); min_length None -> 0, in [0, max_length]."""
+    if num_beams is not None and int(num_beams) != 1:
+        raise ValueError("do_sample takes num_beams None or 1 (beam search does not sample)")
+    max_length = check_generate_args(cfg, max_length, None, 1.0)
+    if temperature is None or not (float(temperature) > 0.0 and math.isfinite(float(temperature))):
+        raise ValueError("temperature must be > 0")
+    top_k = 50 if top_k is None else int(top_k)
+    if not 0 <= top_k <= SAMPLE_MAX_TOP_K:
+        raise ValueError(f"top_k must be in [0, {SAMPLE_MAX_TOP_K}] (0: no filter)")
+    top_p = 1.0 if top_p is None else float(top_p)
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError("top_p must be in (0, 1]")
+    if top_p < 1.0 and top_k == 0:
+        raise ValueError("top_p < 1 needs a top_k filter (1..64): the nucleus is cut out of the top_k candidates")
+    min_length = 0 if min_length is None else int(min_length)
+    if not 0 <= min_length <= max_length:
+        raise ValueError("min_length must be in [0, max_length]")
+    return max_length, top_k, top_p, min_length
+
+
+def sample_step_seed(seed: int, t: int) -> int:
+    """The seed of decoding step t of a sampled ``generate(seed=seed)``."""
+    return (int(seed) + t * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+
 def greedy_loop(max_length: int, n_rows: int, step, read_eos=None, late: bool = True) -> int:
     """Host side of greedy decoding: the number n of tokens to keep (the result is ids[:, :1 + n]).
 
@@ -1198,12 +1318,14 @@ def dummy_waveform(seed: int = DUMMY_AUDIO_SEED) -> np.ndarray:
     return np.random.RandomState(seed).randn(16000 * 30).astype(np.float32)
 
 
-def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beams=1, length_penalty=1.0):
+def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beams=1, length_penalty=1.0, do_sample=False,
+                     temperature=1.0, top_k=None, top_p=None, seed=0):
     """W:962-986: waveform -> log-mel (frontend.LogMelFrontend, channels-first: the layout the encoder reads; the reference
     feeds [frames, 80] un-transposed) -> ``model.generate`` -> ``tokenizer.decode(ids)``, or the ids
     (int32 numpy array, start token first) without a tokenizer.  ``audio``: a waveform (1-D tensor or array, 16 kHz), a
     ``.wav`` path, or None for the reference's 30 s dummy clip (seeded).  ``num_beams`` > 1: beam search (the best
-    hypothesis), with ``length_penalty``."""
+    hypothesis), with ``length_penalty``.  ``do_sample``: sampled decoding with ``temperature``, ``top_k``, ``top_p`` and
+    ``seed`` (``generate(do_sample=True)``)."""
     from .frontend import LogMelFrontend
     if audio is None:
         wav = dummy_waveform()
@@ -1216,7 +1338,10 @@ def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beam
     if fe is None:
         fe = model._frontend = LogMelFrontend(device=model.device, n_mels=model.config.n_mels)
     feats = fe(wav)
-    if num_beams is not None and int(num_beams) > 1:
+    if do_sample:
+        ids = model.generate(feats, max_length=max_length, num_beams=num_beams, do_sample=True, temperature=temperature,
+                             top_k=top_k, top_p=top_p, seed=seed)
+    elif num_beams is not None and int(num_beams) > 1:
         ids = model.generate(feats, max_length=max_length, num_beams=num_beams, length_penalty=length_penalty)
     else:
         ids = model.generate(feats, max_length=max_length)

@@ -7,7 +7,11 @@ bench.py measures training and stays as it is; this is the inference counterpart
 --num_beams K > 1: beam search (B*K decoder rows, EOS disabled so that all steps run), and tmi_lm_head_topk (N = 2K)
 against tmi_lm_head_argmax at equal M (8 and 40, d 768 and 1280), both measured in this run, with their time ratio.
 
-usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2] [--num_beams 1]"""
+--do_sample: sampled decoding (--top_k 50 --top_p 0.9 by default; --top_k 0: Gumbel-max over the vocabulary), EOS disabled,
+and tmi_lm_head_sample at M = 8 in both modes beside tmi_lm_head_argmax (M = 8) and tmi_lm_head_topk (M = 8, N = 16),
+all measured in this run.
+
+usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2] [--num_beams 1] [--do_sample [--top_k K] [--top_p P]]"""
 import argparse
 import json
 import os
@@ -33,13 +37,20 @@ def timed_us(fn, iters=50, warm=5):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
-def argmax_alone(dev, d, M=8, V=51865, Vp=51904, topk_n=0):
-    """tmi_lm_head_argmax (topk_n = 0) or tmi_lm_head_topk with N = topk_n, alone on M rows."""
+def argmax_alone(dev, d, M=8, V=51865, Vp=51904, topk_n=0, sample=None):
+    """tmi_lm_head_argmax (topk_n = 0), tmi_lm_head_topk with N = topk_n, or tmi_lm_head_sample with ``sample`` =
+    (top_k, top_p), alone on M rows."""
     g = torch.Generator(device=dev).manual_seed(d)
     x = torch.randn(M, d, device=dev, generator=g).to(torch.bfloat16)
     w = (torch.randn(d, Vp, device=dev, generator=g) * 0.03).to(torch.bfloat16)
     gamma, beta = torch.ones(d, device=dev), torch.zeros(d, device=dev)
-    if topk_n:
+    if sample is not None:
+        ids, lp = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, device=dev)
+        fin, cnt = torch.zeros(M, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.zeros(ops.lm_head_sample_workspace_elems(M, V, sample[0]), dtype=torch.int64, device=dev)
+        call = lambda: ops.lm_head_sample(x, d, w, Vp, M, d, V, ids, 1, fin, cnt, ws, temperature=0.8,  # noqa: E731
+                                          top_k=sample[0], top_p=sample[1], seed=1, logprob=lp, gamma=gamma, beta=beta)
+    elif topk_n:
         ids = torch.empty(M, topk_n, dtype=torch.int32, device=dev)
         lp = torch.empty(M, topk_n, device=dev)
         ws = torch.zeros(ops.lm_head_topk_workspace_elems(M, V, topk_n), dtype=torch.int64, device=dev)
@@ -69,9 +80,16 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--num_beams", type=int, default=1)
+    ap.add_argument("--do_sample", action="store_true")
+    ap.add_argument("--top_k", type=int, default=50)
+    ap.add_argument("--top_p", type=float, default=0.9)
     args = ap.parse_args()
     K = args.num_beams
     beam = dict(num_beams=K) if K > 1 else {}
+    if args.do_sample:
+        if K > 1:
+            ap.error("--do_sample does not go with --num_beams > 1")
+        beam = dict(do_sample=True, top_k=args.top_k, top_p=args.top_p, temperature=0.8, seed=1)
     dev = "cuda:0"
     model = whisper.create_whisper_model("small", device=dev, precision="bf16")
     B = args.batch
@@ -98,10 +116,17 @@ def main():
         best = dt if best is None else min(best, dt)
     assert tuple(ids.shape) == (B, 1 + args.steps), ids.shape
     decode_s = best - enc_ms / 1e3
-    out = {"workload": "whisper_small_generate" + ("_beam" if K > 1 else ""), "batch": B, "steps": args.steps,
+    out = {"workload": "whisper_small_generate" + ("_beam" if K > 1 else "_sample" if args.do_sample else ""), "batch": B, "steps": args.steps,
            "precision": "bf16", "encoder_ms": round(enc_ms, 3), "generate_s": round(best, 4), "decode_s": round(decode_s, 4),
            "per_step_ms": round(decode_s * 1e3 / args.steps, 3), "tokens_per_s": round(B * args.steps / best, 1)}
-    if K > 1:
+    if args.do_sample:
+        out["top_k"], out["top_p"] = args.top_k, args.top_p
+        out["lm_head_M8_d768"] = {"argmax": argmax_alone(dev, 768), "topk_N16": argmax_alone(dev, 768, topk_n=16),
+                                  "sample_k50_p0.9": argmax_alone(dev, 768, sample=(50, 0.9)),
+                                  "sample_k64_p1": argmax_alone(dev, 768, sample=(64, 1.0)),
+                                  "sample_k1": argmax_alone(dev, 768, sample=(1, 1.0)),
+                                  "sample_k0_gumbel": argmax_alone(dev, 768, sample=(0, 1.0))}
+    elif K > 1:
         out["num_beams"] = K
         out["decoder_rows"] = B * K
         head = {}
