@@ -216,6 +216,11 @@ int tmi_memcpy_async(void* dst, const void* src, int64_t bytes, void* stream);
  */
 int tmi_softmax_fwd(float* s, int64_t rows, int64_t Tq, int64_t Tk, int32_t mask_mode, void* stream);
 int tmi_softmax_bwd(const float* p, float* dp, int64_t rows, int64_t Tk, void* stream);
+/* The same materialised softmax with the additive key term of tmi_attn_desc.mask_mode 2 (V:352-355): s[rows, Tk] in place,
+ * rows = B * H * Tq, row r belongs to batch r / (H * Tq); key j of batch b gets key_bias[b * kb_sb + j] (fp32, natural-log
+ * units) added in fp32 before the row maximum is taken.  Forward only (inference). */
+int tmi_softmax_bias_fwd(float* s, int64_t rows, int64_t Tq, int64_t Tk, int64_t H, const float* key_bias, int64_t kb_sb,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Fused (flash-style) multi-head attention, bf16 in / fp32 accumulate, head_dim 64.
@@ -235,7 +240,7 @@ typedef struct tmi_attn_desc {
   int64_t q_sb, q_st, k_sb, k_st, v_sb, v_st, o_sb, o_st;
   float* stats;
   int64_t B, H, Tq, Tk;
-  int32_t mask_mode;           /* as tmi_softmax_fwd */
+  int32_t mask_mode;           /* 0, 1: as tmi_softmax_fwd; 2: additive key_bias (below), forward only */
   /* backward only */
   const void* d_o; void* dq; void* dk; void* dv;
   int64_t do_sb, do_st, dq_sb, dq_st, dk_sb, dk_st, dv_sb, dv_st;
@@ -267,6 +272,14 @@ typedef struct tmi_attn_desc {
    * pass alone (it also fills `delta`); 2: the dK/dV pass alone, after a dQ pass of the same descriptor has filled `delta`.  Lets a caller put the dK/dV pass of a cross-attention - whose results
    * nothing on the decoder's backward chain waits for (W:255-301: dK, dV feed the shared k/v projections) - on another stream. */
   int32_t bwd_passes;
+  /* mask_mode 2, tmi_attn_fwd only (the padding mask of a batch of clips of different lengths, V:352-355): the score of
+   * (b, head, q, key) is q.k * score_scale + key_bias[b * kb_sb + key].  fp32, natural-log units, the same for every head
+   * and query; the caller passes the reference's (1 - attention_mask) * -10000.  The term is finite, so a row whose keys
+   * all carry it is an ordinary softmax of shifted scores, as in the reference.  Required (non-NULL, kb_sb >= 0) with
+   * mask_mode 2 and ignored otherwise; mask_mode 2 with dropout_p > 0, and tmi_attn_bwd with mask_mode 2, return
+   * TMI_ERR_INVALID.  The key-split path (`workspace`) is never taken.  Callers of mask_mode 0 / 1 leave both fields zero. */
+  const float* key_bias;
+  int64_t kb_sb;
 } tmi_attn_desc;
 int64_t tmi_attn_workspace_bytes(int64_t B, int64_t H, int64_t Tq);
 int64_t tmi_attn_dropmask_bytes(int64_t B, int64_t H, int64_t Tq, int64_t Tk);
@@ -574,6 +587,15 @@ int tmi_segment_clip(float* g, const int64_t* seg_off, const float* sumsq, int64
 /* out[0] = nan_to_zero(a[0] + w * b[0]) * scale  (V:1220-1231: contrastive + 0.1 * (-perplexity),
  * NaN guard, / num_replicas) without a host round trip. */
 int tmi_loss_combine(const float* a, const float* b, float w, float scale, float* out, void* stream);
+
+/* Masked mean over time, the reduction of the reference's classification head (V:1031-1042):
+ *   out[b, c] = sum_t x[b, t, c] * mask[b, t] / sum_t mask[b, t]
+ * x [B, T, C] contiguous (x_dtype TMI_F32 or TMI_BF16, 16-byte aligned, C a multiple of 4 resp. 8), mask [B, T] fp32 or
+ * NULL for the plain mean over T (V:1042), out [B, C] fp32.  Accumulated in fp32 in a fixed order without atomics: two
+ * runs are bit-identical.  Deviation from the reference: a batch row whose mask sums to zero yields zeros, where the
+ * reference's 0 / 0 yields NaN. */
+int tmi_masked_mean_pool(const void* x, int32_t x_dtype, const float* mask, float* out, int64_t B, int64_t T, int64_t C,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Log-mel front end (speech_jobs/whisper_dist.py:739-766, extract_fbank_features; dead in the

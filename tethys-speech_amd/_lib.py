@@ -55,6 +55,7 @@ class AttnDesc(C.Structure):
         ("drop_mask", c_vp), ("drop_mask_bytes", c_i64),
         ("workspace", c_vp), ("workspace_bytes", c_i64),
         ("bwd_passes", c_i32),
+        ("key_bias", c_vp), ("kb_sb", c_i64),
     ]
 
 
@@ -88,6 +89,7 @@ SIGNATURES = {
     "tmi_gelu_bwd_batched": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_vp]),
     "tmi_softmax_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i32, c_vp]),
     "tmi_softmax_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "tmi_softmax_bias_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "tmi_attn_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "tmi_attn_dropmask_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "tmi_attn_fwd": (c_i32, [C.POINTER(AttnDesc), c_vp]),
@@ -132,6 +134,7 @@ SIGNATURES = {
     "tmi_segment_sumsq_chunks": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "tmi_segment_clip": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_f32, c_vp]),
     "tmi_loss_combine": (c_i32, [c_vp, c_vp, c_f32, c_f32, c_vp, c_vp]),
+    "tmi_masked_mean_pool": (c_i32, [c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
     "tmi_lm_head_argmax": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp,
                                    c_i64, c_i32, c_vp, c_vp, c_i64, c_vp]),
     "tmi_lm_head_topk": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32,
@@ -144,7 +147,7 @@ SIGNATURES = {
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
 }
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 _lib = None
 
 

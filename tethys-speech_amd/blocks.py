@@ -483,11 +483,20 @@ class KernelBlocks:
         p = self._drop_p if p is None else p
         return {"dropout_p": p, "dropout_seed": self._site_seed(site)} if p > 0.0 else {}
 
-    def _attn_fwd(self, key, q, k, v, ctx2d, B, H, Tq, Tk, mask, score_scale=1.0, site=None):
-        """score_scale multiplies q·kᵀ (V:349); Whisper pre-scales q instead (W:141) and passes 1."""
+    def _attn_fwd(self, key, q, k, v, ctx2d, B, H, Tq, Tk, mask, score_scale=1.0, site=None, key_bias=None):
+        """score_scale multiplies q·kᵀ (V:349); Whisper pre-scales q instead (W:141) and passes 1.
+        ``key_bias`` (inference, V:352-355): fp32 [B, Tk] added to the scores of every head and query - mask_mode 2 of the
+        fused kernel, tmi_softmax_bias_fwd on the fp32 path; ``mask`` must be 0 and no dropout site given."""
         d = self.hidden
         (qt, qo), (kt, ko), (vt, vo) = q, k, v
+        if key_bias is not None and (mask != 0 or site is not None):
+            raise ValueError("_attn_fwd: key_bias goes with mask 0 and no dropout site")
         if self.precision == "bf16":
+            if key_bias is not None:
+                ops.attn_fwd((qt, qo, Tq * qt.stride(0), qt.stride(0)), (kt, ko, Tk * kt.stride(0), kt.stride(0)),
+                             (vt, vo, Tk * vt.stride(0), vt.stride(0)), (ctx2d, 0, Tq * d, d),
+                             self.ws[key], B, H, Tq, Tk, 2, score_scale=score_scale, key_bias=key_bias)
+                return
             dp = self._drop_attn_p if site is not None else 0.0
             ops.attn_fwd((qt, qo, Tq * qt.stride(0), qt.stride(0)), (kt, ko, Tk * kt.stride(0), kt.stride(0)),
                          (vt, vo, Tk * vt.stride(0), vt.stride(0)), (ctx2d, 0, Tq * d, d),
@@ -502,7 +511,10 @@ class KernelBlocks:
         ops.gemm(qt, kt, P, Tq, Tk, hd, qt.stride(0), 1, 1, kt.stride(0), Tk, nbatch=H, a_sb=hd, b_sb=hd,
                  c_sb=Tq * Tk, a_off=qo, b_off=ko, scale_cols=Tk if score_scale != 1.0 else 0, scale=score_scale,
                  nbatch2=B, a_sb2=Tq * qt.stride(0), b_sb2=Tk * kt.stride(0), c_sb2=H * Tq * Tk)
-        ops.softmax_fwd(P, B * H * Tq, Tq, Tk, mask)
+        if key_bias is not None:
+            ops.softmax_bias_fwd(P, B * H * Tq, Tq, Tk, H, key_bias)
+        else:
+            ops.softmax_fwd(P, B * H * Tq, Tq, Tk, mask)
         ops.gemm(P, vt, ctx2d, Tq, hd, Tk, Tk, 1, vt.stride(0), 1, d, nbatch=H, a_sb=Tq * Tk, b_sb=hd, c_sb=hd,
                  b_off=vo, nbatch2=B, a_sb2=H * Tq * Tk, b_sb2=Tk * vt.stride(0), c_sb2=Tq * d)
 

@@ -36,7 +36,9 @@
 #include "tmi_common.h"
 #include <type_traits>
 #include <utility>
+#include <stddef.h>
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -289,8 +291,34 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
   _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) _Pragma("unroll") for (int e_ = 0; e_ < 16; ++e_) y[i_][e_] = 0.f
 
 // ------------------------------------------------------------------ forward
+// What the kernels receive of tmi_attn_desc: every field in front of key_bias, in the header's order.  The bias pointer
+// travels at the END of AttnP instead, so that the kernel-argument layout the mask_mode 0 / 1 kernels were compiled against
+// (and with it their code) is what it was before the descriptor grew.
+struct AttnD {
+  const void* q; const void* k; const void* v; void* o;
+  int64_t q_sb, q_st, k_sb, k_st, v_sb, v_st, o_sb, o_st;
+  float* stats;
+  int64_t B, H, Tq, Tk;
+  int32_t mask_mode;
+  const void* d_o; void* dq; void* dk; void* dv;
+  int64_t do_sb, do_st, dq_sb, dq_st, dk_sb, dk_st, dv_sb, dv_st;
+  float* delta;
+  float dq_scale;
+  float score_scale;
+  float dropout_p;
+  uint64_t dropout_seed;
+  void* drop_mask;
+  int64_t drop_mask_bytes;
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t bwd_passes;
+};
+static_assert(sizeof(AttnD) == offsetof(tmi_attn_desc, key_bias) && offsetof(AttnD, stats) == offsetof(tmi_attn_desc, stats) &&
+              offsetof(AttnD, delta) == offsetof(tmi_attn_desc, delta) && offsetof(AttnD, drop_mask) == offsetof(tmi_attn_desc, drop_mask) &&
+              offsetof(AttnD, bwd_passes) == offsetof(tmi_attn_desc, bwd_passes), "AttnD is tmi_attn_desc without its tail");
+
 struct AttnP {
-  tmi_attn_desc d;
+  AttnD d;
   float dq_scale;
   float sscale;  // scores = (q . k) * sscale
   float c2;      // sscale * log2(e)
@@ -313,14 +341,25 @@ struct AttnP {
   int ksplit;
   float* part;
   int nq;  // attn_bwd_small_kernel: blocks [0, nq) of a pair run the dQ pass
+  // mask_mode 2 (forward only): fp32 additive term of key `key` of batch b, natural-log units, at kbias[b * kb_sb + key]
+  const float* kbias;
+  int64_t kb_sb;
 };
+inline void set_desc(AttnP& P, const tmi_attn_desc& d) {
+  memcpy(&P.d, &d, sizeof(AttnD));
+  P.kbias = d.key_bias;
+  P.kb_sb = d.kb_sb;
+}
 
 // ABL (diagnostics, TMI_ATTN_ABL): 1 = no softmax arithmetic (p = s), 2 = no second product, 3 = no staging after the
 // prologue (every tile re-reads tile 0's images), 4 = no first product
-template <bool DROP, int OCC, int ABL = 0>
+// BIAS (mask_mode 2): every score gets the per-(batch, key) term P.kbias added, so every tile takes the edge path.  The 64
+// terms of a key tile are fetched one tile ahead by the first wave (one register per lane), converted to log2 units and
+// handed to the other waves through LDS ([2][64] floats behind the images) at the tile seam, like the images themselves.
+template <bool DROP, int OCC, int ABL = 0, bool BIAS = false>
 __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K img | V img]
-  const tmi_attn_desc& d = P.d;
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K img | V img] (BIAS: then [2][64] floats)
+  const AttnD& d = P.d;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 31, h = lane >> 5;
@@ -369,10 +408,17 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   const int t0 = sp * per, ntiles = min(ntiles_all, t0 + per);  // this workgroup's key tiles [t0, ntiles) (host: never empty)
   stage_tile(smem, Ks, t0 * TROWS, wave, lane);
   stage_tile(smem + IMG, Vs, t0 * TROWS, wave, lane);
+  float* kbl = nullptr;            // BIAS: the key terms of the current / next tile in log2 units, [2][64]
+  const float* kbrow = nullptr;
+  if constexpr (BIAS) {
+    kbl = reinterpret_cast<float*>(smem + 4 * IMG);
+    kbrow = P.kbias + b * P.kb_sb;
+    if (threadIdx.x < TROWS) kbl[threadIdx.x] = kbrow[min(t0 * TROWS + (int)threadIdx.x, Tk - 1)] * LOG2E;
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int cur = 0;
-  // one tile; EDGE = needs masking (causal, or the ragged last key tile)
+  // one tile; EDGE = needs masking (causal, a key bias, or the ragged last key tile)
   auto body = [&](int tile, auto edge_tag) {
     constexpr bool edge = decltype(edge_tag)::value;
     const char* Kimg = smem + cur * 2 * IMG;
@@ -381,6 +427,10 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
       char* nx = smem + (cur ^ 1) * 2 * IMG;
       stage_tile(nx, Ks, (tile + 1) * TROWS, wave, lane);
       stage_tile(nx + IMG, Vs, (tile + 1) * TROWS, wave, lane);
+    }
+    float kbnext = 0.f;  // (keys past Tk read the row's last term: in bounds, and those scores become -inf below)
+    if constexpr (BIAS) {
+      if (tile + 1 < ntiles && threadIdx.x < TROWS) kbnext = kbrow[min((tile + 1) * TROWS + (int)threadIdx.x, Tk - 1)];
     }
     f32x16 s[2];
     if constexpr (ABL == 4) {
@@ -431,11 +481,17 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
       float mx = -INFINITY;
 #pragma unroll
       for (int rbk = 0; rbk < 2; ++rbk) {
+        f32x4 kb4[4];  // BIAS: the terms of this lane's 16 keys of the half tile - accumulator quad g is keys 8 g + 4 h .. + 3
+        if constexpr (BIAS) {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) kb4[g] = *reinterpret_cast<const f32x4*>(kbl + cur * TROWS + 32 * rbk + 8 * g + 4 * h);
+        }
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const int key = key0 + 32 * rbk + acc_row(e, h);
           float x = s[rbk][e] * c2;
           if (causal && key <= q) x = x + MASKED2;
+          if constexpr (BIAS) x = x + kb4[e >> 2][e & 3];  // finite (-10000 is not -inf): an all-biased row is an ordinary softmax
           if (key >= Tk) x = -INFINITY;
           s[rbk][e] = x;
           mx = fmaxf(mx, x);
@@ -504,12 +560,16 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
     }
     // (with dropout the mask word is the youngest vector-memory operation of the tile: the seam waits for the DMA in front
     // of it, the store's acknowledgement may arrive during the next tile)
+    if constexpr (BIAS) {
+      PIN(kbnext);  // (the compiler's wait for this load belongs here, at the seam, not in front of the next tile's DMA)
+      if (threadIdx.x < TROWS) kbl[(cur ^ 1) * TROWS + threadIdx.x] = kbnext * LOG2E;  // last read one tile ago, a barrier back
+    }
     if constexpr (DROP) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (ABL != 3) cur ^= 1;
   };
-  const int nfast = causal ? 0 : min(Tk / TROWS, ntiles);  // full, unmasked tiles first
+  const int nfast = (causal || BIAS) ? 0 : min(Tk / TROWS, ntiles);  // full, unmasked tiles first
   int tile = t0;
   for (; tile < nfast; ++tile) body(tile, std::false_type{});
   for (; tile < ntiles; ++tile) body(tile, std::true_type{});
@@ -555,7 +615,7 @@ __device__ __forceinline__ void block_coords(const AttnP& P, int& bx, int& head,
 template <bool DROP>
 __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, const int head, const int64_t b) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K img | V img]
-  const tmi_attn_desc& d = P.d;
+  const AttnD& d = P.d;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 31, h = lane >> 5;
@@ -690,7 +750,7 @@ constexpr int NCONST = 4;  // per streamed query row: m, 1/l, delta (/ keep_scal
 template <bool DROP, bool LOCAL_DELTA>
 __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, const int head, const int64_t b) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][Q img | dO img] then [2][NCONST][64] floats
-  const tmi_attn_desc& d = P.d;
+  const AttnD& d = P.d;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 31, h = lane >> 5;
@@ -988,12 +1048,14 @@ dim3 pick_grid(AttnP& P, unsigned gx) {
 
 int check_common(const tmi_attn_desc& d) {
   if (d.B <= 0 || d.H <= 0 || d.Tq <= 0 || d.Tk <= 0 || d.B > 65535 || d.H > 65535 ||
-      (d.mask_mode != 0 && d.mask_mode != 1) || !d.stats || d.score_scale < 0.f || !(d.dropout_p >= 0.f && tmi_drop_ok(d.dropout_p)) ||
+      d.mask_mode < 0 || d.mask_mode > 2 || !d.stats || d.score_scale < 0.f || !(d.dropout_p >= 0.f && tmi_drop_ok(d.dropout_p)) ||
       (d.dropout_p > 0.f && d.Tk > TMI_DROP_MAX_COLS))
     return 0;
   if (d.dropout_p > 0.f && tmi_drop_thr(d.dropout_p) > 0 &&
       (!d.drop_mask || !al16(d.drop_mask) || d.drop_mask_bytes < tmi_attn_dropmask_bytes(d.B, d.H, d.Tq, d.Tk)))
     return 0;
+  // mask_mode 2: a bias is required, and there is no dropout form of it (inference); the backward refuses it itself
+  if (d.mask_mode == 2 && (!d.key_bias || d.kb_sb < 0 || d.dropout_p > 0.f)) return 0;
   return ok_mat(d.q, d.q_sb, d.q_st) && ok_mat(d.k, d.k_sb, d.k_st) && ok_mat(d.v, d.v_sb, d.v_st) &&
          ok_mat(d.o, d.o_sb, d.o_st);
 }
@@ -1011,11 +1073,11 @@ extern "C" int64_t tmi_attn_workspace_bytes(int64_t B, int64_t H, int64_t Tq) {
 
 static int tmi_attn_fwd_impl(const tmi_attn_desc* dp, void* stream) {
   if (!dp || !check_common(*dp)) {
-    tmi_set_error("tmi_attn_fwd: bad argument (16-byte aligned bf16 operands, strides multiple of 8; dropout_p > 0 needs drop_mask of tmi_attn_dropmask_bytes)");
+    tmi_set_error("tmi_attn_fwd: bad argument (16-byte aligned bf16 operands, strides multiple of 8; dropout_p > 0 needs drop_mask of tmi_attn_dropmask_bytes; mask_mode 2 needs key_bias and dropout_p == 0)");
     return TMI_ERR_INVALID;
   }
   AttnP P;
-  P.d = *dp;
+  set_desc(P, *dp);
   P.dq_scale = 1.f;
   P.sscale = dp->score_scale != 0.f ? dp->score_scale : 1.f;
   P.c2 = P.sscale * LOG2E;
@@ -1031,7 +1093,9 @@ static int tmi_attn_fwd_impl(const tmi_attn_desc* dp, void* stream) {
 #else
   constexpr int focc = 0;
 #endif
-  if (P.drop_thr) {
+  if (dp->mask_mode == 2) {  // (never key-split: pick_ksplit; never with dropout: check_common)
+    hipLaunchKernelGGL((attn_fwd_kernel<false, 3, 0, true>), grid, dim3(256), 4 * IMG + 2 * TROWS * sizeof(float), hs, P);
+  } else if (P.drop_thr) {
 #ifdef TMI_ATTN_EXPERIMENTS
     if (focc == 4) hipLaunchKernelGGL((attn_fwd_kernel<true, 4>), grid, dim3(256), 4 * IMG, hs, P);
     else if (focc == 5) hipLaunchKernelGGL((attn_fwd_kernel<true, 5>), grid, dim3(256), 4 * IMG, hs, P);
@@ -1071,8 +1135,12 @@ static int tmi_attn_bwd_impl(const tmi_attn_desc* dp, void* stream) {
     tmi_set_error("tmi_attn_bwd: bad argument");
     return TMI_ERR_INVALID;
   }
+  if (dp->mask_mode == 2) {
+    tmi_set_error("tmi_attn_bwd: mask_mode 2 (key bias) is forward only");
+    return TMI_ERR_INVALID;
+  }
   AttnP P;
-  P.d = *dp;
+  set_desc(P, *dp);
   P.dq_scale = dp->dq_scale;
   P.sscale = dp->score_scale != 0.f ? dp->score_scale : 1.f;
   P.c2 = P.sscale * LOG2E;

@@ -47,6 +47,45 @@ __global__ __launch_bounds__(256) void softmax_fwd_kernel(float* __restrict__ s,
   }
 }
 
+// The same row softmax with the additive key term of the padding mask (V:352-355): key c of batch b = row / rows_per_batch
+// gets kb[b * kb_sb + c] added in fp32 before the maximum is taken, as the reference adds (1 - mask) * -10000 to the scores.
+__global__ __launch_bounds__(256) void softmax_bias_fwd_kernel(float* __restrict__ s, int64_t rows, int64_t rows_per_batch, int Tk,
+                                                               const float* __restrict__ kb, int64_t kb_sb) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  float* p = s + row * Tk;
+  const float* kbr = kb + (row / rows_per_batch) * kb_sb;
+  float v[SM_E];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < SM_E; ++j) {
+    const int c = j * 64 + lane;
+    if (c < Tk) {
+      const float x = p[c] + kbr[c];
+      v[j] = x;
+      mx = fmaxf(mx, x);
+    } else {
+      v[j] = -INFINITY;
+    }
+  }
+  mx = wave_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < SM_E; ++j) {
+    const int c = j * 64 + lane;
+    const float e = (c < Tk) ? expf(v[j] - mx) : 0.f;
+    v[j] = e;
+    sum += e;
+  }
+  const float inv = 1.0f / wave_sum(sum);
+#pragma unroll
+  for (int j = 0; j < SM_E; ++j) {
+    const int c = j * 64 + lane;
+    if (c < Tk) p[c] = v[j] * inv;
+  }
+}
+
 __global__ __launch_bounds__(256) void softmax_bwd_kernel(const float* __restrict__ p, float* __restrict__ dp,
                                                           int64_t rows, int Tk) {
   const int lane = threadIdx.x & 63;
@@ -389,6 +428,21 @@ static int tmi_softmax_fwd_impl(float* s, int64_t rows, int64_t Tq, int64_t Tk, 
 }
 extern "C" int tmi_softmax_fwd(float* s, int64_t rows, int64_t Tq, int64_t Tk, int32_t mask_mode, void* stream) {
   return tmi_plan_run<tmi_softmax_fwd_impl>(s, rows, Tq, Tk, mask_mode, stream);
+}
+
+static int tmi_softmax_bias_fwd_impl(float* s, int64_t rows, int64_t Tq, int64_t Tk, int64_t H, const float* key_bias, int64_t kb_sb,
+                                     void* stream) {
+  if (!s || !key_bias || rows <= 0 || Tq <= 0 || H <= 0 || Tk <= 0 || Tk > 64 * SM_E || kb_sb < 0 || rows % (H * Tq) != 0) {
+    tmi_set_error("tmi_softmax_bias_fwd: bad argument (Tk <= 2048, rows a multiple of H * Tq, key_bias required)");
+    return TMI_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(softmax_bias_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), s, rows, H * Tq, (int)Tk, key_bias, kb_sb);
+  return tmi_check_launch("tmi_softmax_bias_fwd");
+}
+extern "C" int tmi_softmax_bias_fwd(float* s, int64_t rows, int64_t Tq, int64_t Tk, int64_t H, const float* key_bias, int64_t kb_sb,
+                                    void* stream) {
+  return tmi_plan_run<tmi_softmax_bias_fwd_impl>(s, rows, Tq, Tk, H, key_bias, kb_sb, stream);
 }
 
 static int tmi_softmax_bwd_impl(const float* p, float* dp, int64_t rows, int64_t Tk, void* stream) {

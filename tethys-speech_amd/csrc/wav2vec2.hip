@@ -1200,3 +1200,72 @@ static int tmi_loss_combine_impl(const float* a, const float* b, float w, float 
 extern "C" int tmi_loss_combine(const float* a, const float* b, float w, float scale, float* out, void* stream) {
   return tmi_plan_run<tmi_loss_combine_impl>(a, b, w, scale, out, stream);
 }
+
+// ---------------------------------------------------------------- masked mean over time (V:1031-1042)
+// out[b, c] = sum_t x[b, t, c] * mask[b, t] / sum_t mask[b, t].  A bandwidth kernel: one workgroup per (batch row, slab of
+// 16 x 16-byte channel chunks); thread (tt, tc) walks t = tt, tt + 16, ... over chunk tc with one 16-byte load per step, then
+// thread (0, tc) folds the 16 partials in the order tt = 0 .. 15.  fp32 throughout, no atomics: two runs are bit-identical.
+namespace {
+template <typename T>
+__global__ __launch_bounds__(256) void masked_mean_pool_kernel(const T* __restrict__ x, const float* __restrict__ mask,
+                                                               float* __restrict__ out, int Tn, int C) {
+  constexpr int VEC = 16 / sizeof(T);
+  typedef __attribute__((ext_vector_type(VEC))) T vec_t;
+  __shared__ float red[16][16][VEC + 1];
+  const int tc = threadIdx.x & 15, tt = threadIdx.x >> 4;
+  const int64_t b = blockIdx.y;
+  const int c0 = ((int)blockIdx.x * 16 + tc) * VEC;
+  const bool active = c0 < C;  // (C is a multiple of VEC: a chunk is inside the row or past it)
+  const T* xb = x + b * (int64_t)Tn * C + c0;
+  float acc[VEC];
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
+  float msum = 0.f;
+  for (int t = tt; t < Tn; t += 16) {
+    const float w = mask ? mask[b * Tn + t] : 1.f;
+    msum += w;
+    if (active) {
+      const vec_t v = *reinterpret_cast<const vec_t*>(xb + (int64_t)t * C);
+#pragma unroll
+      for (int i = 0; i < VEC; ++i) acc[i] = fmaf(to_f32(v[i]), w, acc[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) red[tt][tc][i] = acc[i];
+  red[tt][tc][VEC] = msum;
+  __syncthreads();
+  if (tt != 0 || !active) return;
+  float den = 0.f;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
+  for (int r = 0; r < 16; ++r) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) acc[i] += red[r][tc][i];
+    den += red[r][tc][VEC];
+  }
+  // a row whose mask sums to zero: zeros (the reference divides 0 by 0 there)
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) out[b * C + c0 + i] = den > 0.f ? acc[i] / den : 0.f;
+}
+}  // namespace
+
+static int tmi_masked_mean_pool_impl(const void* x, int32_t x_dtype, const float* mask, float* out, int64_t B, int64_t T, int64_t C,
+                                     void* stream) {
+  const int vec = x_dtype == TMI_BF16 ? 8 : 4;
+  if (!x || !out || B <= 0 || T <= 0 || C <= 0 || B > 65535 || T > INT32_MAX || C > INT32_MAX || C % vec != 0 ||
+      (x_dtype != TMI_F32 && x_dtype != TMI_BF16) || (reinterpret_cast<uintptr_t>(x) & 15) != 0) {
+    tmi_set_error("tmi_masked_mean_pool: bad argument (x 16-byte aligned, C a multiple of 4 (fp32) / 8 (bf16), B <= 65535)");
+    return TMI_ERR_INVALID;
+  }
+  const dim3 grid((unsigned)((C / vec + 15) / 16), (unsigned)B);
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  if (x_dtype == TMI_BF16)
+    hipLaunchKernelGGL(masked_mean_pool_kernel<bf16_t>, grid, dim3(256), 0, hs, reinterpret_cast<const bf16_t*>(x), mask, out, (int)T, (int)C);
+  else
+    hipLaunchKernelGGL(masked_mean_pool_kernel<float>, grid, dim3(256), 0, hs, reinterpret_cast<const float*>(x), mask, out, (int)T, (int)C);
+  return tmi_check_launch("tmi_masked_mean_pool");
+}
+extern "C" int tmi_masked_mean_pool(const void* x, int32_t x_dtype, const float* mask, float* out, int64_t B, int64_t T, int64_t C,
+                                    void* stream) {
+  return tmi_plan_run<tmi_masked_mean_pool_impl>(x, x_dtype, mask, out, B, T, C, stream);
+}

@@ -307,6 +307,14 @@ def softmax_fwd(s, rows, Tq, Tk, mask_mode):
     check(lib().tmi_softmax_fwd(s.data_ptr(), rows, Tq, Tk, mask_mode, stream()), "tmi_softmax_fwd")
 
 
+def softmax_bias_fwd(s, rows, Tq, Tk, H, key_bias):
+    """tmi_softmax_fwd with the additive key term ``key_bias`` fp32 [B, Tk] (row r belongs to batch r // (H * Tq))."""
+    if key_bias.dtype != torch.float32 or key_bias.dim() != 2 or key_bias.shape[1] != Tk or key_bias.stride(1) != 1:
+        raise ValueError("key_bias must be float32 [B, Tk] with contiguous rows")
+    check(lib().tmi_softmax_bias_fwd(s.data_ptr(), rows, Tq, Tk, H, key_bias.data_ptr(), key_bias.stride(0), stream()),
+          "tmi_softmax_bias_fwd")
+
+
 def softmax_bwd(p, dp, rows, Tk):
     check(lib().tmi_softmax_bwd(p.data_ptr(), dp.data_ptr(), rows, Tk, stream()), "tmi_softmax_bwd")
 
@@ -366,10 +374,16 @@ def _set_dropout(d, dropout_p, dropout_seed, drop_mask):
         d.drop_mask, d.drop_mask_bytes = drop_mask.data_ptr(), drop_mask.numel() * drop_mask.element_size()
 
 
-def attn_fwd(q, k, v, o, stats, B, H, Tq, Tk, mask_mode=0, score_scale=1.0, dropout_p=0.0, dropout_seed=0, drop_mask=None):
+def attn_fwd(q, k, v, o, stats, B, H, Tq, Tk, mask_mode=0, score_scale=1.0, dropout_p=0.0, dropout_seed=0, drop_mask=None,
+             key_bias=None):
+    """``key_bias`` (mask_mode 2): fp32 [B, Tk], added to the scores of key column j of batch b (natural-log units)."""
     with _probe("attention", 4.0 * B * H * Tq * Tk * 64):
         d = _attn_desc(q, k, v, o, stats, B, H, Tq, Tk, mask_mode, score_scale)
         _set_dropout(d, dropout_p, dropout_seed, drop_mask)
+        if key_bias is not None:
+            if key_bias.dtype != torch.float32 or key_bias.dim() != 2 or key_bias.shape != (B, Tk) or key_bias.stride(1) != 1:
+                raise ValueError("key_bias must be float32 [B, Tk] with contiguous rows")
+            d.key_bias, d.kb_sb = key_bias.data_ptr(), key_bias.stride(0)
         check(lib().tmi_attn_fwd(C.byref(d), stream()), "tmi_attn_fwd")
 
 
@@ -391,6 +405,15 @@ def attn_bwd(q, k, v, o, stats, do, dq, dk, dv, delta, B, H, Tq, Tk, mask_mode=0
     # (3 of the 7 products are the dQ pass, 4 the dK/dV pass)
     with _probe("attention", 8.0 * B * H * Tq * Tk * 64 * (1.0 if passes in (0, 3) else (3.0 / 7.0 if passes == 1 else 4.0 / 7.0))):
         check(lib().tmi_attn_bwd(C.byref(d), stream()), "tmi_attn_bwd")
+
+
+def masked_mean_pool(x, mask, out, B, T, C):
+    """out[b, c] = sum_t x[b, t, c] mask[b, t] / sum_t mask[b, t] (fp32 [B, C]); ``mask`` fp32 [B, T] or None: the plain mean."""
+    if not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C or x.numel() != B * T * C:
+        raise ValueError("masked_mean_pool: x [B, T, C] contiguous, out float32 [B, C] contiguous")
+    if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.numel() != B * T):
+        raise ValueError("masked_mean_pool: mask must be float32 [B, T] contiguous")
+    check(lib().tmi_masked_mean_pool(x.data_ptr(), dt(x), ptr(mask), out.data_ptr(), B, T, C, stream()), "tmi_masked_mean_pool")
 
 
 def fill_zero(t):

@@ -98,6 +98,30 @@ def sample_negative_indices_roll(rng: np.random.Generator, T: int, num_negatives
     return np.stack([np.roll(perm, t + 1)[:n] for t in range(T)])
 
 
+def frame_lengths(cfg: Wav2Vec2Config, sample_lengths) -> List[int]:
+    """Frames each clip of ``sample_lengths`` samples occupies behind the "same"-padded conv stem: ceil(L / stride) per
+    layer (V:283-288 with Keras padding="same")."""
+    out = []
+    for n in sample_lengths:
+        n = int(n)
+        if n < 0:
+            raise ValueError("sample lengths must be >= 0")
+        for s in cfg.conv_stride:
+            n = -(-n // s)
+        out.append(n)
+    return out
+
+
+def frame_attention_mask(cfg: Wav2Vec2Config, sample_lengths, T_in: int) -> torch.Tensor:
+    """The reference's ``attention_mask`` argument for a batch of clips padded to ``T_in`` samples: float32 [B, T] over
+    frames, 1 on the first ``frame_lengths`` frames of each clip and 0 behind them (host tensor)."""
+    if any(int(n) > T_in for n in sample_lengths):
+        raise ValueError("a clip is longer than the padded batch")
+    T = frame_lengths(cfg, [T_in])[0]
+    fl = torch.tensor(frame_lengths(cfg, sample_lengths), dtype=torch.int64)
+    return (torch.arange(T)[None, :] < fl[:, None]).to(torch.float32)
+
+
 class W2VArena(Arena):
     def __init__(self, cfg: Wav2Vec2Config, device):
         H, I = cfg.hidden_size, cfg.intermediate_size
@@ -137,7 +161,7 @@ class W2VArena(Arena):
 
 
 class Wav2Vec2ForPreTraining(KernelBlocks):
-    """V:826-937 (training path only)."""
+    """V:826-937: the pre-training step, and the forward pass alone of the model inside it (V:768-825, ``forward_infer``)."""
 
     def __init__(self, config: Wav2Vec2Config, device="cuda:0", precision: str = "bf16", seed: int = 1234):
         if precision not in ("fp32", "bf16"):
@@ -624,10 +648,207 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         self._join_side()
         return ws["loss"]
 
-    def __call__(self, inputs, neg_indices=None, training=True):
-        if not training or neg_indices is None:
-            raise NotImplementedError("only the training path is on the hot path")
-        return {"loss": self.forward_backward(inputs, neg_indices)}
+    def __call__(self, inputs, neg_indices=None, attention_mask=None, output_hidden_states=False, pool=None, training=None):
+        """V:768-825.  ``training=True`` with ``neg_indices`` is the pre-training step (-> ``{"loss": ...}``); ``training=False``
+        - the default when no ``neg_indices`` are given - is the forward pass alone, see ``forward_infer``."""
+        if training is None:
+            training = neg_indices is not None
+        if training:
+            if neg_indices is None:
+                raise ValueError("the training path takes neg_indices")
+            if attention_mask is not None or output_hidden_states or pool is not None:
+                raise ValueError("attention_mask, output_hidden_states and pool belong to the inference call (training=False)")
+            return {"loss": self.forward_backward(inputs, neg_indices)}
+        if neg_indices is not None:
+            raise ValueError("neg_indices belong to the training call")
+        return self.forward_infer(inputs, attention_mask=attention_mask, output_hidden_states=output_hidden_states, pool=pool)
+
+    # -- inference (forward only): V:768-825 with training=False --------------------------------------------------------
+    # Its own workspace set (``_inf``), never one of ``_ws_sets``: no saved pre-activations, no gradient buffers, every
+    # encoder layer works in the same buffers.  It is ``self.ws`` only for the duration of a call (the blocks read
+    # ``self.ws``); the geometry lives in the set, not in the attributes ``_prepare`` keeps for the step.  Nothing of the
+    # training state (``_ws_key``, ``_ws_sets``, ``_drop_step``, ``arena.g`` / ``g_clean``, recorded plans, the optimizer) is
+    # read or written, and no dropout site is passed: dropout is off even after ``enable_dropout``.
+
+    def _infer_prepare(self, B: int, T_in: int) -> dict:
+        inf = self.__dict__.get("_inf")
+        if inf is not None and inf["key"] == (B, T_in):
+            return inf
+        self._inf = None  # (the previous set is released first)
+        cfg = self.config
+        f32 = torch.float32
+        L, Gn = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups
+        lens, pads, T = [], [], T_in
+        for k, s in zip(cfg.conv_kernel, cfg.conv_stride):
+            To, pl, pr = same_pad(T, k, s)
+            pads.append((pl, pr))
+            lens.append(To)
+            T = To
+        Tp = [([T_in] + lens)[i] + pads[i][0] + pads[i][1] for i in range(L)]
+        c0 = cfg.conv_dim[0]
+        fir0 = (cfg.conv_kernel[0] == 10 and cfg.conv_stride[0] == 5 and c0 % 8 == 0 and 2048 % c0 == 0 and
+                (c0 // Gn) % 8 == 0 and os.environ.get("TMI_W2V_FIR", "1") != "0")
+        kp = cfg.num_conv_pos_embeddings
+        inf = dict(key=(B, T_in), lens=lens, pads=pads, T=T, fir0=fir0, plp=same_pad(T, kp, 1)[1], Tpp=T + kp - 1)
+        saved, self.ws = self.ws, {}
+        try:
+            slack = 2
+            if not fir0:
+                self._buf("in0", (B, Tp[0] + slack + 8, 1), zero=True)
+            for i in range(L):
+                c = cfg.conv_dim[i]
+                if not (i == 0 and fir0):
+                    self._buf(f"u{i}", (B, lens[i], c))
+                if i + 1 < L:
+                    self._buf(f"in{i + 1}", (B, Tp[i + 1] + slack, c), zero=True)  # (the pad rows stay zero: only rows of the clip are written)
+            self._buf("gn.stats", (B, Gn, 2), f32)
+            nch = max([ops.groupnorm_chunks(t) for t in lens] + ([ops.fir_chunks(lens[0])] if fir0 else []))
+            self._buf("gn_part", (B * nch * Gn * 2,), f32)
+            C, H, ff, Hh = cfg.conv_dim[-1], cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads
+            R, Cg = B * T, C // Gn
+            for n, w in (("h_last", C), ("hp", C), ("feats", C), ("fp_pre", H), ("x", H), ("x_mid", H), ("xn", H), ("ctx", H),
+                         ("qkv", 3 * H), ("g", ff)):
+                self._buf(n, (R, w))
+            self._buf("xg", (Gn, B * inf["Tpp"], Cg))
+            self._buf("yg", (Gn, B * inf["Tpp"], Cg))
+            self._buf("ln.mean", (R,), f32)
+            self._buf("ln.rstd", (R,), f32)
+            self._buf("att", (B, Hh, T, 2) if self.precision == "bf16" else (B, Hh, T, T), f32)
+            inf["ws"] = self.ws
+        finally:
+            self.ws = saved
+        self._inf = inf
+        return inf
+
+    def _infer_begin(self, inf):
+        """Enter an inference call: pin the stream, order it behind every parameter update that may still be running on the
+        second stream (a late Adam slice: its persistent event is waited for, ``_late_pending`` is left as it is), and swap
+        the inference workspace in."""
+        self.begin_step()
+        main = self._main or torch.cuda.current_stream(self.device)
+        for ev in self.__dict__.get("_late_done", {}).values():
+            main.wait_event(ev)  # (a wait on an event that has completed, or was never recorded, is free)
+        if self._side is not None:
+            main.wait_stream(self._side)
+        saved = self.ws
+        self.ws = inf["ws"]
+        return saved
+
+    def _infer_end(self, saved):
+        self.ws = saved
+        self.end_step()
+
+    def _check_mask(self, attention_mask, B, T):
+        """[B, T] over frames, values in [0, 1], float or bool -> fp32 on the host."""
+        m = torch.as_tensor(attention_mask).detach().to("cpu")
+        if m.dim() != 2 or tuple(m.shape) != (B, T):
+            raise ValueError(f"attention_mask must be [B, T] over frames = [{B}, {T}] (frame_attention_mask), got {list(m.shape)}")
+        m = m.to(torch.float32)
+        if not bool(((m >= 0) & (m <= 1)).all()):
+            raise ValueError("attention_mask values must lie in [0, 1]")
+        return m.contiguous()
+
+    @torch.no_grad()
+    def forward_infer(self, inputs, attention_mask=None, output_hidden_states=False, pool=None):
+        """The reference's ``Wav2Vec2Model.call(..., training=False)`` (V:768-825): conv stem, grouped positional conv,
+        LayerNorm, feature projection with its LayerNorm, encoder layers; no quantiser, no projection heads, no loss, no
+        dropout.  ``inputs`` float32 [B, T_in].  Returns a dict with ``last_hidden_state`` [B, T, H], ``extract_features``
+        [B, T, C], with ``output_hidden_states`` ``hidden_states`` (the input of every layer and the output of the last:
+        num_hidden_layers + 1 tensors, V:488-537) and with ``pool="mean"`` ``pooled_output`` fp32 [B, H], the masked mean
+        over time of V:1031-1042 (the plain mean without a mask; a clip whose mask is all zero pools to zeros).
+
+        ``attention_mask`` [B, T] over FRAMES (``frame_attention_mask``), values in [0, 1], is the reference's argument as
+        is: the host turns it into (1 - mask) * -10000 once, and every layer's attention adds that to the scores of the
+        masked keys (V:352-355).  Only attention keys are masked, as in the reference: the stem's GroupNorm statistics and
+        the positional conv see the padding, so a padded clip does NOT reproduce the same clip run alone - in the reference
+        or here.  ``None`` runs the unmasked kernels of the training step."""
+        cfg = self.config
+        if pool not in (None, "mean"):
+            raise ValueError('pool must be None or "mean"')
+        if not torch.is_tensor(inputs) or inputs.dim() != 2 or inputs.dtype != torch.float32 or inputs.shape[0] < 1:
+            raise TypeError("inputs must be float32 [B, T_in]")
+        B, T_in = inputs.shape
+        T = frame_lengths(cfg, [T_in])[0]
+        mask = None if attention_mask is None else self._check_mask(attention_mask, B, T)
+        audio = inputs.to(self.device).contiguous()
+        inf = self._infer_prepare(B, T_in)
+        saved = self._infer_begin(inf)
+        try:
+            ws, a = self.ws, self.arena
+            L, Gn = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups
+            H, C, Hh = cfg.hidden_size, cfg.conv_dim[-1], cfg.num_attention_heads
+            lens, pads = inf["lens"], inf["pads"]
+            R = B * T
+            sscale = 1.0 / math.sqrt(H // Hh)
+            key_bias = mask_dev = None
+            if mask is not None:
+                mask_dev = mask.to(self.device)
+                key_bias = ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, on the host, once per call
+
+            # ---- feature encoder (V:283-288)
+            if not inf["fir0"]:
+                in0 = ws["in0"]
+                ops.feat_to_channels_last(audio, in0, B, 1, T_in, pads[0][0], in0.shape[1] - T_in - pads[0][0])
+            cin = 1
+            for i in range(L):
+                c, k, s = cfg.conv_dim[i], cfg.conv_kernel[i], cfg.conv_stride[i]
+                pre = f"feature_extractor.conv_layers.{i}.norm"
+                if i + 1 < L:
+                    y, ysb, yoff = ws[f"in{i + 1}"], ws[f"in{i + 1}"].stride(0), pads[i + 1][0] * c
+                else:
+                    y, ysb, yoff = ws["h_last"], lens[i] * c, 0
+                if i == 0 and inf["fir0"]:
+                    ops.fir_groupnorm_gelu_fwd(audio, pads[0][0], a.param("feature_extractor.conv_layers.0.conv.kernel"), k, s,
+                                               a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb, ws["gn.stats"],
+                                               ws["gn_part"], B, lens[0], c, Gn, 1e-5, y_off=yoff)
+                else:
+                    xin, u = ws[f"in{i}"], ws[f"u{i}"]
+                    self._gemm_xw(xin, f"feature_extractor.conv_layers.{i}.conv.kernel", u, lens[i], c, k * cin, s * cin,
+                                  ldc=c, nbatch=B, a_sb=xin.stride(0), c_sb=u.stride(0))
+                    ops.groupnorm_gelu_fwd(u, u.stride(0), a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb,
+                                           ws["gn.stats"], ws["gn_part"], B, lens[i], c, Gn, 1e-5, y_off=yoff)
+                cin = c
+
+            # ---- grouped positional conv (V:271-277, V:291), LayerNorm, feature projection (V:777-778)
+            kp, Cg, Tpp = cfg.num_conv_pos_embeddings, C // Gn, inf["Tpp"]
+            ops.group_pack(ws["h_last"], ws["xg"], B, T, C, Gn, Tpp, inf["plp"])
+            ops.gemm(ws["xg"], self.pos_wf, ws["yg"], B * Tpp - (kp - 1), Cg, kp * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
+                     a_sb=B * Tpp * Cg, b_sb=kp * Cg * Cg, c_sb=B * Tpp * Cg)
+            ops.group_unpack(ws["yg"], a.param("feature_extractor.pos_conv_embed.bias"), ws["h_last"], ws["hp"], B, T, C, Gn,
+                             Tpp, 0)
+            self._ln_fwd(ws["hp"], "feature_extractor.layer_norm", ws["feats"], "ln")
+            self._dense_fwd(ws["feats"], "feature_projection.kernel", ws["fp_pre"])
+            x = ws["x"]
+            self._ln_fwd(ws["fp_pre"], "feature_projection_layer_norm", x, "ln")
+
+            # ---- encoder (V:419-439, stable layer norm): each layer's output overwrites its input
+            hidden = []
+            for i in range(cfg.num_hidden_layers):
+                p = f"encoder.layers.{i}"
+                if output_hidden_states:
+                    hidden.append(x.view(B, T, H).clone())
+                self._ln_fwd(x, p + ".attention_layer_norm", ws["xn"], "ln")
+                wq, _ = self.W(p + ".attention.qkv3.kernel")
+                qkv = ws["qkv"]
+                ops.gemm(ws["xn"], wq, qkv, R, H, H, H, 1, H, 1, 3 * H, nbatch=3, b_sb=H * H, c_sb=H,
+                         bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
+                self._attn_fwd("att", (qkv, 0), (qkv, H), (qkv, 2 * H), ws["ctx"], B, Hh, T, T, 0, score_scale=sscale,
+                               key_bias=key_bias)
+                self._dense_fwd(ws["ctx"], p + ".attention.out_proj.kernel", ws["x_mid"], resid=x, r_ld=H)
+                self._ln_fwd(ws["x_mid"], p + ".feed_forward_layer_norm", ws["xn"], "ln")
+                self._dense_fwd(ws["xn"], p + ".feed_forward.intermediate_dense.kernel", ws["g"], act=1)
+                self._dense_fwd(ws["g"], p + ".feed_forward.output_dense.kernel", x, resid=ws["x_mid"], r_ld=H)
+            last = x.view(B, T, H).clone()
+            result = {"last_hidden_state": last, "extract_features": ws["feats"].view(B, T, C).clone()}
+            if output_hidden_states:
+                result["hidden_states"] = tuple(hidden) + (last,)
+            if pool == "mean":
+                pooled = torch.empty(B, H, dtype=torch.float32, device=self.device)
+                ops.masked_mean_pool(x, mask_dev, pooled, B, T, H)
+                result["pooled_output"] = pooled
+        finally:
+            self._infer_end(saved)
+        return result
 
 
 def create_full_model(model_type: str = "pretraining", model_size: str = "small", device="cuda:0",
