@@ -11,15 +11,18 @@ namespace {
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, float b1, float b2, float eps,
                                       float step_size, float vcorr_inv_sqrt, int eps_mode, float decay,
                                       float gscale) {
+  // Every multiply-add is spelled out and the compiler may fuse nothing else.  Left to itself it chose per call site: the
+  // dense kernel's 16-byte loop fused b1 * m and b2 * v into the additions, its tail and the segments kernel fused
+  // (1 - b1) * g instead, and the segments kernel's scalar loop fused nothing, so the same data came out one rounding
+  // apart depending on the kernel and on where a variable starts.  The forms below are the dense 16-byte loop's.
+#pragma clang fp contract(off)
   g *= gscale;
-  m = b1 * m + (1.0f - b1) * g;
-  v = b2 * v + (1.0f - b2) * g * g;
-  p *= decay;
-  if (eps_mode == 0) {
-    p -= step_size * m / (sqrtf(v) + eps);  // Keras-V2: eps beside sqrt(v), correction in step_size
-  } else {
-    p -= step_size * m / (sqrtf(v) * vcorr_inv_sqrt + eps);  // torch: eps beside sqrt(v_hat)
-  }
+  m = fmaf(b1, m, (1.0f - b1) * g);
+  v = fmaf(b2, v, ((1.0f - b2) * g) * g);
+  float den = sqrtf(v);
+  if (eps_mode != 0) den *= vcorr_inv_sqrt;  // torch: eps beside sqrt(v_hat); Keras-V2: beside sqrt(v), correction in step_size
+  den += eps;
+  p = fmaf(decay, p, -(step_size * m / den));
 }
 
 // ZG: also write zeros over the gradients just consumed (the next step's backward accumulates into a clean arena
