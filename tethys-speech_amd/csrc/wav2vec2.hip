@@ -15,8 +15,25 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 // x [B][T][C] (batch stride xsb), contiguous channel groups of Cg = C / G.
 // Thread tid of a 256-thread block always sees the same channel chunk (256*VEC % C == 0), hence
 // one group: it keeps (a, b) partial sums for that group over the block's row range.
-// mode 0 (forward stats):   a = sum x,            b = sum x^2
+// mode 0 (forward stats):   a = sum (x - p),      b = sum (x - p)^2,      p = gn_pivot of the (batch row, group)
 // mode 1 (backward sums):   a = sum dz*gamma,     b = sum dz*gamma*xhat,  dz = dy * gelu'(z)
+// The pivot the forward statistics are centred on: the mean of the group's Cg channels at t = 0, summed in channel order
+// (every thread of a group, every chunk and the fold of the consumer compute the same bits).  var = E[(x-p)^2] - E[x-p]^2
+// then cancels by a factor 1 + ((mean - p) / std)^2 ~ 1 + 1/Cg instead of the 1 + (mean / std)^2 of the raw moments: a
+// group with mean = 16 std lost 8 bits of rstd to that.
+template <typename T>
+__device__ __forceinline__ float gn_pivot(const T* __restrict__ row0, int g, int Cg) {
+  constexpr int VEC = 16 / sizeof(T);
+  float s = 0.f;
+  for (int c = 0; c < Cg; c += VEC) {
+    const u32x4 raw = *reinterpret_cast<const u32x4*>(row0 + g * Cg + c);
+    const T* e = reinterpret_cast<const T*>(&raw);
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) s += to_f32(e[i]);
+  }
+  return s / (float)Cg;  // (a division, not a multiply by 1/Cg: nothing for the compiler to contract into `x - p`)
+}
+
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, int64_t xsb,
                                                          const T* __restrict__ dy, int64_t dysb,
@@ -35,19 +52,21 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
   const int r0 = chunk * rows_per_chunk, r1 = min(Tn, r0 + rows_per_chunk);
   const int rstep = 256 / cpr > 0 ? 256 / cpr : 1;
   float a = 0.f, bsum = 0.f;
-  float gm[VEC], bt[VEC], mean = 0.f, rstd = 0.f;
+  float gm[VEC], bt[VEC], mean = 0.f, rstd = 0.f, piv = 0.f;
   if (MODE == 1) {
 #pragma unroll
     for (int i = 0; i < VEC; ++i) { gm[i] = gamma[c0 + i]; bt[i] = beta[c0 + i]; }
     mean = stats[(b * G + g) * 2];
     rstd = stats[(b * G + g) * 2 + 1];
+  } else {
+    piv = gn_pivot<T>(x + (int64_t)b * xsb, g, Cg);
   }
   if (threadIdx.x < cpr * rstep) {
     auto one = [&](const u32x4& raw, const u32x4& rawd) {
       const T* e = reinterpret_cast<const T*>(&raw);
       if (MODE == 0) {
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) { const float v = to_f32(e[i]); a += v; bsum += v * v; }
+        for (int i = 0; i < VEC; ++i) { const float v = to_f32(e[i]) - piv; a += v; bsum += v * v; }
       } else {
         const T* ed = reinterpret_cast<const T*>(&rawd);
 #pragma unroll
@@ -107,11 +126,13 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
 // others costs its duration plus a kernel boundary, 14 times per Wav2Vec2 step): every workgroup of an apply kernel folds
 // the chunk partials of ITS batch row - thread t takes group t % G and every (256 / G)-th chunk from t / G on, in double,
 // then the first G threads add the slices in slice order (a fixed association: the result is a function of the partials
-// alone) - and leaves (v0, v1) per group in `sh` ([2 * G] floats of LDS).  mode 0: (mean, rstd); mode 1: (mean(dxhat),
+// alone) - and leaves (v0, v1) per group in `sh` ([2 * G] floats of LDS).  mode 0: (mean, rstd), the partials being
+// moments about pivot(g) (gn_pivot for the GroupNorm kernels, 0 for the FIR ones); mode 1: (mean(dxhat),
 // mean(dxhat * xhat)).  The workgroups with blockIdx.x == 0 also store the pairs to `out` (the backward reads the
 // statistics again).  `part` is L2-resident (written by the launch before) and 2 * nchunks * G floats per batch row.
+template <typename PIVOT>
 __device__ __forceinline__ void gn_fold_block(const float* __restrict__ part, int b, int G, int nchunks, double count, float eps,
-                                              int mode, float* __restrict__ sh, float* __restrict__ out) {
+                                              int mode, float* __restrict__ sh, float* __restrict__ out, PIVOT pivot) {
   __shared__ double shd[512];
   const int t = threadIdx.x;
   const int nsub = G >= 256 ? 1 : 256 / G;
@@ -135,10 +156,10 @@ __device__ __forceinline__ void gn_fold_block(const float* __restrict__ part, in
     }
     float v0, v1;
     if (mode == 0) {
-      const double mean = A / count;
+      const double mean = A / count;  // about the pivot
       double var = S / count - mean * mean;
       if (var < 0.0) var = 0.0;
-      v0 = (float)mean;
+      v0 = (float)((double)pivot(t) + mean);
       v1 = (float)(1.0 / sqrt(var + (double)eps));
     } else {
       v0 = (float)(A / count);
@@ -166,7 +187,9 @@ __global__ __launch_bounds__(256) void gn_apply_fwd_kernel(const T* __restrict__
   const int b = blockIdx.y;
   const int Cg = C / G;
   __shared__ float shs[512];
-  gn_fold_block(part, b, G, nchunks, count, eps, 0, shs, stats);  // (mean, rstd) of this batch row's groups
+  const T* xb = x + (int64_t)b * xsb;
+  gn_fold_block(part, b, G, nchunks, count, eps, 0, shs, stats,
+                [&](int g_) { return gn_pivot<T>(xb, g_, Cg); });  // (mean, rstd) of this batch row's groups
   const int64_t nvec = (int64_t)Tn * C / VEC;
   // 256 * VEC is a multiple of C (gn_check), so a thread keeps its channels across the grid-stride loop:
   // gamma / beta / statistics are loaded once
@@ -176,7 +199,6 @@ __global__ __launch_bounds__(256) void gn_apply_fwd_kernel(const T* __restrict__
   float gm[VEC], bt[VEC];
 #pragma unroll
   for (int i = 0; i < VEC; ++i) { gm[i] = gamma[c0 + i]; bt[i] = beta[c0 + i]; }
-  const T* xb = x + (int64_t)b * xsb;
   T* yb = y + (int64_t)b * ysb;
   const int64_t step = (int64_t)gridDim.x * 256;
   auto one = [&](const u32x4& raw, int64_t v) {
@@ -213,7 +235,7 @@ __global__ __launch_bounds__(256) void gn_apply_bwd_kernel(const T* __restrict__
   float* red = reinterpret_cast<float*>(smem);  // [rstep][2][C]
   const int b = blockIdx.y, chunk = blockIdx.x;
   __shared__ float shs[512];
-  gn_fold_block(part, b, G, nchunks, count, 0.f, 1, shs, sums);  // (mean(dxhat), mean(dxhat * xhat)) of this batch row's groups
+  gn_fold_block(part, b, G, nchunks, count, 0.f, 1, shs, sums, [](int) { return 0.f; });  // (mean(dxhat), mean(dxhat * xhat)) of this batch row's groups
   const int Cg = C / G;
   const int cpr = C / VEC;
   const int c0 = (threadIdx.x % cpr) * VEC;
@@ -398,7 +420,7 @@ __global__ __launch_bounds__(256) void fir_gn_apply_fwd_kernel(const float* __re
   float* win = reinterpret_cast<float*>(smem);
   const int b = blockIdx.y, chunk = blockIdx.x;
   __shared__ float shs[512];
-  gn_fold_block(part, b, G, nchunks, count, eps, 0, shs, stats);
+  gn_fold_block(part, b, G, nchunks, count, eps, 0, shs, stats, [](int) { return 0.f; });
   const int Cg = C / G, cpr = C / 8;
   const int c0 = (threadIdx.x % cpr) * 8, g = c0 / Cg;
   const int rstep = 256 / cpr;
@@ -435,7 +457,7 @@ __global__ __launch_bounds__(256) void fir_gn_apply_bwd_kernel(const float* __re
   float* red = win + ((rows_per_chunk * S + KW + 3) & ~3);           // [rstep][C] fold buffer
   const int b = blockIdx.y, chunk = blockIdx.x;
   __shared__ float shs[512];
-  gn_fold_block(part, b, G, npart, count, 0.f, 1, shs, sums);
+  gn_fold_block(part, b, G, npart, count, 0.f, 1, shs, sums, [](int) { return 0.f; });
   const int Cg = C / G, cpr = C / 8;
   const int c0 = (threadIdx.x % cpr) * 8, g = c0 / Cg;
   const int rstep = 256 / cpr, rl = threadIdx.x / cpr;
@@ -636,7 +658,11 @@ __global__ __launch_bounds__(256) void vq_perplexity_kernel(const int32_t* __res
   __shared__ float red[4];
   for (int i = threadIdx.x; i < G * Nc; i += 256) cnt[i] = 0;
   __syncthreads();
-  for (int64_t i = threadIdx.x; i < rows * G; i += 256) atomicAdd(&cnt[(i % G) * Nc + idx[i]], 1);
+  for (int64_t i = threadIdx.x; i < rows * G; i += 256) {
+    int bi = idx[i];
+    bi = bi < 0 ? 0 : (bi >= Nc ? Nc - 1 : bi);  // as vq_assign_kernel: the code counted is the code assigned
+    atomicAdd(&cnt[(i % G) * Nc + bi], 1);
+  }
   __syncthreads();
   float total = 0.f;
   for (int g = 0; g < G; ++g) {
@@ -696,7 +722,7 @@ __global__ __launch_bounds__(128) void contrastive_kernel(float* __restrict__ S,
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
   __syncthreads();
   sum = red[0] + red[1];
-  if (threadIdx.x == 0) row_loss[row] = mx + logf(sum) - lg[0];
+  if (threadIdx.x == 0) row_loss[row] = (mx - lg[0]) + logf(sum);  // (not mx + log - lg0: that rounds at the size of the logits, u * 500 for a dominant positive)
   const float inv = 1.0f / sum;
   // scatter d loss / d logits back onto the S row (indices may repeat or equal t): LDS atomics
   for (int i = threadIdx.x; i <= Nn; i += 128) {
