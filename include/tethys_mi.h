@@ -413,6 +413,49 @@ int tmi_beam_step(const int32_t* cand_ids, const float* cand_lp, int64_t N, int6
                   int32_t* done, int32_t* done_count, int32_t finalize, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Teacher-forced scoring without a whole-vocabulary buffer (whisper.py evaluate / score: the loss of W:585-600 and the
+ * SparseCategoricalAccuracy of W:904-907, forward only).  The caller evaluates the LM head in column chunks with tmi_gemm -
+ * chunk c holds the columns [col0, col0 + ncols) of the logits z[M, V..] as chunk[r * ld + j] = z[r, col0 + j] (dtype: F32
+ * or BF16) - and calls this once per chunk, in ascending col0, on one stream.  Running state per row r, in `state`:
+ *   (m_r, s_r)  max and sum exp(z - m_r) over the real columns n < V seen so far (fp32 online softmax).  Inside a chunk
+ *               lane l of the row's wave folds its 16-byte vectors (8 bf16 / 4 fp32 columns at j = (l + 64 i) * 8 or * 4)
+ *               in ascending i, the 64 lane partials meet in a butterfly (lane distance 32, 16, .., 1) in which the lower
+ *               lane's pair is folded first, and the chunk's pair is folded behind the running one: for a fixed sequence of
+ *               (col0, ncols) every output is bit-reproducible;
+ *   best_r      argmax over n < V: the largest stored logit, the smallest column among equals (-0 == +0), as a 64-bit key
+ *               (order-preserving float bits << 32 | ~n, tmi_lm_head_argmax's); a chunk's best replaces the running best
+ *               only when strictly greater, so the earlier chunk wins a tie;
+ *   zt_r        the target logit, taken in the chunk with col0 <= targets[r] < col0 + ncols: read from the chunk (zts_r); for
+ *               BF16 chunks with x and w given also recomputed as x[r * x_ld + k] . w[k * w_sk + targets[r] * w_sn], k < d,
+ *               in fp32 from the bf16 operands the GEMM read (the note on tmi_linear_xent says why).  F32 chunks ignore x, w.
+ * first = 1 (exactly when col0 == 0) initialises the state from this chunk: the buffer needs no zeroing and may hold
+ * anything.  last = 1 (exactly when col0 + ncols >= V) also writes, for every row,
+ *   lse[r] = m_r + log(s_r);   argmax[r] = best column (int32);
+ *   logprob[r] = 0 for targets[r] == -1, else zts_r - lse[r] without a recomputed target logit, else tmi_linear_xent's form
+ *                -log1p(rest * exp(m_r - zt_r)), rest = max(s_r - exp(zts_r - m_r), 0): the log-softmax with the target's own
+ *                term of the sum taken at the recomputed zt_r too, so that both terms see the same target logit (never
+ *                positive; with the stored lse a dominating target would keep half a bf16 ulp of its logit as error).
+ * targets[r] = -1: the row is not scored (lse and argmax are still written).  The pad columns n >= V of a chunk are never
+ * read into any of the three (they may hold anything, NaN included).  Out-of-range targets: the values live in device
+ * memory, so the call does not see them; a target outside [-1, V) is never dereferenced and gives logprob[r] = NaN (the
+ * Python wrapper ops.logprob_fold checks the range on the host before the first chunk).
+ * Everything else is validated before anything is launched, and a rejected call writes nothing: chunk 16-byte aligned, ld
+ * a multiple of 8 (BF16) / 4 (F32) and >= ncols >= 1, 1 <= V, 0 <= col0 < V, M >= 1, and M, V, ld <= 2^30 (the kernel
+ * indexes rows and columns with 32-bit integers); targets 4-byte aligned; x and w both given or both NULL (2-byte aligned,
+ * 1 <= d <= 2^20, x_ld >= d, nonzero w strides); state 8-byte aligned with state_bytes >= tmi_logprob_state_bytes(M) =
+ * 32 * M; first / last in {0, 1} and consistent with col0 / ncols / V; lse / logprob / argmax non-NULL and 4-byte aligned
+ * when last = 1 (ignored otherwise).
+ * No atomics, no workspace besides the caller-owned state.  tmi_logprob_chunk_cols(): the chunk width the library's callers
+ * use (a multiple of the GEMM's widest N tile; measured, DESIGN.md "Evaluation").
+ */
+int64_t tmi_logprob_state_bytes(int64_t M);
+int64_t tmi_logprob_chunk_cols(void);
+int tmi_logprob_fold(const void* chunk, int64_t ld, int32_t dtype, int64_t M, int64_t V, int64_t col0, int64_t ncols,
+                     const int32_t* targets, const void* x, int64_t x_ld, const void* w, int64_t w_sk, int64_t w_sn,
+                     int64_t d, void* state, int64_t state_bytes, int32_t first, int32_t last, float* lse, float* logprob,
+                     int32_t* argmax, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Multi-tensor Adam over a flat fp32 arena (tf.keras.optimizers.Adam, W:901; V:1271-1275).
  *   g' = g * gscale                      (gscale: 1 for Whisper's SUM, 1/N for V:1231)
  *   m <- b1 m + (1-b1) g' ; v <- b2 v + (1-b2) g'^2

@@ -145,6 +145,10 @@ SIGNATURES = {
                                    c_vp]),
     "tmi_beam_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "tmi_logprob_state_bytes": (c_i64, [c_i64]),
+    "tmi_logprob_chunk_cols": (c_i64, []),
+    "tmi_logprob_fold": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
+                                 c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
 }
 
 ABI_VERSION = 31

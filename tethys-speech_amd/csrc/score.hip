@@ -1,0 +1,224 @@
+// Teacher-forced scoring: tmi_logprob_fold (W:585-600 without the gradient, SparseCategoricalAccuracy of W:904-907).
+//
+// The LM head of an evaluation pass is computed by tmi_gemm in column chunks of tmi_logprob_chunk_cols() columns into a
+// scratch [M, chunk] buffer; after each chunk this kernel folds it into 32 bytes of running state per row - the online
+// softmax pair (max, sum exp(z - max)), the best argmax key and the target logit - so that the [M, 51904] logits never
+// exist.  The chunk was written a moment ago by the GEMM and is read once, from the Infinity Cache when it fits.
+//
+// Form (cdna_hip_programming.md, memory-bound recipe): one wave per row, four rows per 256-thread workgroup, 16-byte
+// loads of the row (8 bf16 / 4 fp32 columns per lane and trip), max / exp / sum in fp32.  Every order is fixed: a lane
+// folds its own vectors in column order, the 64 lane partials meet in a butterfly that pairs the lower lane first (the
+// lse fold of decode.hip), and the chunk's result joins the running state behind the earlier chunks.  With a fixed chunk
+// width the outputs are therefore bit-reproducible; there are no atomics and the state has no zero-before-use contract
+// (first = 1 overwrites it).
+//
+// Argmax: decode.hip's 64-bit key, order-preserving float bits << 32 | ~column with -0 folded onto +0: the largest stored
+// logit wins, the smallest column among equals.  The column is the global one, so "a later chunk replaces the running best
+// only when strictly greater" is the plain comparison of keys.
+//
+// Target logit: fp32 chunks carry it; for bf16 chunks the row's wave recomputes x[r, :] . w[:, target] in fp32 from the
+// GEMM's operands (the note on tmi_linear_xent in include/tethys_mi.h), in the chunk that holds the target's column.
+#include "tmi_common.h"
+
+namespace {
+
+constexpr int LP_THREADS = 256;
+constexpr int LP_ROWS = LP_THREADS / TMI_WAVE;  // rows per workgroup
+constexpr int64_t LP_CHUNK_COLS = 8192;         // tmi_logprob_chunk_cols(): a multiple of the fast GEMM's widest N tile (256)
+
+struct LpState {  // tmi_logprob_state_bytes(M) = 32 * M
+  float m, s;     // max and sum exp(z - m) over the real columns seen so far
+  uint64_t best;  // argmax key (0: none yet)
+  float zt;       // the target logit, once its chunk has been folded
+  float zts;      // the target logit as the chunk stores it (== zt unless zt was recomputed)
+  float pad[2];
+};
+static_assert(sizeof(LpState) == 32, "state layout");
+
+__device__ __forceinline__ uint32_t lp_order(float v) {  // decode.hip's am_order
+  const uint32_t u = __float_as_uint(v + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// (am, as) <- (am, as) followed by (bm, bs): decode.hip's tk_fold
+__device__ __forceinline__ void lp_fold(float& am, float& as, float bm, float bs) {
+  if (bm == -INFINITY) return;
+  if (bm > am) {
+    as = as * expf(am - bm) + bs;
+    am = bm;
+  } else {
+    as = as + bs * expf(bm - am);
+  }
+}
+
+template <typename T> struct lp_vec;
+template <> struct lp_vec<bf16_t> {
+  static constexpr int N = 8;
+  u32x4 r;
+  __device__ __forceinline__ void load(const bf16_t* p) { r = *reinterpret_cast<const u32x4*>(p); }
+  __device__ __forceinline__ float get(int c) const {
+    const uint32_t w = r[c >> 1];
+    return __uint_as_float((c & 1) ? (w & 0xffff0000u) : (w << 16));
+  }
+};
+template <> struct lp_vec<float> {
+  static constexpr int N = 4;
+  u32x4 r;
+  __device__ __forceinline__ void load(const float* p) { r = *reinterpret_cast<const u32x4*>(p); }
+  __device__ __forceinline__ float get(int c) const { return __uint_as_float(r[c]); }
+};
+
+template <typename T>
+__global__ __launch_bounds__(LP_THREADS) void lp_fold_kernel(
+    const T* __restrict__ chunk, int64_t ld, int M, int V, int col0, int nreal, const int32_t* __restrict__ targets,
+    const bf16_t* __restrict__ x, int64_t x_ld, const bf16_t* __restrict__ w, int64_t w_sk, int64_t w_sn, int d,
+    LpState* __restrict__ state, int first, int last, float* __restrict__ lse, float* __restrict__ logprob,
+    int32_t* __restrict__ argmax) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * LP_ROWS + (threadIdx.x >> 6);
+  if (row >= M) return;  // (whole waves: no barrier follows)
+  constexpr int N = lp_vec<T>::N;
+  const T* __restrict__ p = chunk + (int64_t)row * ld;
+
+  // ---- this lane's columns j, j + 64 N, ...: online softmax and best key over the real columns [0, nreal) of the chunk
+  float am = -INFINITY, as = 0.f;
+  uint64_t best = 0;
+  for (int j = lane * N; j < nreal; j += 64 * N) {  // (ld is a multiple of N and nreal <= ld: the 16 bytes are inside the row)
+    lp_vec<T> v;
+    v.load(p + j);
+    float z[N];
+    float vm = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+      const bool ok = j + c < nreal;  // a pad column is loaded with its vector and never looked at
+      z[c] = ok ? v.get(c) : -INFINITY;
+      if (ok) {
+        vm = fmaxf(vm, z[c]);
+        const uint64_t key = ((uint64_t)lp_order(z[c]) << 32) | (uint64_t)(~(uint32_t)(col0 + j + c));
+        if (key > best) best = key;
+      }
+    }
+    if (vm > am) {  // (vm == -inf: nothing to add; am == -inf: as is 0 and exp(-inf) = 0)
+      as *= __expf(am - vm);
+      am = vm;
+    }
+    if (am != -INFINITY) {
+      float vs = 0.f;
+#pragma unroll
+      for (int c = 0; c < N; ++c) vs += __expf(z[c] - am);  // (exp(-inf) = 0 for the columns left out)
+      as += vs;
+    }
+  }
+
+  // ---- the 64 partials: a butterfly that pairs the lower lane first, in both lanes
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
+    if (lane & o) {
+      float lm = om, ls = os;
+      lp_fold(lm, ls, am, as);
+      am = lm, as = ls;
+    } else {
+      lp_fold(am, as, om, os);
+    }
+    const uint32_t lo = __shfl_xor((uint32_t)best, o, 64), hi = __shfl_xor((uint32_t)(best >> 32), o, 64);
+    const uint64_t ob = ((uint64_t)hi << 32) | lo;
+    if (ob > best) best = ob;
+  }
+
+  // ---- the target logit, in the chunk that holds its column (a target outside [0, V) is in no chunk)
+  const int t = targets[row];
+  const bool here = t >= col0 && t < col0 + nreal;
+  float zt = 0.f, zts = 0.f;
+  if (here) {  // (uniform over the wave)
+    zt = zts = to_f32(p[t - col0]);
+    if (x != nullptr) {
+      float acc = 0.f;
+      for (int k = lane; k < d; k += 64)
+        acc = fmaf((float)x[(int64_t)row * x_ld + k], (float)w[(int64_t)k * w_sk + (int64_t)t * w_sn], acc);
+      zt = wave_sum(acc);
+    }
+  }
+
+  if (lane != 0) return;
+  LpState st;
+  if (first) {
+    st.m = am, st.s = as, st.best = best, st.zt = zt, st.zts = zts;
+  } else {
+    st = state[row];
+    lp_fold(st.m, st.s, am, as);        // the earlier chunks first
+    if (best > st.best) st.best = best;  // (keys of different columns are never equal: strictly greater value, or an equal one at a smaller column - which an earlier chunk holds)
+    if (here) st.zt = zt, st.zts = zts;
+  }
+  st.pad[0] = st.pad[1] = 0.f;
+  if (!last) {
+    state[row] = st;
+    return;
+  }
+  const float l = st.m + logf(st.s);
+  lse[row] = l;
+  float lp;
+  if (t == -1) {
+    lp = 0.f;
+  } else if (t < 0 || t >= V) {
+    lp = __uint_as_float(0x7fc00000u);  // never found in any chunk: flagged with NaN instead of a number that looks like a score
+  } else if (x != nullptr) {
+    // tmi_linear_xent's form (softmax_xent.hip): both terms of the loss see the SAME target logit - the target's term of the
+    // sum is swapped for exp(zt) too, or a row whose target dominates keeps the rounding error of the stored logit and can
+    // come out positive.  log1p(sum of the OTHER terms * exp(m - zt)): non-negative, free of the m + log(s) - zt cancellation.
+    const float rest = fmaxf(st.s - expf(st.zts - st.m), 0.f);
+    const float dz = st.m - st.zt;
+    lp = -(dz < 80.f ? log1pf(rest * expf(dz)) : dz + logf(rest));
+  } else {
+    lp = st.zt - l;
+  }
+  logprob[row] = lp;
+  argmax[row] = (int32_t)(~(uint32_t)st.best);
+}
+
+inline bool lp_al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int64_t tmi_logprob_state_bytes(int64_t M) { return M < 1 ? -1 : (int64_t)sizeof(LpState) * M; }
+extern "C" int64_t tmi_logprob_chunk_cols(void) { return LP_CHUNK_COLS; }
+
+static int tmi_logprob_fold_impl(const void* chunk, int64_t ld, int32_t dtype, int64_t M, int64_t V, int64_t col0, int64_t ncols,
+                                 const int32_t* targets, const void* x, int64_t x_ld, const void* w, int64_t w_sk,
+                                 int64_t w_sn, int64_t d, void* state, int64_t state_bytes, int32_t first, int32_t last,
+                                 float* lse, float* logprob, int32_t* argmax, void* stream) {
+  const bool dt_ok = dtype == TMI_F32 || dtype == TMI_BF16;
+  const int64_t vec = dtype == TMI_BF16 ? 8 : 4;
+  const bool lm = x != nullptr || w != nullptr;
+  const bool lm_ok = !lm || (x && w && d >= 1 && d <= (1 << 20) && x_ld >= d && w_sk != 0 && w_sn != 0 && lp_al(x, 2) && lp_al(w, 2));
+  const bool out_ok = !last || (lse && logprob && argmax && lp_al(lse, 4) && lp_al(logprob, 4) && lp_al(argmax, 4));
+  if (!chunk || !targets || !lp_al(targets, 4) || !state || !dt_ok || !lm_ok || !out_ok || M < 1 || M > (1 << 30) || V < 1 || V > (1 << 30) ||
+      col0 < 0 || col0 >= V || ncols < 1 || ncols > ld || ld > (1 << 30) || (ld % vec) != 0 || !lp_al(chunk, 16) ||
+      !lp_al(state, 8) || state_bytes < (int64_t)sizeof(LpState) * M || (first != 0 && first != 1) || (last != 0 && last != 1) ||
+      (first && col0 != 0) || (!first && col0 == 0) || (last && col0 + ncols < V) || (!last && col0 + ncols >= V)) {
+    tmi_set_error("tmi_logprob_fold: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  const int64_t nreal = V - col0 < ncols ? V - col0 : ncols;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((M + LP_ROWS - 1) / LP_ROWS));
+  LpState* st = reinterpret_cast<LpState*>(state);
+  if (dtype == TMI_BF16)
+    // (the fp32 recomputation applies to bf16 chunks with operands given)
+    hipLaunchKernelGGL(lp_fold_kernel<bf16_t>, grid, dim3(LP_THREADS), 0, s, reinterpret_cast<const bf16_t*>(chunk), ld, (int)M,
+                       (int)V, (int)col0, (int)nreal, targets, reinterpret_cast<const bf16_t*>(x), x_ld,
+                       reinterpret_cast<const bf16_t*>(w), w_sk, w_sn, (int)d, st, first, last, lse, logprob, argmax);
+  else
+    hipLaunchKernelGGL(lp_fold_kernel<float>, grid, dim3(LP_THREADS), 0, s, reinterpret_cast<const float*>(chunk), ld, (int)M,
+                       (int)V, (int)col0, (int)nreal, targets, (const bf16_t*)nullptr, (int64_t)0, (const bf16_t*)nullptr,
+                       (int64_t)0, (int64_t)0, 0, st, first, last, lse, logprob, argmax);
+  return tmi_check_launch("tmi_logprob_fold");
+}
+
+extern "C" int tmi_logprob_fold(const void* chunk, int64_t ld, int32_t dtype, int64_t M, int64_t V, int64_t col0, int64_t ncols,
+                                const int32_t* targets, const void* x, int64_t x_ld, const void* w, int64_t w_sk, int64_t w_sn,
+                                int64_t d, void* state, int64_t state_bytes, int32_t first, int32_t last, float* lse,
+                                float* logprob, int32_t* argmax, void* stream) {
+  return tmi_plan_run<tmi_logprob_fold_impl>(chunk, ld, dtype, M, V, col0, ncols, targets, x, x_ld, w, w_sk, w_sn, d, state,
+                                             state_bytes, first, last, lse, logprob, argmax, stream);
+}

@@ -540,6 +540,70 @@ def beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow
                               1 if finalize else 0, stream()), "tmi_beam_step")
 
 
+def logprob_chunk_cols() -> int:
+    """The chunk width of the chunked LM head (tmi_logprob_chunk_cols)."""
+    return int(lib().tmi_logprob_chunk_cols())
+
+
+def logprob_state_elems(M: int) -> int:
+    """int64 elements of tmi_logprob_fold's state for M rows (tmi_logprob_state_bytes / 8)."""
+    n = int(lib().tmi_logprob_state_bytes(M))
+    if n < 0:
+        raise ValueError(f"tmi_logprob_fold takes no M {M}")
+    return n // 8
+
+
+def logprob_chunks(V: int, ld: int, nc: int):
+    """The chunk schedule of a [*, ld] LM head with V real columns at chunk width ``nc``: [(col0, ncols)] in ascending col0,
+    ncols = min(nc, ld - col0) the columns the GEMM writes (pad columns of the last chunk included; the fold cuts them at V).
+    The real columns [col0, min(col0 + ncols, V)) tile [0, V) exactly once."""
+    if V < 1 or ld < V or nc < 1:
+        raise ValueError("logprob_chunks: need 1 <= V <= ld and nc >= 1")
+    return [(c0, min(nc, ld - c0)) for c0 in range(0, V, nc)]
+
+
+def check_targets(targets, V: int):
+    """Host check of a target tensor (one device read): every entry in [-1, V)."""
+    if targets.numel():
+        lo, hi = int(targets.min()), int(targets.max())
+        if lo < -1 or hi >= V:
+            raise ValueError(f"targets must be in [-1, {V}) (-1: row not scored); got [{lo}, {hi}]")
+
+
+def logprob_fold(chunk, ld, M, V, col0, ncols, targets, state, first, last, lse=None, logprob=None, argmax=None, lm=None,
+                 validate=True):
+    """One chunk of the chunked log-softmax / argmax / target log-prob (tmi_logprob_fold in include/tethys_mi.h): ``chunk``
+    holds the logit columns [col0, col0 + ncols) of M rows at row stride ``ld``; ``state`` an int64 tensor of at least
+    ``logprob_state_elems(M)`` elements (any contents); ``lm = (x, x_ld, w, w_sk, w_sn, d)``: the bf16 operands the chunk
+    was computed from (the target logit is then recomputed in fp32).  ``validate``: on the first chunk, check on the host
+    that the targets are in [-1, V) - the library cannot see them - and raise before anything is launched."""
+    if targets.dtype != torch.int32 or not targets.is_contiguous() or targets.numel() < M:
+        raise ValueError("logprob_fold: targets must be a contiguous int32 tensor of M entries")
+    for t, want in ((lse, torch.float32), (logprob, torch.float32), (argmax, torch.int32)):
+        if t is not None and (t.dtype != want or not t.is_contiguous() or t.numel() < M):
+            raise ValueError("logprob_fold: lse / logprob float32 and argmax int32, contiguous, M entries")
+    if validate and first:
+        check_targets(targets[:M], V)
+    x, x_ld, w, w_sk, w_sn, d = lm if lm is not None else (None, 0, None, 0, 0, 0)
+    if lm is not None and chunk.dtype == torch.bfloat16 and (x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16):
+        raise TypeError("logprob_fold: the operands of a bf16 chunk must be bf16")
+    with _probe("logprob_fold", 1.0 * M * ncols * chunk.element_size()):
+        check(lib().tmi_logprob_fold(chunk.data_ptr(), ld, dt(chunk), M, V, col0, ncols, targets.data_ptr(), ptr(x), x_ld, ptr(w),
+                                     w_sk, w_sn, d, state.data_ptr(), state.numel() * state.element_size(), 1 if first else 0,
+                                     1 if last else 0, ptr(lse), ptr(logprob), ptr(argmax), stream()), "tmi_logprob_fold")
+
+
+def logprob_from_logits(logits, V, targets, state, lse, logprob, argmax, nc=None, lm=None, validate=True):
+    """A testing hook, not part of the evaluation path (``evaluate`` / ``score`` never hold whole logits): tmi_logprob_fold
+    over a materialised ``logits`` [M, ld] (row stride ld, V real columns), chunk by chunk in place, so that a test can hand
+    the kernel logits it wrote itself."""
+    M, ld = logits.shape[0], logits.stride(0)
+    sched = logprob_chunks(V, ld, nc or logprob_chunk_cols())
+    for i, (c0, n) in enumerate(sched):
+        logprob_fold(logits[:, c0:], ld, M, V, c0, n, targets, state, i == 0, i == len(sched) - 1, lse, logprob, argmax,
+                     lm=lm, validate=validate)
+
+
 def sum_scale(x, out, n, scale):
     check(lib().tmi_sum_scale(x.data_ptr(), out.data_ptr(), n, scale, stream()), "tmi_sum_scale")
 

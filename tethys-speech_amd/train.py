@@ -204,8 +204,11 @@ def make_train_step(strategy, model, optimizer, example_inputs, warmup=2):
 def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4, *, batch_size=1,
                   num_batches=40, precision="bf16", device="cuda:0", checkpoint_dir=None, log=print, seed=1234,
                   model_overrides=None, seq_len=3000, max_target_length=100, tensor_log_dir=None,
-                  resume_from=None, dropout=None, loss_fetch_depth=2):
+                  resume_from=None, dropout=None, loss_fetch_depth=2, eval_every=0, eval_batches=0, eval_seed=4321):
     """W:894-958: model + Adam(1e-4), dummy dataset, per-step log line, checkpoint at epoch end.
+    ``eval_every`` / ``eval_batches`` (both > 0 to take effect): every ``eval_every`` steps and once after the last step,
+    ``evaluate_whisper`` over ``eval_batches`` batches of a second dummy pool drawn with ``eval_seed`` (it must differ from
+    ``seed``: held-out data), logged as "Eval step N, Loss: ..., Accuracy: ..." and kept in ``model.eval_history``.
     ``tensor_log_dir``: also write the tensor-size / skewness report of the reference's
     ``whisper_dist_tensorsize.py`` there (computed from shapes, see tensorsize.py).
     ``resume_from``: checkpoint to restore before training (the reference has no restore)."""
@@ -241,8 +244,23 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
             log(_step_line(i, lv, start_time, t0, time.time()))
             if report is not None:
                 report.log_step(i)
+    do_eval = eval_every > 0 and eval_batches > 0
+    eval_history = []
+    if do_eval:
+        if eval_seed == seed:
+            raise ValueError("eval_seed must differ from seed: the evaluation pool is held-out data")
+        eval_ds = create_dummy_dataset(batch_size, n_mels=model.config.n_mels, seq_len=seq_len,
+                                       max_target_length=max_target_length, device=device, rank=strategy.rank,
+                                       world=strategy.world, seed=eval_seed, drop_remainder=strategy.world > 1)
+        eit = iter(eval_ds)
+        eval_set = [next(eit) for _ in range(eval_batches)]  # drawn once: every evaluation sees the same batches
+
+        def run_eval(at_step):
+            emit(fetch.drain())  # (the step lines first, in order)
+            eval_history.append((at_step, evaluate_whisper(strategy, model, eval_set, log=log, step=at_step)))
     # (one replica on a GPU: the step is recorded once per batch shape and replayed from a launch plan, planned_step)
     train_step = planned_step(strategy, model, optimizer, "whisper", pipelined=True)
+    last_eval = -1
     for epoch in range(num_epochs):
         log(f"Epoch {epoch + 1}/{num_epochs}")
         for _ in range(num_batches):
@@ -252,11 +270,18 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
             # the reference's loss.numpy() (W:951), fetched behind an event so the next step is enqueued meanwhile
             emit(fetch.push(loss, (step, step_start)))
             step += 1
+            if do_eval and step % eval_every == 0:
+                run_eval(step)
+                last_eval = step
         emit(fetch.drain())
         if checkpoint_dir and strategy.rank == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
             save_checkpoint(model, optimizer, os.path.join(checkpoint_dir, f"whisper_{model_type}_epoch_{epoch + 1}.pt"), background=True,
                             dataset=ds, step=step)
+    if do_eval:
+        if last_eval != step:
+            run_eval(step)
+        model.eval_history = eval_history
     if report is not None:
         summ = report.save_final_results()
         report.close()
@@ -268,6 +293,37 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
         model.finish_late()  # whoever looks at the model next does so after its last update
     model.losses = losses
     return model
+
+
+def _eval_line(step, loss, acc):
+    return f"Eval step {step}, Loss: {loss:.4f}, Accuracy: {acc:.4f}"
+
+
+def evaluate_whisper(strategy, model, batches, log=None, step=None):
+    """Held-out evaluation (the metrics ``train_whisper`` compiles the model with, W:904-907): ``model.evaluate`` over the
+    iterable ``batches`` of (features, labels) or (features, labels, decoder_attention_mask), this replica's shard.  The
+    three sums (loss_sum, n_correct, n_tokens; fp64) are added up on the host and, with replicas, reduced ONCE after the
+    loop with the strategy's sum reduction - no collective per batch; an empty shard (no batches, or batches of zero
+    rows) contributes zeros.  -> {"loss", "accuracy", "loss_sum", "n_correct", "n_tokens"}; ``log``: also print
+    "Eval step {step}, Loss: ..., Accuracy: ..." (on every rank, as the step lines)."""
+    sums = [0.0, 0.0, 0.0]
+    for batch in batches:
+        features, labels = batch[0], batch[1]
+        if features.shape[0] == 0:
+            continue
+        r = model.evaluate(features, labels, *batch[2:3])
+        for i, k in enumerate(("loss_sum", "n_correct", "n_tokens")):
+            sums[i] += r[k]
+    if strategy is not None and (strategy.world > 1 or strategy.force_collectives):
+        t = torch.tensor(sums, dtype=torch.float64, device=model.device)
+        sums = [float(v) for v in strategy.reduce_sum(t).cpu()]
+    if not sums[2] > 0.0:
+        raise ValueError("evaluate_whisper: no scored token in any batch")
+    out = {"loss": sums[0] / sums[2], "accuracy": sums[1] / sums[2], "loss_sum": sums[0], "n_correct": sums[1],
+           "n_tokens": sums[2]}
+    if log is not None:
+        log(_eval_line(0 if step is None else step, out["loss"], out["accuracy"]))
+    return out
 
 
 def save_weights(model, path):

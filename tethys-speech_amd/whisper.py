@@ -1186,6 +1186,209 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return seq
 
 
+    # -- evaluation (forward only): teacher-forced loss / accuracy (W:596-600, W:904-907) and sequence scoring -------------
+    def _score_workspace(self, inf, M: int, ldc: int):
+        """The scratch of the chunked LM head for M rows at chunk stride ``ldc``, added to the inference set ``inf`` on the
+        evaluation paths only (as ``_sample_workspace``): the logits chunk [M, ldc] in the compute dtype, tmi_logprob_fold's
+        state (any contents) and its three outputs, and the targets."""
+        ws, dev = inf["ws"], self.device
+        have = ws.get("lp_chunk")
+        if have is None or have.shape[0] < M or have.shape[1] != ldc:
+            ws["lp_chunk"] = torch.empty(M, ldc, dtype=self.dtype, device=dev)
+        have = ws.get("lp_lse")
+        if have is None or have.numel() < M:
+            ws["lp_state"] = torch.empty(ops.logprob_state_elems(M), dtype=torch.int64, device=dev)
+            ws["lp_lse"], ws["lp_logprob"] = torch.empty(M, device=dev), torch.empty(M, device=dev)
+            ws["lp_argmax"], ws["lp_targets"] = (torch.empty(M, dtype=torch.int32, device=dev) for _ in range(2))
+
+    def _lm_head_fold(self, xn, M: int, nc: int):
+        """(lse, logprob, argmax) of the M normalised rows ``xn`` [M, d] against ws["lp_targets"]: the LM head (W:579) chunk
+        by chunk with tmi_gemm into ws["lp_chunk"], each chunk folded by tmi_logprob_fold; no [M, V] buffer exists."""
+        cfg, ws, d = self.config, self.ws, self.config.d_model
+        Vp, chunk = self.arena.v_pad, ws["lp_chunk"]
+        ldc = chunk.stride(0)
+        wl, ldw = self.W("lm_head.kernel")
+        lm = (xn, d, wl, ldw, 1, d) if self.precision == "bf16" else None
+        sched = ops.logprob_chunks(cfg.vocab_size, Vp, nc)
+        for i, (c0, n) in enumerate(sched):
+            self._gemm_xw(xn, "lm_head.kernel", chunk, M, n, d, d, ldc=ldc, n_off=c0)
+            ops.logprob_fold(chunk, ldc, M, cfg.vocab_size, c0, n, ws["lp_targets"], ws["lp_state"], i == 0,
+                             i == len(sched) - 1, ws["lp_lse"], ws["lp_logprob"], ws["lp_argmax"], lm=lm, validate=False)
+        return ws["lp_lse"][:M], ws["lp_logprob"][:M], ws["lp_argmax"][:M]
+
+    def _chunk_cols(self, nc=None) -> int:
+        nc = ops.logprob_chunk_cols() if nc is None else int(nc)
+        if nc < 64 or nc % 64:
+            raise ValueError("the chunk width must be a positive multiple of 64")
+        return nc
+
+    @torch.no_grad()
+    def evaluate(self, features, labels, decoder_attention_mask=None, return_token_logprobs=False, chunk_cols=None):
+        """Forward-only teacher-forced evaluation of one batch: the loss of ``call()`` (W:585-600) and the token accuracy
+        ``train_whisper`` compiles the model with (W:904-907), with no gradient, no dropout (even after ``enable_dropout``)
+        and nothing of the training state touched (the inference workspace, as ``generate``).
+
+        features [B, n_mels, T_in] fp32, labels [B, S] int32 (2 <= S <= max_target_positions).  As in training the decoder
+        reads [start, labels[:, :-1]] (W:559-563) and row (b, t), t < S - 1, is scored against labels[b, t + 1] (W:585-586)
+        - the reference's double shift; row S - 1 is unused.  ``decoder_attention_mask`` [B, S] (None: all ones) gives the
+        weights wgt = mask[:, :-1] (W:597):
+          loss     = sum(wgt * nll) / sum(wgt)                     (W:596-600; the plain mean without a mask)
+          accuracy = sum(wgt * (argmax == target)) / sum(wgt)      (argmax: the smallest column among equal logits)
+        -> {"loss", "accuracy" (floats), "loss_sum", "n_correct", "n_tokens" (the three sums, fp64 on the host: add them
+        over batches or shards and divide once), and with ``return_token_logprobs`` "token_logprobs" [B, S - 1] fp32 (0 where
+        the weight is 0)}.  The encoder and the decoder run once over the S positions; the LM head is evaluated in chunks of
+        ``chunk_cols`` columns (default tmi_logprob_chunk_cols) folded by tmi_logprob_fold, so the [B*S, vocab] logits are
+        never stored.  bf16: the target logit is the fp32 recomputation tmi_linear_xent uses for the training loss.
+        ``chunk_cols`` is a benchmark hook (tools/eval_bench.py sweeps it to choose the library constant): leave it at None;
+        the outputs are bit-reproducible for one width, not across widths."""
+        cfg = self.config
+        features = self._check_features(features)
+        B = features.shape[0]
+        labels = torch.as_tensor(labels).to(device=self.device)
+        mask = None if decoder_attention_mask is None else torch.as_tensor(decoder_attention_mask).to(device=self.device)
+        if labels.dtype != torch.int32:
+            raise TypeError("labels must be int32")
+        wgt = None
+        if mask is not None:
+            check_evaluate_args(cfg, tuple(labels.shape), tuple(mask.shape))
+            wgt = mask[:, :-1].to(torch.float64)
+            check_evaluate_args(cfg, tuple(labels.shape), tuple(mask.shape), mask_sum=float(wgt.sum()),
+                                mask_min=float(wgt.min()))
+        else:
+            check_evaluate_args(cfg, tuple(labels.shape), None)
+        if labels.shape[0] != B:
+            raise ValueError("features and labels disagree on the batch size")
+        S, V, nc = labels.shape[1], cfg.vocab_size, self._chunk_cols(chunk_cols)
+        lo, hi = int(labels.min()), int(labels.max())
+        if lo < 0 or hi >= V:
+            raise ValueError(f"labels must be in [0, {V})")
+        targets = torch.full((B, S), -1, dtype=torch.int32, device=self.device)
+        targets[:, :-1] = labels[:, 1:] if wgt is None else torch.where(wgt > 0, labels[:, 1:], -1)
+        M = B * S
+        inf = self._infer_prepare(B, features.shape[2])
+        self._score_workspace(inf, M, min(nc, self.arena.v_pad))
+        saved = self._infer_begin(inf)
+        try:
+            ws, T = self.ws, inf["T"]
+            lab = ws["labels"][:M].view(B, S)
+            lab.copy_(labels)
+            ws["lp_targets"][:M].copy_(targets.view(-1))
+            enc_out = self._encode_infer(features, inf)
+            self._cross_kv_infer(enc_out)
+            h = self._decode_infer(lab, B, S, T)
+            xn = ws["xn"][:M]
+            self._ln_fwd(h, "decoder.layer_norm", xn, "ln")
+            _, logprob, argmax = self._lm_head_fold(xn, M, nc)
+            lp = logprob.view(B, S)[:, :-1].clone()
+            hit = (argmax.view(B, S)[:, :-1] == targets[:, :-1])
+        finally:
+            self._infer_end(saved)
+        lp64, hit64 = lp.double().cpu(), hit.double().cpu()
+        w64 = torch.ones(B, S - 1, dtype=torch.float64) if wgt is None else wgt.cpu()
+        loss_sum, n_correct, n_tokens = float(-(w64 * lp64).sum()), float((w64 * hit64).sum()), float(w64.sum())
+        out = {"loss": loss_sum / n_tokens, "accuracy": n_correct / n_tokens, "loss_sum": loss_sum, "n_correct": n_correct,
+               "n_tokens": n_tokens}
+        if return_token_logprobs:
+            out["token_logprobs"] = lp
+        return out
+
+    @torch.no_grad()
+    def score(self, features, sequences, lengths=None, chunk_cols=None):
+        """Log-probability of given token sequences under the model, as ``generate`` would have scored them.
+
+        NOT THE TRAINING SHIFT.  This is the plain next-token log-probability: position j predicts sequences[:, j + 1],
+        token t (1-based) is scored by the decoder run over the prefix sequences[:, :t], exactly the state ``generate`` had
+        when it chose that token (under the inverted mask of W:416-418 a position's state depends on the later positions,
+        so every prefix is its own decoder run, as in ``generate``).  ``evaluate`` follows the reference's training loss
+        instead, which shifts twice (decoder input [start, labels[:, :-1]] AND target labels[:, t + 1]).  The two methods
+        share the kernel, not the shift.
+
+        sequences [N, 1 + n] int32, the start token first, as ``generate`` returns them; ``lengths`` [N] (None: n
+        everywhere): row i is scored on its first lengths[i] tokens, whatever follows (pad_token_id) is ignored.
+        features [N, n_mels, T_in], or [B, n_mels, T_in] with N = B * R: row i belongs to item i // R (the layout of
+        ``generate(num_return_sequences=R)``; the encoder then runs once per item).
+        -> {"token_logprobs" [N, n] fp32 (log_softmax of the logits at the token, temperature 1; 0 beyond lengths[i]),
+        "sequences_logprob" [N] fp32 (their sum over the first lengths[i] tokens)}.  ``chunk_cols``: the benchmark hook of
+        ``evaluate``; leave it at None."""
+        cfg = self.config
+        features = self._check_features(features)
+        B, dev, V = features.shape[0], self.device, cfg.vocab_size
+        seq = torch.as_tensor(sequences).to(device=dev)
+        if seq.dtype != torch.int32 or seq.dim() != 2 or seq.shape[1] < 2 or seq.shape[0] < 1 or seq.shape[0] % B:
+            raise ValueError("sequences must be int32 [N, 1 + n], n >= 1, N a multiple of the feature batch")
+        N, n = seq.shape[0], seq.shape[1] - 1
+        R = N // B
+        if n > cfg.max_target_positions:
+            raise ValueError("sequence length exceeds max_target_positions")
+        if not bool((seq[:, 0] == cfg.decoder_start_token_id).all()):
+            raise ValueError("sequences must start with decoder_start_token_id")
+        lens = torch.full((N,), n, dtype=torch.int64, device=dev) if lengths is None else torch.as_tensor(lengths).to(dev).long()
+        if lens.shape != (N,) or int(lens.min()) < 0 or int(lens.max()) > n:
+            raise ValueError("lengths must be [N] with entries in [0, n]")
+        n_eff, nc = int(lens.max()), self._chunk_cols(chunk_cols)
+        tok_lp = torch.zeros(N, n, device=dev)
+        if n_eff == 0:
+            return {"token_logprobs": tok_lp, "sequences_logprob": torch.zeros(N, device=dev)}
+        steps = torch.arange(1, n_eff + 1, device=dev)
+        scored = steps[None, :] <= lens[:, None]                                  # [N, n_eff]
+        toks = seq[:, 1:1 + n_eff]
+        if int(toks[scored].min()) < 0 or int(toks[scored].max()) >= V:
+            raise ValueError(f"scored tokens must be in [0, {V})")
+        feed = torch.where(scored, toks, cfg.pad_token_id).to(torch.int32)         # what the decoder reads: valid ids only
+        targets = torch.where(scored, toks, -1).to(torch.int32).t().contiguous()  # step-major [n_eff, N]
+        M, d = n_eff * N, cfg.d_model
+        inf = self._infer_prepare(B, features.shape[2], R)
+        self._score_workspace(inf, M, min(nc, self.arena.v_pad))
+        have = inf["ws"].get("score_h")
+        if have is None or have.numel() < M * d:
+            inf["ws"]["score_h"] = torch.empty(M * d, dtype=self.dtype, device=dev)
+        saved = self._infer_begin(inf)
+        try:
+            ws, T = self.ws, inf["T"]
+            enc_out = self._encode_infer(features, inf)
+            self._cross_kv_infer(enc_out)
+            if cfg.decoder_layers and R > 1:  # item b's k|v rows -> the row blocks of b*R .. b*R + R - 1, from the back (as beam search)
+                kv = ws["kvc_all"].view(N, T, -1)
+                for b in range(B - 1, -1, -1):
+                    kv[b * R + (1 if b == 0 else 0):(b + 1) * R].copy_(kv[b:b + 1].expand(R - (1 if b == 0 else 0), -1, -1))
+            ws["lp_targets"][:M].copy_(targets.view(-1))
+            lab_flat, hs = ws["labels"], ws["score_h"][:M * d].view(n_eff, N, d)
+            for t in range(1, n_eff + 1):
+                lab = lab_flat[:N * t].view(N, t)
+                if t > 1:
+                    lab[:, :t - 1].copy_(feed[:, :t - 1])
+                h = self._decode_infer(lab, N, t, T)
+                hs[t - 1].copy_(h.view(N, t, d)[:, t - 1])  # the prefix's last position: the row generate's LM head reads
+            xn = ws["xn"][:M]
+            self._ln_fwd(hs.view(M, d), "decoder.layer_norm", xn, "ln")
+            _, logprob, _ = self._lm_head_fold(xn, M, nc)
+            tok_lp[:, :n_eff] = logprob.view(n_eff, N).t()
+        finally:
+            self._infer_end(saved)
+        return {"token_logprobs": tok_lp, "sequences_logprob": tok_lp.sum(dim=1)}
+
+
+def check_evaluate_args(cfg: WhisperConfig, labels_shape, mask_shape=None, mask_sum=None, mask_min=None):
+    """The arguments of ``evaluate`` -> (B, S): labels [B, S] with B >= 1 and 2 <= S <= max_target_positions (S = 1 leaves
+    no scored row), a decoder_attention_mask of the same shape or None.  ``mask_sum`` / ``mask_min``: the sum and the
+    smallest entry of the weights mask[:, :-1] where the caller has them - the reference divides by that sum (W:598), so it
+    must be > 0, and a negative weight has no meaning."""
+    if len(labels_shape) != 2:
+        raise ValueError("labels must be [B, S]")
+    B, S = int(labels_shape[0]), int(labels_shape[1])
+    if B < 1:
+        raise ValueError("empty batch")
+    if not 2 <= S <= cfg.max_target_positions:
+        raise ValueError(f"the target length must be in [2, {cfg.max_target_positions}]")
+    if mask_shape is not None and tuple(int(x) for x in mask_shape) != (B, S):
+        raise ValueError("decoder_attention_mask must have the shape of labels")
+    if mask_min is not None and not float(mask_min) >= 0.0:
+        raise ValueError("decoder_attention_mask must not be negative")
+    if mask_sum is not None and not (float(mask_sum) > 0.0 and math.isfinite(float(mask_sum))):
+        raise ValueError("decoder_attention_mask[:, :-1] must have a positive, finite sum (W:598 divides by it)")
+    return B, S
+
+
 def create_whisper_model(model_type: str = "small", device="cuda:0", precision: str = "bf16", seed: int = 1234,
                          **overrides) -> WhisperForConditionalGeneration:
     """W:852-890."""
