@@ -615,6 +615,43 @@ int tmi_contrastive_fwd_bwd(float* S, const int32_t* neg, int64_t neg_sb, int64_
                             float* row_loss, int64_t B, int64_t T, int64_t Nn, float temperature,
                             float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Wav2Vec2 evaluation (wav2vec2.py evaluate): the contrastive loss of V:866-899 and its argmax accuracy in GATHERED form,
+ * forward only - O(T * Nn * pd) dot products, no [T, T] product, no gradient - with a rule for padded frames.
+ *   h, q   [B][T][pd] of `dtype` (TMI_F32 / TMI_BF16): element (b, t, k) at (b * T + t) * ld + k, ld >= pd, so the call takes
+ *          column slices of wider buffers;
+ *   neg    int32, row (b, t) reads neg[b * neg_sb + t * neg_st + n], n < Nn, exactly as tmi_contrastive_fwd_bwd does
+ *          ([B][Nn]: neg_sb = Nn, neg_st = 0; [T][Nn]: neg_sb = 0, neg_st = Nn).  Indices may repeat and may equal t;
+ *   mask   fp32 [B][T] or NULL (all ones): frame (b, t) is VALID iff mask[b * T + t] > 0.
+ * Row (b, t) of a valid frame: logits z_0 = <h_t, q_t> / temperature, then z_n = <h_t, q_j> / temperature for every
+ * j = neg[..][n - 1] whose frame (b, j) is valid; a negative that names a masked frame is dropped from the row's softmax.
+ *   row_loss[b * T + t]    = logsumexp(z) - z_0, computed as (max - z_0) + log(sum exp(z - max)): never rounded at the size
+ *                            of the logits, never negative;
+ *   row_correct[b * T + t] = 1 iff z_0 >= every kept z_n (tf.argmax takes the first index on a tie; index 0 is the positive);
+ *   a row that keeps no negative has loss 0 and correct 1.  Row (b, t) of a masked frame: loss 0, correct 0.
+ * Arithmetic (one wave per row; lane l owns the items l, l + 64, .. of [positive, negatives]): every logit, the positive's
+ * included, is ONE code path - an fp32 fma chain over k = 0 .. pd-1 in ascending k from the stored operands, times
+ * fl(1 / temperature) - so a negative equal to t ties the positive bit for bit and the row counts as correct.  A lane folds
+ * its items in ascending order into an online (max, sum exp) pair; the row maximum is the exact maximum of the lane maxima,
+ * each lane rescales its sum once by expf(lane max - row max), and the 64 sums are added in a butterfly (lane distance 32,
+ * 16, .., 1).  No float atomics, no workspace: two runs are bit-identical.
+ * Index VALUES live in device memory and are not seen by the call: an index outside [0, T) is never dereferenced and is
+ * dropped like a masked frame (the Python wrapper ops.contrastive_score checks 0 <= idx < T on the host first).  Everything
+ * else is validated before anything is launched, and a rejected call writes nothing: non-NULL h, q, neg, row_loss,
+ * row_correct; h and q 16-byte aligned, the rest 4-byte; pd and ld multiples of 8 (BF16) / 4 (F32), ld >= pd; B, T, Nn >= 1;
+ * B, T, Nn, pd, ld and B * T <= 2^30; neg_sb, neg_st >= 0; temperature > 0. */
+int tmi_contrastive_score(const void* h, const void* q, int64_t ld, int32_t dtype, const int32_t* neg, int64_t neg_sb,
+                          int64_t neg_st, const float* mask, float* row_loss, int32_t* row_correct, int64_t B, int64_t T,
+                          int64_t pd, int64_t Nn, float temperature, void* stream);
+
+/* Code usage of an evaluation set: counts[g * Nc + c] += 1 for every VALID row r (mask[r] > 0; mask fp32 [rows] or NULL:
+ * all rows) and group g with c = clamp(idx[r * G + g], 0, Nc - 1) - the clamp of tmi_vq_assign, so the code counted is the
+ * code assigned.  idx int32 [rows][G], counts int64 [G][Nc] (8-byte aligned).  The call ACCUMULATES: the caller zeroes
+ * counts once per evaluation and reads it once at the end.  Integer adds only (an LDS histogram per workgroup, then 64-bit
+ * global atomic adds): the result is exact and independent of order.  1 <= rows <= 2^30, G * Nc <= 8192 (tmi_vq_nearest's
+ * limit); a rejected call writes nothing. */
+int tmi_vq_count(const int32_t* idx, const float* mask, int64_t* counts, int64_t rows, int64_t G, int64_t Nc, void* stream);
+
 /* Gradient clipping.  seg_off: int64 device array [nseg+1] of element offsets into g.
  * tmi_segment_sumsq: out[s] = sum g[seg_off[s]:seg_off[s+1]]^2.
  * tmi_segment_clip:  g[seg s] *= clip / max(sqrt(sumsq[s]), clip).

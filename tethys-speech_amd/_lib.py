@@ -149,6 +149,9 @@ SIGNATURES = {
     "tmi_logprob_chunk_cols": (c_i64, []),
     "tmi_logprob_fold": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64,
                                  c_vp, c_i64, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+    "tmi_contrastive_score": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                      c_f32, c_vp]),
+    "tmi_vq_count": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

@@ -1,4 +1,6 @@
-// Teacher-forced scoring: tmi_logprob_fold (W:585-600 without the gradient, SparseCategoricalAccuracy of W:904-907).
+// Scoring kernels of the evaluation paths.  First, teacher-forced scoring: tmi_logprob_fold (W:585-600 without the gradient,
+// SparseCategoricalAccuracy of W:904-907).  Behind it, with a header comment of their own, the Wav2Vec2 evaluation kernels
+// tmi_contrastive_score and tmi_vq_count.
 //
 // The LM head of an evaluation pass is computed by tmi_gemm in column chunks of tmi_logprob_chunk_cols() columns into a
 // scratch [M, chunk] buffer; after each chunk this kernel folds it into 32 bytes of running state per row - the online
@@ -221,4 +223,179 @@ extern "C" int tmi_logprob_fold(const void* chunk, int64_t ld, int32_t dtype, in
                                 float* logprob, int32_t* argmax, void* stream) {
   return tmi_plan_run<tmi_logprob_fold_impl>(chunk, ld, dtype, M, V, col0, ncols, targets, x, x_ld, w, w_sk, w_sn, d, state,
                                              state_bytes, first, last, lse, logprob, argmax, stream);
+}
+
+// ---------------------------------------------------------------- Wav2Vec2 evaluation: tmi_contrastive_score, tmi_vq_count
+// The contrastive loss of V:866-899 in gathered form, forward only: row (b, t) takes the dot products of h_t with q_t and
+// with the q rows its negative indices name - O(T N d) - instead of reading them out of the all-pairs [T, T] product that
+// tmi_contrastive_fwd_bwd needs for its gradient.  Frames whose mask is not > 0 score nothing as a query (loss 0, correct 0)
+// and are dropped from every softmax as a negative; so is an index outside [0, T), which is never dereferenced.
+//
+// Form: one wave per row, four rows per 256-thread workgroup.  The wave stages h_t once in LDS in its stored type (CS_KC
+// elements at a time; the projection widths of every model fit one piece); item 0 is the positive (frame t), item n >= 1
+// the n-th negative; lane l owns the items l, l + 64, ... and reads "its" q row with 16-byte loads (8 bf16 / 4 fp32), q
+// staying in L2 (400 KB at the workload's size).
+// Arithmetic order, the same for every item - a negative equal to t therefore reproduces the positive's logit bit for bit:
+//   dot   = fma chain over k = 0 .. pd-1 in ascending k from 0.f (fp32, operands as stored: pd roundings)
+//   logit = dot * (1.f / temperature)                        (the reciprocal is taken once on the host: 2 roundings)
+// A lane folds its items in ascending order into an online pair (m, s = sum exp(z - m)); the row maximum is the exact
+// wave_max of the lane maxima, each lane rescales its own sum once, s * expf(m - max) (a lane with one item: 1 * expf(z - max)),
+// and the 64 sums meet in the xor butterfly of wave_sum (lane distance 32, 16, .., 1): fixed order, no atomics, no
+// workspace, bit-reproducible.  loss = (max - logit_0) + logf(sum), tmi_contrastive_fwd_bwd's form: it never rounds at the
+// size of the logits and is >= 0 (the lane holding the maximum contributes s >= 1).  correct = logit_0 >= every kept
+// negative logit (tf.argmax: the first index wins a tie).
+constexpr int CS_THREADS = 256;
+constexpr int CS_ROWS = CS_THREADS / TMI_WAVE;
+constexpr int CS_KC = 1024;  // elements of h_t staged at a time
+
+namespace {
+
+template <typename T>
+__global__ __launch_bounds__(CS_THREADS) void cs_kernel(const T* __restrict__ h, const T* __restrict__ q, int64_t ld,
+                                                        const int32_t* __restrict__ neg, int64_t neg_sb, int64_t neg_st,
+                                                        const float* __restrict__ mask, int64_t rows, int Tn, int pd, int Nn,
+                                                        float inv_temp, float* __restrict__ row_loss,
+                                                        int32_t* __restrict__ row_correct) {
+  __shared__ __attribute__((aligned(16))) T hs[CS_ROWS][CS_KC];
+  constexpr int N = lp_vec<T>::N;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * CS_ROWS + w;
+  const bool live = row < rows;
+  const int64_t r = live ? row : rows - 1;  // (a wave past the end walks the last row and stores nothing: the barriers below are block-wide)
+  const int64_t b = r / Tn;
+  const int t = (int)(r % Tn);
+  const float* __restrict__ mb = mask ? mask + b * Tn : nullptr;
+  const bool valid = live && (!mb || mb[t] > 0.f);
+  const T* __restrict__ hr = h + r * ld;
+  const T* __restrict__ qb = q + b * Tn * ld;
+  const int32_t* __restrict__ nb = neg + b * neg_sb + (int64_t)t * neg_st;
+
+  float m = -INFINITY, s = 0.f, l0 = 0.f, mneg = -INFINITY;
+  for (int i0 = 0; i0 <= Nn; i0 += 64) {  // (Nn and pd are uniform over the workgroup: so is every barrier)
+    const int it = i0 + lane;
+    int j = -1;  // the frame this lane scores against, -1: none
+    if (valid && it <= Nn) {
+      j = it == 0 ? t : nb[it - 1];
+      if (j < 0 || j >= Tn || (it > 0 && mb && !(mb[j] > 0.f))) j = -1;
+    }
+    float acc = 0.f;
+    for (int k0 = 0; k0 < pd; k0 += CS_KC) {
+      const int kc = pd - k0 < CS_KC ? pd - k0 : CS_KC;
+      if (pd > CS_KC || i0 == 0) {
+        __syncthreads();
+        for (int k = lane * N; k < kc; k += 64 * N)
+          *reinterpret_cast<u32x4*>(&hs[w][k]) = *reinterpret_cast<const u32x4*>(hr + k0 + k);
+        __syncthreads();
+      }
+      if (j >= 0) {
+        const T* __restrict__ qr = qb + (int64_t)j * ld + k0;
+        for (int k = 0; k < kc; k += N) {
+          lp_vec<T> a, c;
+          a.load(&hs[w][k]);
+          c.load(qr + k);
+#pragma unroll
+          for (int e = 0; e < N; ++e) acc = fmaf(a.get(e), c.get(e), acc);
+        }
+      }
+    }
+    if (j >= 0) {
+      const float z = acc * inv_temp;
+      if (it == 0) l0 = z; else mneg = fmaxf(mneg, z);
+      if (z > m) {  // (m == -inf: s is 0 and expf(-inf) = 0)
+        s = s * expf(m - z) + 1.f;
+        m = z;
+      } else {
+        s += expf(z - m);
+      }
+    }
+  }
+  const float mx = wave_max(m);
+  const float sum = wave_sum(m == -INFINITY ? 0.f : s * expf(m - mx));
+  l0 = __shfl(l0, 0, 64);
+  mneg = wave_max(mneg);
+  if (lane != 0 || !live) return;
+  row_loss[row] = valid ? (mx - l0) + logf(sum) : 0.f;  // (no kept negative: max == logit_0 and sum == 1, so exactly 0)
+  row_correct[row] = valid && l0 >= mneg ? 1 : 0;
+}
+
+// counts[g][clamp(idx[r][g])] += 1 over the valid rows: an LDS histogram per workgroup, then one 64-bit atomic add per
+// non-empty bin.  Integer adds only: exact, whatever the order.
+__global__ __launch_bounds__(256) void vq_count_kernel(const int32_t* __restrict__ idx, const float* __restrict__ mask,
+                                                       unsigned long long* __restrict__ counts, int64_t rows, int G, int Nc) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(smem);  // [G * Nc]
+  const int bins = G * Nc;
+  for (int i = threadIdx.x; i < bins; i += 256) cnt[i] = 0u;
+  __syncthreads();
+  const int64_t total = rows * G;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (mask && !(mask[i / G] > 0.f)) continue;
+    int bi = idx[i];
+    bi = bi < 0 ? 0 : (bi >= Nc ? Nc - 1 : bi);  // as vq_assign_kernel: the code counted is the code assigned
+    atomicAdd(&cnt[(int)(i % G) * Nc + bi], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < bins; i += 256)
+    if (cnt[i]) atomicAdd(&counts[i], (unsigned long long)cnt[i]);
+}
+
+}  // namespace
+
+static int tmi_contrastive_score_impl(const void* h, const void* q, int64_t ld, int32_t dtype, const int32_t* neg, int64_t neg_sb,
+                                      int64_t neg_st, const float* mask, float* row_loss, int32_t* row_correct, int64_t B,
+                                      int64_t T, int64_t pd, int64_t Nn, float temperature, void* stream) {
+  const bool dt_ok = dtype == TMI_F32 || dtype == TMI_BF16;
+  const int64_t vec = dtype == TMI_BF16 ? 8 : 4;
+  const int64_t lim = (int64_t)1 << 30;
+  if (!h || !q || !neg || !row_loss || !row_correct || !dt_ok || !lp_al(h, 16) || !lp_al(q, 16) || !lp_al(neg, 4) ||
+      !lp_al(mask, 4) || !lp_al(row_loss, 4) || !lp_al(row_correct, 4) || B < 1 || T < 1 || Nn < 1 || pd < 1 || B > lim ||
+      T > lim || Nn > lim || pd > lim || ld > lim || B * T > lim || (pd % vec) != 0 || ld < pd || (ld % vec) != 0 ||
+      neg_sb < 0 || neg_st < 0 || !(temperature > 0.f)) {
+    tmi_set_error("tmi_contrastive_score: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  const int64_t rows = B * T;
+  const dim3 grid((unsigned)((rows + CS_ROWS - 1) / CS_ROWS));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const float inv_temp = 1.0f / temperature;
+  if (dtype == TMI_BF16)
+    hipLaunchKernelGGL(cs_kernel<bf16_t>, grid, dim3(CS_THREADS), 0, s, reinterpret_cast<const bf16_t*>(h),
+                       reinterpret_cast<const bf16_t*>(q), ld, neg, neg_sb, neg_st, mask, rows, (int)T, (int)pd, (int)Nn, inv_temp,
+                       row_loss, row_correct);
+  else
+    hipLaunchKernelGGL(cs_kernel<float>, grid, dim3(CS_THREADS), 0, s, reinterpret_cast<const float*>(h),
+                       reinterpret_cast<const float*>(q), ld, neg, neg_sb, neg_st, mask, rows, (int)T, (int)pd, (int)Nn, inv_temp,
+                       row_loss, row_correct);
+  return tmi_check_launch("tmi_contrastive_score");
+}
+
+extern "C" int tmi_contrastive_score(const void* h, const void* q, int64_t ld, int32_t dtype, const int32_t* neg, int64_t neg_sb,
+                                     int64_t neg_st, const float* mask, float* row_loss, int32_t* row_correct, int64_t B, int64_t T,
+                                     int64_t pd, int64_t Nn, float temperature, void* stream) {
+  return tmi_plan_run<tmi_contrastive_score_impl>(h, q, ld, dtype, neg, neg_sb, neg_st, mask, row_loss, row_correct, B, T, pd, Nn,
+                                                  temperature, stream);
+}
+
+static int tmi_vq_count_impl(const int32_t* idx, const float* mask, int64_t* counts, int64_t rows, int64_t G, int64_t Nc,
+                             void* stream) {
+  if (!idx || !counts || !lp_al(idx, 4) || !lp_al(mask, 4) || !lp_al(counts, 8) || rows < 1 || rows > ((int64_t)1 << 30) ||
+      G < 1 || Nc < 1 || G > 8192 || Nc > 8192 || G * Nc > 8192) {
+    tmi_set_error("tmi_vq_count: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  // (a workgroup's LDS bins are 32 bit: at most 2^30 items each)
+  const int64_t total = rows * G;
+  int64_t blocks = (total + 2047) / 2048;
+  if (blocks > 1024) blocks = 1024;
+  const int64_t need = (total + ((int64_t)1 << 30) - 1) >> 30;
+  if (blocks < need) blocks = need;
+  hipLaunchKernelGGL(vq_count_kernel, dim3((unsigned)blocks), dim3(256), (size_t)(G * Nc) * sizeof(uint32_t),
+                     reinterpret_cast<hipStream_t>(stream), idx, mask, reinterpret_cast<unsigned long long*>(counts), rows, (int)G,
+                     (int)Nc);
+  return tmi_check_launch("tmi_vq_count");
+}
+
+extern "C" int tmi_vq_count(const int32_t* idx, const float* mask, int64_t* counts, int64_t rows, int64_t G, int64_t Nc,
+                            void* stream) {
+  return tmi_plan_run<tmi_vq_count_impl>(idx, mask, counts, rows, G, Nc, stream);
 }

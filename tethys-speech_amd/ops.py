@@ -793,6 +793,51 @@ def contrastive_fwd_bwd(S, neg, row_loss, B, T, Nn, temperature, grad_scale, per
                                         grad_scale, stream()), "tmi_contrastive_fwd_bwd")
 
 
+def check_negative_indices(neg, T: int):
+    """Host check of a negative-index tensor (one device read): every entry in [0, T)."""
+    if neg.numel():
+        lo, hi = int(neg.min()), int(neg.max())
+        if lo < 0 or hi >= T:
+            raise ValueError(f"negative indices must be in [0, {T}); got [{lo}, {hi}]")
+
+
+def contrastive_score(h, q, neg, row_loss, row_correct, B, T, pd, Nn, temperature, mask=None, per_time=False, ld=None,
+                      validate=True):
+    """Gathered contrastive loss and argmax flag per row (tmi_contrastive_score in include/tethys_mi.h): ``h`` / ``q``
+    [B, T, pd] at row stride ``ld`` (default pd), ``neg`` int32 [B, Nn] or, with ``per_time``, [T, Nn]; ``mask`` float32
+    [B, T] or None.  ``validate``: check on the host that the indices are in [0, T) - the library cannot see them - and
+    raise before anything is launched."""
+    ld = pd if ld is None else ld
+    if h.dtype != q.dtype:
+        raise TypeError("contrastive_score: h and q must have one dtype")
+    if neg.dtype != torch.int32 or not neg.is_contiguous() or neg.numel() < (T if per_time else B) * Nn:
+        raise ValueError("contrastive_score: neg must be a contiguous int32 tensor of [B, Nn] (per_time: [T, Nn]) entries")
+    if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.numel() < B * T):
+        raise ValueError("contrastive_score: mask must be float32 [B, T] contiguous")
+    if (row_loss.dtype != torch.float32 or row_correct.dtype != torch.int32 or not row_loss.is_contiguous()
+            or not row_correct.is_contiguous() or row_loss.numel() < B * T or row_correct.numel() < B * T):
+        raise ValueError("contrastive_score: row_loss float32 and row_correct int32, contiguous, B * T entries")
+    if validate:
+        check_negative_indices(neg, T)
+    sb, st = (0, Nn) if per_time else (Nn, 0)
+    with _probe("contrastive_score", 2.0 * B * T * (Nn + 1) * pd):
+        check(lib().tmi_contrastive_score(h.data_ptr(), q.data_ptr(), ld, dt(h), neg.data_ptr(), sb, st, ptr(mask),
+                                          row_loss.data_ptr(), row_correct.data_ptr(), B, T, pd, Nn, temperature, stream()),
+              "tmi_contrastive_score")
+
+
+def vq_count(idx, mask, counts, rows, G, Nc):
+    """counts[g, clamp(idx[r, g])] += 1 over the rows whose mask is > 0 (tmi_vq_count): ``idx`` int32 [rows, G], ``mask``
+    float32 [rows] or None, ``counts`` int64 [G, Nc].  ACCUMULATES: zero ``counts`` once per evaluation."""
+    if idx.dtype != torch.int32 or not idx.is_contiguous() or idx.numel() < rows * G:
+        raise ValueError("vq_count: idx must be a contiguous int32 tensor of rows * G entries")
+    if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or mask.numel() < rows):
+        raise ValueError("vq_count: mask must be float32 [rows] contiguous")
+    if counts.dtype != torch.int64 or not counts.is_contiguous() or counts.numel() != G * Nc:
+        raise ValueError("vq_count: counts must be a contiguous int64 tensor of G * Nc entries")
+    check(lib().tmi_vq_count(idx.data_ptr(), ptr(mask), counts.data_ptr(), rows, G, Nc, stream()), "tmi_vq_count")
+
+
 def segment_sumsq_chunks(g, chunks, out, nseg):
     """Per-variable sums of squares over the chunk table of ``segment_chunks`` (tmi_segment_sumsq_chunks)."""
     check(lib().tmi_segment_sumsq_chunks(g.data_ptr(), chunks.data_ptr(), chunks.shape[0], out.data_ptr(), nseg, stream()),

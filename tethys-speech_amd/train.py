@@ -498,15 +498,63 @@ def wav2vec2_train_step(strategy, model, audio, neg_indices, optimizer, pipeline
     return strategy.reduce_sum(loss.clone())
 
 
+def _w2v_eval_line(step, loss, acc, ppl):
+    return f"Eval step {step}, Loss: {loss:.4f}, Accuracy: {acc:.4f}, Perplexity: {ppl:.4f}"
+
+
+def evaluate_wav2vec2(strategy, model, batches, log=None, step=None):
+    """Held-out evaluation of the pre-training objective: ``model.evaluate`` over the iterable ``batches`` of (audio, neg) or
+    (audio, neg, attention_mask), this replica's shard; batches of zero rows are skipped.  The host adds up the three sums
+    (loss_sum, n_correct, n_frames; fp64) and the code counts [G, Nc]; with replicas they are reduced ONCE after the loop,
+    as one fp64 tensor of 3 + G * Nc elements (counts are exact in fp64) - no collective per batch; an empty shard
+    contributes zeros and still joins the reduction.  -> {"loss", "contrastive_loss", "accuracy", "perplexity",
+    "code_usage", "code_counts", "loss_sum", "n_correct", "n_frames"}: ``perplexity`` is ``perplexity_from_counts`` of the
+    TOTAL counts, never a mean of batch values; ``code_usage`` the share of codes with a non-zero count; ``loss`` =
+    contrastive_loss - diversity_loss_weight * perplexity (V:1220).  ``log``: also print "Eval step {step}, Loss: ...,
+    Accuracy: ..., Perplexity: ..." (on every rank, as the step lines)."""
+    from .wav2vec2 import perplexity_from_counts
+    cfg = model.config
+    G, Nc = cfg.num_codevector_groups, cfg.num_codevectors_per_group
+    tot = torch.zeros(3 + G * Nc, dtype=torch.float64)
+    for batch in batches:
+        audio, neg = batch[0], batch[1]
+        if audio.shape[0] == 0:
+            continue
+        r = model.evaluate(audio, neg, *batch[2:3])
+        for i, k in enumerate(("loss_sum", "n_correct", "n_frames")):
+            tot[i] += r[k]
+        tot[3:] += torch.as_tensor(r["code_counts"]).reshape(-1).to(torch.float64)
+    if strategy is not None and (strategy.world > 1 or strategy.force_collectives):
+        tot = strategy.reduce_sum(tot.to(model.device)).cpu()
+    loss_sum, n_correct, n_frames = (float(v) for v in tot[:3])
+    if not n_frames > 0.0:
+        raise ValueError("evaluate_wav2vec2: no frame was scored in any batch")
+    counts = tot[3:].round().to(torch.int64).reshape(G, Nc)
+    ppl = perplexity_from_counts(counts)
+    closs = loss_sum / n_frames
+    out = {"loss": closs - cfg.diversity_loss_weight * ppl, "contrastive_loss": closs, "accuracy": n_correct / n_frames,
+           "perplexity": ppl, "code_usage": float((counts > 0).double().mean()), "code_counts": counts,
+           "loss_sum": loss_sum, "n_correct": n_correct, "n_frames": n_frames}
+    if log is not None:
+        log(_w2v_eval_line(0 if step is None else step, out["loss"], out["accuracy"], ppl))
+    return out
+
+
 def train_wav2vec2(strategy, model_type="pretraining", model_size="small", num_epochs=1, learning_rate=3e-5, *,
                    batch_size=1, num_batches=5, precision="bf16", device="cuda:0", checkpoint_dir=None, log=print,
                    seed=1234, clip_samples=32000, model_overrides=None, dropout=None, resume_from=None,
-                   loss_fetch_depth=2, epoch_label="Epoch", init_batches=0, checkpoint_stem=None):
+                   loss_fetch_depth=2, epoch_label="Epoch", init_batches=0, checkpoint_stem=None, eval_every=0,
+                   eval_batches=0, eval_seed=4321):
     """V:1263-1376: model + Adam(3e-5, eps 1e-8, clipnorm 1), 50 x 2 s dummy clips, per-step log
     line, checkpoint every 50 steps and at the end.  speech_jobs/wav2vec2_single.py ("U:") is this loop on one
     replica (U:1118-1175 is V:1186-1260 without the strategy) with ``epoch_label`` "에포크" (U:1240),
     ``init_batches`` 1 (the first batch is consumed by the weight-building call, U:1188-1196) and checkpoints
-    named model_step_N / model_epoch_N (U:1272-1275)."""
+    named model_step_N / model_epoch_N (U:1272-1275).
+    ``eval_every`` / ``eval_batches`` (both > 0 to take effect): every ``eval_every`` steps and once after the last step,
+    ``evaluate_wav2vec2`` over ``eval_batches`` batches of a second dummy pool drawn with ``eval_seed`` (it must differ from
+    ``seed``: held-out data) with negatives from a generator of their own (``eval_seed + 1``: the training stream, and what
+    ``resume_from`` replays of it, does not move); batches and negatives are drawn once.  Logged as "Eval step N, Loss:
+    ..., Accuracy: ..., Perplexity: ..." and kept in ``model.eval_history``."""
     import numpy as np
     from .data import W2VDummyDataset
     from .wav2vec2 import create_full_model, sample_negative_indices
@@ -538,8 +586,29 @@ def train_wav2vec2(strategy, model_type="pretraining", model_size="small", num_e
         model._prepare(batch_size, clip_samples)
         for _ in range(step):  # the negative-index stream continues where the saved run stopped
             sample_negative_indices(rng, ds.global_batch, model.T, model.config.num_negatives)
+    do_eval = eval_every > 0 and eval_batches > 0
+    eval_history = []
+    if do_eval:
+        if eval_seed == seed:
+            raise ValueError("eval_seed must differ from seed: the evaluation pool is held-out data")
+        from .wav2vec2 import frame_lengths
+        eval_ds = W2VDummyDataset(batch_size, length=clip_samples, device=device, rank=strategy.rank, world=strategy.world,
+                                  seed=eval_seed)
+        eit = iter(eval_ds)
+        eval_rng = np.random.default_rng(eval_seed + 1)  # never the training ``rng``
+        T_eval = frame_lengths(model.config, [clip_samples])[0]
+        eval_set = []  # drawn once: every evaluation sees the same batches and the same negatives
+        for _ in range(eval_batches):
+            ea = next(eit)
+            en = sample_negative_indices(eval_rng, eval_ds.global_batch, T_eval, model.config.num_negatives)
+            eval_set.append((ea, torch.from_numpy(en[strategy.rank * batch_size:(strategy.rank + 1) * batch_size]).to(device)))
+
+        def run_eval(at_step):
+            emit(fetch.drain())  # (the step lines first, in order)
+            eval_history.append((at_step, evaluate_wav2vec2(strategy, model, eval_set, log=log, step=at_step)))
     start_time = time.time()
     train_step = planned_step(strategy, model, optimizer, "wav2vec2", pipelined=True)
+    last_eval = -1
     for epoch in range(num_epochs):
         log(f"{epoch_label} {epoch + 1}/{num_epochs}")
         for _ in range(num_batches):
@@ -557,11 +626,18 @@ def train_wav2vec2(strategy, model_type="pretraining", model_size="small", num_e
                 os.makedirs(checkpoint_dir, exist_ok=True)
                 save_checkpoint(model, optimizer, os.path.join(checkpoint_dir, f"{stem}_step_{step}.pt"), background=True,
                                 dataset=ds, step=step)
+            if do_eval and step % eval_every == 0:
+                run_eval(step)
+                last_eval = step
         emit(fetch.drain())
         if checkpoint_dir and strategy.rank == 0:
             os.makedirs(checkpoint_dir, exist_ok=True)
             save_checkpoint(model, optimizer, os.path.join(checkpoint_dir, f"{stem}_epoch_{epoch + 1}.pt"), background=True,
                             dataset=ds, step=step)
+    if do_eval:
+        if last_eval != step:
+            run_eval(step)
+        model.eval_history = eval_history
     # the reference's checkpoint.save sits inside this function (W:916-919, V:1341-1342), i.e. inside the job's JCT window:
     # mid-run writes overlap training, the last one is waited for here, before the caller reads its clock
     wait_for_checkpoints()

@@ -122,6 +122,56 @@ def frame_attention_mask(cfg: Wav2Vec2Config, sample_lengths, T_in: int) -> torc
     return (torch.arange(T)[None, :] < fl[:, None]).to(torch.float32)
 
 
+def perplexity_from_counts(counts) -> float:
+    """V:653-660 over any number of frames: mean_g exp(-sum_c p log(p + 1e-10)), p = clip(count / n, 1e-10, 1) with n the
+    frames counted (the sum of a group's counts), in float64 on the host.  ``counts`` [G, Nc] integers.  The perplexity of
+    an evaluation set is this function of the set's total counts - not a mean of per-batch values."""
+    c = np.asarray(torch.as_tensor(counts).detach().cpu().numpy() if torch.is_tensor(counts) else counts, dtype=np.float64)
+    if c.ndim != 2 or c.size == 0 or (c < 0).any():
+        raise ValueError("perplexity_from_counts: counts must be [G, Nc] non-negative integers")
+    n = c.sum(axis=1, keepdims=True)
+    if not (n > 0).all():
+        raise ValueError("perplexity_from_counts: no frame was counted")
+    p = np.clip(c / n, 1e-10, 1.0)
+    return float(np.exp(-(p * np.log(p + 1e-10)).sum(axis=1)).mean())
+
+
+def check_evaluate_args(cfg: Wav2Vec2Config, audio, neg_indices, attention_mask=None, forced_codes=None, per_time=False):
+    """The host-side checks of ``Wav2Vec2ForPreTraining.evaluate`` (the kernels cannot see values in device memory):
+    ``audio`` float32 [B, T_in] with B >= 1; ``neg_indices`` int32 [B, Nn] (``per_time``: [T, Nn]) with Nn >= 1 and every
+    entry in [0, T); ``attention_mask`` [B, T] over frames with values 0 or 1 only and at least one valid frame;
+    ``forced_codes`` integer, B * T * G entries in [0, Nc).  -> (B, T_in, T, Nn, the mask as float32 on the host or None)."""
+    if not torch.is_tensor(audio) or audio.dim() != 2 or audio.dtype != torch.float32 or audio.shape[0] < 1 or audio.shape[1] < 1:
+        raise TypeError("audio must be float32 [B, T_in]")
+    B, T_in = audio.shape
+    T = frame_lengths(cfg, [T_in])[0]
+    if not torch.is_tensor(neg_indices) or neg_indices.dtype != torch.int32 or neg_indices.dim() != 2:
+        raise TypeError("neg_indices must be int32 [B, Nn] (or [T, Nn] with neg_per_time)")
+    if neg_indices.shape[0] != (T if per_time else B):
+        raise ValueError("neg_indices must have one row per " + ("time step" if per_time else "batch row"))
+    Nn = int(neg_indices.shape[1])
+    if Nn < 1:
+        raise ValueError("neg_indices must hold at least one negative per row")
+    ops.check_negative_indices(neg_indices, T)
+    mask = None
+    if attention_mask is not None:
+        mask = torch.as_tensor(attention_mask).detach().to("cpu")
+        if mask.dim() != 2 or tuple(mask.shape) != (B, T):
+            raise ValueError(f"attention_mask must be [B, T] over frames = [{B}, {T}] (frame_attention_mask), got {list(mask.shape)}")
+        mask = mask.to(torch.float32).contiguous()
+        if not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError("attention_mask must be binary here: a frame is scored or it is not")
+        if not float(mask.sum()) > 0.0:
+            raise ValueError("attention_mask leaves no valid frame")
+    if forced_codes is not None:
+        G, Nc = cfg.num_codevector_groups, cfg.num_codevectors_per_group
+        if not torch.is_tensor(forced_codes) or forced_codes.dtype not in (torch.int32, torch.int64) or forced_codes.numel() != B * T * G:
+            raise ValueError(f"forced_codes must be integer [B, T, G] = [{B}, {T}, {G}]")
+        if int(forced_codes.min()) < 0 or int(forced_codes.max()) >= Nc:
+            raise ValueError(f"forced_codes must be in [0, {Nc})")
+    return B, T_in, T, Nn, mask
+
+
 class W2VArena(Arena):
     def __init__(self, cfg: Wav2Vec2Config, device):
         H, I = cfg.hidden_size, cfg.intermediate_size
@@ -748,6 +798,78 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             raise ValueError("attention_mask values must lie in [0, 1]")
         return m.contiguous()
 
+    def _infer_body(self, audio, inf, key_bias, output_hidden_states=False, on_projection=None):
+        """The forward pass of ``forward_infer`` and ``evaluate`` on the inference workspace (``self.ws`` is ``inf["ws"]``):
+        conv stem, positional conv, LayerNorm, feature projection, encoder layers with ``key_bias`` added to the scores of
+        the masked keys.  -> (the last hidden state [B*T, H], a view of the workspace; the inputs of the layers when asked
+        for).  ``on_projection(x)`` runs between the feature projection and the first layer."""
+        cfg = self.config
+        B, T_in = audio.shape
+        T = inf["T"]
+        ws, a = self.ws, self.arena
+        L, Gn = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups
+        H, C, Hh = cfg.hidden_size, cfg.conv_dim[-1], cfg.num_attention_heads
+        lens, pads = inf["lens"], inf["pads"]
+        R = B * T
+        sscale = 1.0 / math.sqrt(H // Hh)
+        # ---- feature encoder (V:283-288)
+        if not inf["fir0"]:
+            in0 = ws["in0"]
+            ops.feat_to_channels_last(audio, in0, B, 1, T_in, pads[0][0], in0.shape[1] - T_in - pads[0][0])
+        cin = 1
+        for i in range(L):
+            c, k, s = cfg.conv_dim[i], cfg.conv_kernel[i], cfg.conv_stride[i]
+            pre = f"feature_extractor.conv_layers.{i}.norm"
+            if i + 1 < L:
+                y, ysb, yoff = ws[f"in{i + 1}"], ws[f"in{i + 1}"].stride(0), pads[i + 1][0] * c
+            else:
+                y, ysb, yoff = ws["h_last"], lens[i] * c, 0
+            if i == 0 and inf["fir0"]:
+                ops.fir_groupnorm_gelu_fwd(audio, pads[0][0], a.param("feature_extractor.conv_layers.0.conv.kernel"), k, s,
+                                           a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb, ws["gn.stats"],
+                                           ws["gn_part"], B, lens[0], c, Gn, 1e-5, y_off=yoff)
+            else:
+                xin, u = ws[f"in{i}"], ws[f"u{i}"]
+                self._gemm_xw(xin, f"feature_extractor.conv_layers.{i}.conv.kernel", u, lens[i], c, k * cin, s * cin,
+                              ldc=c, nbatch=B, a_sb=xin.stride(0), c_sb=u.stride(0))
+                ops.groupnorm_gelu_fwd(u, u.stride(0), a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb,
+                                       ws["gn.stats"], ws["gn_part"], B, lens[i], c, Gn, 1e-5, y_off=yoff)
+            cin = c
+
+        # ---- grouped positional conv (V:271-277, V:291), LayerNorm, feature projection (V:777-778)
+        kp, Cg, Tpp = cfg.num_conv_pos_embeddings, C // Gn, inf["Tpp"]
+        ops.group_pack(ws["h_last"], ws["xg"], B, T, C, Gn, Tpp, inf["plp"])
+        ops.gemm(ws["xg"], self.pos_wf, ws["yg"], B * Tpp - (kp - 1), Cg, kp * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
+                 a_sb=B * Tpp * Cg, b_sb=kp * Cg * Cg, c_sb=B * Tpp * Cg)
+        ops.group_unpack(ws["yg"], a.param("feature_extractor.pos_conv_embed.bias"), ws["h_last"], ws["hp"], B, T, C, Gn,
+                         Tpp, 0)
+        self._ln_fwd(ws["hp"], "feature_extractor.layer_norm", ws["feats"], "ln")
+        self._dense_fwd(ws["feats"], "feature_projection.kernel", ws["fp_pre"])
+        x = ws["x"]
+        self._ln_fwd(ws["fp_pre"], "feature_projection_layer_norm", x, "ln")
+
+        if on_projection is not None:
+            on_projection(x)  # (evaluate's quantiser branch, V:784: it reads the projection before the encoder overwrites it)
+
+        # ---- encoder (V:419-439, stable layer norm): each layer's output overwrites its input
+        hidden = []
+        for i in range(cfg.num_hidden_layers):
+            p = f"encoder.layers.{i}"
+            if output_hidden_states:
+                hidden.append(x.view(B, T, H).clone())
+            self._ln_fwd(x, p + ".attention_layer_norm", ws["xn"], "ln")
+            wq, _ = self.W(p + ".attention.qkv3.kernel")
+            qkv = ws["qkv"]
+            ops.gemm(ws["xn"], wq, qkv, R, H, H, H, 1, H, 1, 3 * H, nbatch=3, b_sb=H * H, c_sb=H,
+                     bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
+            self._attn_fwd("att", (qkv, 0), (qkv, H), (qkv, 2 * H), ws["ctx"], B, Hh, T, T, 0, score_scale=sscale,
+                           key_bias=key_bias)
+            self._dense_fwd(ws["ctx"], p + ".attention.out_proj.kernel", ws["x_mid"], resid=x, r_ld=H)
+            self._ln_fwd(ws["x_mid"], p + ".feed_forward_layer_norm", ws["xn"], "ln")
+            self._dense_fwd(ws["xn"], p + ".feed_forward.intermediate_dense.kernel", ws["g"], act=1)
+            self._dense_fwd(ws["g"], p + ".feed_forward.output_dense.kernel", x, resid=ws["x_mid"], r_ld=H)
+        return x, hidden
+
     @torch.no_grad()
     def forward_infer(self, inputs, attention_mask=None, output_hidden_states=False, pool=None):
         """The reference's ``Wav2Vec2Model.call(..., training=False)`` (V:768-825): conv stem, grouped positional conv,
@@ -774,70 +896,13 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         inf = self._infer_prepare(B, T_in)
         saved = self._infer_begin(inf)
         try:
-            ws, a = self.ws, self.arena
-            L, Gn = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups
-            H, C, Hh = cfg.hidden_size, cfg.conv_dim[-1], cfg.num_attention_heads
-            lens, pads = inf["lens"], inf["pads"]
-            R = B * T
-            sscale = 1.0 / math.sqrt(H // Hh)
+            ws = self.ws
+            H, C = cfg.hidden_size, cfg.conv_dim[-1]
             key_bias = mask_dev = None
             if mask is not None:
                 mask_dev = mask.to(self.device)
                 key_bias = ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, on the host, once per call
-
-            # ---- feature encoder (V:283-288)
-            if not inf["fir0"]:
-                in0 = ws["in0"]
-                ops.feat_to_channels_last(audio, in0, B, 1, T_in, pads[0][0], in0.shape[1] - T_in - pads[0][0])
-            cin = 1
-            for i in range(L):
-                c, k, s = cfg.conv_dim[i], cfg.conv_kernel[i], cfg.conv_stride[i]
-                pre = f"feature_extractor.conv_layers.{i}.norm"
-                if i + 1 < L:
-                    y, ysb, yoff = ws[f"in{i + 1}"], ws[f"in{i + 1}"].stride(0), pads[i + 1][0] * c
-                else:
-                    y, ysb, yoff = ws["h_last"], lens[i] * c, 0
-                if i == 0 and inf["fir0"]:
-                    ops.fir_groupnorm_gelu_fwd(audio, pads[0][0], a.param("feature_extractor.conv_layers.0.conv.kernel"), k, s,
-                                               a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb, ws["gn.stats"],
-                                               ws["gn_part"], B, lens[0], c, Gn, 1e-5, y_off=yoff)
-                else:
-                    xin, u = ws[f"in{i}"], ws[f"u{i}"]
-                    self._gemm_xw(xin, f"feature_extractor.conv_layers.{i}.conv.kernel", u, lens[i], c, k * cin, s * cin,
-                                  ldc=c, nbatch=B, a_sb=xin.stride(0), c_sb=u.stride(0))
-                    ops.groupnorm_gelu_fwd(u, u.stride(0), a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb,
-                                           ws["gn.stats"], ws["gn_part"], B, lens[i], c, Gn, 1e-5, y_off=yoff)
-                cin = c
-
-            # ---- grouped positional conv (V:271-277, V:291), LayerNorm, feature projection (V:777-778)
-            kp, Cg, Tpp = cfg.num_conv_pos_embeddings, C // Gn, inf["Tpp"]
-            ops.group_pack(ws["h_last"], ws["xg"], B, T, C, Gn, Tpp, inf["plp"])
-            ops.gemm(ws["xg"], self.pos_wf, ws["yg"], B * Tpp - (kp - 1), Cg, kp * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
-                     a_sb=B * Tpp * Cg, b_sb=kp * Cg * Cg, c_sb=B * Tpp * Cg)
-            ops.group_unpack(ws["yg"], a.param("feature_extractor.pos_conv_embed.bias"), ws["h_last"], ws["hp"], B, T, C, Gn,
-                             Tpp, 0)
-            self._ln_fwd(ws["hp"], "feature_extractor.layer_norm", ws["feats"], "ln")
-            self._dense_fwd(ws["feats"], "feature_projection.kernel", ws["fp_pre"])
-            x = ws["x"]
-            self._ln_fwd(ws["fp_pre"], "feature_projection_layer_norm", x, "ln")
-
-            # ---- encoder (V:419-439, stable layer norm): each layer's output overwrites its input
-            hidden = []
-            for i in range(cfg.num_hidden_layers):
-                p = f"encoder.layers.{i}"
-                if output_hidden_states:
-                    hidden.append(x.view(B, T, H).clone())
-                self._ln_fwd(x, p + ".attention_layer_norm", ws["xn"], "ln")
-                wq, _ = self.W(p + ".attention.qkv3.kernel")
-                qkv = ws["qkv"]
-                ops.gemm(ws["xn"], wq, qkv, R, H, H, H, 1, H, 1, 3 * H, nbatch=3, b_sb=H * H, c_sb=H,
-                         bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
-                self._attn_fwd("att", (qkv, 0), (qkv, H), (qkv, 2 * H), ws["ctx"], B, Hh, T, T, 0, score_scale=sscale,
-                               key_bias=key_bias)
-                self._dense_fwd(ws["ctx"], p + ".attention.out_proj.kernel", ws["x_mid"], resid=x, r_ld=H)
-                self._ln_fwd(ws["x_mid"], p + ".feed_forward_layer_norm", ws["xn"], "ln")
-                self._dense_fwd(ws["xn"], p + ".feed_forward.intermediate_dense.kernel", ws["g"], act=1)
-                self._dense_fwd(ws["g"], p + ".feed_forward.output_dense.kernel", x, resid=ws["x_mid"], r_ld=H)
+            x, hidden = self._infer_body(audio, inf, key_bias, output_hidden_states)
             last = x.view(B, T, H).clone()
             result = {"last_hidden_state": last, "extract_features": ws["feats"].view(B, T, C).clone()}
             if output_hidden_states:
@@ -846,6 +911,99 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                 pooled = torch.empty(B, H, dtype=torch.float32, device=self.device)
                 ops.masked_mean_pool(x, mask_dev, pooled, B, T, H)
                 result["pooled_output"] = pooled
+        finally:
+            self._infer_end(saved)
+        return result
+
+
+    # -- evaluation (forward only): the held-out contrastive loss, its accuracy and the code usage ------------------------
+    def _eval_buffers(self, inf):
+        """The buffers ``evaluate`` needs beyond ``forward_infer``'s, added to the inference set on the first call."""
+        if "row_loss" in inf["ws"]:
+            return
+        cfg = self.config
+        B = inf["key"][0]
+        R = B * inf["T"]
+        cd, pd = cfg.codevector_dim, cfg.proj_codevector_dim
+        saved, self.ws = self.ws, inf["ws"]
+        try:
+            for n, w in (("qin", cd), ("quant", cd), ("pq_pre", pd), ("pq", pd), ("ph_pre", pd), ("ph", pd)):
+                self._buf(n, (R, w))
+            self._buf("code_idx", (R, cfg.num_codevector_groups), torch.int32)
+            self._buf("perplexity", (1,), torch.float32)
+            self._buf("row_loss", (R,), torch.float32)
+            self._buf("row_correct", (R,), torch.int32)
+            self._buf("code_counts", (cfg.num_codevector_groups, cfg.num_codevectors_per_group), torch.int64)
+        finally:
+            self.ws = saved
+
+    @torch.no_grad()
+    def evaluate(self, audio, neg_indices, attention_mask=None, forced_codes=None, return_rows=False):
+        """Held-out pre-training metrics of one batch, forward only (V:768-825 with training=False, the quantiser of V:784,
+        the heads of V:550-561 and the loss of V:866-899; the combination of V:1220): on the inference workspace, dropout
+        off, nothing of the training state read or written (see ``forward_infer``).
+
+        ``audio`` float32 [B, T_in]; ``neg_indices`` int32 [B, Nn], or [T, Nn] when ``neg_per_time`` is set, as in
+        ``forward_backward``; ``attention_mask`` [B, T] over frames (``frame_attention_mask``), binary: it masks the
+        attention keys as in ``forward_infer``, a masked frame is not scored as a query, and a negative that names a masked
+        frame is dropped from its row's softmax (tmi_contrastive_score); ``forced_codes`` int [B, T, G] replace the
+        quantiser's argmin (tmi_vq_assign).  Returns Python numbers, float64 on the host: ``loss_sum``, ``n_correct``,
+        ``n_frames`` (sums over the valid frames), ``code_counts`` (int64 [G, Nc] CPU tensor: this call's counts over the
+        valid frames), ``contrastive_loss`` = loss_sum / n_frames, ``accuracy``, ``perplexity``
+        (``perplexity_from_counts(code_counts)``) and ``loss`` = contrastive_loss - diversity_loss_weight * perplexity.
+        With ``return_rows`` also the device tensors ``row_loss`` fp32 / ``row_correct`` int32 [B, T], ``code_indices``
+        int32 [B, T, G], ``projected_states`` and ``projected_quantized_features`` [B, T, pd]."""
+        cfg = self.config
+        per_time = bool(getattr(self, "neg_per_time", False))
+        B, T_in, T, Nn, mask = check_evaluate_args(cfg, audio, neg_indices, attention_mask, forced_codes, per_time)
+        audio = audio.to(self.device).contiguous()
+        neg = neg_indices.to(self.device).contiguous()
+        forced = None if forced_codes is None else forced_codes.to(self.device, torch.int32).reshape(B * T, -1).contiguous()
+        inf = self._infer_prepare(B, T_in)
+        self._eval_buffers(inf)
+        saved = self._infer_begin(inf)
+        try:
+            ws, a = self.ws, self.arena
+            R = B * T
+            Gq, Nc = cfg.num_codevector_groups, cfg.num_codevectors_per_group
+            gd, pd = cfg.codevector_dim // Gq, cfg.proj_codevector_dim
+            key_bias = mask_dev = None
+            if mask is not None:
+                mask_dev = mask.to(self.device)
+                key_bias = ((1.0 - mask) * -10000.0).to(self.device)
+
+            def quantise(hproj):  # V:784: the quantiser sees the projected features; then project_q (V:557-559)
+                self._dense_fwd(hproj, "quantizer.projection.kernel", ws["qin"])
+                if forced is not None:
+                    ops.copy(ws["code_idx"], forced)
+                    ops.vq_assign(a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"], R, Gq, Nc, gd)
+                else:  # (the kernel's own perplexity counts the padding too: ignored, the counts below replace it)
+                    ops.vq_nearest(ws["qin"], a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"],
+                                   R, Gq, Nc, gd)
+                self._dense_fwd(ws["quant"], "project_q.dense.kernel", ws["pq_pre"])
+                self._ln_fwd(ws["pq_pre"], "project_q.layer_norm", ws["pq"], "ln")
+
+            x, _ = self._infer_body(audio, inf, key_bias, on_projection=quantise)
+            self._dense_fwd(x, "project_hid.dense.kernel", ws["ph_pre"])
+            self._ln_fwd(ws["ph_pre"], "project_hid.layer_norm", ws["ph"], "ln")
+            ops.contrastive_score(ws["ph"], ws["pq"], neg, ws["row_loss"], ws["row_correct"], B, T, pd, Nn,
+                                  cfg.contrastive_logits_temperature, mask=mask_dev, per_time=per_time, validate=False)
+            ops.fill_zero(ws["code_counts"])
+            ops.vq_count(ws["code_idx"], mask_dev, ws["code_counts"], R, Gq, Nc)
+            # the sums in float64 on the host (rows of masked frames hold 0 / 0)
+            loss_sum = float(ws["row_loss"].cpu().double().sum())
+            n_correct = float(ws["row_correct"].cpu().double().sum())
+            counts = ws["code_counts"].cpu().clone()
+            n_frames = float(R if mask is None else mask.double().sum())
+            result = {"loss_sum": loss_sum, "n_correct": n_correct, "n_frames": n_frames, "code_counts": counts,
+                      "contrastive_loss": loss_sum / n_frames, "accuracy": n_correct / n_frames,
+                      "perplexity": perplexity_from_counts(counts)}
+            result["loss"] = result["contrastive_loss"] - cfg.diversity_loss_weight * result["perplexity"]
+            if return_rows:
+                result.update(row_loss=ws["row_loss"].view(B, T).clone(), row_correct=ws["row_correct"].view(B, T).clone(),
+                              code_indices=ws["code_idx"].view(B, T, Gq).clone(),
+                              projected_states=ws["ph"].view(B, T, pd).clone(),
+                              projected_quantized_features=ws["pq"].view(B, T, pd).clone())
         finally:
             self._infer_end(saved)
         return result
