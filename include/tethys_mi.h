@@ -285,6 +285,18 @@ int64_t tmi_attn_workspace_bytes(int64_t B, int64_t H, int64_t Tq);
 int64_t tmi_attn_dropmask_bytes(int64_t B, int64_t H, int64_t Tq, int64_t Tk);
 int tmi_attn_fwd(const tmi_attn_desc* d, void* stream);
 int tmi_attn_bwd(const tmi_attn_desc* d, void* stream);
+/* The attention weights of a call tmi_attn_fwd has made (the reference's `attention_probs`, W:176 / V:376; inference:
+ * output_attentions): probs[(b*H + h)*p_sbh + q*p_sq + key] = softmax(scores)[b, h, q, key] for q < Tq, key < Tk, and
+ * nothing else is written.  One launch recomputes the scores from q and k exactly as the backward passes do and
+ * normalises them with `stats` as tmi_attn_fwd left them for the same descriptor (key-split or not), so the result is
+ * the forward's own normalisation: x = q.k * score_scale * log2(e) (+ the fp32 -1e9 * log2(e) for keys j <= i in
+ * mask_mode 1, + key_bias * log2(e) in mask_mode 2), p = exp2(x - m) * (1/l).  It is the probability BEFORE dropout.
+ * Reads q, k with their strides, stats, B, H, Tq, Tk, mask_mode (0, 1, 2), score_scale, key_bias / kb_sb; v, o, the
+ * backward fields and the workspace are ignored.  probs_dtype: TMI_F32 or TMI_BF16; strides in elements, p_sq >= Tk,
+ * p_sbh >= Tq * p_sq, no alignment beyond the element size (every Tk >= 1 works).  No atomics, no workspace: two calls
+ * are bit-identical.  TMI_ERR_INVALID for a NULL descriptor / probs / stats, a bad dtype or stride, q or k that
+ * tmi_attn_fwd would refuse, mask_mode 2 without key_bias, and dropout_p > 0 (these are inference-time weights). */
+int tmi_attn_probs(const tmi_attn_desc* d, void* probs, int32_t probs_dtype, int64_t p_sbh, int64_t p_sq, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Decoder token embedding + positional encoding (W:405-408) with the teacher-forcing

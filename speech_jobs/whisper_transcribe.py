@@ -9,6 +9,11 @@ the reference's seeded 30 s dummy clip into log-mel features on the GPU, and dec
 --min_length --seed``; adds "logprob", the sum of the tokens' log-probabilities).  Prints one JSON line per returned sequence, {"clip", "ids", "n_tokens"} (ids start
 with the decoder start token; beam search adds "rank" and "score"), then one timing line.  No tokenizer ships
 with the project, so the output is token ids.
+
+``--save_cross_attentions PATH`` writes, after decoding, the cross-attention weights of each clip's (best) transcript to
+an ``.npz``: one more forward pass over [start, tokens] with ``output_attentions=("cross",)`` - under the reference's
+inverted decoder mask every decoding step recomputes the whole prefix, so this pass is the last step's computation -
+saved as ``attn_<i>`` fp32 [decoder_layers, S, T] (the mean over the heads), ``ids_<i>`` int32 [S] and ``clips`` (names).
 """
 import argparse
 import json
@@ -38,6 +43,8 @@ def main(argv=None):
     parser.add_argument("--top_p", type=float, default=1.0, help="sampling: nucleus mass within the top_k, in (0, 1]")
     parser.add_argument("--min_length", type=int, default=0, help="sampling: no end-of-text in the first this many tokens")
     parser.add_argument("--seed", type=int, default=0, help="sampling: the seed (a seeded run repeats)")
+    parser.add_argument("--save_cross_attentions", default=None, metavar="PATH",
+                        help="write the head-mean cross-attention weights [layers, S, T] of each transcript to this .npz")
     args = parser.parse_args(argv)
     if args.do_sample and args.num_beams > 1:
         parser.error("--do_sample does not go with --num_beams > 1")
@@ -77,8 +84,25 @@ def main(argv=None):
     groups = {}
     for name, wav in clips:
         groups.setdefault(len(wav), []).append((name, wav))
+    saved = {"clips": []}
+
+    def save_cross(name, feats_row, ids):
+        """One clip: forward over its transcript, head-mean of every layer's cross-attention weights."""
+        if not args.save_cross_attentions:
+            return
+        ids = list(ids)[:model.config.max_target_positions]
+        dec = torch.tensor([ids], dtype=torch.int32, device=device)
+        out = model.forward_infer(feats_row[None], decoder_input_ids=dec, output_attentions=("cross",),
+                                  attentions_dtype=torch.float32)
+        i = len(saved["clips"])
+        saved["clips"].append(name)
+        saved[f"attn_{i}"] = torch.stack([a[0].mean(dim=0) for a in out["cross_attentions"]]).cpu().numpy()
+        saved[f"ids_{i}"] = np.asarray(ids, dtype=np.int32)
+
     for items in groups.values():
         wave = torch.from_numpy(np.stack([w for _, w in items])).to(device)
+        if args.save_cross_attentions:
+            feats_all = fe(wave)
         if sample:
             out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample)
             seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
@@ -86,12 +110,16 @@ def main(argv=None):
                 n_tok += int(n)
                 print(json.dumps({"clip": name, "ids": row[:1 + int(n)].tolist(), "n_tokens": int(n), "logprob": float(sc)}),
                       flush=True)
+            for j, ((name, _), row, n) in enumerate(zip(items, seqs, lens)):
+                save_cross(name, feats_all[j] if args.save_cross_attentions else None, row[:1 + int(n)].tolist())
             continue
         if not beam:
             ids = model.generate(fe(wave), max_length=args.max_length).cpu()
             for (name, _), row in zip(items, ids):
                 n_tok += row.numel() - 1
                 print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1)}), flush=True)
+            for j, ((name, _), row) in enumerate(zip(items, ids)):
+                save_cross(name, feats_all[j] if args.save_cross_attentions else None, row.tolist())
             continue
         R = args.num_return_sequences
         out = model.generate(fe(wave), max_length=args.max_length, num_beams=args.num_beams,
@@ -102,6 +130,10 @@ def main(argv=None):
             n_tok += n
             print(json.dumps({"clip": items[i // R][0], "rank": i % R, "ids": row[:1 + n].tolist(), "n_tokens": n,
                               "score": float(scores[i])}), flush=True)
+            if i % R == 0:  # (the best hypothesis of the clip)
+                save_cross(items[i // R][0], feats_all[i // R] if args.save_cross_attentions else None, row[:1 + n].tolist())
+    if args.save_cross_attentions:
+        np.savez(args.save_cross_attentions, **{k: (np.asarray(v) if k == "clips" else v) for k, v in saved.items()})
     torch.cuda.synchronize()
     dt = time.time() - t0
     print(json.dumps({"clips": len(clips), "seconds": round(dt, 4), "tokens": n_tok,

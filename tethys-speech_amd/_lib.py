@@ -94,6 +94,7 @@ SIGNATURES = {
     "tmi_attn_dropmask_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     "tmi_attn_fwd": (c_i32, [C.POINTER(AttnDesc), c_vp]),
     "tmi_attn_bwd": (c_i32, [C.POINTER(AttnDesc), c_vp]),
+    "tmi_attn_probs": (c_i32, [C.POINTER(AttnDesc), c_vp, c_i32, c_i64, c_i64, c_vp]),
     "tmi_embed_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     "tmi_embed_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     "tmi_xent_fwd_bwd": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_f32, c_i32, c_vp]),

@@ -518,6 +518,28 @@ class KernelBlocks:
         ops.gemm(P, vt, ctx2d, Tq, hd, Tk, Tk, 1, vt.stride(0), 1, d, nbatch=H, a_sb=Tq * Tk, b_sb=hd, c_sb=hd,
                  b_off=vo, nbatch2=B, a_sb2=H * Tq * Tk, b_sb2=Tk * vt.stride(0), c_sb2=Tq * d)
 
+    def _attn_probs(self, key, q, k, B, H, Tq, Tk, mask, score_scale=1.0, key_bias=None, dtype=None):
+        """The attention weights [B, H, Tq, Tk] (W:176, V:376) of the ``_attn_fwd`` call just made with the same ``key``, q,
+        k, mask, score_scale and key_bias, as a NEW tensor of ``dtype`` (None: the compute dtype).  Called right after that
+        ``_attn_fwd``: the statistics scratch (or the fp32 path's P) and the qkv buffers are shared and the next attention
+        call overwrites them.  bf16: tmi_attn_probs recomputes the scores and normalises them with the forward's own
+        statistics; fp32: P is already materialised in ``ws[key]``, so this is a copy (a cast if asked)."""
+        dtype = dtype or self.dtype
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("attention weights come as torch.float32 or torch.bfloat16")
+        if self.precision == "bf16":
+            (qt, qo), (kt, ko) = q, k
+            out = torch.empty(B, H, Tq, Tk, dtype=dtype, device=self.device)
+            ops.attn_probs((qt, qo, Tq * qt.stride(0), qt.stride(0)), (kt, ko, Tk * kt.stride(0), kt.stride(0)), self.ws[key],
+                           out, B, H, Tq, Tk, 2 if key_bias is not None else mask, score_scale=score_scale, key_bias=key_bias)
+            return out
+        P = self.ws[key].view(B, H, Tq, Tk)
+        if dtype == P.dtype:
+            out = torch.empty_like(P)
+            ops.copy(out, P)
+            return out
+        return P.to(dtype)
+
     def _attn_dropmask(self, key, B, H, Tq, Tk):
         """The stored keep bits of attention call ``key`` (W:160: TF keeps the mask it drew for the gradient): one buffer per
         call site, alive from its forward to its backward like the softmax statistics next to it."""

@@ -988,6 +988,122 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_small_kernel(const AttnP P) {
     attn_bwd_dkv_body<DROP, true>(P, bx - P.nq, (int)blockIdx.y, (int64_t)blockIdx.z);
 }
 
+// ------------------------------------------------------------------ probabilities (owner = key)
+// tmi_attn_probs: the score recompute of the backward passes with a store in place of the second product.  The dK/dV
+// orientation - key on the lane, query rows in the accumulator registers - so that one store instruction of a wave lands
+// on 32 contiguous keys of each of two query rows (128 contiguous bytes per row in fp32); the kernel is bound by these
+// writes.  A workgroup owns 128 keys and walks PQT query tiles of 64 rows, staged like every other tile here; the row
+// constants (m, 1/l, log2(1/l) - m) travel through LDS as in the dK/dV pass.  Arithmetic per element = the backward's:
+// full tiles of mask_mode 0 take exp2(fma(s, c2, nM)), every other tile exp2(x - m) * (1/l) with x built as the forward
+// builds it (s * c2, + MASKED2 for keys j <= i in mode 1, + key_bias * log2(e) in mode 2).  No atomics, no workspace.
+constexpr int PQT = 4;     // query tiles per workgroup
+constexpr int PCONST = 3;  // per streamed query row: m, 1/l, log2(1/l) - m
+template <int MODE, typename OT>
+__global__ __launch_bounds__(256, 4) void attn_probs_kernel(const AttnP P, OT* __restrict__ probs, const int64_t p_sbh,
+                                                            const int64_t p_sq, const int nqb) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][Q img] then [2][PCONST][64] floats
+  const AttnD& d = P.d;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = lane & 31, h = lane >> 5;
+  const int kblk = (int)blockIdx.x / nqb, qblk = (int)blockIdx.x - kblk * nqb;
+  const int head = (int)blockIdx.y;
+  const int64_t b = (int64_t)blockIdx.z;
+  const int key = kblk * 128 + wave * 32 + c;
+  const int Tq = (int)d.Tq, Tk = (int)d.Tk;
+  const float c2 = P.c2;
+  const bf16_t* qb = reinterpret_cast<const bf16_t*>(d.q) + b * d.q_sb + head * HD;
+  const bf16_t* kb = reinterpret_cast<const bf16_t*>(d.k) + b * d.k_sb + head * HD;
+  const float* stats = d.stats + (b * d.H + head) * Tq * 2;
+  float* rowc_base = reinterpret_cast<float*>(smem + 2 * IMG);
+
+  bf16x8 kf[4];
+  load_owner(kf, kb, d.k_st, key, Tk, h);
+  float kbv = 0.f;  // mode 2: this key's term in log2 units, as the forward adds it
+  if constexpr (MODE == 2) kbv = P.kbias[b * P.kb_sb + min(key, Tk - 1)] * LOG2E;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) PIN(kf[kk]);
+  PIN(kbv);
+  const bool key_ok = key < Tk;
+  OT* out = probs + (b * d.H + head) * p_sbh + key;
+
+  // per-tile row constants: thread t carries (which = t / 64, row = t % 64); the fourth wave carries none
+  const int cwhich = threadIdx.x >> 6;
+  auto load_consts = [&](int row0, float& x0, float& x1) {
+    const int qi = row0 + (threadIdx.x & 63);
+    x0 = 0.f;
+    x1 = 1.f;
+    if (qi < Tq && cwhich < PCONST) {
+      x0 = stats[qi * 2];
+      x1 = stats[qi * 2 + 1];
+    }
+  };
+  auto make_const = [&](float x0, float x1) -> float { return cwhich == 1 ? x1 : (cwhich == 2 ? lg2(x1) - x0 : x0); };
+
+  const LaneSrc Qs = lane_src(qb, d.q_st, Tq, wave, lane);
+  const int ntiles_all = (Tq + TROWS - 1) / TROWS;
+  const int t0 = qblk * PQT, ntiles = min(ntiles_all, t0 + PQT);  // this workgroup's query tiles [t0, ntiles) (host: never empty)
+  stage_tile(smem, Qs, t0 * TROWS, wave, lane);
+  {
+    float x0, x1;
+    load_consts(t0 * TROWS, x0, x1);
+    if (cwhich < PCONST) rowc_base[threadIdx.x] = make_const(x0, x1);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int cur = 0;
+  auto body = [&](int tile, auto edge_tag) {
+    constexpr bool edge = decltype(edge_tag)::value;
+    const char* Qimg = smem + cur * IMG;
+    const float* rowc = rowc_base + cur * (PCONST * 64);
+    float cn0 = 0.f, cn1 = 1.f;
+    const bool more = tile + 1 < ntiles;
+    if (more) {
+      stage_tile(smem + (cur ^ 1) * IMG, Qs, (tile + 1) * TROWS, wave, lane);
+      load_consts((tile + 1) * TROWS, cn0, cn1);
+    }
+    const int q0 = tile * TROWS;
+#pragma unroll
+    for (int rbk = 0; rbk < 2; ++rbk) {
+      f32x16 s = first_product(Qimg, 32 * rbk, kf, c, h);  // s[q][key]
+      if constexpr (!edge) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int r = 32 * rbk + 8 * g + 4 * h;
+          const f32x4 nM = *reinterpret_cast<const f32x4*>(rowc + 128 + r);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) s[4 * g + i] = ex2(fmaf(s[4 * g + i], c2, nM[i]));
+        }
+        if (key_ok) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) out[(int64_t)(q0 + 32 * rbk + acc_row(e, h)) * p_sq] = (OT)s[e];
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int r = 32 * rbk + acc_row(e, h);
+          const int qi = q0 + r;
+          float x = s[e] * c2;
+          if (MODE == 1 && key <= qi) x = x + MASKED2;
+          if constexpr (MODE == 2) x = x + kbv;
+          const float pe = ex2(x - rowc[r]) * rowc[64 + r];
+          if (key_ok && qi < Tq) out[(int64_t)qi * p_sq] = (OT)pe;
+        }
+      }
+    }
+    if (more && cwhich < PCONST) rowc_base[(cur ^ 1) * (PCONST * 64) + threadIdx.x] = make_const(cn0, cn1);
+    PIN(cn0);  // the compiler's wait for these two loads belongs here, on every path, not after the
+    PIN(cn1);  // next iteration's DMA issue
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    cur ^= 1;
+  };
+  const int nfast = MODE == 0 ? min(Tq / TROWS, ntiles) : 0;  // full, unmasked tiles first
+  int tile = t0;
+  for (; tile < nfast; ++tile) body(tile, std::false_type{});
+  for (; tile < ntiles; ++tile) body(tile, std::true_type{});
+}
+
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool ok_mat(const void* p, int64_t sb, int64_t st) { return p && al16(p) && sb % 8 == 0 && st % 8 == 0; }
 
@@ -1214,3 +1330,48 @@ static int tmi_attn_bwd_impl(const tmi_attn_desc* dp, void* stream) {
   return tmi_check_launch("tmi_attn_bwd(dkv)");
 }
 extern "C" int tmi_attn_bwd(const tmi_attn_desc* dp, void* stream) { return tmi_plan_run_desc<tmi_attn_bwd_impl>(dp, stream); }
+
+// ------------------------------------------------------------------ tmi_attn_probs
+template <int MODE, typename OT>
+static void launch_probs(const AttnP& P, void* probs, int64_t p_sbh, int64_t p_sq, hipStream_t hs) {
+  const int nqb = (int)(((P.d.Tq + TROWS - 1) / TROWS + PQT - 1) / PQT);
+  const dim3 grid((unsigned)((P.d.Tk + 127) / 128 * nqb), (unsigned)P.d.H, (unsigned)P.d.B);
+  hipLaunchKernelGGL((attn_probs_kernel<MODE, OT>), grid, dim3(256), 2 * IMG + 2 * PCONST * 64 * sizeof(float), hs, P,
+                     reinterpret_cast<OT*>(probs), p_sbh, p_sq, nqb);
+}
+
+static int tmi_attn_probs_impl(const tmi_attn_desc* dp, void* probs, int32_t probs_dtype, int64_t p_sbh, int64_t p_sq,
+                               void* stream) {
+  constexpr int64_t TMAX = (1ll << 31) - 256;  // (row and key indices are ints in the kernel; the grid's x is 32 bits)
+  if (!dp || !probs || !dp->stats || (probs_dtype != TMI_F32 && probs_dtype != TMI_BF16) || dp->B <= 0 || dp->H <= 0 ||
+      dp->Tq <= 0 || dp->Tk <= 0 || dp->B > 65535 || dp->H > 65535 || dp->Tq > TMAX || dp->Tk > TMAX || dp->mask_mode < 0 ||
+      dp->mask_mode > 2 || !(dp->score_scale >= 0.f) || !(dp->dropout_p == 0.f) || !ok_mat(dp->q, dp->q_sb, dp->q_st) ||
+      !ok_mat(dp->k, dp->k_sb, dp->k_st) || p_sq < dp->Tk || p_sbh / dp->Tq < p_sq || (dp->Tk + 127) / 128 * ((dp->Tq + 255) / 256) > TMAX ||
+      (dp->mask_mode == 2 && (!dp->key_bias || dp->kb_sb < 0))) {
+    tmi_set_error("tmi_attn_probs: bad argument (probs, stats non-NULL; probs_dtype TMI_F32 or TMI_BF16; p_sq >= Tk, p_sbh >= Tq * p_sq; "
+                  "16-byte aligned bf16 q, k with strides multiple of 8; mask_mode 2 needs key_bias; dropout_p must be 0)");
+    return TMI_ERR_INVALID;
+  }
+  AttnP P;
+  memset(&P, 0, sizeof(P));
+  set_desc(P, *dp);
+  P.sscale = dp->score_scale != 0.f ? dp->score_scale : 1.f;
+  P.c2 = P.sscale * LOG2E;
+  hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
+  const bool f32 = probs_dtype == TMI_F32;
+  switch (dp->mask_mode) {
+    case 0: f32 ? launch_probs<0, float>(P, probs, p_sbh, p_sq, hs) : launch_probs<0, bf16_t>(P, probs, p_sbh, p_sq, hs); break;
+    case 1: f32 ? launch_probs<1, float>(P, probs, p_sbh, p_sq, hs) : launch_probs<1, bf16_t>(P, probs, p_sbh, p_sq, hs); break;
+    default: f32 ? launch_probs<2, float>(P, probs, p_sbh, p_sq, hs) : launch_probs<2, bf16_t>(P, probs, p_sbh, p_sq, hs); break;
+  }
+  return tmi_check_launch("tmi_attn_probs");
+}
+extern "C" int tmi_attn_probs(const tmi_attn_desc* dp, void* probs, int32_t probs_dtype, int64_t p_sbh, int64_t p_sq, void* stream) {
+  if (tmi_plan_recording() && dp)
+    tmi_plan_push([c = *dp, probs, probs_dtype, p_sbh, p_sq, stream]() -> int {
+      tmi_plan_scope in;
+      return tmi_attn_probs_impl(&c, probs, probs_dtype, p_sbh, p_sq, stream);
+    });
+  tmi_plan_scope in;
+  return tmi_attn_probs_impl(dp, probs, probs_dtype, p_sbh, p_sq, stream);
+}

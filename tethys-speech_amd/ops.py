@@ -407,6 +407,21 @@ def attn_bwd(q, k, v, o, stats, do, dq, dk, dv, delta, B, H, Tq, Tk, mask_mode=0
         check(lib().tmi_attn_bwd(C.byref(d), stream()), "tmi_attn_bwd")
 
 
+def attn_probs(q, k, stats, out, B, H, Tq, Tk, mask_mode=0, score_scale=1.0, key_bias=None):
+    """The attention weights of the ``attn_fwd`` call that left ``stats`` (tmi_attn_probs): ``out`` fp32 or bf16 with
+    ``out[b, h, q, key]`` at ``(b * H + h) * out.stride(1) + q * out.stride(2) + key`` (4-D, unit stride along the keys,
+    ``stride(0) == H * stride(1)``); q, k as for ``attn_fwd``.  The probabilities before dropout."""
+    if out.dim() != 4 or tuple(out.shape) != (B, H, Tq, Tk) or out.stride(3) != 1 or (B > 1 and out.stride(0) != H * out.stride(1)):
+        raise ValueError("attn_probs: out must be [B, H, Tq, Tk] with unit key stride and stride(0) == H * stride(1)")
+    d = _attn_desc(q, k, q, q, stats, B, H, Tq, Tk, mask_mode, score_scale)
+    d.workspace, d.workspace_bytes = None, 0
+    if key_bias is not None:
+        if key_bias.dtype != torch.float32 or key_bias.dim() != 2 or key_bias.shape != (B, Tk) or key_bias.stride(1) != 1:
+            raise ValueError("key_bias must be float32 [B, Tk] with contiguous rows")
+        d.key_bias, d.kb_sb = key_bias.data_ptr(), key_bias.stride(0)
+    check(lib().tmi_attn_probs(C.byref(d), out.data_ptr(), dt(out), out.stride(1), out.stride(2), stream()), "tmi_attn_probs")
+
+
 def masked_mean_pool(x, mask, out, B, T, C):
     """out[b, c] = sum_t x[b, t, c] mask[b, t] / sum_t mask[b, t] (fp32 [B, C]); ``mask`` fp32 [B, T] or None: the plain mean."""
     if not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C or x.numel() != B * T * C:

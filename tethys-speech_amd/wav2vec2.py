@@ -698,7 +698,8 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         self._join_side()
         return ws["loss"]
 
-    def __call__(self, inputs, neg_indices=None, attention_mask=None, output_hidden_states=False, pool=None, training=None):
+    def __call__(self, inputs, neg_indices=None, attention_mask=None, output_hidden_states=False, pool=None, training=None,
+                 output_attentions=False, attentions_dtype=None):
         """V:768-825.  ``training=True`` with ``neg_indices`` is the pre-training step (-> ``{"loss": ...}``); ``training=False``
         - the default when no ``neg_indices`` are given - is the forward pass alone, see ``forward_infer``."""
         if training is None:
@@ -706,12 +707,14 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         if training:
             if neg_indices is None:
                 raise ValueError("the training path takes neg_indices")
-            if attention_mask is not None or output_hidden_states or pool is not None:
-                raise ValueError("attention_mask, output_hidden_states and pool belong to the inference call (training=False)")
+            if attention_mask is not None or output_hidden_states or pool is not None or output_attentions or attentions_dtype is not None:
+                raise ValueError("attention_mask, output_hidden_states, output_attentions, attentions_dtype and pool belong to the "
+                                 "inference call (training=False)")
             return {"loss": self.forward_backward(inputs, neg_indices)}
         if neg_indices is not None:
             raise ValueError("neg_indices belong to the training call")
-        return self.forward_infer(inputs, attention_mask=attention_mask, output_hidden_states=output_hidden_states, pool=pool)
+        return self.forward_infer(inputs, attention_mask=attention_mask, output_hidden_states=output_hidden_states, pool=pool,
+                                  output_attentions=output_attentions, attentions_dtype=attentions_dtype)
 
     # -- inference (forward only): V:768-825 with training=False --------------------------------------------------------
     # Its own workspace set (``_inf``), never one of ``_ws_sets``: no saved pre-activations, no gradient buffers, every
@@ -798,11 +801,13 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             raise ValueError("attention_mask values must lie in [0, 1]")
         return m.contiguous()
 
-    def _infer_body(self, audio, inf, key_bias, output_hidden_states=False, on_projection=None):
+    def _infer_body(self, audio, inf, key_bias, output_hidden_states=False, on_projection=None, attentions=None,
+                    attentions_dtype=None):
         """The forward pass of ``forward_infer`` and ``evaluate`` on the inference workspace (``self.ws`` is ``inf["ws"]``):
         conv stem, positional conv, LayerNorm, feature projection, encoder layers with ``key_bias`` added to the scores of
         the masked keys.  -> (the last hidden state [B*T, H], a view of the workspace; the inputs of the layers when asked
-        for).  ``on_projection(x)`` runs between the feature projection and the first layer."""
+        for).  ``on_projection(x)`` runs between the feature projection and the first layer.  ``attentions``: a list that
+        receives every layer's attention weights [B, Hh, T, T] (V:376) in ``attentions_dtype``."""
         cfg = self.config
         B, T_in = audio.shape
         T = inf["T"]
@@ -864,6 +869,9 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                      bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
             self._attn_fwd("att", (qkv, 0), (qkv, H), (qkv, 2 * H), ws["ctx"], B, Hh, T, T, 0, score_scale=sscale,
                            key_bias=key_bias)
+            if attentions is not None:
+                attentions.append(self._attn_probs("att", (qkv, 0), (qkv, H), B, Hh, T, T, 0, score_scale=sscale,
+                                                   key_bias=key_bias, dtype=attentions_dtype))
             self._dense_fwd(ws["ctx"], p + ".attention.out_proj.kernel", ws["x_mid"], resid=x, r_ld=H)
             self._ln_fwd(ws["x_mid"], p + ".feed_forward_layer_norm", ws["xn"], "ln")
             self._dense_fwd(ws["xn"], p + ".feed_forward.intermediate_dense.kernel", ws["g"], act=1)
@@ -871,13 +879,17 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         return x, hidden
 
     @torch.no_grad()
-    def forward_infer(self, inputs, attention_mask=None, output_hidden_states=False, pool=None):
+    def forward_infer(self, inputs, attention_mask=None, output_hidden_states=False, pool=None, output_attentions=False,
+                      attentions_dtype=None):
         """The reference's ``Wav2Vec2Model.call(..., training=False)`` (V:768-825): conv stem, grouped positional conv,
         LayerNorm, feature projection with its LayerNorm, encoder layers; no quantiser, no projection heads, no loss, no
         dropout.  ``inputs`` float32 [B, T_in].  Returns a dict with ``last_hidden_state`` [B, T, H], ``extract_features``
         [B, T, C], with ``output_hidden_states`` ``hidden_states`` (the input of every layer and the output of the last:
         num_hidden_layers + 1 tensors, V:488-537) and with ``pool="mean"`` ``pooled_output`` fp32 [B, H], the masked mean
-        over time of V:1031-1042 (the plain mean without a mask; a clip whose mask is all zero pools to zeros).
+        over time of V:1031-1042 (the plain mean without a mask; a clip whose mask is all zero pools to zeros).  With
+        ``output_attentions`` ``attentions``: one tensor [B, Hh, T, T] per layer (V:333-376, V:481-546), the softmax weights
+        before dropout - with an ``attention_mask`` the masked ones - in ``attentions_dtype`` (None: the compute dtype;
+        torch.float32 is allowed on the bf16 model).
 
         ``attention_mask`` [B, T] over FRAMES (``frame_attention_mask``), values in [0, 1], is the reference's argument as
         is: the host turns it into (1 - mask) * -10000 once, and every layer's attention adds that to the scores of the
@@ -887,6 +899,8 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         cfg = self.config
         if pool not in (None, "mean"):
             raise ValueError('pool must be None or "mean"')
+        if attentions_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("attentions_dtype must be None, torch.float32 or torch.bfloat16")
         if not torch.is_tensor(inputs) or inputs.dim() != 2 or inputs.dtype != torch.float32 or inputs.shape[0] < 1:
             raise TypeError("inputs must be float32 [B, T_in]")
         B, T_in = inputs.shape
@@ -902,11 +916,15 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             if mask is not None:
                 mask_dev = mask.to(self.device)
                 key_bias = ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, on the host, once per call
-            x, hidden = self._infer_body(audio, inf, key_bias, output_hidden_states)
+            attentions = [] if output_attentions else None
+            x, hidden = self._infer_body(audio, inf, key_bias, output_hidden_states, attentions=attentions,
+                                         attentions_dtype=attentions_dtype)
             last = x.view(B, T, H).clone()
             result = {"last_hidden_state": last, "extract_features": ws["feats"].view(B, T, C).clone()}
             if output_hidden_states:
                 result["hidden_states"] = tuple(hidden) + (last,)
+            if output_attentions:
+                result["attentions"] = tuple(attentions)
             if pool == "mean":
                 pooled = torch.empty(B, H, dtype=torch.float32, device=self.device)
                 ops.masked_mean_pool(x, mask_dev, pooled, B, T, H)

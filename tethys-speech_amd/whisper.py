@@ -380,15 +380,20 @@ class WhisperForConditionalGeneration(KernelBlocks):
                       c_sb=T * d, bias=a.param("encoder.conv2.bias"), act=1, aux_out=u2, resid=self.pe_enc_t,
                       r_ld=d, r_sb=0)
 
-    def _enc_layer(self, i, b, B, T, sites):
-        """W:218-236: encoder layer i, b["x_in"] -> b["x_out"]."""
+    def _enc_layer(self, i, b, B, T, sites, capture=None):
+        """W:218-236: encoder layer i, b["x_in"] -> b["x_out"].  ``capture`` (inference, ``_Capture``): collects the layer's
+        input and its attention weights when they were asked for."""
         cfg, d = self.config, self.config.d_model
         p, He = f"encoder.layers.{i}", cfg.encoder_attention_heads
+        if capture is not None:
+            capture.layer_input("encoder", b["x_in"], B, T, d)
         self._ln_fwd(b["x_in"], p + ".self_attn_layer_norm", b["xn1"], b["ln1"])
         self._dense_fwd(b["xn1"], p + ".self_attn.qkv.kernel", b["qkv"], scale_cols=d, scale=(d // He) ** -0.5)
         qkv = b["qkv"]
         self._attn_fwd(b["att"], (qkv, 0), (qkv, d), (qkv, 2 * d), b["ctx"], B, He, T, T, 0,
                        site=SITE_ENC_ATTN + i if sites else None)
+        if capture is not None and capture.wants("encoder"):
+            capture.attention("encoder", self._attn_probs(b["att"], (qkv, 0), (qkv, d), B, He, T, T, 0, dtype=capture.dtype))
         self._dense_fwd(b["ctx"], p + ".self_attn.out_proj.kernel", b["x_mid"], resid=b["x_in"], r_ld=d)
         self._ln_fwd(b["x_mid"], p + ".final_layer_norm", b["xn2"], b["ln2"])
         self._dense_fwd(b["xn2"], p + ".feed_forward.fc1.kernel", b["g"], act=1, aux_out=b["u"])
@@ -396,28 +401,35 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self._dense_fwd(b["g"], p + ".feed_forward.fc2.kernel", b["x_out"], resid=b["x_mid"], r_ld=d,
                         **(self._drop_epi(SITE_ENC_FFN + i) if sites else {}))
 
-    def _dec_self_block(self, i, b, B, S, sites):
+    def _dec_self_block(self, i, b, B, S, sites, capture=None):
         """Decoder layer i (W:394-466) up to the cross-attention query: needs nothing from the encoder."""
         cfg, d = self.config, self.config.d_model
         p, Hd = f"decoder.layers.{i}", cfg.decoder_attention_heads
         scal = (d // Hd) ** -0.5
+        if capture is not None:
+            capture.layer_input("decoder", b["x_in"], B, S, d)
         self._ln_fwd(b["x_in"], p + ".self_attn_layer_norm", b["xn1"], b["ln1"])
         self._dense_fwd(b["xn1"], p + ".self_attn.qkv.kernel", b["qkv"], scale_cols=d, scale=scal)
         qkv = b["qkv"]
         # the inverted mask of W:416-418 (mask_mode 1): each query sees the strictly later positions only
         self._attn_fwd(b["att"], (qkv, 0), (qkv, d), (qkv, 2 * d), b["ctx"], B, Hd, S, S, 1,
                        site=SITE_DEC_SELF + i if sites else None)
+        if capture is not None and capture.wants("decoder"):
+            capture.attention("decoder", self._attn_probs(b["att"], (qkv, 0), (qkv, d), B, Hd, S, S, 1, dtype=capture.dtype))
         self._dense_fwd(b["ctx"], p + ".self_attn.out_proj.kernel", b["x_mid"], resid=b["x_in"], r_ld=d)
         # cross attention (W:278-290): k/v projections of the encoder output in every layer
         self._ln_fwd(b["x_mid"], p + ".encoder_attn_layer_norm", b["xn2"], b["ln2"])
         self._dense_fwd(b["xn2"], p + ".encoder_attn.q_proj.kernel", b["qc"], scale_cols=d, scale=scal)
 
-    def _dec_cross_ffn(self, i, b, B, S, T, sites):
+    def _dec_cross_ffn(self, i, b, B, S, T, sites, capture=None):
         """Decoder layer i from its cross-attention on: b["x_mid"] -> b["x_out"]."""
         cfg, d = self.config, self.config.d_model
         p, Hd, kvc = f"decoder.layers.{i}", cfg.decoder_attention_heads, b["kvc"]
         self._attn_fwd(b["attc"], (b["qc"], 0), (kvc, 2 * i * d), (kvc, (2 * i + 1) * d), b["ctxc"], B, Hd, S, T, 0,
                        site=SITE_DEC_CROSS + i if sites else None)
+        if capture is not None and capture.wants("cross"):
+            capture.attention("cross", self._attn_probs(b["attc"], (b["qc"], 0), (kvc, 2 * i * d), B, Hd, S, T, 0,
+                                                        dtype=capture.dtype))
         self._dense_fwd(b["ctxc"], p + ".encoder_attn.out_proj.kernel", b["x_mid2"], resid=b["x_mid"], r_ld=d)
         self._ln_fwd(b["x_mid2"], p + ".final_layer_norm", b["xn3"], b["ln3"])
         self._dense_fwd(b["xn3"], p + ".feed_forward.fc1.kernel", b["g"], act=1, aux_out=b["u"])
@@ -774,21 +786,28 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self._join_side()
         return ws["loss"]
 
-    def __call__(self, features, decoder_input_ids=None, labels=None, training=None):
+    def __call__(self, features, decoder_input_ids=None, labels=None, training=None, output_attentions=False,
+                 output_hidden_states=False, attentions_dtype=None):
         """Reference call surface (W:547-616).  ``training=True`` (the default when labels are given): the training step,
         {"loss": ...} with the gradients as a side effect (W:829).  ``training=False``: the forward pass alone (no dropout,
         no gradients, nothing of the training state touched) -> {"loss": None, "logits" [B, S, V], "last_hidden_state"
         [B, S, d], "encoder_last_hidden_state" [B, T, d]}, in the model's compute dtype.  The decoder reads
         ``decoder_input_ids`` [B, S] (their first column must be the start token: every sequence the reference feeds its
         decoder starts with it, W:559-563 / W:663), else ``labels`` shifted right behind the start token (W:555-563), else
-        the start token alone."""
+        the start token alone.  ``output_attentions`` / ``output_hidden_states`` / ``attentions_dtype``: the inference call's
+        extra outputs, see ``forward_infer``."""
         if training is None:
             training = labels is not None
         if training:
             if labels is None or decoder_input_ids is not None:
                 raise ValueError("the training path takes labels (and forms the decoder input from them itself)")
+            if output_attentions or output_hidden_states or attentions_dtype is not None:
+                raise ValueError("output_attentions, output_hidden_states and attentions_dtype belong to the inference call "
+                                 "(training=False)")
             return {"loss": self.forward_backward(features, labels)}
-        return self.forward_infer(features, decoder_input_ids=decoder_input_ids, labels=labels)
+        return self.forward_infer(features, decoder_input_ids=decoder_input_ids, labels=labels,
+                                  output_attentions=output_attentions, output_hidden_states=output_hidden_states,
+                                  attentions_dtype=attentions_dtype)
 
     # -- inference (forward only): W:547-616 with training=False, greedy generate W:636-709 --------------------------
     # Its own workspace set (``_inf``), never one of ``_ws_sets``: the per-layer activations training keeps for backward are
@@ -876,7 +895,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return {"x_in": x, "xn1": xn, "qkv": qkv, "ctx": ctx, "x_mid": x_mid, "xn2": xn, "g": g, "u": None, "qc": qc,
                 "ctxc": ctx, "x_mid2": x_mid2, "xn3": xn, "x_out": x, "ln1": "ln", "ln2": "ln", "ln3": "ln"}
 
-    def _encode_infer(self, features, inf):
+    def _encode_infer(self, features, inf, capture=None):
         """W:324-372 with training=False into ws["enc_out"] [B*T, d]: the training forward's blocks, the pre-activations
         backward would need not saved."""
         cfg = self.config
@@ -885,7 +904,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         b["att"] = self._att("att", B, cfg.encoder_attention_heads, T, T)
         self._stem(features, inf, b["x_in"])
         for i in range(cfg.encoder_layers):
-            self._enc_layer(i, b, B, T, False)
+            self._enc_layer(i, b, B, T, False, capture)
         self._ln_fwd(b["x_in"], "encoder.layer_norm", self.ws["enc_out"], "ln")
         return self.ws["enc_out"]
 
@@ -894,7 +913,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if self.config.decoder_layers:
             self._dense_fwd(enc_out, "decoder.cross_kv.kernel", self.ws["kvc_all"][:enc_out.shape[0]])
 
-    def _decode_infer(self, labels, B, S, T):
+    def _decode_infer(self, labels, B, S, T, capture=None):
         """W:394-466 (training=False) over S positions without the final LayerNorm: returns the residual stream
         [B*S, d].  ``labels`` [B, S] int32: the decoder reads [start, labels[:, :-1]] (tmi_embed_fwd's shift)."""
         cfg = self.config
@@ -904,8 +923,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
         ops.embed_fwd(labels, self.arena.param("decoder.embed_tokens.embeddings"), self.pe_dec, b["x_in"], B, S, cfg.d_model,
                       cfg.decoder_start_token_id)
         for i in range(cfg.decoder_layers):
-            self._dec_self_block(i, b, B, S, False)
-            self._dec_cross_ffn(i, b, B, S, T, False)
+            self._dec_self_block(i, b, B, S, False, capture)
+            self._dec_cross_ffn(i, b, B, S, T, False, capture)
         return b["x_in"]
 
     def _check_features(self, features):
@@ -918,9 +937,23 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return features.to(self.device).contiguous()
 
     @torch.no_grad()
-    def forward_infer(self, features, decoder_input_ids=None, labels=None):
-        """The forward pass alone (W:547-616, training=False); see ``__call__``."""
+    def forward_infer(self, features, decoder_input_ids=None, labels=None, output_attentions=False,
+                      output_hidden_states=False, attentions_dtype=None):
+        """The forward pass alone (W:547-616, training=False); see ``__call__``.
+
+        ``output_attentions``: True, or a subset of ("encoder", "decoder", "cross") - the encoder's weights are about 99 % of
+        the bytes, and token-to-frame alignment needs only "cross".  Adds, per kind asked for, a tuple with one tensor per
+        layer (W:345-371, W:420-466): ``encoder_attentions`` [B, He, T, T], ``decoder_attentions`` [B, Hd, S, S] (under the
+        inverted mask of W:416-418: row i holds exact zeros at keys j <= i, the last row is uniform), ``cross_attentions``
+        [B, Hd, S, T]; the probabilities before dropout, in ``attentions_dtype`` (None: the compute dtype; torch.float32 is
+        allowed on the bf16 model).  ``output_hidden_states`` adds ``encoder_hidden_states`` / ``decoder_hidden_states``: the
+        input of every layer (W:348-349, W:427-428; ``encoder_layers`` / ``decoder_layers`` tensors [B, T or S, d]); the
+        post-LayerNorm output stays in ``*last_hidden_state``.  Keys that were not asked for are absent."""
         cfg = self.config
+        kinds = check_output_attentions(cfg, output_attentions)
+        if attentions_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("attentions_dtype must be None, torch.float32 or torch.bfloat16")
+        capture = _Capture(kinds, bool(output_hidden_states), attentions_dtype or self.dtype) if (kinds or output_hidden_states) else None
         features = self._check_features(features)
         B = features.shape[0]
         start = cfg.decoder_start_token_id
@@ -947,9 +980,9 @@ class WhisperForConditionalGeneration(KernelBlocks):
             ws, d, T = self.ws, cfg.d_model, inf["T"]
             lab = ws["labels"][:B * S].view(B, S)
             lab.copy_(shifted)
-            enc_out = self._encode_infer(features, inf)
+            enc_out = self._encode_infer(features, inf, capture)
             self._cross_kv_infer(enc_out)
-            h = self._decode_infer(lab, B, S, T)
+            h = self._decode_infer(lab, B, S, T, capture)
             out = torch.empty(B * S, d, dtype=self.dtype, device=self.device)
             self._ln_fwd(h, "decoder.layer_norm", out, "ln")
             Vp = self.arena.v_pad
@@ -959,6 +992,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
                       "logits": logits.view(B, S, Vp)[:, :, :cfg.vocab_size],
                       "last_hidden_state": out.view(B, S, d),
                       "encoder_last_hidden_state": enc_out.view(B, T, d).clone()}
+            if capture is not None:
+                result.update(capture.results())
         finally:
             self._infer_end(saved)
         return result
@@ -1366,6 +1401,54 @@ class WhisperForConditionalGeneration(KernelBlocks):
         finally:
             self._infer_end(saved)
         return {"token_logprobs": tok_lp, "sequences_logprob": tok_lp.sum(dim=1)}
+
+
+ATTENTION_KINDS = ("encoder", "decoder", "cross")
+
+
+def check_output_attentions(cfg: WhisperConfig, output_attentions) -> Tuple[str, ...]:
+    """Host validation of ``forward_infer``'s ``output_attentions`` (no GPU needed): False / None -> (), True -> every
+    kind, else an iterable of names out of ("encoder", "decoder", "cross") -> those, in that fixed order."""
+    if output_attentions is None or output_attentions is False:
+        return ()
+    if output_attentions is True:
+        return ATTENTION_KINDS
+    if isinstance(output_attentions, (str, bytes)):
+        raise ValueError('output_attentions must be True, False or a subset of ("encoder", "decoder", "cross"), e.g. ("cross",)')
+    try:
+        asked = list(output_attentions)
+    except TypeError:
+        raise ValueError('output_attentions must be True, False or a subset of ("encoder", "decoder", "cross")') from None
+    for n in asked:
+        if n not in ATTENTION_KINDS:
+            raise ValueError(f'output_attentions: unknown kind {n!r}; choose from ("encoder", "decoder", "cross")')
+    return tuple(k for k in ATTENTION_KINDS if k in asked)
+
+
+class _Capture:
+    """What an inference call collects on its way through the layers: the attention weights of the kinds asked for and,
+    when asked for, the input of every layer.  The layer blocks take one as an optional argument; training passes none."""
+
+    def __init__(self, kinds, hidden: bool, dtype):
+        self.kinds, self.dtype = tuple(kinds), dtype
+        self.att = {k: [] for k in self.kinds}
+        self.hidden = {"encoder": [], "decoder": []} if hidden else None
+
+    def wants(self, kind: str) -> bool:
+        return kind in self.att
+
+    def attention(self, kind: str, probs):
+        self.att[kind].append(probs)
+
+    def layer_input(self, side: str, x2d, B: int, T: int, d: int):
+        if self.hidden is not None:
+            self.hidden[side].append(x2d[:B * T].view(B, T, d).clone())
+
+    def results(self) -> dict:
+        out = {f"{k}_attentions": tuple(v) for k, v in self.att.items()}
+        if self.hidden is not None:
+            out.update({f"{k}_hidden_states": tuple(v) for k, v in self.hidden.items()})
+        return out
 
 
 def check_evaluate_args(cfg: WhisperConfig, labels_shape, mask_shape=None, mask_sum=None, mask_min=None):
