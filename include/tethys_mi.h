@@ -334,6 +334,40 @@ int tmi_linear_xent(const void* x, int64_t x_ld, const void* w, int64_t w_sk, in
 int tmi_sum_scale(const float* x, float* out, int64_t n, float scale, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The weighted loss of W:596-598 (a decoder_attention_mask was given):
+ *   loss = sum(nll * mask[:, :-1]) / sum(mask[:, :-1])
+ * on the training path.  The normaliser is a sum over the mask, which lives in device memory: it is taken on the device and
+ * handed from kernel to kernel there (inv_wsum), so the step never reads it on the host and a recorded launch plan replays
+ * unchanged for every mask.
+ *
+ * tmi_xent_weights: the row weights of a [B, S] fp32 mask (row stride mask_ld) and their normaliser, one workgroup:
+ *   row_w[b*S+t] = max(mask[b, t], 0) for t < S-1, and 0 for t = S-1 (W:597 slices the last column off: it is never read);
+ *                  an entry that is not > 0 (negative, NaN) counts as 0
+ *   wsum         = sum(row_w), in fp32 in a fixed order (tmi_sum_scale's): bit-reproducible, exact for 0/1 masks
+ *   inv_wsum[0]  = 1.0f / wsum if wsum > 0, else 0
+ * wsum == 0 (every weight 0): the reference would divide 0 by 0; here the batch then contributes loss 0 and all-zero
+ * gradients, as a replica whose slice of the batch is empty does.
+ *
+ * tmi_xent_weighted / tmi_linear_xent_weighted: tmi_xent_fwd_bwd / tmi_linear_xent with a weight per row.
+ *   scored row   (row_w[r] > 0): the unweighted arithmetic, unchanged in each of the three kernels, with
+ *                grad_scale = loss_scale * row_w[r] * inv_wsum[0] (in this order) and row_loss[r] = row_w[r] * nll.  With an
+ *                all-ones mask and loss_scale = 1 that is fl(1 / (B*(S-1))), the scalar the unweighted call is given: the
+ *                results are bit-identical.
+ *   unscored row (row_w[r] == 0, and every row t = S-1): the row of logits is NOT read; its gradient is +0 over all ld
+ *                columns and row_loss[r] = 0, whatever the row held, non-finite values included (TensorFlow's inf * 0 is
+ *                NaN; this is a defined departure, and the only work the mask saves: the LM-head GEMMs still run over all
+ *                rows).
+ * The loss is tmi_sum_scale_dev(row_loss, loss, B*S, inv_wsum): out[0] = sum(x[0..n)) * scale[0], tmi_sum_scale with the
+ * scale read from device memory.  None of the four takes an argument that changes from step to step. */
+int tmi_xent_weights(const float* mask, int64_t mask_ld, int64_t B, int64_t S, float* row_w, float* inv_wsum, void* stream);
+int tmi_xent_weighted(void* logits, int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum,
+                      float* row_loss, int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype, void* stream);
+int tmi_linear_xent_weighted(const void* x, int64_t x_ld, const void* w, int64_t w_sk, int64_t w_sn, int64_t d, void* logits,
+                             int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum, float* row_loss,
+                             int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype, void* stream);
+int tmi_sum_scale_dev(const float* x, float* out, int64_t n, const float* scale, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Greedy decoding's next token (W:675 / W:697: argmax(lm_head(decoder_out)[:, -1, :]), with the final decoder LayerNorm of
  * W:466 in front): for each of M hidden-state rows x[r * x_ld + k] (k < d; fp32 or bf16: x_dtype)
  *   y    = gamma, beta given ? LayerNorm_eps(x[r, :]) (fp32 statistics, W:392) : x[r, :]

@@ -7,7 +7,7 @@ Same flags (--batch_size per replica, --num_batches), same stdout lines (banner,
 ``/workspace/model.txt``.  One process per GPU; the cluster comes from TF_CONFIG (as the
 TFJob harness sets it) or from RANK/WORLD_SIZE (torchrun).  Roots are overridable by
 TETHYS_WORKSPACE / TETHYS_RESULT so it also runs outside the pod.  Extra, optional flags
-(--precision, --model_type) default to the reference's behaviour (model "small").
+(--precision, --model_type, --mask_padding) default to the reference's behaviour (model "small", plain-mean loss).
 """
 import argparse
 import os
@@ -31,6 +31,9 @@ def main(argv=None, model_overrides=None, train_kw=None):
     parser.add_argument("--tensor_logs", default=None,
                         help="directory for the tensor-size / skewness report (whisper_dist_tensorsize.py's files)")
     parser.add_argument("--resume_from", default=None, help="checkpoint to restore before training")
+    parser.add_argument("--mask_padding", action="store_true",
+                        help="train on the weighted loss of W:596-598 with decoder_attention_mask = (labels != 0): pad positions "
+                             "are not scored (default: the plain mean over every position, as the reference's job runs)")
     args = parser.parse_args(argv)
 
     import torch
@@ -69,7 +72,7 @@ network profile started!
                                 checkpoint_dir=os.path.join(workspace, "checkpoints"),
                                 tensor_log_dir=args.tensor_logs, resume_from=args.resume_from,
                                 dropout=None if args.dropout is None else args.dropout == "reference",
-                                model_overrides=model_overrides, **(train_kw or {}))
+                                model_overrides=model_overrides, **{"mask_padding": args.mask_padding, **(train_kw or {})})
     jct = time.time() - start_time
     print("Training completed.")
     print("jct:", jct)

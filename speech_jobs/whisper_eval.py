@@ -30,6 +30,8 @@ def main(argv=None):
     parser.add_argument("--max_target_length", type=int, default=100, help="target tokens per item")
     parser.add_argument("--seed", type=int, default=4321, help="seed of the evaluation pool")
     parser.add_argument("--out", default="whisper_eval.json", help="result file")
+    parser.add_argument("--mask_padding", action="store_true",
+                        help="score with decoder_attention_mask = (labels != 0), the objective of a --mask_padding training run")
     args = parser.parse_args(argv)
     if args.batch_size < 1 or args.num_batches < 1:
         parser.error("--batch_size and --num_batches must be at least 1")
@@ -47,7 +49,8 @@ def main(argv=None):
     if args.weights:
         train.load_weights(model, args.weights)
     ds = iter(create_dummy_dataset(args.batch_size, n_mels=model.config.n_mels, seq_len=args.seq_len,
-                                   max_target_length=args.max_target_length, device=device, seed=args.seed))
+                                   max_target_length=args.max_target_length, device=device, seed=args.seed,
+                                   with_mask=args.mask_padding))
     torch.cuda.synchronize()
     t0 = time.time()
     res = train.evaluate_whisper(None, model, (next(ds) for _ in range(args.num_batches)))

@@ -126,17 +126,46 @@ __device__ __forceinline__ float lm_target_logit(const LmOperands& lm, int64_t r
   return block_sum_256(z, red);
 }
 
+// The weighted loss of W:596-598 (tmi_xent_weighted / tmi_linear_xent_weighted): row r has the weight row_w[r] (tmi_xent_weights:
+// mask[b, t] for t < S - 1, 0 for t = S - 1) and the batch the normaliser inv_wsum[0] = 1 / sum(row_w), both in device memory.
+// A row with weight 0 is an unused row: its logits are not read, its gradient is +0, its loss 0.  A scored row is the
+// unweighted arithmetic with grad_scale = loss_scale * w * inv_wsum (an all-ones mask: 1 * 1 * fl(1 / n), the host scalar's bits)
+// and row_loss = w * nll.  The kernels below are ONE body each, instantiated twice: the weighted form passes a RowWeights as the
+// trailing parameter pack, the unweighted form an empty pack - its parameter list, and every statement it compiles, are the ones
+// it had before there were weights (WEIGHTED is a compile-time constant).
+struct RowWeights {
+  const float* row_w;     // [B*S]
+  const float* inv_wsum;  // [1]
+};
+// A value every lane of the workgroup loads from the same address, moved to a scalar register: left in a vector register the
+// two weights cost the on-chip kernel, which sits at its 128-VGPR budget, a spill.
+__device__ __forceinline__ float uniform_f32(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
 // One 256-thread block per logits row.  Pass 1: online (max, sum); pass 2: write gradient.
-template <typename T>
+template <typename T, typename... RW>
 __global__ __launch_bounds__(256) void xent_kernel(T* __restrict__ logits, int64_t ld, const int32_t* __restrict__ labels,
-                                                   float* __restrict__ row_loss, int S, int64_t V, float grad_scale, const LmOperands lm) {
+                                                   float* __restrict__ row_loss, int S, int64_t V, float grad_scale, const LmOperands lm,
+                                                   const RW... rw) {
+  constexpr bool WEIGHTED = sizeof...(RW) > 0;
   constexpr int VEC = 16 / sizeof(T);
   __shared__ float red[4];
   const int64_t row = blockIdx.x;
   const int b = (int)(row / S), t = (int)(row % S);
   T* lr = logits + row * ld;
   const int64_t nch = ld / VEC;  // ld is a multiple of VEC (host-checked)
-  if (t >= S - 1) {  // unused row (W:586 drops the last position): zero gradient
+  float wgt = 1.0f;
+  if constexpr (WEIGHTED) {
+    const RowWeights w_ = (rw, ...);
+    wgt = uniform_f32(w_.row_w[row]);
+    grad_scale = grad_scale * wgt * uniform_f32(w_.inv_wsum[0]);  // (grad_scale is loss_scale here; this order: see above)
+  }
+  auto weighted = [&](float nll) -> float {
+    if constexpr (WEIGHTED) return wgt * nll;
+    else return nll;
+  };
+  if (t >= S - 1 || (WEIGHTED && !(wgt > 0.f))) {  // unused row (W:586 drops the last position; weight 0): zero gradient
     alignas(16) T z[VEC];
 #pragma unroll
     for (int i = 0; i < VEC; ++i) z[i] = from_f32<T>(0.f);
@@ -179,9 +208,9 @@ __global__ __launch_bounds__(256) void xent_kernel(T* __restrict__ logits, int64
     if (lm.x) {
       const float rest = fmaxf(gsum - expf(to_f32(lr[target]) - gmx), 0.f);
       const float dz = gmx - zt;
-      row_loss[row] = dz < 80.f ? log1pf(rest * expf(dz)) : dz + logf(rest);
+      row_loss[row] = weighted(dz < 80.f ? log1pf(rest * expf(dz)) : dz + logf(rest));
     } else {
-      row_loss[row] = lse - to_f32(lr[target]);
+      row_loss[row] = weighted(lse - to_f32(lr[target]));
     }
   }
   __syncthreads();  // the target logit is read before anyone overwrites it
@@ -211,16 +240,28 @@ __global__ __launch_bounds__(256) void xent_kernel(T* __restrict__ logits, int64
 // With all 26-28 chunks in registers the kernel needed 156 VGPRs = 3 workgroups per CU = 768 resident rows, and the step's
 // 800 rows ran as a full round plus a 32-row tail (64 us); at <= 128 VGPRs and 36 KiB four workgroups fit: one round.
 constexpr int XREG = 17, XLDS = 9, XR = XREG + XLDS;
+template <typename... RW>
 __global__ __launch_bounds__(256, 4) void xent_rows_bf16_kernel(bf16_t* __restrict__ logits, int64_t ld, const int32_t* __restrict__ labels,
                                                                 float* __restrict__ row_loss, int S, int64_t V, float grad_scale,
-                                                                const LmOperands lm) {
+                                                                const LmOperands lm, const RW... rw) {
+  constexpr bool WEIGHTED = sizeof...(RW) > 0;
   __shared__ float red[4];
   __shared__ u32x4 spill[XLDS * 256];  // chunk XREG + k of thread t at spill[k * 256 + t]
   const int64_t row = blockIdx.x;
   const int b = (int)(row / S), t = (int)(row % S);
   bf16_t* lr = logits + row * ld;
   const int nch = (int)(ld / 8);
-  if (t >= S - 1) {
+  float wgt = 1.0f;
+  if constexpr (WEIGHTED) {
+    const RowWeights w_ = (rw, ...);
+    wgt = uniform_f32(w_.row_w[row]);
+    grad_scale = grad_scale * wgt * uniform_f32(w_.inv_wsum[0]);  // (grad_scale is loss_scale here)
+  }
+  auto weighted = [&](float nll) -> float {
+    if constexpr (WEIGHTED) return wgt * nll;
+    else return nll;
+  };
+  if (t >= S - 1 || (WEIGHTED && !(wgt > 0.f))) {
     const u32x4 z = u32x4{0u, 0u, 0u, 0u};
     for (int ch = threadIdx.x; ch < nch; ch += 256) reinterpret_cast<u32x4*>(lr)[ch] = z;
     if (threadIdx.x == 0) row_loss[row] = 0.f;
@@ -305,9 +346,9 @@ __global__ __launch_bounds__(256, 4) void xent_rows_bf16_kernel(bf16_t* __restri
     if (lm.x) {  // (the log-sum-exp with the target's term at the recomputed logit too: see xent_kernel)
       const float rest = fmaxf(gsum - __builtin_amdgcn_exp2f(fmaf((float)lr[target], L2E, nb)), 0.f);
       const float dz = gmx - zt;
-      row_loss[row] = dz < 80.f ? log1pf(rest * expf(dz)) : dz + logf(rest);
+      row_loss[row] = weighted(dz < 80.f ? log1pf(rest * expf(dz)) : dz + logf(rest));
     } else {
-      row_loss[row] = gmx + logf(gsum) - (float)lr[target];
+      row_loss[row] = weighted(gmx + logf(gsum) - (float)lr[target]);
     }
   }
   __syncthreads();  // the target logit is read before anyone overwrites it
@@ -339,6 +380,37 @@ __global__ __launch_bounds__(256, 4) void xent_rows_bf16_kernel(bf16_t* __restri
     __builtin_amdgcn_sched_barrier(0);
     emit((XREG + k) * 256 + (int)threadIdx.x, spill[k * 256 + threadIdx.x]);
   }
+}
+
+// tmi_xent_weights: the row weights and their normaliser, one workgroup.  The sum is taken in sum_scale_kernel's order (thread
+// i adds elements i, i + 256, ... in turn, then the fixed block fold): the same bits on every run, exact for 0/1 masks.  An entry
+// that is not > 0 (negative, NaN) counts as 0: the host never reads the mask.
+__global__ __launch_bounds__(256) void xent_weights_kernel(const float* __restrict__ mask, int64_t mask_ld, int64_t n, int S,
+                                                           float* __restrict__ row_w, float* __restrict__ inv_wsum) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += 256) {
+    const int64_t b = i / S;
+    const int t = (int)(i - b * S);
+    float w = 0.f;
+    if (t < S - 1) {
+      const float m = mask[b * mask_ld + t];
+      w = m > 0.f ? m : 0.f;
+    }
+    row_w[i] = w;
+    s += w;
+  }
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) inv_wsum[0] = s > 0.f ? 1.0f / s : 0.f;
+}
+
+__global__ __launch_bounds__(256) void sum_scale_dev_kernel(const float* __restrict__ x, float* __restrict__ out, int64_t n,
+                                                            const float* __restrict__ scale) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int64_t i = threadIdx.x; i < n; i += 256) s += x[i];
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) out[0] = s * scale[0];
 }
 
 __global__ __launch_bounds__(256) void sum_scale_kernel(const float* __restrict__ x, float* __restrict__ out,
@@ -458,6 +530,11 @@ extern "C" int tmi_softmax_bwd(const float* p, float* dp, int64_t rows, int64_t 
   return tmi_plan_run<tmi_softmax_bwd_impl>(p, dp, rows, Tk, stream);
 }
 
+static int xent_generic() {
+  static const int gen = [] { const char* e = getenv("TMI_XENT_GENERIC"); return e ? atoi(e) : 0; }();
+  return gen;
+}
+
 static int xent_launch(void* logits, int64_t ld, const int32_t* labels, float* row_loss, int64_t B, int64_t S, int64_t V,
                        float grad_scale, int32_t dtype, const LmOperands& lm, void* stream, const char* what) {
   const int vec = dtype == TMI_BF16 ? 8 : 4;
@@ -467,9 +544,9 @@ static int xent_launch(void* logits, int64_t ld, const int32_t* labels, float* r
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)(B * S));
-  static const int gen = [] { const char* e = getenv("TMI_XENT_GENERIC"); return e ? atoi(e) : 0; }();
+  const int gen = xent_generic();
   if (dtype == TMI_BF16 && !gen && ld <= (int64_t)256 * 8 * XR)
-    hipLaunchKernelGGL(xent_rows_bf16_kernel, grid, dim3(256), 0, s, (bf16_t*)logits, ld, labels, row_loss, (int)S, V, grad_scale, lm);
+    hipLaunchKernelGGL(xent_rows_bf16_kernel<>, grid, dim3(256), 0, s, (bf16_t*)logits, ld, labels, row_loss, (int)S, V, grad_scale, lm);
   else if (dtype == TMI_BF16)
     hipLaunchKernelGGL(xent_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)logits, ld, labels, row_loss, (int)S, V,
                        grad_scale, lm);
@@ -506,6 +583,92 @@ extern "C" int tmi_linear_xent(const void* x, int64_t x_ld, const void* w, int64
                                float grad_scale, int32_t dtype, void* stream) {
   return tmi_plan_run<tmi_linear_xent_impl>(x, x_ld, w, w_sk, w_sn, d, logits, ld, labels, row_loss, B, S, V, grad_scale, dtype,
                                             stream);
+}
+
+// The weighted forms: the same three kernels, chosen by the same rule.
+static int xent_weighted_launch(void* logits, int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum,
+                                float* row_loss, int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype,
+                                const LmOperands& lm, void* stream, const char* what) {
+  const int vec = dtype == TMI_BF16 ? 8 : 4;
+  if (!logits || !labels || !row_loss || !row_w || !inv_wsum || B <= 0 || S <= 1 || V <= 0 || ld < V || ld % vec || !al16(logits) ||
+      B * S > INT32_MAX) {
+    tmi_set_error("tmi_xent_weighted / tmi_linear_xent_weighted: bad argument (row_w and inv_wsum required; ld must be a multiple "
+                  "of 16 bytes, >= V)");
+    return TMI_ERR_INVALID;
+  }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  dim3 grid((unsigned)(B * S));
+  const RowWeights rw{row_w, inv_wsum};
+  if (dtype == TMI_BF16 && !xent_generic() && ld <= (int64_t)256 * 8 * XR)
+    hipLaunchKernelGGL((xent_rows_bf16_kernel<RowWeights>), grid, dim3(256), 0, s, (bf16_t*)logits, ld, labels, row_loss, (int)S, V,
+                       loss_scale, lm, rw);
+  else if (dtype == TMI_BF16)
+    hipLaunchKernelGGL((xent_kernel<bf16_t, RowWeights>), grid, dim3(256), 0, s, (bf16_t*)logits, ld, labels, row_loss, (int)S, V,
+                       loss_scale, lm, rw);
+  else if (dtype == TMI_F32)
+    hipLaunchKernelGGL((xent_kernel<float, RowWeights>), grid, dim3(256), 0, s, (float*)logits, ld, labels, row_loss, (int)S, V,
+                       loss_scale, LmOperands{}, rw);  // (fp32 logits carry their target logit exactly)
+  else
+    return TMI_ERR_UNSUPPORTED;
+  return tmi_check_launch(what);
+}
+
+static int tmi_xent_weights_impl(const float* mask, int64_t mask_ld, int64_t B, int64_t S, float* row_w, float* inv_wsum,
+                                 void* stream) {
+  if (!mask || !row_w || !inv_wsum || B <= 0 || S <= 1 || mask_ld < S || B * S > INT32_MAX) {
+    tmi_set_error("tmi_xent_weights: bad argument (mask [B, S] with row stride mask_ld >= S, S >= 2)");
+    return TMI_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(xent_weights_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), mask, mask_ld, B * S, (int)S,
+                     row_w, inv_wsum);
+  return tmi_check_launch("tmi_xent_weights");
+}
+extern "C" int tmi_xent_weights(const float* mask, int64_t mask_ld, int64_t B, int64_t S, float* row_w, float* inv_wsum,
+                                void* stream) {
+  return tmi_plan_run<tmi_xent_weights_impl>(mask, mask_ld, B, S, row_w, inv_wsum, stream);
+}
+
+static int tmi_xent_weighted_impl(void* logits, int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum,
+                                  float* row_loss, int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype, void* stream) {
+  return xent_weighted_launch(logits, ld, labels, row_w, inv_wsum, row_loss, B, S, V, loss_scale, dtype, LmOperands{}, stream,
+                              "tmi_xent_weighted");
+}
+extern "C" int tmi_xent_weighted(void* logits, int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum,
+                                 float* row_loss, int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype, void* stream) {
+  return tmi_plan_run<tmi_xent_weighted_impl>(logits, ld, labels, row_w, inv_wsum, row_loss, B, S, V, loss_scale, dtype, stream);
+}
+
+static int tmi_linear_xent_weighted_impl(const void* x, int64_t x_ld, const void* w, int64_t w_sk, int64_t w_sn, int64_t d,
+                                         void* logits, int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum,
+                                         float* row_loss, int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype,
+                                         void* stream) {
+  if (!x || !w || d <= 0 || d > (1 << 20) || x_ld < d || w_sk == 0 || w_sn == 0) {
+    tmi_set_error("tmi_linear_xent_weighted: bad LM-head operands");
+    return TMI_ERR_INVALID;
+  }
+  LmOperands lm{};
+  if (dtype == TMI_BF16) lm = LmOperands{(const bf16_t*)x, (const bf16_t*)w, x_ld, w_sk, w_sn, (int)d};
+  return xent_weighted_launch(logits, ld, labels, row_w, inv_wsum, row_loss, B, S, V, loss_scale, dtype, lm, stream,
+                              "tmi_linear_xent_weighted");
+}
+extern "C" int tmi_linear_xent_weighted(const void* x, int64_t x_ld, const void* w, int64_t w_sk, int64_t w_sn, int64_t d,
+                                        void* logits, int64_t ld, const int32_t* labels, const float* row_w, const float* inv_wsum,
+                                        float* row_loss, int64_t B, int64_t S, int64_t V, float loss_scale, int32_t dtype,
+                                        void* stream) {
+  return tmi_plan_run<tmi_linear_xent_weighted_impl>(x, x_ld, w, w_sk, w_sn, d, logits, ld, labels, row_w, inv_wsum, row_loss, B, S, V,
+                                                     loss_scale, dtype, stream);
+}
+
+static int tmi_sum_scale_dev_impl(const float* x, float* out, int64_t n, const float* scale, void* stream) {
+  if (!x || !out || !scale || n <= 0) {
+    tmi_set_error("tmi_sum_scale_dev: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(sum_scale_dev_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, out, n, scale);
+  return tmi_check_launch("tmi_sum_scale_dev");
+}
+extern "C" int tmi_sum_scale_dev(const float* x, float* out, int64_t n, const float* scale, void* stream) {
+  return tmi_plan_run<tmi_sum_scale_dev_impl>(x, out, n, scale, stream);
 }
 
 static int tmi_sum_scale_impl(const float* x, float* out, int64_t n, float scale, void* stream) {

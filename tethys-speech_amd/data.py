@@ -31,13 +31,16 @@ def make_pool(seed=1234, n_mels=80, seq_len=3000, max_target_length=100, num_sam
 class DummyDataset:
     """Iterator over per-replica batches.  The global batch of step i is samples
     [i*GB, (i+1)*GB) of the repeating pool pass (short last batch of each pass kept, as the
-    reference); replica r takes rows [r*B, (r+1)*B) of it (possibly fewer, possibly none)."""
+    reference); replica r takes rows [r*B, (r+1)*B) of it (possibly fewer, possibly none).
+    ``with_mask``: every batch is (features, labels, decoder_attention_mask) with the mask (labels != 0) as float32 - 0 is
+    the pool's pad id - resident on the device like the pool; without it the tuples are (features, labels)."""
 
     def __init__(self, batch_size, n_mels=80, seq_len=3000, max_target_length=100, device="cuda:0",
-                 rank=0, world=1, seed=1234, drop_remainder=False, num_samples=50):
+                 rank=0, world=1, seed=1234, drop_remainder=False, num_samples=50, with_mask=False):
         f, l = make_pool(seed, n_mels, seq_len, max_target_length, num_samples)
         self.features = torch.from_numpy(f).to(device)
         self.labels = torch.from_numpy(l).to(device)
+        self.mask = torch.from_numpy((l != 0).astype(np.float32)).to(device) if with_mask else None
         self.batch_size, self.rank, self.world = batch_size, rank, world
         self.global_batch = batch_size * world
         self.n = num_samples
@@ -55,12 +58,15 @@ class DummyDataset:
         self._pos = e
         lo = min(e, s + self.rank * self.batch_size)
         hi = min(e, lo + self.batch_size)
+        if self.mask is not None:
+            return self.features[lo:hi], self.labels[lo:hi], self.mask[lo:hi]
         return self.features[lo:hi], self.labels[lo:hi]
 
 
 def create_dummy_dataset(batch_size, n_mels=80, seq_len=3000, max_target_length=100, **kw):
     """W:784 signature; ``batch_size`` is the PER-REPLICA batch (the reference passes the
-    global batch and lets tf.distribute split it; rank/world are keyword arguments here)."""
+    global batch and lets tf.distribute split it; rank/world are keyword arguments here, and so is ``with_mask``:
+    batches of (features, labels, labels != 0) for the weighted loss of W:596-598)."""
     return DummyDataset(batch_size, n_mels, seq_len, max_target_length, **kw)
 
 

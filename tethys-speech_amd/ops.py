@@ -491,6 +491,40 @@ def xent_fwd_bwd(logits, ld, labels, row_loss, B, S, V, grad_scale, lm=None):
                                         row_loss.data_ptr(), B, S, V, grad_scale, dt(logits), stream()), "tmi_linear_xent")
 
 
+def _f32_flat(t, n, what):
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{what}: float32, contiguous, at least {n} elements")
+
+
+def xent_weights(mask, B, S, row_w, inv_wsum):
+    """tmi_xent_weights: row_w[b*S+t] = mask[b, t] (t < S-1; 0 for t = S-1 and for entries that are not > 0) and
+    inv_wsum[0] = 1 / sum(row_w), or 0 when that sum is 0 - on the device, in a fixed order, with no host read.
+    ``mask`` [B, S] float32 with unit column stride (any row stride >= S)."""
+    if mask.dtype != torch.float32 or tuple(mask.shape) != (B, S) or mask.stride(1) != 1 or (B > 1 and mask.stride(0) < S):
+        raise ValueError("xent_weights: mask must be float32 [B, S] with unit column stride")
+    _f32_flat(row_w, B * S, "xent_weights: row_w")
+    _f32_flat(inv_wsum, 1, "xent_weights: inv_wsum")
+    check(lib().tmi_xent_weights(mask.data_ptr(), mask.stride(0) if B > 1 else S, B, S, row_w.data_ptr(), inv_wsum.data_ptr(),
+                                 stream()), "tmi_xent_weights")
+
+
+def xent_fwd_bwd_weighted(logits, ld, labels, row_w, inv_wsum, row_loss, B, S, V, loss_scale, lm=None):
+    """``xent_fwd_bwd`` under the row weights of ``xent_weights`` (W:596-598): a row with weight 0 is not read, its gradient is
+    +0 and its loss 0; a scored row's gradient scale is loss_scale * row_w[r] * inv_wsum[0] and row_loss[r] = row_w[r] * nll.
+    Every weight 0: loss 0 and all-zero gradients (the reference would divide 0 by 0).  ``lm`` as in ``xent_fwd_bwd``."""
+    _f32_flat(row_w, B * S, "xent_fwd_bwd_weighted: row_w")
+    _f32_flat(inv_wsum, 1, "xent_fwd_bwd_weighted: inv_wsum")
+    with _probe("xent", 2.0 * B * S * V * logits.element_size()):
+        if lm is None:
+            check(lib().tmi_xent_weighted(logits.data_ptr(), ld, labels.data_ptr(), row_w.data_ptr(), inv_wsum.data_ptr(),
+                                          row_loss.data_ptr(), B, S, V, loss_scale, dt(logits), stream()), "tmi_xent_weighted")
+        else:
+            x, x_ld, w, w_sk, w_sn, d = lm
+            check(lib().tmi_linear_xent_weighted(x.data_ptr(), x_ld, w.data_ptr(), w_sk, w_sn, d, logits.data_ptr(), ld,
+                                                 labels.data_ptr(), row_w.data_ptr(), inv_wsum.data_ptr(), row_loss.data_ptr(), B, S,
+                                                 V, loss_scale, dt(logits), stream()), "tmi_linear_xent_weighted")
+
+
 def lm_head_argmax(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma=None, beta=None, eps=1e-5, eos_id=-1,
                    eos_count=None):
     """ids[r * ids_ld] = argmax_{n < V} (LayerNorm(x[r]) . w)[n] for M rows of x (row stride x_ld), w the LM head in its
@@ -621,6 +655,12 @@ def logprob_from_logits(logits, V, targets, state, lse, logprob, argmax, nc=None
 
 def sum_scale(x, out, n, scale):
     check(lib().tmi_sum_scale(x.data_ptr(), out.data_ptr(), n, scale, stream()), "tmi_sum_scale")
+
+
+def sum_scale_dev(x, out, n, scale):
+    """out[0] = sum(x[:n]) * scale[0], ``sum_scale`` with the scale in device memory (a 1-element float32 tensor)."""
+    _f32_flat(scale, 1, "sum_scale_dev: scale")
+    check(lib().tmi_sum_scale_dev(x.data_ptr(), out.data_ptr(), n, scale.data_ptr(), stream()), "tmi_sum_scale_dev")
 
 
 def adam_step(p, g, m, v, n, lr, beta1, beta2, eps, step, eps_mode=0, weight_decay=0.0, gscale=1.0, mirror=None,

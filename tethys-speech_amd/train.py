@@ -36,8 +36,14 @@ def distributed_train_step(strategy, model, dist_inputs, optimizer, pipelined=Fa
     Adam); returns ``strategy.reduce(SUM, per_replica_loss)`` as a 1-element device tensor.
     A replica whose slice of a short final batch is empty contributes zero gradients.
     ``pipelined``: the caller's next access to the model is another step or ``model.finish_late()`` - the decoder layers'
-    Adam slice may then still be running on the second stream when this returns."""
-    features, labels = dist_inputs
+    Adam slice may then still be running on the second stream when this returns.
+    ``dist_inputs``: (features, labels) or (features, labels, decoder_attention_mask) - with the mask the step optimises the
+    weighted loss of W:596-598 (``model.forward_backward``): each replica normalises by the sum of its OWN weights, the
+    gradients are summed over replicas and the returned loss is the sum of the per-replica weighted means (W:829-836)."""
+    if len(dist_inputs) not in (2, 3):
+        raise ValueError("dist_inputs is (features, labels) or (features, labels, decoder_attention_mask)")
+    features, labels = dist_inputs[0], dist_inputs[1]
+    masked = {"decoder_attention_mask": dist_inputs[2]} if len(dist_inputs) == 3 else {}
     if hasattr(model, "finish_late") and features.shape[0] == 0:
         model.finish_late()  # (no forward to do the waiting)
     strategy.begin_gradients(model.arena.g)
@@ -62,7 +68,7 @@ def distributed_train_step(strategy, model, dist_inputs, optimizer, pipelined=Fa
         early_buckets = True
     try:
         if features.shape[0] > 0:
-            loss = model.forward_backward(features, labels, grad_ready=strategy.gradients_ready, early_update=early)
+            loss = model.forward_backward(features, labels, grad_ready=strategy.gradients_ready, early_update=early, **masked)
         else:
             # same reports as a real backward, so this rank's bucket launches match its peers' one for one
             model.report_zero_gradients(strategy.gradients_ready)
@@ -100,11 +106,12 @@ def plan_ok(strategy, model):
 
 def planned_step(strategy, model, optimizer, kind="whisper", pipelined=True):
     """``step(*inputs) -> loss`` for the training loops and the bench: ``distributed_train_step`` (kind "whisper": inputs
-    features, labels), ``wav2vec2_train_step`` ("wav2vec2": audio, neg_indices) or ``single_train_step`` ("single":
+    features, labels and optionally a decoder_attention_mask - float32, or converted to it here, before the plan sees it;
+    two- and three-input steps have plans of their own, keyed by the input signature), ``wav2vec2_train_step`` ("wav2vec2": audio, neg_indices) or ``single_train_step`` ("single":
     audio, neg_indices_t), through a launch plan when ``plan_ok`` and eagerly otherwise.  ``step.planned`` is the
     PlannedStep (or None)."""
     if kind == "whisper":
-        eager = lambda f, l: distributed_train_step(strategy, model, (f, l), optimizer, pipelined=pipelined)
+        eager = lambda *inputs: distributed_train_step(strategy, model, inputs, optimizer, pipelined=pipelined)
     elif kind == "wav2vec2":
         eager = lambda audio, negs: wav2vec2_train_step(strategy, model, audio, negs, optimizer, pipelined=pipelined)
     elif kind == "single":
@@ -117,7 +124,11 @@ def planned_step(strategy, model, optimizer, kind="whisper", pipelined=True):
     from .plan import PlannedStep
     ps = PlannedStep(eager, model, optimizer, loss_buffer=lambda: model.ws["loss"],
                      finish=lambda t: strategy.reduce_sum(t.clone()))
-    step = lambda *inputs: ps(*inputs)
+    if kind == "whisper":
+        # (a bool / integer mask becomes float32 OUTSIDE the plan: a torch kernel inside a recording is lost on replay)
+        step = lambda f, l, *m: ps(f, l, *(t if t.dtype == torch.float32 else t.to(torch.float32) for t in m))
+    else:
+        step = lambda *inputs: ps(*inputs)
     step.planned = ps
     return step
 
@@ -139,6 +150,9 @@ class GraphedTrainStep:
         if strategy.world != 1:
             raise ValueError("GraphedTrainStep is for a single replica (RCCL is not captured)")
         self.strategy, self.model, self.opt = strategy, model, optimizer
+        if len(example_inputs) != 2:
+            raise ValueError("GraphedTrainStep captures the (features, labels) step only: a decoder_attention_mask needs "
+                             "train.planned_step or the eager distributed_train_step")
         f, l = example_inputs
         self.feats = torch.empty_like(f)
         self.labels = torch.empty_like(l)
@@ -165,6 +179,9 @@ class GraphedTrainStep:
         self.scal.copy_(self._host, non_blocking=True)
 
     def __call__(self, inputs):
+        if len(inputs) != 2:
+            raise ValueError("GraphedTrainStep captures the (features, labels) step only: a decoder_attention_mask needs "
+                             "train.planned_step or the eager distributed_train_step")
         f, l = inputs
         if f.shape != self.feats.shape or l.shape != self.labels.shape:
             return distributed_train_step(self.strategy, self.model, inputs, self.opt)
@@ -204,8 +221,12 @@ def make_train_step(strategy, model, optimizer, example_inputs, warmup=2):
 def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4, *, batch_size=1,
                   num_batches=40, precision="bf16", device="cuda:0", checkpoint_dir=None, log=print, seed=1234,
                   model_overrides=None, seq_len=3000, max_target_length=100, tensor_log_dir=None,
-                  resume_from=None, dropout=None, loss_fetch_depth=2, eval_every=0, eval_batches=0, eval_seed=4321):
+                  resume_from=None, dropout=None, loss_fetch_depth=2, eval_every=0, eval_batches=0, eval_seed=4321,
+                  mask_padding=False):
     """W:894-958: model + Adam(1e-4), dummy dataset, per-step log line, checkpoint at epoch end.
+    ``mask_padding``: train on the reference's weighted loss (W:596-598) with decoder_attention_mask = (labels != 0), the pad
+    id of the dummy pool (W:784-815), instead of the plain mean that spends 30-45 % of its positions on pad after pad; the
+    evaluation batches then carry the same mask, so the "Eval step" lines report the objective being trained.
     ``eval_every`` / ``eval_batches`` (both > 0 to take effect): every ``eval_every`` steps and once after the last step,
     ``evaluate_whisper`` over ``eval_batches`` batches of a second dummy pool drawn with ``eval_seed`` (it must differ from
     ``seed``: held-out data), logged as "Eval step N, Loss: ..., Accuracy: ..." and kept in ``model.eval_history``.
@@ -231,7 +252,7 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
         report.log_parameters(0)
     ds = create_dummy_dataset(batch_size, n_mels=model.config.n_mels, seq_len=seq_len,
                               max_target_length=max_target_length, device=device, rank=strategy.rank,
-                              world=strategy.world, seed=seed, drop_remainder=strategy.world > 1)
+                              world=strategy.world, seed=seed, drop_remainder=strategy.world > 1, with_mask=mask_padding)
     it = iter(ds)
     step = load_checkpoint(model, optimizer, resume_from, dataset=ds) if resume_from else 0
     losses = []
@@ -251,7 +272,8 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
             raise ValueError("eval_seed must differ from seed: the evaluation pool is held-out data")
         eval_ds = create_dummy_dataset(batch_size, n_mels=model.config.n_mels, seq_len=seq_len,
                                        max_target_length=max_target_length, device=device, rank=strategy.rank,
-                                       world=strategy.world, seed=eval_seed, drop_remainder=strategy.world > 1)
+                                       world=strategy.world, seed=eval_seed, drop_remainder=strategy.world > 1,
+                                       with_mask=mask_padding)
         eit = iter(eval_ds)
         eval_set = [next(eit) for _ in range(eval_batches)]  # drawn once: every evaluation sees the same batches
 

@@ -317,6 +317,10 @@ class WhisperForConditionalGeneration(KernelBlocks):
         self._buf("logits", (Rd, self.ldl), **z)
         self._buf("row_loss", (Rd,), f32)
         self._buf("loss", (1,), f32)
+        # the weighted loss (decoder_attention_mask): row weights and 1 / their sum, written on the device each step; part of
+        # every set so that a plan recorded with a mask finds them at the addresses it baked in
+        self._buf("row_w", (Rd,), f32)
+        self._buf("inv_wsum", (1,), f32)
         # backward scratch, shared by every layer
         Rm = max(R, Rd)
         self._buf("dres_enc", (R, d))
@@ -503,24 +507,42 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return [(a.offsets["lm_head.kernel"], a.numel), (e_lo, e_lo + a.grad("decoder.embed_tokens.embeddings").numel())]
 
     def forward_backward(self, features: torch.Tensor, labels: torch.Tensor, loss_scale: float = 1.0,
-                         grad_ready=None, early_update=None):
+                         grad_ready=None, early_update=None, decoder_attention_mask=None):
         """Pins the launch stream for the duration of the step (KernelBlocks.begin_step), then runs
-        ``_forward_backward``."""
+        ``_forward_backward``.
+
+        ``decoder_attention_mask`` [B, S] (None: the plain mean over B*(S-1) positions, W:600): the reference's weighted
+        loss (W:596-598), wgt = mask[:, :-1] (column S-1 is ignored),
+          loss = sum(wgt * nll) / sum(wgt)
+        with non-negative real weights, not only 0/1, as in ``evaluate``.  The mask weights the LOSS only: the decoder keeps
+        the reference's inverted triangular mask (W:509 hands the [B, S] mask to the decoder in place of the [1, S, S] one,
+        which cannot broadcast - the same reading as ``evaluate``).  A float32 device tensor is used as it is; a bool /
+        integer / other float mask is converted once, here, before the step; a host array goes through
+        ``check_evaluate_args`` (shape, no negative entry) and is uploaded.  Shape and dtype errors raise on the host; the
+        step never reads the mask, or its sum, back: the normaliser stays in device memory (tmi_xent_weights), so one
+        recorded launch plan serves every mask.  Rows of weight 0 are not read by the loss kernel (gradient +0, whatever
+        the logits hold).  A mask whose weights are all 0 gives loss 0 and zero gradients - the reference would divide 0 by
+        0; an empty replica already contributes zeros the same way.  With replicas every replica normalises by the sum of
+        its OWN weights and the gradients are summed (W:829-836)."""
+        mask = None
+        if decoder_attention_mask is not None:
+            mask = prepare_loss_mask(self.config, tuple(labels.shape), decoder_attention_mask, self.device)
         self.begin_step()
         try:
-            return self._forward_backward(features, labels, loss_scale, grad_ready, early_update)
+            return self._forward_backward(features, labels, loss_scale, grad_ready, early_update, mask)
         finally:
             self.end_step()
             self._drop_step += 1  # next step draws fresh masks
 
     def _forward_backward(self, features: torch.Tensor, labels: torch.Tensor, loss_scale: float = 1.0,
-                         grad_ready=None, early_update=None):
+                         grad_ready=None, early_update=None, loss_mask=None):
         """One replica's forward + backward (W:826-833).  features [B, n_mels, T_in] fp32,
         labels [B, S] int32, both on the device.  Gradients land in ``arena.g`` (which is
         zeroed first); returns the device scalar loss (mean over B*(S-1), W:600).
         ``grad_ready(lo, hi)`` is called during backward each time the gradients of the arena
         range [lo, hi) are final, last range first (the data-parallel strategy all-reduces them
-        under the rest of backward).  ``early_update(lo, hi)`` (optim.Adam.begin_early, one replica): the optimizer
+        under the rest of backward).  ``loss_mask``: ``forward_backward``'s decoder_attention_mask as a float32 [B, S] device
+        tensor (the weighted mean of W:596-598 instead).  ``early_update(lo, hi)`` (optim.Adam.begin_early, one replica): the optimizer
         update of an arena range, called on the second stream as soon as that range's gradients are final and its
         weights have been read for the last time in this step - the LM head and the embedding table, under the
         decoder's backward chain."""
@@ -612,10 +634,18 @@ class WhisperForConditionalGeneration(KernelBlocks):
         wl, ldw = self.W("lm_head.kernel")
         Vp = self.ldl  # pad columns of the stored kernel are zero: their logits are 0 and ignored by xent
         self._gemm_xw(ws["dec_out"], "lm_head.kernel", logits, B * S, Vp, d, d, ldc=Vp)
-        gs = loss_scale / (B * (S - 1))
-        # (tmi_linear_xent: the loss's target logit in fp32 from the LM head's own operands - bf16 logits have lost its low bits)
-        ops.xent_fwd_bwd(logits, self.ldl, labels, ws["row_loss"], B, S, V, gs, lm=(ws["dec_out"], d, wl, ldw, 1, d))
-        ops.sum_scale(ws["row_loss"], ws["loss"], B * S, 1.0 / (B * (S - 1)))
+        lm = (ws["dec_out"], d, wl, ldw, 1, d)
+        if loss_mask is None:
+            gs = loss_scale / (B * (S - 1))
+            # (tmi_linear_xent: the loss's target logit in fp32 from the LM head's own operands - bf16 logits have lost its low bits)
+            ops.xent_fwd_bwd(logits, self.ldl, labels, ws["row_loss"], B, S, V, gs, lm=lm)
+            ops.sum_scale(ws["row_loss"], ws["loss"], B * S, 1.0 / (B * (S - 1)))
+        else:
+            # W:596-598: the per-row scale loss_scale * w / sum(w) is formed on the device (no host read of the sum)
+            ops.xent_weights(loss_mask, B, S, ws["row_w"], ws["inv_wsum"])
+            ops.xent_fwd_bwd_weighted(logits, self.ldl, labels, ws["row_w"], ws["inv_wsum"], ws["row_loss"], B, S, V, loss_scale,
+                                      lm=lm)
+            ops.sum_scale_dev(ws["row_loss"], ws["loss"], B * S, ws["inv_wsum"])
 
         # ================= backward =================
         dres = ws["dres_dec"]
@@ -787,7 +817,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return ws["loss"]
 
     def __call__(self, features, decoder_input_ids=None, labels=None, training=None, output_attentions=False,
-                 output_hidden_states=False, attentions_dtype=None):
+                 output_hidden_states=False, attentions_dtype=None, decoder_attention_mask=None):
         """Reference call surface (W:547-616).  ``training=True`` (the default when labels are given): the training step,
         {"loss": ...} with the gradients as a side effect (W:829).  ``training=False``: the forward pass alone (no dropout,
         no gradients, nothing of the training state touched) -> {"loss": None, "logits" [B, S, V], "last_hidden_state"
@@ -795,7 +825,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
         ``decoder_input_ids`` [B, S] (their first column must be the start token: every sequence the reference feeds its
         decoder starts with it, W:559-563 / W:663), else ``labels`` shifted right behind the start token (W:555-563), else
         the start token alone.  ``output_attentions`` / ``output_hidden_states`` / ``attentions_dtype``: the inference call's
-        extra outputs, see ``forward_infer``."""
+        extra outputs, see ``forward_infer``.  ``decoder_attention_mask`` [B, S]: the loss weights of the training step
+        (W:596-598, see ``forward_backward``); the forward-only call computes no loss and refuses it (``evaluate`` takes it)."""
         if training is None:
             training = labels is not None
         if training:
@@ -804,7 +835,9 @@ class WhisperForConditionalGeneration(KernelBlocks):
             if output_attentions or output_hidden_states or attentions_dtype is not None:
                 raise ValueError("output_attentions, output_hidden_states and attentions_dtype belong to the inference call "
                                  "(training=False)")
-            return {"loss": self.forward_backward(features, labels)}
+            return {"loss": self.forward_backward(features, labels, decoder_attention_mask=decoder_attention_mask)}
+        if decoder_attention_mask is not None:
+            raise ValueError("decoder_attention_mask weights the loss: it belongs to the training call and to evaluate()")
         return self.forward_infer(features, decoder_input_ids=decoder_input_ids, labels=labels,
                                   output_attentions=output_attentions, output_hidden_states=output_hidden_states,
                                   attentions_dtype=attentions_dtype)
@@ -1470,6 +1503,28 @@ def check_evaluate_args(cfg: WhisperConfig, labels_shape, mask_shape=None, mask_
     if mask_sum is not None and not (float(mask_sum) > 0.0 and math.isfinite(float(mask_sum))):
         raise ValueError("decoder_attention_mask[:, :-1] must have a positive, finite sum (W:598 divides by it)")
     return B, S
+
+
+def prepare_loss_mask(cfg: WhisperConfig, labels_shape, mask, device) -> torch.Tensor:
+    """The decoder_attention_mask of the training step as a float32 [B, S] tensor on ``device``, checked on the host only.
+    A tensor already on an accelerator: shape and dtype (bool, integer or real) - its values are never read.  A host array
+    or CPU tensor: ``check_evaluate_args`` on its shape and its smallest weight (a negative weight has no meaning), then
+    one upload.  An all-zero mask is NOT an error here (``forward_backward`` says what it gives)."""
+    if isinstance(mask, torch.Tensor) and mask.device.type != "cpu":
+        check_evaluate_args(cfg, labels_shape, tuple(mask.shape))
+        if not (mask.dtype == torch.bool or mask.dtype.is_floating_point or mask.dtype in _INT_DTYPES):
+            raise TypeError("decoder_attention_mask must be bool, integer or real")
+        return mask.to(device=device, dtype=torch.float32).contiguous()
+    host = mask.numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+    if host.dtype.kind not in "biuf":
+        raise TypeError("decoder_attention_mask must be bool, integer or real")
+    check_evaluate_args(cfg, labels_shape, host.shape)
+    w = host[:, :-1].astype(np.float64)
+    check_evaluate_args(cfg, labels_shape, host.shape, mask_min=float(w.min()) if np.isfinite(w).all() else float("nan"))
+    return torch.from_numpy(np.ascontiguousarray(host, dtype=np.float32)).to(device)
+
+
+_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 
 
 def create_whisper_model(model_type: str = "small", device="cuda:0", precision: str = "bf16", seed: int = 1234,
