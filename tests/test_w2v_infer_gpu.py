@@ -306,6 +306,65 @@ def test_masked_forward_matches_restatement(dev, precision, clips):
     assert model_err(precision, out["last_hidden_state"][2], out0["last_hidden_state"][2].double().cpu()) > 1e-3
 
 
+def _clips_and_negatives(model, T_in, dev):
+    from tethys_speech_amd import wav2vec2
+    cfg = model.config
+    T = wav2vec2.frame_lengths(cfg, [T_in])[0]
+    audio = torch.from_numpy(V.create_dummy_pool(seed=21, num_samples=B_M, length=T_in)).to(dev)
+    neg = torch.from_numpy(wav2vec2.sample_negative_indices(np.random.default_rng(3), B_M, T, cfg.num_negatives)).to(dev)
+    return audio, neg, T
+
+
+@pytest.mark.parametrize("T_in", [T_IN, 1990])  # 130 frames; 100 frames behind an odd conv length (398 -> 199 -> 100)
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_forward_infer_is_the_training_forward_bit_for_bit(dev, precision, T_in):
+    """The step and ``forward_infer`` run the same forward blocks on different buffers: without dropout the last hidden
+    state and the extracted features of an inference call are the bits the training step left in ws["enc_x"] and
+    ws["feats"] for the same clips and weights.  Neither T is a multiple of the 64-key attention tile, and the positional
+    conv pads both (3 rows in front, 4 behind)."""
+    from tethys_speech_amd import ops
+    model, _, _ = build(precision, dev)
+    cfg = model.config
+    audio, neg, T = _clips_and_negatives(model, T_in, dev)
+    assert T == {T_IN: 130, 1990: 100}[T_in] and T % 64 != 0
+    was = ops.set_deterministic(True)
+    try:
+        model.forward_backward(audio, neg)
+        assert model.T == T
+        enc_x = model.ws["enc_x"].view(B_M, T, cfg.hidden_size).clone()
+        feats = model.ws["feats"].view(B_M, T, cfg.conv_dim[-1]).clone()
+        out = model.forward_infer(audio)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_deterministic(was)
+    assert bool(torch.isfinite(enc_x.float()).all())
+    assert torch.equal(out["extract_features"], feats)
+    assert torch.equal(out["last_hidden_state"], enc_x)
+
+
+def test_inference_after_a_dropout_step_passes_no_site(dev):
+    """After ``enable_dropout`` and one training step, two inference calls agree bit for bit, and the step counter of the
+    dropout masks has moved by the training step alone."""
+    from tethys_speech_amd import ops
+    model, _, _ = build("bf16", dev)
+    c = model.config
+    model.enable_dropout(c.hidden_dropout, c.attention_dropout, seed=11, act_p=c.activation_dropout)
+    audio, neg, _ = _clips_and_negatives(model, T_IN, dev)
+    was = ops.set_deterministic(True)
+    try:
+        assert model._drop_step == 0
+        model.forward_backward(audio, neg)
+        assert model._drop_step == 1
+        first = model.forward_infer(audio)
+        second = model.forward_infer(audio)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_deterministic(was)
+    assert model._drop_step == 1
+    for n in ("last_hidden_state", "extract_features"):
+        assert torch.equal(first[n], second[n]), n
+
+
 def _train_inputs(model, B, T_in, seed, dev):
     cfg = model.config
     from tethys_speech_amd import wav2vec2

@@ -4,6 +4,7 @@ backward expressed as C-ABI calls.  A model class supplies ``arena``, ``precisio
 ``device``, ``mirror``, ``ws`` and ``hidden`` (the attention model width)."""
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Dict, List, Tuple
@@ -307,6 +308,37 @@ class KernelBlocks:
         """Cm = A · W[:, n_off:n_off+N] with W the natural [K, N_total] kernel (forward)."""
         w, ldw = self.W(wname)
         ops.gemm(A, w, Cm, M, N, K, a_sm, 1, ldw, 1, b_off=n_off, **kw)
+
+    def _select_ws_set(self, key) -> bool:
+        """Make the workspace set of batch shape ``key`` (and of the dropout mode) ``self.ws``; -> whether it already was.
+        One set per batch shape, kept alive across shape changes: a captured HIP graph or a recorded plan has the addresses
+        of the set it was made with baked in (a short final batch must not free them), and the zero pad rows of the conv
+        buffers are an invariant of each set."""
+        if self._ws_key == key:
+            return True
+        self.ws = self._ws_sets.setdefault((key, self._drop_p > 0.0), {})
+        while len(self._ws_sets) > 4:  # (a holder of an evicted set, e.g. GraphedTrainStep, keeps it alive itself)
+            self._ws_sets.pop(next(k for k in self._ws_sets if self._ws_sets[k] is not self.ws))
+        self._ws_key = key
+        return False
+
+    @contextlib.contextmanager
+    def _inference(self, inf):
+        """An inference call on the workspace set ``inf["ws"]``: pin the stream, order it behind every parameter update
+        that may still be running on the second stream (the late Adam slices: their persistent events are waited for,
+        ``_late_pending`` is left as it is), and swap the inference workspace in as ``self.ws`` until the block ends."""
+        self.begin_step()
+        main = self._main or torch.cuda.current_stream(self.device)
+        for ev in self.__dict__.get("_late_done", {}).values():
+            main.wait_event(ev)  # (a wait on an event that has completed, or was never recorded, is free)
+        if self._side is not None:
+            main.wait_stream(self._side)
+        saved, self.ws = self.ws, inf["ws"]
+        try:
+            yield
+        finally:
+            self.ws = saved
+            self.end_step()
 
     def _buf(self, name, shape, dtype=None, zero=False):
         t = self.ws.get(name)

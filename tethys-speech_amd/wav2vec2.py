@@ -286,38 +286,44 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                                  cfg.conv_dim[-1] // G, G, w_off=self.arena.offsets["feature_extractor.pos_conv_embed.kernel"])
 
     # -- workspaces --------------------------------------------------------------------
+    def _geometry(self, T_in: int) -> dict:
+        """Geometry of the "same"-padded conv stem and of the grouped positional conv for ``T_in`` samples: per conv layer
+        the output length ``lens``, the (left, right) ``pads`` and the padded input length ``Tp`` (layer 0's input is the
+        audio itself, C = 1); the frame count ``T``; whether layer 0 runs as the fused filter bank (``fir0``); the
+        positional conv's pads ``plp`` / ``prp`` and its padded lengths ``Tpp`` (forward) and ``Tpp2`` (gradient: full
+        correlation).  Shared by training and inference."""
+        cfg = self.config
+        lens, pads, T = [], [], T_in
+        for k, s in zip(cfg.conv_kernel, cfg.conv_stride):
+            To, pl, pr = same_pad(T, k, s)
+            pads.append((pl, pr))
+            lens.append(To)
+            T = To
+        Tp = [([T_in] + lens)[i] + pads[i][0] + pads[i][1] for i in range(len(lens))]
+        # conv layer 0 runs as a filter bank fused with its GroupNorm + GELU straight from the audio (tmi_fir_groupnorm_gelu_*)
+        # whenever the reference's first-layer geometry holds (kernel 10, stride 5: every size of V:24-128)
+        c0, Gn = cfg.conv_dim[0], cfg.num_conv_pos_embedding_groups
+        fir0 = (cfg.conv_kernel[0] == 10 and cfg.conv_stride[0] == 5 and c0 % 8 == 0 and 2048 % c0 == 0 and
+                (c0 // Gn) % 8 == 0 and os.environ.get("TMI_W2V_FIR", "1") != "0")
+        kp = cfg.num_conv_pos_embeddings
+        plp, prp = same_pad(T, kp, 1)[1:]
+        return {"lens": lens, "pads": pads, "Tp": Tp, "T": T, "fir0": fir0, "plp": plp, "prp": prp, "Tpp": T + kp - 1,
+                "Tpp2": T + 2 * (kp - 1)}
+
     def _prepare(self, B: int, T_in: int):
-        key = (B, T_in)
-        if self._ws_key == key:
+        if self._select_ws_set((B, T_in)):
             return
-        # one workspace set per batch shape, kept alive across shape changes: a captured HIP graph has the
-        # addresses of the set it was captured with baked in (a short final batch must not free them), and the
-        # zero pad rows of the conv buffers are an invariant of each set
-        self.ws = self._ws_sets.setdefault((key, self._drop_p > 0.0), {})
-        while len(self._ws_sets) > 4:  # (a holder of an evicted set, e.g. GraphedTrainStep, keeps it alive itself)
-            self._ws_sets.pop(next(k for k in self._ws_sets if self._ws_sets[k] is not self.ws))
-        self._ws_key = key
         cfg = self.config
         f32 = torch.float32
         L = len(cfg.conv_dim)
-        self.lens, self.pads = [], []
-        T = T_in
-        for k, s in zip(cfg.conv_kernel, cfg.conv_stride):
-            To, pl, pr = same_pad(T, k, s)
-            self.pads.append((pl, pr))
-            self.lens.append(To)
-            T = To
-        self.T = T
+        geo = self._geo = self._geometry(T_in)
+        # (the shape attributes model.T, model.lens, ...: the backward, tests, tools and bench read them)
+        self.lens, self.pads, self.Tp, self.T, self.fir0, self.plp, self.prp, self.Tpp, self.Tpp2 = (
+            geo[n] for n in ("lens", "pads", "Tp", "T", "fir0", "plp", "prp", "Tpp", "Tpp2"))
         Gn = cfg.num_conv_pos_embedding_groups
         slack = 2
         z = dict(zero=True)
-        # input of conv layer i (padded, channels-last): i = 0 is the audio itself (C = 1)
-        self.Tp = [([T_in] + self.lens)[i] + self.pads[i][0] + self.pads[i][1] for i in range(L)]
-        # conv layer 0 runs as a filter bank fused with its GroupNorm + GELU straight from the audio (tmi_fir_groupnorm_gelu_*)
-        # whenever the reference's first-layer geometry holds (kernel 10, stride 5: every size of V:24-128)
         c0_ = cfg.conv_dim[0]
-        self.fir0 = (cfg.conv_kernel[0] == 10 and cfg.conv_stride[0] == 5 and c0_ % 8 == 0 and 2048 % c0_ == 0 and
-                     (c0_ // Gn) % 8 == 0 and os.environ.get("TMI_W2V_FIR", "1") != "0")
         if not self.fir0:
             self._buf("in0", (B, self.Tp[0] + slack + 8, 1), **z)
         else:
@@ -334,11 +340,7 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             cin = c
         C, H = cfg.conv_dim[-1], cfg.hidden_size
         R = B * self.T
-        k = cfg.num_conv_pos_embeddings
         Cg = C // Gn
-        self.plp, self.prp = same_pad(self.T, k, 1)[1:]
-        self.Tpp = self.T + k - 1            # forward geometry of the grouped conv
-        self.Tpp2 = self.T + 2 * (k - 1)     # gradient geometry (full correlation)
         self._buf("h_last", (R, C))
         self._buf("xg", (Gn, B * self.Tpp, Cg))
         self._buf("yg", (Gn, B * self.Tpp, Cg))
@@ -404,6 +406,123 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         self._buf("clip_all", (1,), f32)
         self._buf("clip_vars", (self.n_var,), f32)
 
+    # -- forward blocks, shared by the training step, forward_infer and evaluate ------------------------------------------
+    # Each takes a map of what differs between its callers: training passes the buffers and statistics it keeps for the
+    # backward (``_train_bufs``), inference buffers every layer shares, without the GELU pre-activation ``u`` (None)
+    # (``_infer_bufs``).  Buffers that have the same name in both workspace sets (in{i}, u{i}, h_last, xg, yg, hp, feats,
+    # fp_pre, qin, quant, code_idx, perplexity, pq_pre, pq, ph_pre, ph) are read from ``self.ws``.  ``sites``: the dropout
+    # sites apply (the training step; inference runs without dropout even after enable_dropout).  Map keys: x_out (the
+    # feature projection's output, then each layer's), the layer's activations x_in, xn1, qkv, ctx, x_mid, xn2, g, u; the
+    # names of the statistics: gn (GroupNorm of conv layer i: formatted with i), fe_ln, fp_ln, pq_ln, ph_ln, ln1, ln2, and
+    # of the attention scratch att.
+
+    def _feature_encoder(self, audio, geo, b, sites):
+        """V:283-296, V:777-779: conv -> GroupNorm -> GELU per layer (each output lands in the padded buffer that is the
+        next conv's im2col matrix), the grouped positional conv as one batched window-GEMM, LayerNorm into ws["feats"],
+        the feature projection and its LayerNorm into b["x_out"] [B*T, H]."""
+        cfg, ws, a = self.config, self.ws, self.arena
+        B, T_in = audio.shape
+        L, Gn, C = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups, cfg.conv_dim[-1]
+        lens, pads, T = geo["lens"], geo["pads"], geo["T"]
+        if not geo["fir0"]:
+            in0 = ws["in0"]
+            ops.feat_to_channels_last(audio, in0, B, 1, T_in, pads[0][0], in0.shape[1] - T_in - pads[0][0])
+        cin = 1
+        for i in range(L):
+            c, k, s = cfg.conv_dim[i], cfg.conv_kernel[i], cfg.conv_stride[i]
+            pre = f"feature_extractor.conv_layers.{i}.norm"
+            stats = ws[b["gn"].format(i)]
+            if i + 1 < L:
+                y, ysb, yoff = ws[f"in{i + 1}"], ws[f"in{i + 1}"].stride(0), pads[i + 1][0] * c
+            else:
+                y, ysb, yoff = ws["h_last"], lens[i] * c, 0
+            if i == 0 and geo["fir0"]:
+                # C_in = 1: a filter bank, fused with GroupNorm + GELU, its output never written (fp32 master taps)
+                ops.fir_groupnorm_gelu_fwd(audio, pads[0][0], a.param("feature_extractor.conv_layers.0.conv.kernel"), k, s,
+                                           a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb, stats,
+                                           ws["gn_part"], B, lens[0], c, Gn, 1e-5, y_off=yoff)
+            else:
+                xin, u = ws[f"in{i}"], ws[f"u{i}"]
+                self._gemm_xw(xin, f"feature_extractor.conv_layers.{i}.conv.kernel", u, lens[i], c, k * cin, s * cin,
+                              ldc=c, nbatch=B, a_sb=xin.stride(0), c_sb=u.stride(0))
+                ops.groupnorm_gelu_fwd(u, u.stride(0), a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb,
+                                       stats, ws["gn_part"], B, lens[i], c, Gn, 1e-5, y_off=yoff)
+            cin = c
+        # grouped positional conv (V:271-277, V:291) as one batched window-GEMM
+        kp, Cg, Tpp = cfg.num_conv_pos_embeddings, C // Gn, geo["Tpp"]
+        ops.group_pack(ws["h_last"], ws["xg"], B, T, C, Gn, Tpp, geo["plp"])
+        ops.gemm(ws["xg"], self.pos_wf, ws["yg"], B * Tpp - (kp - 1), Cg, kp * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
+                 a_sb=B * Tpp * Cg, b_sb=kp * Cg * Cg, c_sb=B * Tpp * Cg)
+        ops.group_unpack(ws["yg"], a.param("feature_extractor.pos_conv_embed.bias"), ws["h_last"], ws["hp"], B, T, C, Gn,
+                         Tpp, 0)
+        # V:296, V:779: LayerNorm + Dropout in one pass (the quantiser sees the dropped features too, V:784)
+        self._ln_fwd(ws["hp"], "feature_extractor.layer_norm", ws["feats"], b["fe_ln"], drop_site=SITE_FE if sites else None)
+        self._dense_fwd(ws["feats"], "feature_projection.kernel", ws["fp_pre"])
+        self._ln_fwd(ws["fp_pre"], "feature_projection_layer_norm", b["x_out"], b["fp_ln"],
+                     drop_site=SITE_FP if sites else None)
+
+    def _quantise(self, hproj, b, forced, sites):
+        """V:784, V:557-560: the quantiser on the projected features ``hproj`` [B*T, H] (codes into ws["code_idx"], code
+        vectors into ws["quant"]), then project_q and its LayerNorm into ws["pq"].  ``forced``: the caller has put the
+        codes into ws["code_idx"] and tmi_vq_assign takes them instead of the argmin.  (The kernels' own perplexity counts
+        every row, padding too.)"""
+        cfg, ws, a = self.config, self.ws, self.arena
+        R, Gq, Nc = hproj.shape[0], cfg.num_codevector_groups, cfg.num_codevectors_per_group
+        gd = cfg.codevector_dim // Gq
+        self._dense_fwd(hproj, "quantizer.projection.kernel", ws["qin"])
+        if forced:
+            ops.vq_assign(a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"], R, Gq, Nc, gd)
+        else:
+            ops.vq_nearest(ws["qin"], a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"], R,
+                           Gq, Nc, gd)
+        self._dense_fwd(ws["quant"], "project_q.dense.kernel", ws["pq_pre"])
+        self._ln_fwd(ws["pq_pre"], "project_q.layer_norm", ws["pq"], b["pq_ln"], drop_site=SITE_PQ if sites else None)  # V:560
+
+    def _enc_layer(self, i, b, B, T, sites, key_bias=None, attentions=None, attentions_dtype=None):
+        """V:419-439 (stable layer norm): encoder layer i, b["x_in"] -> b["x_out"].  ``key_bias`` (inference): added to the
+        scores of the masked keys; ``attentions``: a list that receives the layer's attention weights [B, Hh, T, T]
+        (V:376) in ``attentions_dtype``."""
+        cfg, a, H = self.config, self.arena, self.config.hidden_size
+        p, Hh = f"encoder.layers.{i}", cfg.num_attention_heads
+        R, sscale = B * T, 1.0 / math.sqrt(H // Hh)
+        self._ln_fwd(b["x_in"], p + ".attention_layer_norm", b["xn1"], b["ln1"])
+        wq, _ = self.W(p + ".attention.qkv3.kernel")  # [3H, H] view of the three blocks
+        qkv = b["qkv"]
+        ops.gemm(b["xn1"], wq, qkv, R, H, H, H, 1, H, 1, 3 * H, nbatch=3, b_sb=H * H, c_sb=H,
+                 bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
+        self._attn_fwd(b["att"], (qkv, 0), (qkv, H), (qkv, 2 * H), b["ctx"], B, Hh, T, T, 0, score_scale=sscale,
+                       site=SITE_ATTN + i if sites else None, key_bias=key_bias)
+        if attentions is not None:
+            attentions.append(self._attn_probs(b["att"], (qkv, 0), (qkv, H), B, Hh, T, T, 0, score_scale=sscale,
+                                               key_bias=key_bias, dtype=attentions_dtype))
+        # V:431: x + Dropout(attention output): the mask is a term of the GEMM epilogue
+        self._dense_fwd(b["ctx"], p + ".attention.out_proj.kernel", b["x_mid"], resid=b["x_in"], r_ld=H,
+                        **(self._drop_epi(SITE_ATTN_OUT + i) if sites else {}))
+        self._ln_fwd(b["x_mid"], p + ".feed_forward_layer_norm", b["xn2"], b["ln2"])
+        self._dense_fwd(b["xn2"], p + ".feed_forward.intermediate_dense.kernel", b["g"], act=1, aux_out=b["u"],
+                        **(self._drop_epi(SITE_FFN_MID + i, p=self._drop_act_p) if sites else {}))  # V:393 on the GELU output
+        self._dense_fwd(b["g"], p + ".feed_forward.output_dense.kernel", b["x_out"], resid=b["x_mid"], r_ld=H,
+                        **(self._drop_epi(SITE_FFN_OUT + i) if sites else {}))  # V:396
+
+    def _project_hid(self, x, b, sites):
+        """V:550-561: the projection head on the encoder output ``x`` [B*T, H] into ws["ph"]."""
+        self._dense_fwd(x, "project_hid.dense.kernel", self.ws["ph_pre"])
+        self._ln_fwd(self.ws["ph_pre"], "project_hid.layer_norm", self.ws["ph"], b["ph_ln"],
+                     drop_site=SITE_PH if sites else None)  # V:560
+
+    def _train_bufs(self, i=None):
+        """Training's buffer map: encoder layer i's own workspace entries (kept for the backward), or without ``i`` the map
+        of the blocks around the encoder (the projection lands in the first layer's input: the encoder's input IS it)."""
+        ws, Lh = self.ws, self.config.num_hidden_layers
+        if i is None:
+            return {"x_out": ws["enc0.x_in"] if Lh else ws["enc_x"], "gn": "gn{}.stats", "fe_ln": "fe_ln", "fp_ln": "fp_ln",
+                    "pq_ln": "pq_ln", "ph_ln": "ph_ln"}
+        k = f"enc{i}."
+        b = {n: ws[k + n] for n in ("x_in", "xn1", "qkv", "ctx", "x_mid", "xn2", "g", "u")}
+        b.update(ln1=k + "ln1", ln2=k + "ln2", att=k + ("stats" if self.precision == "bf16" else "P"),
+                 x_out=ws[f"enc{i + 1}.x_in"] if i + 1 < Lh else ws["enc_x"])
+        return b
+
     # -- forward + backward ----------------------------------------------------------------
     def forward_backward(self, audio: torch.Tensor, neg_indices: torch.Tensor, num_replicas: int = 1, forced_codes=None):
         """Pins the launch stream for the duration of the step (KernelBlocks.begin_step), then runs
@@ -440,89 +559,28 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             ops.fill_zero(a.g)
         a.g_clean = False
 
-        # ---- feature encoder (V:283-288): conv -> GroupNorm -> GELU, 7 times
-        if not self.fir0:
-            in0 = ws["in0"]
-            ops.feat_to_channels_last(audio, in0, B, 1, T_in, self.pads[0][0], in0.shape[1] - T_in - self.pads[0][0])
-        cin = 1
-        for i in range(L):
-            c, k, s = cfg.conv_dim[i], cfg.conv_kernel[i], cfg.conv_stride[i]
-            pre = f"feature_extractor.conv_layers.{i}.norm"
-            if i + 1 < L:
-                y, ysb, yoff = ws[f"in{i + 1}"], ws[f"in{i + 1}"].stride(0), self.pads[i + 1][0] * c
-            else:
-                y, ysb, yoff = ws["h_last"], self.lens[i] * c, 0
-            if i == 0 and self.fir0:
-                # C_in = 1: a filter bank, fused with GroupNorm + GELU, its output never written (fp32 master taps)
-                ops.fir_groupnorm_gelu_fwd(audio, self.pads[0][0], a.param("feature_extractor.conv_layers.0.conv.kernel"), k, s,
-                                           a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb, ws["gn0.stats"],
-                                           ws["gn_part"], B, self.lens[0], c, Gn, 1e-5, y_off=yoff)
-                cin = c
-                continue
-            xin, u = ws[f"in{i}"], ws[f"u{i}"]
-            self._gemm_xw(xin, f"feature_extractor.conv_layers.{i}.conv.kernel", u, self.lens[i], c, k * cin, s * cin,
-                          ldc=c, nbatch=B, a_sb=xin.stride(0), c_sb=u.stride(0))
-            ops.groupnorm_gelu_fwd(u, u.stride(0), a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb,
-                                   ws[f"gn{i}.stats"], ws["gn_part"], B, self.lens[i], c, Gn, 1e-5, y_off=yoff)
-            cin = c
-
-        # ---- grouped positional conv (V:271-277, V:291) as one batched window-GEMM
         k = cfg.num_conv_pos_embeddings
         Cg = C // Gn
-        h_last = ws["h_last"]
-        ops.group_pack(h_last, ws["xg"], B, T, C, Gn, self.Tpp, self.plp)
-        Mw = B * self.Tpp - (k - 1)
-        ops.gemm(ws["xg"], self.pos_wf, ws["yg"], Mw, Cg, k * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
-                 a_sb=B * self.Tpp * Cg, b_sb=k * Cg * Cg, c_sb=B * self.Tpp * Cg)
-        ops.group_unpack(ws["yg"], a.param("feature_extractor.pos_conv_embed.bias"), h_last, ws["hp"], B, T, C, Gn,
-                         self.Tpp, 0)
+        Mw = B * self.Tpp - (k - 1)  # rows of the positional conv's window GEMM
         drop = self._drop_p > 0.0
         pa = self._drop_act_p
-        self._ln_fwd(ws["hp"], "feature_extractor.layer_norm", ws["feats"], "fe_ln", drop_site=SITE_FE)  # V:296 (LayerNorm + Dropout, one pass)
-        self._dense_fwd(ws["feats"], "feature_projection.kernel", ws["fp_pre"])
-        hproj = ws["enc0.x_in"] if cfg.num_hidden_layers else ws["enc_x"]  # the encoder's input IS the projection
-        self._ln_fwd(ws["fp_pre"], "feature_projection_layer_norm", hproj, "fp_ln", drop_site=SITE_FP)  # V:779 (the quantiser sees the dropped features too, V:784)
-
-        # ---- quantiser on the projected features (V:784): no gradient flows back through it
         Gq, Nc = cfg.num_codevector_groups, cfg.num_codevectors_per_group
         gd = cfg.codevector_dim // Gq
-        self._dense_fwd(hproj, "quantizer.projection.kernel", ws["qin"])
-        if forced is not None:  # teacher-forced run: int32 [B*T, G] codes replace the argmin (tmi_vq_assign)
-            ws["code_idx"].copy_(forced.reshape(ws["code_idx"].shape))
-            ops.vq_assign(a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"], R, Gq, Nc, gd)
-        else:
-            ops.vq_nearest(ws["qin"], a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"], R,
-                           Gq, Nc, gd)
-        self._dense_fwd(ws["quant"], "project_q.dense.kernel", ws["pq_pre"])
-        self._ln_fwd(ws["pq_pre"], "project_q.layer_norm", ws["pq"], "pq_ln", drop_site=SITE_PQ)  # V:560
+        pd = cfg.proj_codevector_dim
 
-        # ---- encoder (V:419-439, stable layer norm)
+        # ---- forward: the shared blocks on the layers' own buffers, dropout sites on
+        b = self._train_bufs()
+        self._feature_encoder(audio, self._geo, b, True)
+        if forced is not None:  # teacher-forced run: int32 [B*T, G] codes replace the argmin (a torch copy, as it always was)
+            ws["code_idx"].copy_(forced.reshape(ws["code_idx"].shape))
+        self._quantise(b["x_out"], b, forced is not None, True)  # on the projected features (V:784): no gradient flows back through it
         for i in range(cfg.num_hidden_layers):
-            p, kk = f"encoder.layers.{i}", f"enc{i}."
-            x_in = ws[kk + "x_in"]
             if i == self._late_first:
                 self._wait_late()  # the previous step's Adam slice for this layer and everything after it, if left running
-            self._ln_fwd(x_in, p + ".attention_layer_norm", ws[kk + "xn1"], kk + "ln1")
-            wq, _ = self.W(p + ".attention.qkv3.kernel")  # [3H, H] view of the three blocks
-            ops.gemm(ws[kk + "xn1"], wq, ws[kk + "qkv"], R, H, H, H, 1, H, 1, 3 * H, nbatch=3, b_sb=H * H, c_sb=H,
-                     bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
-            qkv = ws[kk + "qkv"]
-            self._attn_fwd(kk + ("stats" if self.precision == "bf16" else "P"), (qkv, 0), (qkv, H), (qkv, 2 * H),
-                           ws[kk + "ctx"], B, Hh, T, T, 0, score_scale=sscale, site=SITE_ATTN + i)
-            # V:431: x + Dropout(attention output): the mask is a term of the GEMM epilogue
-            self._dense_fwd(ws[kk + "ctx"], p + ".attention.out_proj.kernel", ws[kk + "x_mid"], resid=x_in, r_ld=H,
-                            **self._drop_epi(SITE_ATTN_OUT + i))
-            self._ln_fwd(ws[kk + "x_mid"], p + ".feed_forward_layer_norm", ws[kk + "xn2"], kk + "ln2")
-            self._dense_fwd(ws[kk + "xn2"], p + ".feed_forward.intermediate_dense.kernel", ws[kk + "g"], act=1,
-                            aux_out=ws[kk + "u"], **self._drop_epi(SITE_FFN_MID + i, p=pa))  # V:393 on the GELU output
-            nxt = ws[f"enc{i + 1}.x_in"] if i + 1 < cfg.num_hidden_layers else ws["enc_x"]
-            self._dense_fwd(ws[kk + "g"], p + ".feed_forward.output_dense.kernel", nxt, resid=ws[kk + "x_mid"], r_ld=H,
-                            **self._drop_epi(SITE_FFN_OUT + i))  # V:396
+            self._enc_layer(i, self._train_bufs(i), B, T, True)
+        self._project_hid(ws["enc_x"], b, True)
 
-        # ---- projection head + contrastive loss (V:550-561, V:866-899)
-        pd = cfg.proj_codevector_dim
-        self._dense_fwd(ws["enc_x"], "project_hid.dense.kernel", ws["ph_pre"])
-        self._ln_fwd(ws["ph_pre"], "project_hid.layer_norm", ws["ph"], "ph_ln", drop_site=SITE_PH)  # V:560
+        # ---- contrastive loss (V:866-899)
         S = ws["S"]
         ops.gemm(ws["ph"], ws["pq"], S, T, T, pd, pd, 1, 1, pd, T, nbatch=B, a_sb=T * pd, b_sb=T * pd, c_sb=T * T)
         Nn = neg_indices.shape[1]
@@ -731,18 +789,8 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         cfg = self.config
         f32 = torch.float32
         L, Gn = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups
-        lens, pads, T = [], [], T_in
-        for k, s in zip(cfg.conv_kernel, cfg.conv_stride):
-            To, pl, pr = same_pad(T, k, s)
-            pads.append((pl, pr))
-            lens.append(To)
-            T = To
-        Tp = [([T_in] + lens)[i] + pads[i][0] + pads[i][1] for i in range(L)]
-        c0 = cfg.conv_dim[0]
-        fir0 = (cfg.conv_kernel[0] == 10 and cfg.conv_stride[0] == 5 and c0 % 8 == 0 and 2048 % c0 == 0 and
-                (c0 // Gn) % 8 == 0 and os.environ.get("TMI_W2V_FIR", "1") != "0")
-        kp = cfg.num_conv_pos_embeddings
-        inf = dict(key=(B, T_in), lens=lens, pads=pads, T=T, fir0=fir0, plp=same_pad(T, kp, 1)[1], Tpp=T + kp - 1)
+        inf = dict(self._geometry(T_in), key=(B, T_in))
+        lens, Tp, T, fir0 = inf["lens"], inf["Tp"], inf["T"], inf["fir0"]
         saved, self.ws = self.ws, {}
         try:
             slack = 2
@@ -773,24 +821,6 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         self._inf = inf
         return inf
 
-    def _infer_begin(self, inf):
-        """Enter an inference call: pin the stream, order it behind every parameter update that may still be running on the
-        second stream (a late Adam slice: its persistent event is waited for, ``_late_pending`` is left as it is), and swap
-        the inference workspace in."""
-        self.begin_step()
-        main = self._main or torch.cuda.current_stream(self.device)
-        for ev in self.__dict__.get("_late_done", {}).values():
-            main.wait_event(ev)  # (a wait on an event that has completed, or was never recorded, is free)
-        if self._side is not None:
-            main.wait_stream(self._side)
-        saved = self.ws
-        self.ws = inf["ws"]
-        return saved
-
-    def _infer_end(self, saved):
-        self.ws = saved
-        self.end_step()
-
     def _check_mask(self, attention_mask, B, T):
         """[B, T] over frames, values in [0, 1], float or bool -> fp32 on the host."""
         m = torch.as_tensor(attention_mask).detach().to("cpu")
@@ -801,6 +831,14 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             raise ValueError("attention_mask values must lie in [0, 1]")
         return m.contiguous()
 
+    def _infer_bufs(self):
+        """Inference's buffer map: every layer works in the same shared buffers, one LayerNorm-statistics buffer and one
+        GroupNorm-statistics buffer serve every call, no GELU pre-activation, each layer's output overwrites its input."""
+        ws = self.ws
+        return {"x_in": ws["x"], "xn1": ws["xn"], "qkv": ws["qkv"], "ctx": ws["ctx"], "x_mid": ws["x_mid"], "xn2": ws["xn"],
+                "g": ws["g"], "u": None, "x_out": ws["x"], "gn": "gn.stats", "att": "att",
+                **{n: "ln" for n in ("fe_ln", "fp_ln", "pq_ln", "ph_ln", "ln1", "ln2")}}
+
     def _infer_body(self, audio, inf, key_bias, output_hidden_states=False, on_projection=None, attentions=None,
                     attentions_dtype=None):
         """The forward pass of ``forward_infer`` and ``evaluate`` on the inference workspace (``self.ws`` is ``inf["ws"]``):
@@ -809,73 +847,17 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         for).  ``on_projection(x)`` runs between the feature projection and the first layer.  ``attentions``: a list that
         receives every layer's attention weights [B, Hh, T, T] (V:376) in ``attentions_dtype``."""
         cfg = self.config
-        B, T_in = audio.shape
-        T = inf["T"]
-        ws, a = self.ws, self.arena
-        L, Gn = len(cfg.conv_dim), cfg.num_conv_pos_embedding_groups
-        H, C, Hh = cfg.hidden_size, cfg.conv_dim[-1], cfg.num_attention_heads
-        lens, pads = inf["lens"], inf["pads"]
-        R = B * T
-        sscale = 1.0 / math.sqrt(H // Hh)
-        # ---- feature encoder (V:283-288)
-        if not inf["fir0"]:
-            in0 = ws["in0"]
-            ops.feat_to_channels_last(audio, in0, B, 1, T_in, pads[0][0], in0.shape[1] - T_in - pads[0][0])
-        cin = 1
-        for i in range(L):
-            c, k, s = cfg.conv_dim[i], cfg.conv_kernel[i], cfg.conv_stride[i]
-            pre = f"feature_extractor.conv_layers.{i}.norm"
-            if i + 1 < L:
-                y, ysb, yoff = ws[f"in{i + 1}"], ws[f"in{i + 1}"].stride(0), pads[i + 1][0] * c
-            else:
-                y, ysb, yoff = ws["h_last"], lens[i] * c, 0
-            if i == 0 and inf["fir0"]:
-                ops.fir_groupnorm_gelu_fwd(audio, pads[0][0], a.param("feature_extractor.conv_layers.0.conv.kernel"), k, s,
-                                           a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb, ws["gn.stats"],
-                                           ws["gn_part"], B, lens[0], c, Gn, 1e-5, y_off=yoff)
-            else:
-                xin, u = ws[f"in{i}"], ws[f"u{i}"]
-                self._gemm_xw(xin, f"feature_extractor.conv_layers.{i}.conv.kernel", u, lens[i], c, k * cin, s * cin,
-                              ldc=c, nbatch=B, a_sb=xin.stride(0), c_sb=u.stride(0))
-                ops.groupnorm_gelu_fwd(u, u.stride(0), a.param(pre + ".gamma"), a.param(pre + ".beta"), y, ysb,
-                                       ws["gn.stats"], ws["gn_part"], B, lens[i], c, Gn, 1e-5, y_off=yoff)
-            cin = c
-
-        # ---- grouped positional conv (V:271-277, V:291), LayerNorm, feature projection (V:777-778)
-        kp, Cg, Tpp = cfg.num_conv_pos_embeddings, C // Gn, inf["Tpp"]
-        ops.group_pack(ws["h_last"], ws["xg"], B, T, C, Gn, Tpp, inf["plp"])
-        ops.gemm(ws["xg"], self.pos_wf, ws["yg"], B * Tpp - (kp - 1), Cg, kp * Cg, Cg, 1, Cg, 1, Cg, nbatch=Gn,
-                 a_sb=B * Tpp * Cg, b_sb=kp * Cg * Cg, c_sb=B * Tpp * Cg)
-        ops.group_unpack(ws["yg"], a.param("feature_extractor.pos_conv_embed.bias"), ws["h_last"], ws["hp"], B, T, C, Gn,
-                         Tpp, 0)
-        self._ln_fwd(ws["hp"], "feature_extractor.layer_norm", ws["feats"], "ln")
-        self._dense_fwd(ws["feats"], "feature_projection.kernel", ws["fp_pre"])
-        x = ws["x"]
-        self._ln_fwd(ws["fp_pre"], "feature_projection_layer_norm", x, "ln")
-
+        B, T, H = audio.shape[0], inf["T"], cfg.hidden_size
+        b = self._infer_bufs()
+        x = b["x_in"]
+        self._feature_encoder(audio, inf, b, False)
         if on_projection is not None:
             on_projection(x)  # (evaluate's quantiser branch, V:784: it reads the projection before the encoder overwrites it)
-
-        # ---- encoder (V:419-439, stable layer norm): each layer's output overwrites its input
         hidden = []
-        for i in range(cfg.num_hidden_layers):
-            p = f"encoder.layers.{i}"
+        for i in range(cfg.num_hidden_layers):  # (each layer's output overwrites its input)
             if output_hidden_states:
                 hidden.append(x.view(B, T, H).clone())
-            self._ln_fwd(x, p + ".attention_layer_norm", ws["xn"], "ln")
-            wq, _ = self.W(p + ".attention.qkv3.kernel")
-            qkv = ws["qkv"]
-            ops.gemm(ws["xn"], wq, qkv, R, H, H, H, 1, H, 1, 3 * H, nbatch=3, b_sb=H * H, c_sb=H,
-                     bias=a.param(p + ".attention.qkv3.bias"), bias_sb=H)
-            self._attn_fwd("att", (qkv, 0), (qkv, H), (qkv, 2 * H), ws["ctx"], B, Hh, T, T, 0, score_scale=sscale,
-                           key_bias=key_bias)
-            if attentions is not None:
-                attentions.append(self._attn_probs("att", (qkv, 0), (qkv, H), B, Hh, T, T, 0, score_scale=sscale,
-                                                   key_bias=key_bias, dtype=attentions_dtype))
-            self._dense_fwd(ws["ctx"], p + ".attention.out_proj.kernel", ws["x_mid"], resid=x, r_ld=H)
-            self._ln_fwd(ws["x_mid"], p + ".feed_forward_layer_norm", ws["xn"], "ln")
-            self._dense_fwd(ws["xn"], p + ".feed_forward.intermediate_dense.kernel", ws["g"], act=1)
-            self._dense_fwd(ws["g"], p + ".feed_forward.output_dense.kernel", x, resid=ws["x_mid"], r_ld=H)
+            self._enc_layer(i, b, B, T, False, key_bias, attentions, attentions_dtype)
         return x, hidden
 
     @torch.no_grad()
@@ -908,8 +890,7 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         mask = None if attention_mask is None else self._check_mask(attention_mask, B, T)
         audio = inputs.to(self.device).contiguous()
         inf = self._infer_prepare(B, T_in)
-        saved = self._infer_begin(inf)
-        try:
+        with self._inference(inf):
             ws = self.ws
             H, C = cfg.hidden_size, cfg.conv_dim[-1]
             key_bias = mask_dev = None
@@ -929,8 +910,6 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                 pooled = torch.empty(B, H, dtype=torch.float32, device=self.device)
                 ops.masked_mean_pool(x, mask_dev, pooled, B, T, H)
                 result["pooled_output"] = pooled
-        finally:
-            self._infer_end(saved)
         return result
 
 
@@ -979,31 +958,22 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         forced = None if forced_codes is None else forced_codes.to(self.device, torch.int32).reshape(B * T, -1).contiguous()
         inf = self._infer_prepare(B, T_in)
         self._eval_buffers(inf)
-        saved = self._infer_begin(inf)
-        try:
-            ws, a = self.ws, self.arena
+        with self._inference(inf):
+            ws, b = self.ws, self._infer_bufs()
             R = B * T
-            Gq, Nc = cfg.num_codevector_groups, cfg.num_codevectors_per_group
-            gd, pd = cfg.codevector_dim // Gq, cfg.proj_codevector_dim
+            Gq, Nc, pd = cfg.num_codevector_groups, cfg.num_codevectors_per_group, cfg.proj_codevector_dim
             key_bias = mask_dev = None
             if mask is not None:
                 mask_dev = mask.to(self.device)
                 key_bias = ((1.0 - mask) * -10000.0).to(self.device)
 
             def quantise(hproj):  # V:784: the quantiser sees the projected features; then project_q (V:557-559)
-                self._dense_fwd(hproj, "quantizer.projection.kernel", ws["qin"])
                 if forced is not None:
                     ops.copy(ws["code_idx"], forced)
-                    ops.vq_assign(a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"], R, Gq, Nc, gd)
-                else:  # (the kernel's own perplexity counts the padding too: ignored, the counts below replace it)
-                    ops.vq_nearest(ws["qin"], a.param("quantizer.codevectors"), ws["code_idx"], ws["quant"], ws["perplexity"],
-                                   R, Gq, Nc, gd)
-                self._dense_fwd(ws["quant"], "project_q.dense.kernel", ws["pq_pre"])
-                self._ln_fwd(ws["pq_pre"], "project_q.layer_norm", ws["pq"], "ln")
+                self._quantise(hproj, b, forced is not None, False)  # (its perplexity is ignored: the counts below replace it)
 
             x, _ = self._infer_body(audio, inf, key_bias, on_projection=quantise)
-            self._dense_fwd(x, "project_hid.dense.kernel", ws["ph_pre"])
-            self._ln_fwd(ws["ph_pre"], "project_hid.layer_norm", ws["ph"], "ln")
+            self._project_hid(x, b, False)
             ops.contrastive_score(ws["ph"], ws["pq"], neg, ws["row_loss"], ws["row_correct"], B, T, pd, Nn,
                                   cfg.contrastive_logits_temperature, mask=mask_dev, per_time=per_time, validate=False)
             ops.fill_zero(ws["code_counts"])
@@ -1022,8 +992,6 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                               code_indices=ws["code_idx"].view(B, T, Gq).clone(),
                               projected_states=ws["ph"].view(B, T, pd).clone(),
                               projected_quantized_features=ws["pq"].view(B, T, pd).clone())
-        finally:
-            self._infer_end(saved)
         return result
 
 

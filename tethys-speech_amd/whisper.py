@@ -111,6 +111,13 @@ def same_pad(T: int, k: int, s: int) -> Tuple[int, int, int]:
     return out, total // 2, total - total // 2
 
 
+def _repeat_rows_per_item(kv: torch.Tensor, B: int, K: int):
+    """In place on ``kv`` [B*K, ...] whose first B row blocks hold one block per item: item b's block -> the blocks
+    b*K .. b*K + K - 1 (K beams or return sequences per item), from the back so that no source is overwritten first."""
+    for b in range(B - 1, -1, -1):
+        kv[b * K + (1 if b == 0 else 0):(b + 1) * K].copy_(kv[b:b + 1].expand(K - (1 if b == 0 else 0), -1, -1))
+
+
 def positional_encoding(max_len: int, d_model: int) -> np.ndarray:
     """W:49-69."""
     pe = np.zeros((max_len, d_model))
@@ -251,16 +258,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
             self.ws.pop("w1pad", None)
 
     def _prepare(self, B: int, T_in: int, S: int):
-        key = (B, T_in, S)
-        if self._ws_key == key:
+        if self._select_ws_set((B, T_in, S)):
             return
-        # one workspace set per batch shape, kept alive across shape changes: a captured HIP graph has the
-        # addresses of the set it was captured with baked in (a short final batch must not free them), and the
-        # zero pad rows of the conv buffers are an invariant of each set
-        self.ws = self._ws_sets.setdefault((key, self._drop_p > 0.0), {})
-        while len(self._ws_sets) > 4:  # (a holder of an evicted set, e.g. GraphedTrainStep, keeps it alive itself)
-            self._ws_sets.pop(next(k for k in self._ws_sets if self._ws_sets[k] is not self.ws))
-        self._ws_key = key
         cfg = self.config
         if S > cfg.max_target_positions:
             raise ValueError("target length exceeds max_target_positions")
@@ -896,24 +895,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if have is None or have.numel() < need:
             inf["ws"]["sample_ws"] = torch.zeros(need, dtype=torch.int64, device=self.device)
 
-    def _infer_begin(self, inf):
-        """Enter an inference call: pin the stream, order it behind every parameter update that may still be running on
-        the second stream (the late Adam slices: their persistent events are waited for, ``_late_pending`` is left as it
-        is), and swap the inference workspace in."""
-        self.begin_step()
-        main = self._main or torch.cuda.current_stream(self.device)
-        for ev in self.__dict__.get("_late_done", {}).values():
-            main.wait_event(ev)  # (a wait on an event that has completed, or was never recorded, is free)
-        if self._side is not None:
-            main.wait_stream(self._side)
-        saved = self.ws
-        self.ws = inf["ws"]
-        return saved
-
-    def _infer_end(self, saved):
-        self.ws = saved
-        self.end_step()
-
     def _att(self, key, B, H, Tq, Tk):
         """The shared attention scratch as call ``key``'s statistics [B, H, Tq, 2] (bf16) or scores [B, H, Tq, Tk] (fp32)."""
         flat = self.ws["att_flat"]
@@ -1008,8 +989,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if not 1 <= S <= cfg.max_target_positions:
             raise ValueError("target length exceeds max_target_positions")
         inf = self._infer_prepare(B, features.shape[2])
-        saved = self._infer_begin(inf)
-        try:
+        with self._inference(inf):
             ws, d, T = self.ws, cfg.d_model, inf["T"]
             lab = ws["labels"][:B * S].view(B, S)
             lab.copy_(shifted)
@@ -1027,8 +1007,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
                       "encoder_last_hidden_state": enc_out.view(B, T, d).clone()}
             if capture is not None:
                 result.update(capture.results())
-        finally:
-            self._infer_end(saved)
         return result
 
     @torch.no_grad()
@@ -1077,8 +1055,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
         host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
         events = [torch.cuda.Event(), torch.cuda.Event()]
-        saved = self._infer_begin(inf)
-        try:
+        with self._inference(inf):
             ws, d, T = self.ws, cfg.d_model, inf["T"]
             ids[:, 0] = cfg.decoder_start_token_id
             enc_out = self._encode_infer(features, inf)
@@ -1106,8 +1083,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 return int(host[t])
 
             n = greedy_loop(max_length, B, step, read_eos if eos >= 0 else None)
-        finally:
-            self._infer_end(saved)
         torch.cuda.current_stream(dev).synchronize()
         return ids[:, :1 + n].clone()
 
@@ -1137,8 +1112,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
             counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
             host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
             events = [torch.cuda.Event(), torch.cuda.Event()]
-            saved = self._infer_begin(inf)
-            try:
+            with self._inference(inf):
                 ws, d, T = self.ws, cfg.d_model, inf["T"]
                 enc_out = self._encode_infer(features, inf)
                 self._cross_kv_infer(enc_out)
@@ -1166,8 +1140,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
                     return int(host[t])
 
                 n = greedy_loop(max_length, B, step, read_finished if eos >= 0 else None)
-            finally:
-                self._infer_end(saved)
             torch.cuda.current_stream(dev).synchronize()
         seq = ids[:, :1 + n].clone()
         if not return_dict:
@@ -1208,15 +1180,12 @@ class WhisperForConditionalGeneration(KernelBlocks):
         host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
         events = [torch.cuda.Event(), torch.cuda.Event()]
         len_pow = lambda n: float(np.float32(float(n) ** length_penalty))  # noqa: E731
-        saved = self._infer_begin(inf)
-        try:
+        with self._inference(inf):
             ws, d, T = self.ws, cfg.d_model, inf["T"]
             enc_out = self._encode_infer(features, inf)
             self._cross_kv_infer(enc_out)
-            if cfg.decoder_layers:  # item b's k|v rows [b*T, (b+1)*T) -> the row blocks of b*K .. b*K + K - 1, from the back
-                kv = ws["kvc_all"].view(BK, T, -1)
-                for b in range(B - 1, -1, -1):
-                    kv[b * K + (1 if b == 0 else 0):(b + 1) * K].copy_(kv[b:b + 1].expand(K - (1 if b == 0 else 0), -1, -1))
+            if cfg.decoder_layers:
+                _repeat_rows_per_item(ws["kvc_all"].view(BK, T, -1), B, K)
             lab_flat = ws["labels"]
             wl, ldw = self.W("lm_head.kernel")
             gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
@@ -1242,8 +1211,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
             n = greedy_loop(max_length, B, step, read_done if eos >= 0 else None)
             ops.beam_step(None, None, N, B, K, sums, prefix[(n + 1) & 1], None, L1, n, eos, len_pow(n), early_stopping,
                           pool_ids, pool_scores, pool_len, pool_cnt, done, n_done, finalize=True)
-        finally:
-            self._infer_end(saved)
         lengths = pool_len[:, :R].reshape(B * R)
         n_out = int(lengths.max())
         seq = pool_ids[:, :R, :1 + n_out].reshape(B * R, 1 + n_out)
@@ -1335,8 +1302,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         M = B * S
         inf = self._infer_prepare(B, features.shape[2])
         self._score_workspace(inf, M, min(nc, self.arena.v_pad))
-        saved = self._infer_begin(inf)
-        try:
+        with self._inference(inf):
             ws, T = self.ws, inf["T"]
             lab = ws["labels"][:M].view(B, S)
             lab.copy_(labels)
@@ -1349,8 +1315,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
             _, logprob, argmax = self._lm_head_fold(xn, M, nc)
             lp = logprob.view(B, S)[:, :-1].clone()
             hit = (argmax.view(B, S)[:, :-1] == targets[:, :-1])
-        finally:
-            self._infer_end(saved)
         lp64, hit64 = lp.double().cpu(), hit.double().cpu()
         w64 = torch.ones(B, S - 1, dtype=torch.float64) if wgt is None else wgt.cpu()
         loss_sum, n_correct, n_tokens = float(-(w64 * lp64).sum()), float((w64 * hit64).sum()), float(w64.sum())
@@ -1410,15 +1374,12 @@ class WhisperForConditionalGeneration(KernelBlocks):
         have = inf["ws"].get("score_h")
         if have is None or have.numel() < M * d:
             inf["ws"]["score_h"] = torch.empty(M * d, dtype=self.dtype, device=dev)
-        saved = self._infer_begin(inf)
-        try:
+        with self._inference(inf):
             ws, T = self.ws, inf["T"]
             enc_out = self._encode_infer(features, inf)
             self._cross_kv_infer(enc_out)
-            if cfg.decoder_layers and R > 1:  # item b's k|v rows -> the row blocks of b*R .. b*R + R - 1, from the back (as beam search)
-                kv = ws["kvc_all"].view(N, T, -1)
-                for b in range(B - 1, -1, -1):
-                    kv[b * R + (1 if b == 0 else 0):(b + 1) * R].copy_(kv[b:b + 1].expand(R - (1 if b == 0 else 0), -1, -1))
+            if cfg.decoder_layers and R > 1:  # (as beam search)
+                _repeat_rows_per_item(ws["kvc_all"].view(N, T, -1), B, R)
             ws["lp_targets"][:M].copy_(targets.view(-1))
             lab_flat, hs = ws["labels"], ws["score_h"][:M * d].view(n_eff, N, d)
             for t in range(1, n_eff + 1):
@@ -1431,8 +1392,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
             self._ln_fwd(hs.view(M, d), "decoder.layer_norm", xn, "ln")
             _, logprob, _ = self._lm_head_fold(xn, M, nc)
             tok_lp[:, :n_eff] = logprob.view(n_eff, N).t()
-        finally:
-            self._infer_end(saved)
         return {"token_logprobs": tok_lp, "sequences_logprob": tok_lp.sum(dim=1)}
 
 

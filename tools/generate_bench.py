@@ -99,11 +99,8 @@ def main():
     inf = model._infer_prepare(B, 3000, K)
 
     def encode():
-        saved = model._infer_begin(inf)
-        try:
+        with model._inference(inf):
             model._cross_kv_infer(model._encode_infer(feats_d, inf))
-        finally:
-            model._infer_end(saved)
     enc_ms = timed_us(encode, iters=10, warm=2) / 1e3
     model.generate(feats_d, max_length=4, eos_token_id=-1, **beam)  # warm-up: workspace, kernels
     torch.cuda.synchronize()
