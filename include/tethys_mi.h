@@ -72,8 +72,15 @@ int tmi_set_deterministic(int on);
  * workspace (optional scratch in device memory, contents irrelevant, owned by the call while it
  * runs on its stream; TMI_GEMM_WORKSPACE_MIN bytes always suffice): when given, a library-chosen
  * split (splitk == 0) of a long reduction is reduced WITHOUT atomics — every split runs the epilogue
- * into its own fp32 slab there and a streaming pass sums the slabs into C, so C needs no zeroing
- * and fp32 atomics (~0.5 TB/s on MI355X) leave the path.
+ * into its own fp32 slab there and a streaming pass sums the slabs into C, so fp32 atomics (~0.5 TB/s on
+ * MI355X) leave the path and that launch does not read C.  Which launches go through the slabs is the library's choice
+ * (long reductions on the fast kernels; short ones, and every split of the generic kernel of csrc/gemm.hip - operands that
+ * miss the fast kernels' alignment, TMI_GEMM_GENERIC=1 - still use atomics), so a caller of splitk == 0 without
+ * `accumulate` pre-zeroes C whether it passes a workspace or not: the step does (tests/test_gemm_forced_gpu.py runs the
+ * same launches on every kernel and found the generic kernel summing into whatever C held).
+ * Operand padding: a k-strided operand (row stride >= round_up(cols, 8)) is read in whole 16-byte chunks, and the padding
+ * columns cols .. round_up(cols, 8) - 1 may hold anything, NaN included - they only reach accumulator rows / columns that are
+ * never stored (tests/test_gemm_forms_gpu.py poisons them).
  * in_dtype: type of A and B; out_dtype: type of C, aux_*, resid.  Valid pairs:
  * (F32,F32), (BF16,BF16), (BF16,F32).  fp32 inputs use the exact-fp32 MFMA
  * (v_mfma_f32_32x32x2_f32); bf16 inputs use v_mfma_f32_32x32x16_bf16.
@@ -105,6 +112,21 @@ typedef struct tmi_gemm_desc {
   int64_t nbatch2, a_sb2, b_sb2, c_sb2;
 } tmi_gemm_desc;
 int tmi_gemm(const tmi_gemm_desc* d, void* stream);
+/* Diagnostic, host only: which kernel the last tmi_gemm launched from the calling thread ran on (0: none yet) - the
+ * numbering of the TMI_GEMM_CFG switch (csrc/gemm_fast.hip: 4, 5, 6, 12, 13, 15, 16 the bf16 tiles, 10 / 14 the eight-phase
+ * kernel with 256- / 192-row tiles), TMI_GEMM_KERNEL_F32 the fp32-operand kernel, TMI_GEMM_KERNEL_GENERIC the kernel of
+ * csrc/gemm.hip.  *nsplit: the number of K ranges (1 = no split); *flags: TMI_GEMM_PATH_* bits.  Either may be NULL.
+ * The record is written just before the launch; the tests assert it, so that a dispatch threshold that moves shows up as
+ * a failed expectation instead of as lost coverage. */
+#define TMI_GEMM_KERNEL_GENERIC 1
+#define TMI_GEMM_KERNEL_F32 32
+#define TMI_GEMM_PATH_PERSISTENT 1   /* eight-phase kernel, 256 workgroups walking the tile slots */
+#define TMI_GEMM_PATH_ATOMIC 2       /* split-K summed with fp32 atomics into C */
+#define TMI_GEMM_PATH_SLABS 4        /* split-K through workspace slabs and the reduce pass */
+#define TMI_GEMM_PATH_XCD_GROUPS 8   /* the 2 / 4 / 8 K ranges dealt over groups of XCDs */
+#define TMI_GEMM_PATH_XCD_DEAL 16    /* eight-phase kernel, 16 / 32 K ranges, two / four per XCD */
+#define TMI_GEMM_PATH_WIDE 32        /* 16-byte epilogue accesses (clear: element by element) */
+int tmi_gemm_last_path(int32_t* nsplit, int32_t* flags);
 
 /* ------------------------------------------------------------------------------------
  * LayerNorm over the last axis of x[rows, C].  Replaces

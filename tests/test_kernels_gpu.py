@@ -41,6 +41,41 @@ def rnd(shape, dtype, dev, seed, scale=1.0):
     return x.to(dev)
 
 
+def gemm_path():
+    """(kernel, split count, flags) of the last tmi_gemm of this thread (tmi_gemm_last_path): the tests that are named after a
+    path assert that they are still on it, so that a dispatch threshold that moves fails here instead of silently taking the
+    shape off its kernel.  Kernels in the TMI_GEMM_CFG numbering: 4 Tile128x128, 5 Tile256x256, 6 Tile64Waves2, 12
+    Tile64Waves4, 13 Tile64Waves4Ring4, 15 Tile64KGroups2Ring4, 16 Tile64KGroups2Ring2, 10 / 14 eight-phase with 256- /
+    192-row tiles."""
+    import ctypes
+    from tethys_speech_amd import _lib
+    ns, fl = ctypes.c_int32(0), ctypes.c_int32(0)
+    kern = _lib.lib().tmi_gemm_last_path(ctypes.byref(ns), ctypes.byref(fl))
+    path = (int(kern), int(ns.value), int(fl.value))
+    import os
+    _GEMM_PATHS.setdefault(os.environ.get("PYTEST_CURRENT_TEST", "?").split("::")[-1].split(" ")[0], []).append(path)
+    return path
+
+
+_GEMM_PATHS = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_gemm_paths():
+    """With TMI_GEMM_PATHS_DIR set (test-side), the paths gemm_path() saw go to a file for tools/gemm_path_report.py."""
+    yield
+    import json
+    import os
+    out = os.environ.get("TMI_GEMM_PATHS_DIR")
+    if out and _GEMM_PATHS:
+        os.makedirs(out, exist_ok=True)
+        with open(os.path.join(out, "gemm_paths_kernel_tests.json"), "w") as f:
+            json.dump(_GEMM_PATHS, f, indent=1, sort_keys=True)
+
+
+PERSISTENT, ATOMIC, SLABS, XCD_GROUPS, XCD_DEAL, WIDE = 1, 2, 4, 8, 16, 32   # TMI_GEMM_PATH_*
+
+
 # ----------------------------------------------------------------------------- GEMM
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("layout", ["nn", "nt", "tn"])
@@ -162,7 +197,11 @@ def test_gemm_kbatch_splitk(dev):
 @pytest.mark.parametrize("M,N,K", [(800, 768, 768), (333, 200, 448), (64, 64, 64), (130, 72, 1024), (800, 768, 576),
                                    # CFG 14 (257..512 tiles, K >= 1024: two workgroups per CU on 2-stage rings): Whisper-large's
                                    # decoder shapes, an odd trip count (K = 1088: 17 tiles) with ragged edges
-                                   (800, 1280, 1280), (800, 1280, 5120), (790, 1300, 1088)])
+                                   (800, 1280, 1280), (800, 1280, 5120), (790, 1300, 1088),
+                                   # (N = 1300 is no multiple of 8: with the weights k-strided, rows 1300 apart, that launch
+                                   # is not the fast kernels' at all, only its k-contiguous form is - N = 1304 keeps the odd
+                                   # trip count and the ragged edges (1304 = 20 * 64 + 24) and runs both layouts on CFG 16)
+                                   (790, 1304, 1088)])
 def test_gemm_k_groups_inside_the_workgroup(dev, M, N, K):
     """Grids of at most one 64x64 tile per CU with K % 64 == 0 run two K-groups of four waves (gemm_fast.hip CFG 13; CFG 14 up
     to two tiles per CU when K >= 1024): group g
@@ -171,6 +210,11 @@ def test_gemm_k_groups_inside_the_workgroup(dev, M, N, K):
     and the qkv-dgrad form whose reduction runs over three K batches."""
     ops = _ops()
     bf = torch.bfloat16
+    # the kernel the rules give each shape: the K-groups on 4-stage rings (15) up to 256 tiles of 64 x 64, on 2-stage rings
+    # (16) up to 512 - both only from K_total = 512, so (333, 200, 448) and (64, 64, 64) run the plain four-wave tile (12)
+    # today; the single-K-tile case with an idle second group is run by forcing the kernels (tests/test_gemm_forced_gpu.py)
+    want = {(800, 768, 768): 15, (333, 200, 448): 12, (64, 64, 64): 12, (130, 72, 1024): 15, (800, 768, 576): 15,
+            (800, 1280, 1280): 16, (800, 1280, 5120): 16, (790, 1300, 1088): 16, (790, 1304, 1088): 16}[(M, N, K)]
     A = rnd((M, K), bf, dev, 41)
     W = rnd((K, N), bf, dev, 42, 0.1)
     bias = rnd((N,), torch.float32, dev, 43)
@@ -181,12 +225,16 @@ def test_gemm_k_groups_inside_the_workgroup(dev, M, N, K):
         Cm = torch.full((M, N), float("nan"), dtype=bf, device=dev)
         U = torch.full((M, N), float("nan"), dtype=bf, device=dev)
         ops.gemm(A, Bm, Cm, M, N, K, K, 1, bsk, bsn, N, bias=bias, act=1, aux_out=U, resid=R, r_ld=N)
+        # (rows of C that are not whole 16-byte chunks apart, N = 1300: the element epilogue; a k-strided B with such rows: not
+        # the fast kernels' at all, the generic kernel of gemm.hip)
+        assert gemm_path() == ((1, 1, 0) if bsn == 1 and bsk % 8 else (want, 1, WIDE if N % 8 == 0 else 0))
         assert rel_err(U, pre) <= 1.5e-2 and rel_err(Cm, ref) <= 1.5e-2
     if K % 192 == 0:  # dX = sum_j dY[:, j-th block] @ W_j^T, W_j = three [H, H] kernels side by side (W:89-92's q / k / v)
         H = K // 3
         Wq = rnd((3, H, N), bf, dev, 45, 0.1)           # [j][k][n]
         Cm = torch.empty((M, N), dtype=bf, device=dev)
         ops.gemm(A, Wq, Cm, M, N, H, K, 1, N, 1, N, kbatch=3, a_skb=H, b_skb=H * N)
+        assert gemm_path() == (15, 1, WIDE)    # (K_total = K >= 512 over three K batches)
         ref3 = sum(A[:, j * H:(j + 1) * H].double() @ Wq[j].double() for j in range(3))
         assert rel_err(Cm, ref3) <= 1.5e-2
 
@@ -211,6 +259,7 @@ def test_gemm_eight_phase_paths(dev, M, N, K, b_kn):
     resid = rnd((M, N), bf, dev, 14)
     pre = A.double() @ Bm.double() + bias.double()
     Cm = torch.empty((M, N), dtype=bf, device=dev)
+    want = 10 if (M, N) in ((8192, 2048), (2048, 6144)) else 14     # eight-phase kernel, 256- / 192-row tiles
     if b_kn:  # forward layout: B [K, N], k-strided
         U = torch.empty_like(Cm)
         ops.gemm(A, Bm, Cm, M, N, K, K, 1, N, 1, N, bias=bias, act=1, aux_out=U, resid=resid, r_ld=N)
@@ -221,6 +270,7 @@ def test_gemm_eight_phase_paths(dev, M, N, K, b_kn):
         Bt = Bm.t().contiguous()
         ops.gemm(A, Bt, Cm, M, N, K, K, 1, 1, K, N, bias=bias, resid=resid, r_ld=N)
         ref = pre + resid.double()
+    assert gemm_path() == (want, 1, WIDE)   # (at most 256 tile slots in all of these: the plain form)
     assert rel_err(Cm, ref) <= 1.5e-2
 
 
@@ -274,6 +324,7 @@ def test_gemm_lean_epilogue_classes_and_persistent_tiles(dev, cls, M, N, K, b_kn
         aux = torch.empty_like(Cm)
         kw, ref = dict(bias=bias, act=1, aux_out=aux, resid=X, r_ld=N), gelu(acc + bias.double()) + X.double()
     ops.gemm(A, Bop, Cm, M, N, K, K, 1, b_sk, b_sn, N, **kw)
+    assert gemm_path() == (14, 1, PERSISTENT | WIDE), cls    # all three shapes: 192-row tiles, more than 256 tile slots
     assert rel_err(Cm, ref) <= 1.5e-2, cls
     # row- and column-wise: no tile may be off (a skipped tile is an O(1) relative error of ITS rows only)
     err_r = ((Cm.double() - ref).norm(dim=1) / ref.norm(dim=1).clamp_min(1e-6)).max().item()
@@ -305,11 +356,18 @@ def test_gemm_lm_head_shapes(dev, R, d, Vp):
         err_c = ((got.double() - ref).norm(dim=0) / ref.norm(dim=0).clamp_min(1e-9)).max().item()
         assert err_r <= tol and err_c <= tol, (err_r, err_c)
 
+    # the paths the docstring names belong to the first shape; the other two are there for the dgrad's split counts
+    fwd, wg, dg = {(800, 768, 51904): ((10, 1, PERSISTENT | WIDE), (10, 1, WIDE), (14, 16, SLABS | XCD_DEAL | WIDE)),
+                   (520, 512, 16448): ((4, 1, WIDE), (4, 1, WIDE), (14, 8, SLABS | XCD_GROUPS | WIDE)),
+                   (520, 256, 66048): ((10, 1, PERSISTENT | WIDE), (4, 1, WIDE), (14, 32, SLABS | XCD_DEAL | WIDE))}[(R, d, Vp)]
     ops.gemm(x, W, logits, R, Vp, d, d, 1, Vp, 1, Vp)
+    assert gemm_path() == fwd
     check(logits, x.double() @ W.double(), 1e-2)               # bf16 output rounding
     ops.gemm(x, dlog, dW, d, Vp, R, 1, d, Vp, 1, Vp, splitk=0)
+    assert gemm_path() == wg
     check(dW, x.double().t() @ dlog.double(), 1e-5)            # fp32 accumulation of exact bf16 products
     ops.gemm(dlog, W, dx, R, d, Vp, Vp, 1, 1, Vp, d, splitk=0)
+    assert gemm_path() == dg
     check(dx, dlog.double() @ W.double().t(), 1e-5)
     again = torch.zeros_like(dx)
     ops.gemm(dlog, W, again, R, d, Vp, Vp, 1, 1, Vp, d, splitk=0)
@@ -325,29 +383,58 @@ def test_gemm_weight_gradient_paths(dev, T, Kin, N):
     X = rnd((T, Kin), bf, dev, 21)
     dY = rnd((T, N), bf, dev, 22)
     ref = X.double().t() @ dY.double()
-    dW = torch.full((Kin, N), 7.0, dtype=torch.float32, device=dev)   # slabs overwrite: no zeroing needed
+    # (these shapes go through workspace slabs under the rules - asserted below - and a slab launch does not read C, which the
+    # 7.0 shows; a caller cannot count on that form and zeroes C: tmi_gemm in tethys_mi.h)
+    dW = torch.full((Kin, N), 7.0, dtype=torch.float32, device=dev)
+    p8 = (T, Kin, N) in ((4128, 768, 2304), (4640, 1544, 1160))
     ops.gemm(X, dY, dW, Kin, N, T, 1, Kin, N, 1, N, splitk=0)
+    assert gemm_path() == ((10, 4, SLABS | XCD_GROUPS | WIDE) if p8 else (4, 8, SLABS | XCD_GROUPS | WIDE))
     assert rel_err(dW, ref) <= 1e-4
     # accumulate into an existing gradient
     base = rnd((Kin, N), torch.float32, dev, 23)
     dW2 = base.clone()
     ops.gemm(X, dY, dW2, Kin, N, T, 1, Kin, N, 1, N, splitk=0, accumulate=True)
+    # (the eight-phase kernel splits an accumulating launch too - its reduce pass adds C; the 128x128 kernel does not split it)
+    assert gemm_path() == ((10, 4, SLABS | XCD_GROUPS | WIDE) if p8 else (4, 1, WIDE))
     assert rel_err(dW2, ref + base.double()) <= 1e-4
 
 
 @pytest.mark.parametrize("M,N,K", [(800, 768, 3072), (792, 512, 1536), (100, 768, 2304)])
 def test_gemm_deep_ring_small_tiles(dev, M, N, K):
+    """Long reductions on at most one 64x64 tile per CU: the 4-stage rings.  With K % 64 == 0 the rules give these shapes
+    the two K-groups on 4-stage rings (15); the single-group ring (13) is left to reductions with a K tail
+    (test_gemm_deep_ring_with_k_tail)."""
     ops = _ops()
     bf = torch.bfloat16
     A = rnd((M, K), bf, dev, 31)
     W = rnd((K, N), bf, dev, 32, 0.1)
     Cm = torch.empty((M, N), dtype=bf, device=dev)
     ops.gemm(A, W, Cm, M, N, K, K, 1, N, 1, N)                       # k-strided B
+    assert gemm_path() == (15, 1, WIDE)
     ref = A.double() @ W.double()
     assert rel_err(Cm, ref) <= 1.5e-2
     Wt = W.t().contiguous()
     ops.gemm(A, Wt, Cm, M, N, K, K, 1, 1, K, N)                      # k-contiguous B
+    assert gemm_path() == (15, 1, WIDE)
     assert rel_err(Cm, ref) <= 1.5e-2
+
+
+def test_gemm_deep_ring_with_k_tail(dev):
+    """Tile64Waves4Ring4 (13) under the rules: at most 256 tiles of 64x64, K_total >= 1536 and K % 64 != 0 - which only a
+    launch with both operands k-strided can have (K = 1544: 24 K-tiles and a tail of 8)."""
+    ops = _ops()
+    bf = torch.bfloat16
+    M, N, K = 800, 768, 1544
+    At = rnd((K, M), bf, dev, 33)
+    W = rnd((K, N), bf, dev, 34, 0.1)
+    Cm = torch.full((M, N), float("nan"), dtype=bf, device=dev)
+    ops.gemm(At, W, Cm, M, N, K, 1, M, N, 1, N)
+    assert gemm_path() == (13, 1, WIDE)
+    ref = At.double().t() @ W.double()
+    assert rel_err(Cm, ref) <= 1.5e-2
+    err_r = ((Cm.double() - ref).norm(dim=1) / ref.norm(dim=1).clamp_min(1e-6)).max().item()
+    err_c = ((Cm.double() - ref).norm(dim=0) / ref.norm(dim=0).clamp_min(1e-6)).max().item()
+    assert err_r <= 3e-2 and err_c <= 3e-2, (err_r, err_c)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -77,6 +77,7 @@ SIGNATURES = {
     "tmi_memset2d_async": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i64, c_vp]),
     "tmi_memcpy_async": (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     "tmi_gemm": (c_i32, [C.POINTER(GemmDesc), c_vp]),
+    "tmi_gemm_last_path": (c_i32, [C.POINTER(c_i32), C.POINTER(c_i32)]),
     "tmi_layernorm_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_i32, c_vp]),
     "tmi_layernorm_dropout_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, C.c_uint64, c_i32, c_vp]),
     "tmi_layernorm_dropout_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, C.c_uint64, c_vp, c_i64, c_i32, c_vp]),

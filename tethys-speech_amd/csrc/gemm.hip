@@ -12,6 +12,8 @@
 #include "gemm_epilogue.h"
 #include <stdlib.h>
 
+void tmi_gemm_note_path(int kernel, int nsplit, int flags);  // record for tmi_gemm_last_path (below)
+
 namespace {
 
 constexpr int BM = 128, BN = 128;
@@ -218,6 +220,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams P) {
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// tmi_gemm_last_path: what the last launch of this thread chose (host bookkeeping only)
+thread_local int g_path_kernel = 0, g_path_nsplit = 0, g_path_flags = 0;
+
 int pick_mode(const void* p, int64_t s_row, int64_t s_k, int64_t sb, int64_t skb, int vec) {
   const bool strides_ok = (sb % vec == 0) && (skb % vec == 0) && al16(p);
   if (s_k == 1 && strides_ok && (s_row % vec == 0)) return MODE_KVEC;
@@ -248,6 +253,7 @@ int launch(const tmi_gemm_desc& d, hipStream_t stream) {
     splitk = want < 1 ? 1 : (int)want;
   }
   dim3 grid((unsigned)(P.tiles_m * P.tiles_n), (unsigned)splitk, (unsigned)(d.nbatch * (d.nbatch2 > 1 ? d.nbatch2 : 1)));
+  tmi_gemm_note_path(TMI_GEMM_KERNEL_GENERIC, splitk, splitk > 1 ? TMI_GEMM_PATH_ATOMIC : 0);
   hipLaunchKernelGGL((gemm_kernel<T, TC>), grid, dim3(256), 2 * TILE_BYTES, stream, P);
   return tmi_check_launch("tmi_gemm");
 }
@@ -255,6 +261,17 @@ int launch(const tmi_gemm_desc& d, hipStream_t stream) {
 }  // namespace
 
 int tmi_gemm_fast_try(const tmi_gemm_desc& d, hipStream_t stream, int* rc);  // gemm_fast.hip
+
+void tmi_gemm_note_path(int kernel, int nsplit, int flags) {
+  g_path_kernel = kernel;
+  g_path_nsplit = nsplit;
+  g_path_flags = flags;
+}
+extern "C" int tmi_gemm_last_path(int32_t* nsplit, int32_t* flags) {
+  if (nsplit) *nsplit = g_path_nsplit;
+  if (flags) *flags = g_path_flags;
+  return g_path_kernel;
+}
 
 static bool fast_disabled() {
   static const bool off = [] {

@@ -28,6 +28,8 @@
 #include <stdlib.h>
 #include <type_traits>
 
+void tmi_gemm_note_path(int kernel, int nsplit, int flags);  // gemm.hip: the record behind tmi_gemm_last_path
+
 namespace {
 
 constexpr int FT_BYTES = 16384;  // one operand tile
@@ -606,6 +608,17 @@ struct Tile64KGroups2Ring4 { static constexpr int BM = 64, BN = 64, WM = 32, WN 
 // where the 128 KiB of Tile64KGroups2Ring4 would run a second, nearly empty round (Whisper-large's decoder: [800, 1280] =
 // 260 tiles).
 struct Tile64KGroups2Ring2 { static constexpr int BM = 64, BN = 64, WM = 32, WN = 32, NSTAGE = 2, KG = 2; };
+
+// The TMI_GEMM_CFG number of a tile (launch_fast), as tmi_gemm_last_path reports it.
+template <typename K> constexpr int tile_cfg_id() {
+  if (std::is_same<K, Tile128x128>::value) return 4;
+  if (std::is_same<K, Tile256x256>::value) return 5;
+  if (std::is_same<K, Tile64Waves2>::value) return 6;
+  if (std::is_same<K, Tile64Waves4>::value) return 12;
+  if (std::is_same<K, Tile64Waves4Ring4>::value) return 13;
+  if (std::is_same<K, Tile64KGroups2Ring4>::value) return 15;
+  return 16;  // Tile64KGroups2Ring2
+}
 
 // Split-K through the workspace: every split runs the ordinary (non-atomic) epilogue into its own
 // fp32 slab [nbatch][M][N] of the caller's workspace, and splitk_reduce_kernel, launched right
@@ -1377,6 +1390,9 @@ int launch_cfg(const tmi_gemm_desc& d, hipStream_t stream) {
   const int nsplit = splitk;
   if (xsplit_over_groups(P, splitk)) splitk = 1;  // (grid.y)
   dim3 grid((unsigned)(8 * P.ptm * P.ptn), (unsigned)splitk, (unsigned)d.nbatch);
+  tmi_gemm_note_path(tile_cfg_id<K>(), nsplit,
+                     (ws_split ? TMI_GEMM_PATH_SLABS : nsplit > 1 ? TMI_GEMM_PATH_ATOMIC : 0) | (P.xsplit ? TMI_GEMM_PATH_XCD_GROUPS : 0) |
+                         ((ws_split ? d.N % 4 == 0 : P.wide != 0) ? TMI_GEMM_PATH_WIDE : 0));
   if (ws_split) return launch_with_slabs(P, nsplit, stream, [&](const FastParams& Q) {
     hipLaunchKernelGGL(kern, grid, dim3(NW * 64 * K::KG), LDS_BYTES, stream, Q);
   });
@@ -1439,6 +1455,7 @@ int launch_p8(const tmi_gemm_desc& d, hipStream_t stream) {
       static const hipError_t attr_p = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_p8_kernel<TC, A_KS, B_KS, BM, true>),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_P);
       if (attr_p == hipSuccess) {
+        tmi_gemm_note_path(BM == 192 ? 14 : 10, 1, TMI_GEMM_PATH_PERSISTENT | (P.wide ? TMI_GEMM_PATH_WIDE : 0));
         hipLaunchKernelGGL((gemm_p8_kernel<TC, A_KS, B_KS, BM, true>), dim3(256), dim3(512), LDS_P, stream, P);
         return tmi_check_launch("tmi_gemm(p8 persistent)");
       }
@@ -1456,6 +1473,9 @@ int launch_p8(const tmi_gemm_desc& d, hipStream_t stream) {
     P.slots = 8 * P.ptm * P.ptn;
     grid = dim3((unsigned)P.slots, 1u, 1u);
   }
+  tmi_gemm_note_path(BM == 192 ? 14 : 10, splitk,
+                     (splitk > 1 ? TMI_GEMM_PATH_SLABS : 0) | (P.xsplit >= 16 ? TMI_GEMM_PATH_XCD_DEAL : P.xsplit ? TMI_GEMM_PATH_XCD_GROUPS : 0) |
+                         ((splitk > 1 ? d.N % 4 == 0 : P.wide != 0) ? TMI_GEMM_PATH_WIDE : 0));
   if (splitk > 1) return launch_with_slabs(P, splitk, stream, [&](const FastParams& Q) {
     hipLaunchKernelGGL(kern, grid, dim3(512), 2 * P8_BUF, stream, Q);
   });
@@ -1770,6 +1790,9 @@ int launch_f32(const tmi_gemm_desc& d, hipStream_t stream) {
     splitk = want < 1 ? 1 : (int)want;
   }
   dim3 grid((unsigned)(8 * P.ptm * P.ptn), (unsigned)splitk, (unsigned)(d.nbatch * (d.nbatch2 > 1 ? d.nbatch2 : 1)));
+  tmi_gemm_note_path(TMI_GEMM_KERNEL_F32, splitk,
+                     (ws_split ? TMI_GEMM_PATH_SLABS : splitk > 1 ? TMI_GEMM_PATH_ATOMIC : 0) |
+                         ((ws_split ? d.N % 4 == 0 : P.wide != 0) ? TMI_GEMM_PATH_WIDE : 0));
   if (ws_split) return launch_with_slabs(P, splitk, stream, [&](const FastParams& Q) {
     hipLaunchKernelGGL(kern, grid, dim3(256), 65536, stream, Q);
   });
