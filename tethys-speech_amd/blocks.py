@@ -515,6 +515,12 @@ class KernelBlocks:
         p = self._drop_p if p is None else p
         return {"dropout_p": p, "dropout_seed": self._site_seed(site)} if p > 0.0 else {}
 
+    @staticmethod
+    def _attn_mat(t, off, T):
+        """(tensor, element offset, batch stride, token stride) of ``T`` tokens per sample, one row of ``t`` per token: the
+        operand form of ops.attn_fwd / attn_bwd / attn_probs."""
+        return (t, off, T * t.stride(0), t.stride(0))
+
     def _attn_fwd(self, key, q, k, v, ctx2d, B, H, Tq, Tk, mask, score_scale=1.0, site=None, key_bias=None):
         """score_scale multiplies q·kᵀ (V:349); Whisper pre-scales q instead (W:141) and passes 1.
         ``key_bias`` (inference, V:352-355): fp32 [B, Tk] added to the scores of every head and query - mask_mode 2 of the
@@ -524,15 +530,13 @@ class KernelBlocks:
         if key_bias is not None and (mask != 0 or site is not None):
             raise ValueError("_attn_fwd: key_bias goes with mask 0 and no dropout site")
         if self.precision == "bf16":
+            m = self._attn_mat
+            mats = (m(qt, qo, Tq), m(kt, ko, Tk), m(vt, vo, Tk), m(ctx2d, 0, Tq))  # (ctx2d: one row of ``hidden`` per token)
             if key_bias is not None:
-                ops.attn_fwd((qt, qo, Tq * qt.stride(0), qt.stride(0)), (kt, ko, Tk * kt.stride(0), kt.stride(0)),
-                             (vt, vo, Tk * vt.stride(0), vt.stride(0)), (ctx2d, 0, Tq * d, d),
-                             self.ws[key], B, H, Tq, Tk, 2, score_scale=score_scale, key_bias=key_bias)
+                ops.attn_fwd(*mats, self.ws[key], B, H, Tq, Tk, 2, score_scale=score_scale, key_bias=key_bias)
                 return
             dp = self._drop_attn_p if site is not None else 0.0
-            ops.attn_fwd((qt, qo, Tq * qt.stride(0), qt.stride(0)), (kt, ko, Tk * kt.stride(0), kt.stride(0)),
-                         (vt, vo, Tk * vt.stride(0), vt.stride(0)), (ctx2d, 0, Tq * d, d),
-                         self.ws[key], B, H, Tq, Tk, mask, score_scale=score_scale,
+            ops.attn_fwd(*mats, self.ws[key], B, H, Tq, Tk, mask, score_scale=score_scale,
                          dropout_p=dp, dropout_seed=self._site_seed(site) if dp > 0 else 0,
                          drop_mask=self._attn_dropmask(key, B, H, Tq, Tk) if dp > 0 else None)
             return
@@ -562,7 +566,7 @@ class KernelBlocks:
         if self.precision == "bf16":
             (qt, qo), (kt, ko) = q, k
             out = torch.empty(B, H, Tq, Tk, dtype=dtype, device=self.device)
-            ops.attn_probs((qt, qo, Tq * qt.stride(0), qt.stride(0)), (kt, ko, Tk * kt.stride(0), kt.stride(0)), self.ws[key],
+            ops.attn_probs(self._attn_mat(qt, qo, Tq), self._attn_mat(kt, ko, Tk), self.ws[key],
                            out, B, H, Tq, Tk, 2 if key_bias is not None else mask, score_scale=score_scale, key_bias=key_bias)
             return out
         P = self.ws[key].view(B, H, Tq, Tk)
@@ -589,8 +593,7 @@ class KernelBlocks:
         (dqt, dqo), (dkt, dko), (dvt, dvo) = dq, dk, dv
         self._guard_write(dqt, dkt, dvt)
         if self.precision == "bf16":
-            def m(t, off, T):
-                return (t, off, T * t.stride(0), t.stride(0))
+            m = self._attn_mat
             split = dkv_on_side and self._side is not None
             # (a pass on another stream reads delta later: its own buffer, not the one every attention backward shares)
             delta = self._buf(key + ".delta", (B, H, Tq), torch.float32) if split else self.ws["delta"]

@@ -37,7 +37,6 @@
 #include <type_traits>
 #include <utility>
 #include <stddef.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace {
@@ -148,6 +147,14 @@ __device__ __forceinline__ void stage_tile(char* img, const LaneSrc& L, int row0
   } else {
     stage_img(img, L.base, L.st, row0, L.T, wave, lane);
   }
+}
+
+// first element of (batch b, head) of an operand: [B][T][.. H x 64 ..] with batch stride sb elements
+__device__ __forceinline__ const bf16_t* head_of(const void* p, int64_t sb, int64_t b, int head) {
+  return reinterpret_cast<const bf16_t*>(p) + b * sb + head * HD;
+}
+__device__ __forceinline__ bf16_t* head_of(void* p, int64_t sb, int64_t b, int head) {
+  return reinterpret_cast<bf16_t*>(p) + b * sb + head * HD;
 }
 
 // owner vectors: lane (c, h) holds Own[o][16kk + 8h .. +7], kk = 0..3
@@ -345,24 +352,23 @@ struct AttnP {
   const float* kbias;
   int64_t kb_sb;
 };
-inline void set_desc(AttnP& P, const tmi_attn_desc& d) {
-  memcpy(&P.d, &d, sizeof(AttnD));
-  P.kbias = d.key_bias;
-  P.kb_sb = d.kb_sb;
+
+// the stored mask's column of the lane (query q, lane half h): its word of key tile t is at [t * 2 * P.TQP]
+__device__ __forceinline__ uint32_t* mask_column(const AttnP& P, int64_t b, int head, int h, int q) {
+  return P.dmask + (((int64_t)(b * P.d.H + head) * P.NT) * 2 + h) * P.TQP + (q & ~63) + mask_pos(q & 63);
 }
 
-// ABL (diagnostics, TMI_ATTN_ABL): 1 = no softmax arithmetic (p = s), 2 = no second product, 3 = no staging after the
-// prologue (every tile re-reads tile 0's images), 4 = no first product
 // BIAS (mask_mode 2): every score gets the per-(batch, key) term P.kbias added, so every tile takes the edge path.  The 64
 // terms of a key tile are fetched one tile ahead by the first wave (one register per lane), converted to log2 units and
 // handed to the other waves through LDS ([2][64] floats behind the images) at the tile seam, like the images themselves.
-template <bool DROP, int OCC, int ABL = 0, bool BIAS = false>
+template <bool DROP, int OCC, bool BIAS = false>
 __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K img | V img] (BIAS: then [2][64] floats)
   const AttnD& d = P.d;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 31, h = lane >> 5;
+  // (block_coords below, inline: calling the helper here changes the instruction schedule of all three forward kernels)
   int bx_, head_;
   int64_t b_;
   if (P.gx > 0) {
@@ -383,9 +389,9 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   const int Tq = (int)d.Tq, Tk = (int)d.Tk;
   const bool causal = d.mask_mode == 1;
   const float c2 = P.c2;
-  const bf16_t* qb = reinterpret_cast<const bf16_t*>(d.q) + b * d.q_sb + head * HD;
-  const bf16_t* kb = reinterpret_cast<const bf16_t*>(d.k) + b * d.k_sb + head * HD;
-  const bf16_t* vb = reinterpret_cast<const bf16_t*>(d.v) + b * d.v_sb + head * HD;
+  const bf16_t* qb = head_of(d.q, d.q_sb, b, head);
+  const bf16_t* kb = head_of(d.k, d.k_sb, b, head);
+  const bf16_t* vb = head_of(d.v, d.v_sb, b, head);
 
   bf16x8 qf[4];
   load_owner(qf, qb, d.q_st, q, Tq, h);
@@ -399,7 +405,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   const tmi_rowkey qrk = tmi_row_key(skey, (uint32_t)q);  // the mask row of this lane's query: one avalanche per kernel
   // this lane's column of the stored mask: word (b*H + head, tile, h, q); q < TQP for every lane of the grid
   uint32_t* mrow = nullptr;
-  if constexpr (DROP) mrow = P.dmask + (((int64_t)(b * d.H + head) * P.NT) * 2 + h) * P.TQP + (q & ~63) + mask_pos(q & 63);
+  if constexpr (DROP) mrow = mask_column(P, b, head, h, q);
 
   const LaneSrc Ks = lane_src(kb, d.k_st, Tk, wave, lane);
   const LaneSrc Vs = lane_src(vb, d.v_st, Tk, wave, lane);
@@ -423,7 +429,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
     constexpr bool edge = decltype(edge_tag)::value;
     const char* Kimg = smem + cur * 2 * IMG;
     const char* Vimg = Kimg + IMG;
-    if (ABL != 3 && tile + 1 < ntiles) {
+    if (tile + 1 < ntiles) {
       char* nx = smem + (cur ^ 1) * 2 * IMG;
       stage_tile(nx, Ks, (tile + 1) * TROWS, wave, lane);
       stage_tile(nx + IMG, Vs, (tile + 1) * TROWS, wave, lane);
@@ -433,20 +439,11 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
       if (tile + 1 < ntiles && threadIdx.x < TROWS) kbnext = kbrow[min((tile + 1) * TROWS + (int)threadIdx.x, Tk - 1)];
     }
     f32x16 s[2];
-    if constexpr (ABL == 4) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { s[0][e] = (float)(tile + e) * 0.01f; s[1][e] = (float)(tile - e) * 0.01f; }
-      asm volatile("" : "+v"(s[0]), "+v"(s[1]));
-    } else {
     s[0] = first_product(Kimg, 0, qf, c, h);   // s[key][q], keys 0..31 of the tile
     s[1] = first_product(Kimg, 32, qf, c, h);  // keys 32..63
-    }
     const int key0 = tile * TROWS;
     float rs = 0.f;
-    if constexpr (ABL == 1) {
-      asm volatile("" : "+v"(s[0]), "+v"(s[1]));
-      rs = 1.f;
-    } else if constexpr (!edge) {
+    if constexpr (!edge) {
       // branch-free tile: maximum over the raw products (c2 > 0), lazy rescale
       float mx = max3(s[0][0], s[0][1], s[0][2]);
 #pragma unroll
@@ -551,12 +548,9 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
       mrow[(int64_t)tile * (2 * P.TQP)] = w;
       second_product_b(Vimg, 0, pb[0], o, lane);
       second_product_b(Vimg, 32, pb[1], o, lane);
-    } else
-    if constexpr (ABL == 2) {
-      asm volatile("" :: "v"(s[0]), "v"(s[1]));
     } else {
-    second_product(Vimg, 0, s[0], o, lane);
-    second_product(Vimg, 32, s[1], o, lane);
+      second_product(Vimg, 0, s[0], o, lane);
+      second_product(Vimg, 32, s[1], o, lane);
     }
     // (with dropout the mask word is the youngest vector-memory operation of the tile: the seam waits for the DMA in front
     // of it, the store's acknowledgement may arrive during the next tile)
@@ -567,14 +561,14 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
     if constexpr (DROP) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (ABL != 3) cur ^= 1;
+    cur ^= 1;
   };
   const int nfast = (causal || BIAS) ? 0 : min(Tk / TROWS, ntiles);  // full, unmasked tiles first
   int tile = t0;
   for (; tile < nfast; ++tile) body(tile, std::false_type{});
   for (; tile < ntiles; ++tile) body(tile, std::true_type{});
   l += __shfl_xor(l, 32, 64);
-  if (ks > 1) {  // partial of this key range: un-normalised o, (m, l); attn_combine_fwd_kernel finishes
+  if (ks > 1) {  // partial of this key range: un-normalised o, (m, l); attn_combine_kernel<true> finishes
     if (q < Tq) {
       const int64_t row = (((int64_t)b * d.H + head) * ks + sp) * Tq + q;
       store_owner_f32(o, P.part + row * HD, h);
@@ -587,7 +581,7 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
     return;
   }
   const float inv = 1.0f / l;
-  bf16_t* ob = reinterpret_cast<bf16_t*>(d.o) + b * d.o_sb + head * HD;
+  bf16_t* ob = head_of(d.o, d.o_sb, b, head);
   store_owner(o, ob, d.o_st, q, Tq, h, DROP ? inv * P.keep_scale : inv);
   if (h == 0 && q < Tq) {
     float* st = d.stats + ((b * d.H + head) * Tq + q) * 2;
@@ -624,11 +618,11 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, c
   const int Tq = (int)d.Tq, Tk = (int)d.Tk;
   const bool causal = d.mask_mode == 1;
   const float c2 = P.c2;
-  const bf16_t* qb = reinterpret_cast<const bf16_t*>(d.q) + b * d.q_sb + head * HD;
-  const bf16_t* kb = reinterpret_cast<const bf16_t*>(d.k) + b * d.k_sb + head * HD;
-  const bf16_t* vb = reinterpret_cast<const bf16_t*>(d.v) + b * d.v_sb + head * HD;
-  const bf16_t* ob = reinterpret_cast<const bf16_t*>(d.o) + b * d.o_sb + head * HD;
-  const bf16_t* dob = reinterpret_cast<const bf16_t*>(d.d_o) + b * d.do_sb + head * HD;
+  const bf16_t* qb = head_of(d.q, d.q_sb, b, head);
+  const bf16_t* kb = head_of(d.k, d.k_sb, b, head);
+  const bf16_t* vb = head_of(d.v, d.v_sb, b, head);
+  const bf16_t* ob = head_of(d.o, d.o_sb, b, head);
+  const bf16_t* dob = head_of(d.d_o, d.do_sb, b, head);
 
   bf16x8 qf[4], dof[4];
   float delta = 0.f;
@@ -665,7 +659,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, c
   const uint32_t ks_bits = __float_as_uint(P.keep_scale);
   // the stored keep bits of this lane's scores: the word the forward lane of the same (query, lane half) wrote per key tile
   const uint32_t* mrow = nullptr;
-  if constexpr (DROP) mrow = P.dmask + (((int64_t)(b * d.H + head) * P.NT) * 2 + h) * P.TQP + (q & ~63) + mask_pos(q & 63);
+  if constexpr (DROP) mrow = mask_column(P, b, head, h, q);
 
   const LaneSrc Ks = lane_src(kb, d.k_st, Tk, wave, lane);
   const LaneSrc Vs = lane_src(vb, d.v_st, Tk, wave, lane);
@@ -726,11 +720,11 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, c
   int tile = t0;
   for (; tile < nfast; ++tile) body(tile, std::false_type{});
   for (; tile < ntiles; ++tile) body(tile, std::true_type{});
-  if (ks > 1) {  // partial dQ of this key range (unscaled); attn_combine_dq_kernel sums and scales
+  if (ks > 1) {  // partial dQ of this key range (unscaled); attn_combine_kernel<false> sums and scales
     if (q < Tq) store_owner_f32(dq, P.part + ((((int64_t)b * d.H + head) * ks + sp) * Tq + q) * HD, h);
     return;
   }
-  bf16_t* dqb = reinterpret_cast<bf16_t*>(d.dq) + b * d.dq_sb + head * HD;
+  bf16_t* dqb = head_of(d.dq, d.dq_sb, b, head);
   store_owner(dq, dqb, d.dq_st, q, Tq, h, P.dq_scale * P.sscale);
 }
 
@@ -768,11 +762,11 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
   const int Tq = (int)d.Tq, Tk = (int)d.Tk;
   const bool causal = d.mask_mode == 1;
   const float c2 = P.c2;
-  const bf16_t* qb = reinterpret_cast<const bf16_t*>(d.q) + b * d.q_sb + head * HD;
-  const bf16_t* kb = reinterpret_cast<const bf16_t*>(d.k) + b * d.k_sb + head * HD;
-  const bf16_t* vb = reinterpret_cast<const bf16_t*>(d.v) + b * d.v_sb + head * HD;
-  const bf16_t* dob = reinterpret_cast<const bf16_t*>(d.d_o) + b * d.do_sb + head * HD;
-  const bf16_t* ob = reinterpret_cast<const bf16_t*>(d.o) + b * d.o_sb + head * HD;
+  const bf16_t* qb = head_of(d.q, d.q_sb, b, head);
+  const bf16_t* kb = head_of(d.k, d.k_sb, b, head);
+  const bf16_t* vb = head_of(d.v, d.v_sb, b, head);
+  const bf16_t* dob = head_of(d.d_o, d.do_sb, b, head);
+  const bf16_t* ob = head_of(d.o, d.o_sb, b, head);
   const float* stats = d.stats + (b * d.H + head) * Tq * 2;
   const float* deltas = d.delta + (b * d.H + head) * Tq;
   float* rowc_base = reinterpret_cast<float*>(smem + 4 * IMG);
@@ -790,8 +784,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
   ZERO2(dv);
   // The wave's rows of the stored mask, as 64-bit scalars: pair (rbk, e) of query tile `tile` = words of rows
   // acc_row(e, 0) | acc_row(e, 1) of that 32-row half = the select mask of accumulator register e (scalar loads: the
-  // address is wave-uniform, the data is read-only here)
-  // acc_row(e, 1) of that 32-row half = the select mask of accumulator register e.  The 64 words of a tile are fetched by
+  // address is wave-uniform, the data is read-only here).  The 64 words of a tile are fetched by
   // four s_load_dwordx16 issued at the END of the previous tile, just before its vmcnt(0) + barrier (scalar loads share
   // lgkmcnt with the LDS reads and return out of order, so the first LDS wait after them drains them: the only place their
   // latency hides is a stretch without LDS waits, and the tile seam is one), and waited for right after the barrier; a
@@ -962,8 +955,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
   int tile = 0;
   for (; tile < nfast; ++tile) body(tile, std::false_type{});
   for (; tile < ntiles; ++tile) body(tile, std::true_type{});
-  bf16_t* dkb = reinterpret_cast<bf16_t*>(d.dk) + b * d.dk_sb + head * HD;
-  bf16_t* dvb = reinterpret_cast<bf16_t*>(d.dv) + b * d.dv_sb + head * HD;
+  bf16_t* dkb = head_of(d.dk, d.dk_sb, b, head);
+  bf16_t* dvb = head_of(d.dv, d.dv_sb, b, head);
   store_owner(dk, dkb, d.dk_st, key, Tk, h, DROP ? P.sscale * P.keep_scale : P.sscale);
   store_owner(dv, dvb, d.dv_st, key, Tk, h, DROP ? P.keep_scale : 1.0f);
 }
@@ -1012,8 +1005,8 @@ __global__ __launch_bounds__(256, 4) void attn_probs_kernel(const AttnP P, OT* _
   const int key = kblk * 128 + wave * 32 + c;
   const int Tq = (int)d.Tq, Tk = (int)d.Tk;
   const float c2 = P.c2;
-  const bf16_t* qb = reinterpret_cast<const bf16_t*>(d.q) + b * d.q_sb + head * HD;
-  const bf16_t* kb = reinterpret_cast<const bf16_t*>(d.k) + b * d.k_sb + head * HD;
+  const bf16_t* qb = head_of(d.q, d.q_sb, b, head);
+  const bf16_t* kb = head_of(d.k, d.k_sb, b, head);
   const float* stats = d.stats + (b * d.H + head) * Tq * 2;
   float* rowc_base = reinterpret_cast<float*>(smem + 2 * IMG);
 
@@ -1107,38 +1100,22 @@ __global__ __launch_bounds__(256, 4) void attn_probs_kernel(const AttnP P, OT* _
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool ok_mat(const void* p, int64_t sb, int64_t st) { return p && al16(p) && sb % 8 == 0 && st % 8 == 0; }
 
-#ifndef TMI_ATTN_DROP_OCC
-#define TMI_ATTN_DROP_OCC 2
-#endif
-#ifndef TMI_ATTN_DQ_DROP_OCC
-#define TMI_ATTN_DQ_DROP_OCC 2
-#endif
-// workgroups per CU of the dropout variants (the forward's generator and mask packing need registers: 3 per CU spills, and
-// measured 124.5 us against 122.9 at 2 per CU on the encoder layer; the dQ kernel spills at 3 per CU too)
-constexpr int DROP_OCC = TMI_ATTN_DROP_OCC, DQ_DROP_OCC = TMI_ATTN_DQ_DROP_OCC;
+// Workgroups per CU.  Forward and dQ: 3, but 2 with dropout (the forward's generator and mask packing need registers: 3 per
+// CU spills, and measured 124.5 us against 122.9 at 2 per CU on the encoder layer; the dQ kernel spills at 3 per CU too).
+// dK/dV: 2.  Every higher occupancy spills (DESIGN_HISTORY.md, profiles/r03_attention_occupancy.txt).
+constexpr int FWD_OCC = 3, DQ_OCC = 3, DROP_OCC = 2, DQ_DROP_OCC = 2, DKV_OCC = 2;
+constexpr int KSPLIT_MAX = 4;  // key ranges of the key split (measured: 4 ranges 9.03, 8 ranges 9.10, one chain 9.17 ms/step)
+constexpr size_t FWD_LDS = 4 * IMG, DKV_LDS = 4 * IMG + 2 * NCONST * 64 * sizeof(float);
 
 int64_t mask_tiles(int64_t Tk) { return (Tk + TROWS - 1) / TROWS; }
 int64_t mask_rows(int64_t Tq) { return (Tq + 127) / 128 * 128; }
 
-void set_dropout(AttnP& P) {
-  P.drop_thr = tmi_drop_thr(P.d.dropout_p);
-  P.keep_scale = tmi_keep_scale(P.drop_thr);
-  P.seed_lo = (uint32_t)P.d.dropout_seed;
-  P.seed_hi = (uint32_t)(P.d.dropout_seed >> 32);
-  P.tm1 = (((uint32_t)((int32_t)P.drop_thr - 32768 - 1)) & 0xffffu) * 0x10001u;
-  P.dmask = reinterpret_cast<uint32_t*>(P.d.drop_mask);
-  P.NT = (int)mask_tiles(P.d.Tk);
-  P.TQP = (int)mask_rows(P.d.Tq);
-}
-
 // key split of the forward / dQ passes: a single query tile against >= 8 key tiles with no causal mask, when the caller
-// gave a workspace (tmi_attn_workspace_bytes).  2..8 ranges, never an empty one.
+// gave a workspace (tmi_attn_workspace_bytes).  2..KSPLIT_MAX ranges, never an empty one.
 int pick_ksplit(const tmi_attn_desc& d) {
-  static const int off = [] { const char* e = getenv("TMI_ATTN_NO_KSPLIT"); return e ? atoi(e) : 0; }();
   const int64_t ntiles = (d.Tk + TROWS - 1) / TROWS;
-  if (off || d.mask_mode != 0 || d.Tq > 128 || ntiles < 8 || !d.workspace) return 1;
-  static const int maxks = [] { const char* e = getenv("TMI_ATTN_KSPLIT_MAX"); return e ? atoi(e) : 4; }();  // measured: 4 ranges 9.03, 8 ranges 9.10, one chain 9.17 ms/step
-  int ks = maxks < 1 ? 1 : (maxks > 8 ? 8 : maxks);
+  if (d.mask_mode != 0 || d.Tq > 128 || ntiles < 8 || !d.workspace) return 1;
+  int ks = KSPLIT_MAX;
   while (ks > 1) {
     const int64_t per = (ntiles + ks - 1) / ks;
     if ((ks - 1) * per < ntiles && d.B * d.H * ks <= 1024 &&
@@ -1149,17 +1126,53 @@ int pick_ksplit(const tmi_attn_desc& d) {
   return ks;
 }
 
+// The kernels' argument for one descriptor: every field set (gx and nq are zero until the launch that uses them sets them).
+AttnP make_params(const tmi_attn_desc& d, float dq_scale) {
+  AttnP P;
+  memset(&P, 0, sizeof(P));
+  memcpy(&P.d, &d, sizeof(AttnD));
+  P.kbias = d.key_bias;
+  P.kb_sb = d.kb_sb;
+  P.dq_scale = dq_scale;
+  P.sscale = d.score_scale != 0.f ? d.score_scale : 1.f;
+  P.c2 = P.sscale * LOG2E;
+  P.drop_thr = tmi_drop_thr(d.dropout_p);
+  P.keep_scale = tmi_keep_scale(P.drop_thr);
+  P.seed_lo = (uint32_t)d.dropout_seed;
+  P.seed_hi = (uint32_t)(d.dropout_seed >> 32);
+  P.tm1 = (((uint32_t)((int32_t)P.drop_thr - 32768 - 1)) & 0xffffu) * 0x10001u;
+  P.dmask = reinterpret_cast<uint32_t*>(d.drop_mask);
+  P.NT = (int)mask_tiles(d.Tk);
+  P.TQP = (int)mask_rows(d.Tq);
+  P.ksplit = pick_ksplit(d);
+  P.part = reinterpret_cast<float*>(d.workspace);
+  return P;
+}
+
 // launch grid of `gx` blocks per (batch, head): XCD-aware 1-D form when the pairs divide over the 8 XCDs and there is more
-// than one block per pair to share rows (TMI_ATTN_XCD=0 switches it off)
+// than one block per pair to share rows
 dim3 pick_grid(AttnP& P, unsigned gx) {
-  static const int on = [] { const char* e = getenv("TMI_ATTN_XCD"); return e ? atoi(e) : 1; }();
   const int64_t bh = P.d.B * P.d.H;
-  if (on && gx > 1 && bh % 8 == 0 && bh * gx < (1ll << 31)) {
+  if (gx > 1 && bh % 8 == 0 && bh * gx < (1ll << 31)) {
     P.gx = (int)gx;
     return dim3((unsigned)(bh * gx), 1, 1);
   }
   P.gx = 0;
   return dim3(gx, (unsigned)P.d.H, (unsigned)P.d.B);
+}
+
+using AttnKernel = void (*)(const AttnP);
+void launch(AttnKernel kernel, dim3 grid, size_t lds, hipStream_t s, const AttnP& P) {
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, P);
+}
+
+// fold of the key-split partials into `out` (forward: o and stats; dQ: dq, stats == nullptr)
+void launch_combine(const AttnP& P, void* out, int64_t o_sb, int64_t o_st, float* stats, float out_scale, hipStream_t s) {
+  const AttnD& d = P.d;
+  const int64_t rows = d.B * d.H * d.Tq;
+  hipLaunchKernelGGL((stats ? attn_combine_kernel<true> : attn_combine_kernel<false>), dim3((unsigned)((rows * 16 + 255) / 256)),
+                     dim3(256), 0, s, P.part, P.ksplit, d.B * d.H, (int)d.Tq, reinterpret_cast<bf16_t*>(out), o_sb, o_st,
+                     (int)d.H, stats, out_scale);
 }
 
 int check_common(const tmi_attn_desc& d) {
@@ -1192,55 +1205,14 @@ static int tmi_attn_fwd_impl(const tmi_attn_desc* dp, void* stream) {
     tmi_set_error("tmi_attn_fwd: bad argument (16-byte aligned bf16 operands, strides multiple of 8; dropout_p > 0 needs drop_mask of tmi_attn_dropmask_bytes; mask_mode 2 needs key_bias and dropout_p == 0)");
     return TMI_ERR_INVALID;
   }
-  AttnP P;
-  set_desc(P, *dp);
-  P.dq_scale = 1.f;
-  P.sscale = dp->score_scale != 0.f ? dp->score_scale : 1.f;
-  P.c2 = P.sscale * LOG2E;
-  set_dropout(P);
-  P.ksplit = pick_ksplit(*dp);
-  P.part = reinterpret_cast<float*>(dp->workspace);
-  dim3 grid = pick_grid(P, (unsigned)((dp->Tq + 127) / 128 * P.ksplit));
+  AttnP P = make_params(*dp, 1.f);
+  const dim3 grid = pick_grid(P, (unsigned)((dp->Tq + 127) / 128 * P.ksplit));
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-  // (workgroups per CU: 2 with dropout, 3 without - measured, tools/ab_attn.sh; the other occupancies (TMI_ATTN_FWD_OCC,
-  // ..._DQ_OCC, ..._DKV_OCC: they spill) and the ablation kernels are built with `make EXPERIMENTS=1` only)
-#ifdef TMI_ATTN_EXPERIMENTS
-  static const int focc = [] { const char* e = getenv("TMI_ATTN_FWD_OCC"); return e ? atoi(e) : 0; }();
-#else
-  constexpr int focc = 0;
-#endif
-  if (dp->mask_mode == 2) {  // (never key-split: pick_ksplit; never with dropout: check_common)
-    hipLaunchKernelGGL((attn_fwd_kernel<false, 3, 0, true>), grid, dim3(256), 4 * IMG + 2 * TROWS * sizeof(float), hs, P);
-  } else if (P.drop_thr) {
-#ifdef TMI_ATTN_EXPERIMENTS
-    if (focc == 4) hipLaunchKernelGGL((attn_fwd_kernel<true, 4>), grid, dim3(256), 4 * IMG, hs, P);
-    else if (focc == 5) hipLaunchKernelGGL((attn_fwd_kernel<true, 5>), grid, dim3(256), 4 * IMG, hs, P);
-    else if (focc == 3) hipLaunchKernelGGL((attn_fwd_kernel<true, 3>), grid, dim3(256), 4 * IMG, hs, P);
-    else
-#endif
-    hipLaunchKernelGGL((attn_fwd_kernel<true, DROP_OCC>), grid, dim3(256), 4 * IMG, hs, P);
-  } else if (focc == 4 || focc == 5) {
-#ifdef TMI_ATTN_EXPERIMENTS
-    if (focc == 4) hipLaunchKernelGGL((attn_fwd_kernel<false, 4>), grid, dim3(256), 4 * IMG, hs, P);
-    else hipLaunchKernelGGL((attn_fwd_kernel<false, 5>), grid, dim3(256), 4 * IMG, hs, P);
-#endif
-  } else {
-#ifdef TMI_ATTN_EXPERIMENTS  // ablation builds of the forward (diagnostics; not in the shipped library)
-    static const int abl = [] { const char* e = getenv("TMI_ATTN_ABL"); return e ? atoi(e) : 0; }();
-    if (abl == 1) hipLaunchKernelGGL((attn_fwd_kernel<false, 3, 1>), grid, dim3(256), 4 * IMG, hs, P);
-    else if (abl == 2) hipLaunchKernelGGL((attn_fwd_kernel<false, 3, 2>), grid, dim3(256), 4 * IMG, hs, P);
-    else if (abl == 3) hipLaunchKernelGGL((attn_fwd_kernel<false, 3, 3>), grid, dim3(256), 4 * IMG, hs, P);
-    else if (abl == 4) hipLaunchKernelGGL((attn_fwd_kernel<false, 3, 4>), grid, dim3(256), 4 * IMG, hs, P);
-    else
-#endif
-    hipLaunchKernelGGL((attn_fwd_kernel<false, 3>), grid, dim3(256), 4 * IMG, hs, P);
-  }
-  if (P.ksplit > 1) {
-    const int64_t rows = dp->B * dp->H * dp->Tq;
-    hipLaunchKernelGGL((attn_combine_kernel<true>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, hs, P.part, P.ksplit,
-                       dp->B * dp->H, (int)dp->Tq, reinterpret_cast<bf16_t*>(dp->o), dp->o_sb, dp->o_st, (int)dp->H, dp->stats,
-                       P.drop_thr ? P.keep_scale : 1.f);
-  }
+  if (dp->mask_mode == 2)  // (never key-split: pick_ksplit; never with dropout: check_common)
+    launch(attn_fwd_kernel<false, FWD_OCC, true>, grid, FWD_LDS + 2 * TROWS * sizeof(float), hs, P);
+  else
+    launch(P.drop_thr ? attn_fwd_kernel<true, DROP_OCC> : attn_fwd_kernel<false, FWD_OCC>, grid, FWD_LDS, hs, P);
+  if (P.ksplit > 1) launch_combine(P, dp->o, dp->o_sb, dp->o_st, dp->stats, P.drop_thr ? P.keep_scale : 1.f, hs);
   return tmi_check_launch("tmi_attn_fwd");
 }
 extern "C" int tmi_attn_fwd(const tmi_attn_desc* dp, void* stream) { return tmi_plan_run_desc<tmi_attn_fwd_impl>(dp, stream); }
@@ -1255,78 +1227,32 @@ static int tmi_attn_bwd_impl(const tmi_attn_desc* dp, void* stream) {
     tmi_set_error("tmi_attn_bwd: mask_mode 2 (key bias) is forward only");
     return TMI_ERR_INVALID;
   }
-  AttnP P;
-  set_desc(P, *dp);
-  P.dq_scale = dp->dq_scale;
-  P.sscale = dp->score_scale != 0.f ? dp->score_scale : 1.f;
-  P.c2 = P.sscale * LOG2E;
-  set_dropout(P);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool do_dq = dp->bwd_passes != 2, do_dkv = dp->bwd_passes != 1;
   if (dp->bwd_passes < 0 || dp->bwd_passes > 3) {
     tmi_set_error("tmi_attn_bwd: bwd_passes must be 0 (both), 1 (dQ), 2 (dK/dV) or 3 (both)");
     return TMI_ERR_INVALID;
   }
-  P.ksplit = pick_ksplit(*dp);
-  P.part = reinterpret_cast<float*>(dp->workspace);
-  P.nq = 0;
+  AttnP P = make_params(*dp, dp->dq_scale);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool do_dq = dp->bwd_passes != 2, do_dkv = dp->bwd_passes != 1;
   // one or two query blocks against one or two key blocks (decoder self-attention, Wav2Vec2 at 2 s and 5 s clips): each pass
-  // is a 10-13 us kernel, mostly launch latency, so both go out as ONE launch (TMI_ATTN_BWD_FUSE=0: two)
-  static const int fuse = [] { const char* e = getenv("TMI_ATTN_BWD_FUSE"); return e ? atoi(e) : 1; }();
-  if (fuse && do_dq && do_dkv && P.ksplit == 1 && dp->Tq <= 256 && dp->Tk <= 256) {
-    P.gx = 0;
+  // is a 10-13 us kernel, mostly launch latency, so both go out as ONE launch on the plain grid
+  if (do_dq && do_dkv && P.ksplit == 1 && dp->Tq <= 256 && dp->Tk <= 256) {
     P.nq = (int)((dp->Tq + 127) / 128);
     const dim3 g((unsigned)(P.nq + (dp->Tk + 127) / 128), (unsigned)dp->H, (unsigned)dp->B);
-    const size_t lds = 4 * IMG + 2 * NCONST * 64 * sizeof(float);
-    if (P.drop_thr) hipLaunchKernelGGL((attn_bwd_small_kernel<true>), g, dim3(256), lds, s, P);
-    else hipLaunchKernelGGL((attn_bwd_small_kernel<false>), g, dim3(256), lds, s, P);
+    launch(P.drop_thr ? attn_bwd_small_kernel<true> : attn_bwd_small_kernel<false>, g, DKV_LDS, s, P);
     return tmi_check_launch("tmi_attn_bwd(small)");
   }
   if (do_dq) {
-  dim3 gq = pick_grid(P, (unsigned)((dp->Tq + 127) / 128 * P.ksplit));
-#ifdef TMI_ATTN_EXPERIMENTS
-  static const int qocc = [] { const char* e = getenv("TMI_ATTN_DQ_OCC"); return e ? atoi(e) : 0; }();
-#else
-  constexpr int qocc = 0;
-#endif
-  if (P.drop_thr) {
-#ifdef TMI_ATTN_EXPERIMENTS
-    if (qocc == 3) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 3>), gq, dim3(256), 4 * IMG, s, P);
-    else if (qocc == 4) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 4>), gq, dim3(256), 4 * IMG, s, P);
-    else if (qocc == 5) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, 5>), gq, dim3(256), 4 * IMG, s, P);
-    else
-#endif
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, DQ_DROP_OCC>), gq, dim3(256), 4 * IMG, s, P);
-  } else if (qocc == 4 || qocc == 5) {
-#ifdef TMI_ATTN_EXPERIMENTS
-    if (qocc == 4) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 4>), gq, dim3(256), 4 * IMG, s, P);
-    else hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 5>), gq, dim3(256), 4 * IMG, s, P);
-#endif
-  } else
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, 3>), gq, dim3(256), 4 * IMG, s, P);
-  if (P.ksplit > 1) {
-    const int64_t rows = dp->B * dp->H * dp->Tq;
-    hipLaunchKernelGGL((attn_combine_kernel<false>), dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, s, P.part, P.ksplit,
-                       dp->B * dp->H, (int)dp->Tq, reinterpret_cast<bf16_t*>(dp->dq), dp->dq_sb, dp->dq_st, (int)dp->H,
-                       (float*)nullptr, P.dq_scale * P.sscale);
-  }
-  int rc = tmi_check_launch("tmi_attn_bwd(dq)");
-  if (rc) return rc;
+    const dim3 gq = pick_grid(P, (unsigned)((dp->Tq + 127) / 128 * P.ksplit));
+    launch(P.drop_thr ? attn_bwd_dq_kernel<true, DQ_DROP_OCC> : attn_bwd_dq_kernel<false, DQ_OCC>, gq, FWD_LDS, s, P);
+    if (P.ksplit > 1) launch_combine(P, dp->dq, dp->dq_sb, dp->dq_st, nullptr, P.dq_scale * P.sscale, s);
+    int rc = tmi_check_launch("tmi_attn_bwd(dq)");
+    if (rc) return rc;
   }
   if (!do_dkv) return TMI_OK;
   P.ksplit = 1;
-  dim3 gk = pick_grid(P, (unsigned)((dp->Tk + 127) / 128));
-  const size_t klds = 4 * IMG + 2 * NCONST * 64 * sizeof(float);
-#ifdef TMI_ATTN_EXPERIMENTS
-  static const int kocc = [] { const char* e = getenv("TMI_ATTN_DKV_OCC"); return e ? atoi(e) : 0; }();
-  if (P.drop_thr && kocc == 3) hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 3>), gk, dim3(256), klds, s, P);
-  else if (P.drop_thr && kocc == 4) hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 4>), gk, dim3(256), klds, s, P);
-  else if (!P.drop_thr && kocc == 3) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 3>), gk, dim3(256), klds, s, P);
-  else if (!P.drop_thr && kocc == 4) hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 4>), gk, dim3(256), klds, s, P);
-  else
-#endif
-  if (P.drop_thr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 2>), gk, dim3(256), klds, s, P);
-  else hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 2>), gk, dim3(256), klds, s, P);
+  const dim3 gk = pick_grid(P, (unsigned)((dp->Tk + 127) / 128));
+  launch(P.drop_thr ? attn_bwd_dkv_kernel<true, DKV_OCC> : attn_bwd_dkv_kernel<false, DKV_OCC>, gk, DKV_LDS, s, P);
   return tmi_check_launch("tmi_attn_bwd(dkv)");
 }
 extern "C" int tmi_attn_bwd(const tmi_attn_desc* dp, void* stream) { return tmi_plan_run_desc<tmi_attn_bwd_impl>(dp, stream); }
@@ -1352,11 +1278,7 @@ static int tmi_attn_probs_impl(const tmi_attn_desc* dp, void* probs, int32_t pro
                   "16-byte aligned bf16 q, k with strides multiple of 8; mask_mode 2 needs key_bias; dropout_p must be 0)");
     return TMI_ERR_INVALID;
   }
-  AttnP P;
-  memset(&P, 0, sizeof(P));
-  set_desc(P, *dp);
-  P.sscale = dp->score_scale != 0.f ? dp->score_scale : 1.f;
-  P.c2 = P.sscale * LOG2E;
+  const AttnP P = make_params(*dp, 1.f);
   hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
   const bool f32 = probs_dtype == TMI_F32;
   switch (dp->mask_mode) {

@@ -374,16 +374,21 @@ def _set_dropout(d, dropout_p, dropout_seed, drop_mask):
         d.drop_mask, d.drop_mask_bytes = drop_mask.data_ptr(), drop_mask.numel() * drop_mask.element_size()
 
 
+def _set_key_bias(d, key_bias, B, Tk):
+    if key_bias is None:
+        return
+    if key_bias.dtype != torch.float32 or key_bias.dim() != 2 or key_bias.shape != (B, Tk) or key_bias.stride(1) != 1:
+        raise ValueError("key_bias must be float32 [B, Tk] with contiguous rows")
+    d.key_bias, d.kb_sb = key_bias.data_ptr(), key_bias.stride(0)
+
+
 def attn_fwd(q, k, v, o, stats, B, H, Tq, Tk, mask_mode=0, score_scale=1.0, dropout_p=0.0, dropout_seed=0, drop_mask=None,
              key_bias=None):
     """``key_bias`` (mask_mode 2): fp32 [B, Tk], added to the scores of key column j of batch b (natural-log units)."""
     with _probe("attention", 4.0 * B * H * Tq * Tk * 64):
         d = _attn_desc(q, k, v, o, stats, B, H, Tq, Tk, mask_mode, score_scale)
         _set_dropout(d, dropout_p, dropout_seed, drop_mask)
-        if key_bias is not None:
-            if key_bias.dtype != torch.float32 or key_bias.dim() != 2 or key_bias.shape != (B, Tk) or key_bias.stride(1) != 1:
-                raise ValueError("key_bias must be float32 [B, Tk] with contiguous rows")
-            d.key_bias, d.kb_sb = key_bias.data_ptr(), key_bias.stride(0)
+        _set_key_bias(d, key_bias, B, Tk)
         check(lib().tmi_attn_fwd(C.byref(d), stream()), "tmi_attn_fwd")
 
 
@@ -415,10 +420,7 @@ def attn_probs(q, k, stats, out, B, H, Tq, Tk, mask_mode=0, score_scale=1.0, key
         raise ValueError("attn_probs: out must be [B, H, Tq, Tk] with unit key stride and stride(0) == H * stride(1)")
     d = _attn_desc(q, k, q, q, stats, B, H, Tq, Tk, mask_mode, score_scale)
     d.workspace, d.workspace_bytes = None, 0
-    if key_bias is not None:
-        if key_bias.dtype != torch.float32 or key_bias.dim() != 2 or key_bias.shape != (B, Tk) or key_bias.stride(1) != 1:
-            raise ValueError("key_bias must be float32 [B, Tk] with contiguous rows")
-        d.key_bias, d.kb_sb = key_bias.data_ptr(), key_bias.stride(0)
+    _set_key_bias(d, key_bias, B, Tk)
     check(lib().tmi_attn_probs(C.byref(d), out.data_ptr(), dt(out), out.stride(1), out.stride(2), stream()), "tmi_attn_probs")
 
 
