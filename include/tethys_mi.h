@@ -341,6 +341,8 @@ int tmi_embed_bwd(const int32_t* labels, const void* dy, float* dtable, int64_t 
  *                                                              the pad columns [V, ld))
  * grad_scale is 1 / (B*(S-1)) for the reference's reduce_mean.  tmi_mean_rows folds
  * row_loss into loss[0] = sum(row_loss) * scale.
+ * The pad columns [V, ld) and the unused rows are masked by index and never enter the result: on entry they may hold
+ * anything, NaN included (as for tmi_logprob_fold); on return they are +0.
  */
 int tmi_xent_fwd_bwd(void* logits, int64_t ld, const int32_t* labels, float* row_loss,
                      int64_t B, int64_t S, int64_t V, float grad_scale, int32_t dtype, void* stream);
