@@ -321,6 +321,52 @@ int tmi_attn_bwd(const tmi_attn_desc* d, void* stream);
 int tmi_attn_probs(const tmi_attn_desc* d, void* probs, int32_t probs_dtype, int64_t p_sbh, int64_t p_sq, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Token-to-frame alignment (inference): cross-attention weights -> a cost, and dynamic time warping over it.
+ *
+ * tmi_align_cost.  probs: one decoder layer's cross-attention weights, element (n, h, s, t) at
+ * probs[(n*H + h)*p_sbh + s*p_sq + t], TMI_F32 or TMI_BF16, as tmi_attn_probs writes them (p_sq >= T, p_sbh >= S*p_sq;
+ * the caller points past the start token's row).  rows[N], cols[N]: device int32, the tokens to align and the valid
+ * encoder frames of item n, 1 <= rows[n] <= S, medfilt_width/2 < cols[n] <= T.  head_weight[H]: device fp32; a head
+ * of weight 0 is skipped and its weights are never read.  medfilt_width: odd, 1..9 (1: no filter).  Per item n, head h
+ * of non-zero weight and frame t < cols[n], in fp32:
+ *   normalise  z[s,t] = (p[s,t] - mean[t]) * rsqrt(var[t] + 1e-20), mean and var over the rows s < rows[n] only, var the
+ *              population variance (/ rows[n]) of the deviations from that mean (two passes), so rows[n] == 1 gives
+ *              exactly 0; normalize == 0: z = p.
+ *   filter     m[s,t] = the median of z[s, t - w/2 .. t + w/2], indices reflected about the ends of [0, cols[n]) without
+ *              repeating the end sample (-k -> k, cols-1+k -> cols-1-k: numpy pad "reflect", scipy.ndimage "mirror").
+ *              The median selects one of the z: it adds no rounding.
+ *   combine    acc = accumulate ? cost[n,s,t] : 0;  for h ascending: acc = fma(-head_weight[h], m_h[s,t], acc);
+ *              cost[n*c_sn + s*c_ss + t] = acc.
+ * Elements with s >= rows[n] or t >= cols[n] are not written (c_ss >= T, c_sn >= S*c_ss); an item with rows[n] < 1 is
+ * skipped by both kernels (nothing of it is read or written).  Several layers are folded
+ * by successive calls with accumulate = 1 on one stream.  No atomics, no workspace: the same call gives the same bits.
+ * tmi_align_cost_tile: the output frames of one workgroup for a width (64 - (w - 1)), -1 for a width that is refused.
+ * TMI_ERR_INVALID: a NULL pointer, a bad dtype / width / flag / stride, N outside 1..65535, H outside 1..32, T <= w/2.
+ *
+ * tmi_dtw.  cost: element (n, i, j) at cost[n*c_sn + i*c_ss + j], fp32; rows, cols as above (cols[n] >= 1).  With
+ * D[-1][-1] = 0 and every other border +inf,
+ *   D[i][j] = cost[i][j] + min(c0 = D[i-1][j-1], c1 = D[i-1][j], c2 = D[i][j-1])                      (fp32)
+ *   move    = 0 (diagonal) if c0 < c1 && c0 < c2, else 1 (up) if c1 < c0 && c1 < c2, else 2 (left)
+ * so the first column moves up, the first row moves left, and a tie goes left - also the tie c0 == c1 < c2, in which
+ * the path then leaves the minimum that D took.  The path is traced back from (rows-1, cols-1) to (0, 0).
+ *   tok_start[n*S_max + i], tok_end[n*S_max + i]: the first frame of the path in row i, and its last frame + 1
+ *   total[n] = D[rows-1][cols-1]
+ *   path (may be NULL, then path_len too): int32 (i, j) pairs in forward order at path[(n*(S_max+T_max-1) + k)*2],
+ *   k < path_len[n]
+ * Entries at or past rows[n] / path_len[n] are not written.  One workgroup per item, one thread per row: S_max <= 1024,
+ * T_max <= 4096, N <= 65535.  workspace: tmi_dtw_workspace_bytes (the moves, 2 bits per cell; -1 outside those
+ * limits), any contents.  No atomics: the same call gives the same bits. */
+int64_t tmi_align_cost_tile(int32_t medfilt_width);
+int tmi_align_cost(const void* probs, int32_t probs_dtype, int64_t p_sbh, int64_t p_sq, const int32_t* rows,
+                   const int32_t* cols, const float* head_weight, float* cost, int64_t c_sn, int64_t c_ss, int64_t N,
+                   int64_t H, int64_t S, int64_t T, int32_t medfilt_width, int32_t normalize, int32_t accumulate,
+                   void* stream);
+int64_t tmi_dtw_workspace_bytes(int64_t N, int64_t S_max, int64_t T_max);
+int tmi_dtw(const float* cost, int64_t c_sn, int64_t c_ss, const int32_t* rows, const int32_t* cols, int64_t N,
+            int64_t S_max, int64_t T_max, int32_t* tok_start, int32_t* tok_end, float* total, int32_t* path,
+            int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Decoder token embedding + positional encoding (W:405-408) with the teacher-forcing
  * shift of W:559-563 folded in: id(b,t) = t == 0 ? start_id : labels[b, t-1].
  *   out[b,t,:] = table[id(b,t), :] + pe[t, :]

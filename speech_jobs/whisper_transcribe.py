@@ -14,6 +14,10 @@ with the project, so the output is token ids.
 an ``.npz``: one more forward pass over [start, tokens] with ``output_attentions=("cross",)`` - under the reference's
 inverted decoder mask every decoding step recomputes the whole prefix, so this pass is the last step's computation -
 saved as ``attn_<i>`` fp32 [decoder_layers, S, T] (the mean over the heads), ``ids_<i>`` int32 [S] and ``clips`` (names).
+
+``--timestamps`` prints, after each transcript, one ``[start -> end] id`` line per token: the seconds at which the token
+begins and ends (``model.align``: dynamic time warping over the cross-attention weights, on the GPU).  Aligning the last
+token needs one more decoder position than choosing it, so ``--max_length`` is capped at 447.
 """
 import argparse
 import json
@@ -45,6 +49,9 @@ def main(argv=None):
     parser.add_argument("--seed", type=int, default=0, help="sampling: the seed (a seeded run repeats)")
     parser.add_argument("--save_cross_attentions", default=None, metavar="PATH",
                         help="write the head-mean cross-attention weights [layers, S, T] of each transcript to this .npz")
+    parser.add_argument("--timestamps", action="store_true",
+                        help="after each transcript, one '[start -> end] id' line per token (seconds; DTW over the "
+                             "cross-attention weights); caps --max_length at 447")
     args = parser.parse_args(argv)
     if args.do_sample and args.num_beams > 1:
         parser.error("--do_sample does not go with --num_beams > 1")
@@ -59,6 +66,8 @@ def main(argv=None):
     torch.cuda.set_device(local_rank)
     device = f"cuda:{local_rank}"
     model = whisper.create_whisper_model(args.model_type, device=device, precision=args.precision)
+    if args.timestamps:
+        args.max_length = min(args.max_length, model.config.max_target_positions - 1)
     beam = args.num_beams > 1
     sample = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                   min_length=args.min_length, seed=args.seed) if args.do_sample else None
@@ -99,25 +108,45 @@ def main(argv=None):
         saved[f"attn_{i}"] = torch.stack([a[0].mean(dim=0) for a in out["cross_attentions"]]).cpu().numpy()
         saved[f"ids_{i}"] = np.asarray(ids, dtype=np.int32)
 
+    def stamps(feats, seqs, lens, wav_len, rows):
+        """The token lines of the sequences ``rows`` (indices into seqs) -> {row: text}."""
+        if not args.timestamps:
+            return {}
+        frames = (fe.num_frames(wav_len) + 1) // 2  # encoder frames of the clips of this group
+        al = model.align(feats, seqs.to(device), None if lens is None else lens.to(device),
+                         num_frames=[frames] * feats.shape[0])
+        t0s, t1s = al["token_start_times"].cpu(), al["token_end_times"].cpu()
+        out = {}
+        for r in rows:
+            n = seqs.shape[1] - 1 if lens is None else int(lens[r])
+            out[r] = "\n".join(f"[{float(t0s[r, k]):.2f} -> {float(t1s[r, k]):.2f}] {int(seqs[r, 1 + k])}" for k in range(n))
+        return out
+
     for items in groups.values():
         wave = torch.from_numpy(np.stack([w for _, w in items])).to(device)
-        if args.save_cross_attentions:
+        if args.save_cross_attentions or args.timestamps:
             feats_all = fe(wave)
         if sample:
             out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample)
             seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
-            for (name, _), row, sc, n in zip(items, seqs, scores, lens):
+            lines = stamps(feats_all, seqs, lens, wave.shape[1], range(len(items))) if args.timestamps else {}
+            for j, ((name, _), row, sc, n) in enumerate(zip(items, seqs, scores, lens)):
                 n_tok += int(n)
                 print(json.dumps({"clip": name, "ids": row[:1 + int(n)].tolist(), "n_tokens": int(n), "logprob": float(sc)}),
                       flush=True)
+                if lines.get(j):
+                    print(lines[j], flush=True)
             for j, ((name, _), row, n) in enumerate(zip(items, seqs, lens)):
                 save_cross(name, feats_all[j] if args.save_cross_attentions else None, row[:1 + int(n)].tolist())
             continue
         if not beam:
             ids = model.generate(fe(wave), max_length=args.max_length).cpu()
-            for (name, _), row in zip(items, ids):
+            lines = stamps(feats_all, ids, None, wave.shape[1], range(len(items))) if args.timestamps else {}
+            for j, ((name, _), row) in enumerate(zip(items, ids)):
                 n_tok += row.numel() - 1
                 print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1)}), flush=True)
+                if lines.get(j):
+                    print(lines[j], flush=True)
             for j, ((name, _), row) in enumerate(zip(items, ids)):
                 save_cross(name, feats_all[j] if args.save_cross_attentions else None, row.tolist())
             continue
@@ -125,11 +154,14 @@ def main(argv=None):
         out = model.generate(fe(wave), max_length=args.max_length, num_beams=args.num_beams,
                              length_penalty=args.length_penalty, num_return_sequences=R, return_dict_in_generate=True)
         seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
+        lines = stamps(feats_all, seqs, lens, wave.shape[1], range(len(seqs))) if args.timestamps else {}
         for i, row in enumerate(seqs):
             n = int(lens[i])
             n_tok += n
             print(json.dumps({"clip": items[i // R][0], "rank": i % R, "ids": row[:1 + n].tolist(), "n_tokens": n,
                               "score": float(scores[i])}), flush=True)
+            if lines.get(i):
+                print(lines[i], flush=True)
             if i % R == 0:  # (the best hypothesis of the clip)
                 save_cross(items[i // R][0], feats_all[i // R] if args.save_cross_attentions else None, row[:1 + n].tolist())
     if args.save_cross_attentions:

@@ -159,6 +159,11 @@ SIGNATURES = {
     "tmi_contrastive_score": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
                                       c_f32, c_vp]),
     "tmi_vq_count": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]),
+    "tmi_align_cost_tile": (c_i64, [c_i32]),
+    "tmi_align_cost": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
+                               c_i32, c_i32, c_i32, c_vp]),
+    "tmi_dtw_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "tmi_dtw": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

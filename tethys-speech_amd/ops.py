@@ -424,6 +424,71 @@ def attn_probs(q, k, stats, out, B, H, Tq, Tk, mask_mode=0, score_scale=1.0, key
     check(lib().tmi_attn_probs(C.byref(d), out.data_ptr(), dt(out), out.stride(1), out.stride(2), stream()), "tmi_attn_probs")
 
 
+def _i32_dev(t, n, what):
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"{what} must be a contiguous int32 tensor of at least {n} entries")
+
+
+def align_cost_tile(medfilt_width: int) -> int:
+    """Output frames per workgroup of tmi_align_cost for this filter width."""
+    n = int(lib().tmi_align_cost_tile(int(medfilt_width)))
+    if n < 0:
+        raise ValueError(f"medfilt_width must be odd in 1..9, got {medfilt_width}")
+    return n
+
+
+def align_cost(probs, rows, cols, head_weight, cost, medfilt_width=7, normalize=True, accumulate=False):
+    """The DTW cost of one decoder layer's cross-attention weights (tmi_align_cost in include/tethys_mi.h): ``probs``
+    [N, H, S, T] fp32 or bf16 with unit stride along T and ``stride(0) == H * stride(1)`` (a slice past the start token's
+    row is fine), ``rows`` / ``cols`` int32 [N] on the device, ``head_weight`` fp32 [H] on the device (0: head skipped),
+    ``cost`` fp32 [N, S, T] with unit stride along T; ``accumulate`` adds onto what ``cost`` holds."""
+    if probs.dim() != 4 or probs.stride(3) != 1 or (probs.shape[0] > 1 and probs.stride(0) != probs.shape[1] * probs.stride(1)):
+        raise ValueError("align_cost: probs must be [N, H, S, T] with unit frame stride and stride(0) == H * stride(1)")
+    N, H, S, T = probs.shape
+    if cost.dtype != torch.float32 or cost.dim() != 3 or tuple(cost.shape) != (N, S, T) or cost.stride(2) != 1:
+        raise ValueError("align_cost: cost must be float32 [N, S, T] with unit frame stride")
+    _i32_dev(rows, N, "align_cost: rows")
+    _i32_dev(cols, N, "align_cost: cols")
+    _f32_flat(head_weight, H, "align_cost: head_weight")
+    with _probe("align_cost", 1.0 * N * H * S * T * probs.element_size()):
+        check(lib().tmi_align_cost(probs.data_ptr(), dt(probs), probs.stride(1), probs.stride(2), rows.data_ptr(), cols.data_ptr(),
+                                   head_weight.data_ptr(), cost.data_ptr(), cost.stride(0), cost.stride(1), N, H, S, T,
+                                   int(medfilt_width), 1 if normalize else 0, 1 if accumulate else 0, stream()), "tmi_align_cost")
+
+
+def dtw_workspace_elems(N: int, S_max: int, T_max: int) -> int:
+    """int32 elements of tmi_dtw's workspace (tmi_dtw_workspace_bytes / 4)."""
+    n = int(lib().tmi_dtw_workspace_bytes(N, S_max, T_max))
+    if n < 0:
+        raise ValueError(f"tmi_dtw takes 1 <= N <= 65535 items of at most 1024 rows x 4096 columns, got {N} x {S_max} x {T_max}")
+    return n // 4
+
+
+def dtw(cost, rows, cols, tok_start, tok_end, total, workspace, path=None, path_len=None):
+    """Dynamic time warping over ``cost`` fp32 [N, S_max, T_max] (unit stride along the columns), item n on its first
+    rows[n] x cols[n] cells (tmi_dtw in include/tethys_mi.h): ``tok_start`` / ``tok_end`` int32 [N, S_max], ``total`` fp32 [N],
+    optionally ``path`` int32 [N, S_max + T_max - 1, 2] with ``path_len`` int32 [N]; ``workspace`` int32,
+    ``dtw_workspace_elems`` entries, any contents."""
+    if cost.dtype != torch.float32 or cost.dim() != 3 or cost.stride(2) != 1:
+        raise ValueError("dtw: cost must be float32 [N, S_max, T_max] with unit column stride")
+    N, S, T = cost.shape
+    _i32_dev(rows, N, "dtw: rows")
+    _i32_dev(cols, N, "dtw: cols")
+    _i32_dev(tok_start, N * S, "dtw: tok_start")
+    _i32_dev(tok_end, N * S, "dtw: tok_end")
+    _f32_flat(total, N, "dtw: total")
+    _i32_dev(workspace, dtw_workspace_elems(N, S, T), "dtw: workspace")
+    if (path is None) != (path_len is None):
+        raise ValueError("dtw: path and path_len come together")
+    if path is not None:
+        _i32_dev(path, N * (S + T - 1) * 2, "dtw: path")
+        _i32_dev(path_len, N, "dtw: path_len")
+    with _probe("dtw", 4.0 * N * S * T):
+        check(lib().tmi_dtw(cost.data_ptr(), cost.stride(0), cost.stride(1), rows.data_ptr(), cols.data_ptr(), N, S, T,
+                            tok_start.data_ptr(), tok_end.data_ptr(), total.data_ptr(), ptr(path), ptr(path_len),
+                            workspace.data_ptr(), workspace.numel() * 4, stream()), "tmi_dtw")
+
+
 def masked_mean_pool(x, mask, out, B, T, C):
     """out[b, c] = sum_t x[b, t, c] mask[b, t] / sum_t mask[b, t] (fp32 [B, C]); ``mask`` fp32 [B, T] or None: the plain mean."""
     if not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C or x.numel() != B * T * C:

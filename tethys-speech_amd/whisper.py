@@ -927,13 +927,15 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if self.config.decoder_layers:
             self._dense_fwd(enc_out, "decoder.cross_kv.kernel", self.ws["kvc_all"][:enc_out.shape[0]])
 
-    def _decode_infer(self, labels, B, S, T, capture=None):
+    def _decode_infer(self, labels, B, S, T, capture=None, kvc=None):
         """W:394-466 (training=False) over S positions without the final LayerNorm: returns the residual stream
-        [B*S, d].  ``labels`` [B, S] int32: the decoder reads [start, labels[:, :-1]] (tmi_embed_fwd's shift)."""
+        [B*S, d].  ``labels`` [B, S] int32: the decoder reads [start, labels[:, :-1]] (tmi_embed_fwd's shift).  ``kvc``: the
+        cross-attention k|v rows [B*T, layers * 2d] of these B rows when they are not the first B of ws["kvc_all"]."""
         cfg = self.config
         Hd = cfg.decoder_attention_heads
         b = self._infer_bufs(B * S)
-        b.update(att=self._att("att", B, Hd, S, S), attc=self._att("attc", B, Hd, S, T), kvc=self.ws["kvc_all"][:B * T])
+        b.update(att=self._att("att", B, Hd, S, S), attc=self._att("attc", B, Hd, S, T),
+                 kvc=self.ws["kvc_all"][:B * T] if kvc is None else kvc)
         ops.embed_fwd(labels, self.arena.param("decoder.embed_tokens.embeddings"), self.pe_dec, b["x_in"], B, S, cfg.d_model,
                       cfg.decoder_start_token_id)
         for i in range(cfg.decoder_layers):
@@ -1012,7 +1014,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
     @torch.no_grad()
     def generate(self, input_features, max_length=None, min_length=None, num_beams=None, temperature=1.0, top_k=None,
                  top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None, length_penalty=1.0,
-                 early_stopping=False, num_return_sequences=1, return_dict_in_generate=False, do_sample=False, seed=0):
+                 early_stopping=False, num_return_sequences=1, return_dict_in_generate=False, do_sample=False, seed=0,
+                 return_token_timestamps=False):
         """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.  ``num_beams`` of 2 to
         8: beam search (``_generate_beam``; the reference accepts num_beams at W:637 and leaves it as a ``pass`` at
         W:696-698); None or 1: the greedy path below, unchanged.
@@ -1029,8 +1032,25 @@ class WhisperForConditionalGeneration(KernelBlocks):
 
         Per step: the embedding of [start, tokens so far] (tmi_embed_fwd), the decoder over the prefix, and
         tmi_lm_head_argmax on the B last rows (final LayerNorm, LM head and argmax in one launch).  The EOS count of a step
-        is read one step late (``greedy_loop``), so the device never idles on the host's check."""
+        is read one step late (``greedy_loop``), so the device never idles on the host's check.
+
+        ``return_token_timestamps=True`` (every mode): the result is the dict form - {"sequences"} and what the mode's
+        ``return_dict_in_generate`` adds - with the outputs of ``align`` for the returned sequences (over "lengths" where
+        the mode reports them) added: one more encoder pass and one teacher-forced decoder pass per distinct length.
+        Aligning token n needs position n of the decoder, so ``max_length`` is then at most max_target_positions - 1 (and
+        defaults to it).  False: nothing changes."""
         cfg = self.config
+        if return_token_timestamps:
+            max_length = check_timestamp_length(cfg, max_length)
+            out = self.generate(input_features, max_length=max_length, min_length=min_length, num_beams=num_beams,
+                                temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
+                                attention_mask=attention_mask, eos_token_id=eos_token_id, length_penalty=length_penalty,
+                                early_stopping=early_stopping, num_return_sequences=num_return_sequences,
+                                return_dict_in_generate=True, do_sample=do_sample, seed=seed)
+            if not isinstance(out, dict):  # (the greedy path has no dict form of its own)
+                out = {"sequences": out}
+            out.update(self.align(input_features, out["sequences"], out.get("lengths")))
+            return out
         if do_sample:
             max_length, top_k, top_p, min_length = sample_args(cfg, max_length, num_beams, temperature, top_k, top_p, min_length)
             eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
@@ -1394,8 +1414,212 @@ class WhisperForConditionalGeneration(KernelBlocks):
             tok_lp[:, :n_eff] = logprob.view(n_eff, N).t()
         return {"token_logprobs": tok_lp, "sequences_logprob": tok_lp.sum(dim=1)}
 
+    # -- token timestamps: DTW over the cross-attention weights -------------------------------------------------------
+    @torch.no_grad()
+    def align(self, features, sequences, lengths=None, num_frames=None, alignment_heads=None, medfilt_width=7,
+              normalize=True, return_path=False):
+        """When each token of given sequences was spoken: dynamic time warping over the cross-attention weights.
+
+        ``features``, ``sequences`` [N, 1 + n] int32 (the start token first) and ``lengths`` [N] are what ``score`` takes,
+        the N = B * R layout of ``generate(num_return_sequences=R)`` included.  ``num_frames`` [N] or [B]: the valid
+        encoder frames of each clip (default: all T); the warp of a row ends at its clip's last valid frame.
+        ``alignment_heads``: None - every head of the upper half of the decoder layers - or (layer, head) pairs; each
+        selected head weighs 1 / their number.  ``medfilt_width``: odd, 1 to 9.
+
+        Row i: the decoder reads sequences[i, :1 + lengths[i]] in one teacher-forced pass - the computation of generate's
+        last step - the start token's row of the weights is dropped and rows 1 .. lengths[i] align tokens 1 .. lengths[i],
+        so 1 + lengths[i] <= max_target_positions.  Under the inverted mask of W:416-418 a row attends to the LATER
+        positions, so padding behind a shorter row would change its weights: the rows are grouped by length and every
+        distinct length is one decoder pass over its rows.  The encoder and the cross-attention k|v run once.  Per pass
+        and selected layer the weights (fp32, tmi_attn_probs on the bf16 model) are folded into the cost at once by
+        tmi_align_cost (normalise over the tokens, median filter along the frames, minus the weighted mean of the heads:
+        include/tethys_mi.h has the exact definition) and released; one tmi_dtw launch then warps every row.  The
+        arguments are read on the host before anything runs; nothing else is until the paths are cut (``return_path``).
+
+        -> {"token_start_frames", "token_end_frames" [N, n] int32: the first encoder frame of token k + 1 and its last
+        frame + 1, -1 beyond lengths[i]; "token_start_times", "token_end_times" [N, n] fp32 seconds = frames *
+        FRAME_SECONDS (-1 beyond lengths[i]); "path_cost" [N] fp32 (0 for an empty row)}; ``return_path`` adds "paths" (a
+        list of N int32 [len, 2] tensors of (token - 1, frame) pairs) and "cost" [N, max length, T] fp32 (0 where a row
+        has no token or frame).  Everything stays on the device."""
+        cfg = self.config
+        features = self._check_features(features)
+        B, dev, V = features.shape[0], self.device, cfg.vocab_size
+        seq = torch.as_tensor(sequences).to(device=dev)
+        if seq.dtype != torch.int32 or seq.dim() != 2:
+            raise ValueError("sequences must be int32 [N, 1 + n]")
+        host = lambda x: None if x is None else [int(v) for v in torch.as_tensor(x).reshape(-1).tolist()]  # noqa: E731
+        a = check_align_args(cfg, tuple(seq.shape), host(lengths), host(num_frames), alignment_heads, medfilt_width)
+        N, n, lens, width = a["N"], a["n"], a["lengths"], a["medfilt_width"]
+        if N % B:
+            raise ValueError("the number of sequences must be a multiple of the feature batch")
+        R = N // B
+        if not bool((seq[:, 0] == cfg.decoder_start_token_id).all()):
+            raise ValueError("sequences must start with decoder_start_token_id")
+        inf = self._infer_prepare(B, features.shape[2], R)
+        T = inf["T"]
+        nf = a["num_frames"]
+        if nf is None:
+            nf = [T] * N
+        elif len(nf) == B and R > 1:
+            nf = [v for v in nf for _ in range(R)]
+        if len(nf) != N or max(nf) > T:
+            raise ValueError(f"num_frames must be [N] or [B] with entries in ({width // 2}, {T}]")
+        i32 = dict(dtype=torch.int32, device=dev)
+        n_eff = max(lens) if lens else 0
+        starts, ends = torch.full((N, n), -1, **i32), torch.full((N, n), -1, **i32)
+        total = torch.zeros(N, device=dev)
+        result = {"token_start_frames": starts, "token_end_frames": ends, "path_cost": total}
+        order = sorted(range(N), key=lambda r: lens[r])  # (stable: rows of one length keep their order)
+        cost = path = path_len = None
+        if n_eff > 0:
+            lens_t = torch.tensor(lens, device=dev)
+            scored = torch.arange(1, n_eff + 1, device=dev)[None, :] <= lens_t[:, None]
+            toks = seq[:, 1:1 + n_eff]
+            if int(toks[scored].min()) < 0 or int(toks[scored].max()) >= V:
+                raise ValueError(f"aligned tokens must be in [0, {V})")
+            feed = torch.where(scored, toks, cfg.pad_token_id).to(torch.int32)
+            order_t = torch.tensor(order, device=dev)
+            rows_d = torch.tensor([lens[r] for r in order], **i32)
+            cols_d = torch.tensor([nf[r] for r in order], **i32)
+            weights = {l: torch.tensor(w, dtype=torch.float32, device=dev) for l, w in a["head_weights"].items()}
+            cost = torch.zeros(N, n_eff, T, device=dev)  # (in the order of ``order``)
+            with self._inference(inf):
+                ws = self.ws
+                enc_out = self._encode_infer(features, inf)
+                self._cross_kv_infer(enc_out)
+                if cfg.decoder_layers and R > 1:  # (as beam search)
+                    _repeat_rows_per_item(ws["kvc_all"].view(N, T, -1), B, R)
+                kv_all = ws["kvc_all"][:N * T]
+                lo = 0
+                while lo < N:
+                    L = lens[order[lo]]
+                    hi = lo
+                    while hi < N and lens[order[hi]] == L:
+                        hi += 1
+                    if L > 0:
+                        g, S = hi - lo, 1 + L
+                        idx = order_t[lo:hi]
+                        lab = ws["labels"][:g * S].view(g, S)
+                        lab[:, :L].copy_(feed[idx, :L])
+                        lab[:, L:].fill_(cfg.pad_token_id)  # (the shifted-out column: never read)
+                        whole = g == N and order == list(range(N))
+                        kvc = None if whole else kv_all.view(N, T, -1).index_select(0, idx).view(g * T, -1)
+                        fold = _AlignFold(weights, rows_d[lo:hi], cols_d[lo:hi], cost[lo:hi, :L], width, bool(normalize))
+                        self._decode_infer(lab, g, S, T, fold, kvc=kvc)
+                    lo = hi
+                st, en, tot = torch.full((N, n_eff), -1, **i32), torch.full((N, n_eff), -1, **i32), torch.zeros(N, device=dev)
+                if return_path:
+                    path = torch.zeros(N, n_eff + T - 1, 2, **i32)
+                    path_len = torch.zeros(N, **i32)
+                dtw_ws = torch.empty(ops.dtw_workspace_elems(N, n_eff, T), **i32)
+                ops.dtw(cost, rows_d, cols_d, st, en, tot, dtw_ws, path, path_len)
+                inv = torch.empty_like(order_t)
+                inv[order_t] = torch.arange(N, device=dev)
+                starts[:, :n_eff] = st.index_select(0, inv)
+                ends[:, :n_eff] = en.index_select(0, inv)
+                total.copy_(tot.index_select(0, inv))
+        for k in ("start", "end"):
+            fr = result[f"token_{k}_frames"]
+            result[f"token_{k}_times"] = torch.where(fr >= 0, fr.float() * FRAME_SECONDS, -1.0)
+        if return_path:
+            if n_eff > 0:
+                plen = path_len.index_select(0, inv).tolist()  # the one host read
+                psrc = path.index_select(0, inv)
+                result["paths"] = [psrc[r, :plen[r]] for r in range(N)]
+                result["cost"] = cost.index_select(0, inv)
+            else:
+                result["paths"] = [torch.zeros(0, 2, **i32) for _ in range(N)]
+                result["cost"] = torch.zeros(N, 0, T, device=dev)
+        return result
+
 
 ATTENTION_KINDS = ("encoder", "decoder", "cross")
+
+# seconds per encoder frame: the log-mel hop (160 samples at 16 kHz) times the stride 2 of the stem's second convolution
+FRAME_SECONDS = 160 / 16000 * 2
+
+
+class _AlignFold:
+    """The capture ``align`` hands to the decoder blocks: it asks for the cross-attention weights of the layers that hold a
+    selected head only, folds each into the cost at once (tmi_align_cost; the first selected layer overwrites, the later
+    ones accumulate: layer order) and keeps nothing."""
+    dtype = torch.float32
+
+    def __init__(self, weights, rows, cols, cost, width, normalize):
+        self.weights, self.rows, self.cols, self.cost = weights, rows, cols, cost
+        self.width, self.normalize = width, normalize
+        self.layer, self.folded = -1, 0
+
+    def wants(self, kind: str) -> bool:
+        if kind != "cross":
+            return False
+        self.layer += 1  # (the decoder asks once per layer, in layer order)
+        return self.layer in self.weights
+
+    def attention(self, kind: str, probs):
+        ops.align_cost(probs[:, :, 1:, :], self.rows, self.cols, self.weights[self.layer], self.cost, self.width,
+                       self.normalize, accumulate=self.folded > 0)
+        self.folded += 1
+
+    def layer_input(self, side, x2d, B, T, d):
+        pass
+
+
+def check_timestamp_length(cfg: WhisperConfig, max_length=None) -> int:
+    """``generate(return_token_timestamps=True)``'s max_length: aligning the last token needs one more decoder position
+    than choosing it, so at most max_target_positions - 1 (the default)."""
+    top = cfg.max_target_positions - 1
+    max_length = top if max_length is None else int(max_length)
+    if max_length < 0 or max_length > top:
+        raise ValueError(f"with token timestamps max_length must be in [0, {top}]")
+    return max_length
+
+
+def check_align_args(cfg: WhisperConfig, seq_shape, lengths=None, num_frames=None, alignment_heads=None, medfilt_width=7):
+    """Host validation of ``align`` (no GPU needed).  ``seq_shape`` (N, 1 + n); ``lengths`` None (n everywhere) or N
+    integers in [0, n] with 1 + lengths <= max_target_positions; ``num_frames`` None or integers in
+    (medfilt_width // 2, n_ctx] (``align`` checks their count and the clip's own T); ``alignment_heads`` None - every head of
+    the layers >= decoder_layers // 2 - or (layer, head) pairs, no duplicates, in range; ``medfilt_width`` odd in 1..9.
+    -> {"N", "n", "lengths" (list), "num_frames" (list or None), "medfilt_width", "heads" (sorted pairs), "head_weights"
+    {layer: [weight of head 0, ...]} with 1 / len(heads) at the selected heads and 0 elsewhere}."""
+    if len(seq_shape) != 2 or seq_shape[0] < 1 or seq_shape[1] < 1:
+        raise ValueError("sequences must be [N, 1 + n] with N >= 1")
+    N, n = int(seq_shape[0]), int(seq_shape[1]) - 1
+    if isinstance(medfilt_width, bool) or int(medfilt_width) != medfilt_width or not 1 <= int(medfilt_width) <= 9 or int(medfilt_width) % 2 == 0:
+        raise ValueError("medfilt_width must be an odd integer in 1..9")
+    width = int(medfilt_width)
+    lens = [n] * N if lengths is None else [int(v) for v in lengths]
+    if len(lens) != N or any(v < 0 or v > n for v in lens):
+        raise ValueError("lengths must be [N] with entries in [0, n]")
+    if lens and 1 + max(lens) > cfg.max_target_positions:
+        raise ValueError(f"aligning a token needs its decoder position: 1 + lengths must be <= {cfg.max_target_positions}")
+    nf = None
+    if num_frames is not None:
+        nf = [int(v) for v in num_frames]
+        if not nf or any(v <= width // 2 or v > cfg.n_ctx for v in nf):
+            raise ValueError(f"num_frames must be in ({width // 2}, {cfg.n_ctx}]")
+    Ld, Hd = cfg.decoder_layers, cfg.decoder_attention_heads
+    if alignment_heads is None:
+        heads = [(l, h) for l in range(Ld // 2, Ld) for h in range(Hd)]
+    else:
+        try:
+            heads = [(int(l), int(h)) for l, h in alignment_heads]
+        except (TypeError, ValueError):
+            raise ValueError("alignment_heads must be None or (layer, head) pairs") from None
+        if len(set(heads)) != len(heads):
+            raise ValueError("alignment_heads holds a pair twice")
+        for l, h in heads:
+            if not (0 <= l < Ld and 0 <= h < Hd):
+                raise ValueError(f"alignment_heads: ({l}, {h}) is outside {Ld} layers x {Hd} heads")
+    if not heads:
+        raise ValueError("no alignment head: alignment_heads is empty or the model has no decoder layer")
+    if Hd > 32:
+        raise ValueError("tmi_align_cost takes at most 32 heads per layer")
+    heads = sorted(heads)
+    weights = {}
+    for l, h in heads:
+        weights.setdefault(l, [0.0] * Hd)[h] = 1.0 / len(heads)
+    return {"N": N, "n": n, "lengths": lens, "num_frames": nf, "medfilt_width": width, "heads": heads, "head_weights": weights}
 
 
 def check_output_attentions(cfg: WhisperConfig, output_attentions) -> Tuple[str, ...]:
@@ -1619,13 +1843,16 @@ def dummy_waveform(seed: int = DUMMY_AUDIO_SEED) -> np.ndarray:
 
 
 def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beams=1, length_penalty=1.0, do_sample=False,
-                     temperature=1.0, top_k=None, top_p=None, seed=0):
+                     temperature=1.0, top_k=None, top_p=None, seed=0, return_timestamps=False):
     """W:962-986: waveform -> log-mel (frontend.LogMelFrontend, channels-first: the layout the encoder reads; the reference
     feeds [frames, 80] un-transposed) -> ``model.generate`` -> ``tokenizer.decode(ids)``, or the ids
     (int32 numpy array, start token first) without a tokenizer.  ``audio``: a waveform (1-D tensor or array, 16 kHz), a
     ``.wav`` path, or None for the reference's 30 s dummy clip (seeded).  ``num_beams`` > 1: beam search (the best
     hypothesis), with ``length_penalty``.  ``do_sample``: sampled decoding with ``temperature``, ``top_k``, ``top_p`` and
-    ``seed`` (``generate(do_sample=True)``)."""
+    ``seed`` (``generate(do_sample=True)``).  ``return_timestamps=True``: -> {"text" (with a tokenizer) or "ids",
+    "token_start_times", "token_end_times" (fp32 numpy arrays, seconds, one entry per token after the start token)} from
+    ``model.align`` with the clip's own number of encoder frames; ``max_length`` is then capped at
+    max_target_positions - 1."""
     from .frontend import LogMelFrontend
     if audio is None:
         wav = dummy_waveform()
@@ -1638,13 +1865,28 @@ def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beam
     if fe is None:
         fe = model._frontend = LogMelFrontend(device=model.device, n_mels=model.config.n_mels)
     feats = fe(wav)
+    if return_timestamps:
+        max_length = min(int(max_length), model.config.max_target_positions - 1)
     if do_sample:
         ids = model.generate(feats, max_length=max_length, num_beams=num_beams, do_sample=True, temperature=temperature,
-                             top_k=top_k, top_p=top_p, seed=seed)
+                             top_k=top_k, top_p=top_p, seed=seed, return_dict_in_generate=bool(return_timestamps))
     elif num_beams is not None and int(num_beams) > 1:
-        ids = model.generate(feats, max_length=max_length, num_beams=num_beams, length_penalty=length_penalty)
+        ids = model.generate(feats, max_length=max_length, num_beams=num_beams, length_penalty=length_penalty,
+                             return_dict_in_generate=bool(return_timestamps))
     else:
         ids = model.generate(feats, max_length=max_length)
+    if return_timestamps:
+        out = ids if isinstance(ids, dict) else {"sequences": ids}
+        seqs = out["sequences"][:1]
+        n = int(out["lengths"][0]) if "lengths" in out else seqs.shape[1] - 1
+        # the clip's encoder frames: its log-mel frames through the stride-2 stem ("SAME" padding: rounded up)
+        frames = (fe.num_frames(wav.numel()) + 1) // 2
+        al = model.align(feats, seqs, [n], num_frames=[frames])
+        row = seqs[0, :1 + n].cpu().numpy()
+        res = {"token_start_times": al["token_start_times"][0, :n].cpu().numpy(),
+               "token_end_times": al["token_end_times"][0, :n].cpu().numpy()}
+        res["text" if tokenizer is not None else "ids"] = tokenizer.decode(row) if tokenizer is not None else row
+        return res
     ids = ids[0].cpu().numpy()
     if tokenizer is not None:
         return tokenizer.decode(ids)
