@@ -367,6 +367,66 @@ int tmi_dtw(const float* cost, int64_t c_sn, int64_t c_ss, const int32_t* rows, 
             int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * CTC inference (wav2vec2.py Wav2Vec2ForCTC: V:940-1001, forward only): the head's log-softmax, the greedy collapse, the
+ * loss and the forced alignment.  All arithmetic is fp32; `blank` is an argument; -inf is the additive zero, and a
+ * log-sum-exp LSE whose inputs are all -inf is -inf, never NaN.  No atomics, no allocation, no synchronisation: the same
+ * call gives the same bits.  Values in device memory (labels, lengths, argmaxes) are not seen by the calls: a length is
+ * clamped to its tensor, a symbol outside [0, lp_st) resp. [0, lp_ld) is never dereferenced.
+ *
+ * tmi_ctc_logsoftmax.  logits fp32, element (r, c) at logits[r*ld + c]; per row r < R over the columns c < V:
+ *   m = max x,  lse = m + log(sum exp(x - m)),  logp[r*lp_ld + c] = x[c] - lse,
+ *   argmax[r] = the smallest column among equal maxima of the given logits (a comparison of fp32 values: exact).
+ * 2 <= V <= 64 (one lane per column), ld >= V, lp_ld >= V, R <= 2^30.  Columns past V and rows past R are neither read
+ * nor written.  A row that is -inf throughout gives NaN.
+ *
+ * tmi_ctc_greedy.  argmax int32 [N][T_max], logp fp32 [N][T_max][lp_ld], frame_lens int32 [N].  With a = argmax of item n
+ * and len = min(frame_lens[n], T_max): frame t < len emits its token when a[t] != blank && (t == 0 || a[t] != a[t-1]).
+ *   tokens[n*T_max + k]    the k-th emitted token, in frame order, dense
+ *   tok_start[n*T_max + k] that frame;  tok_end[n*T_max + k] the last frame of its run of equal argmaxes, plus 1
+ *   out_len[n]             the number of emitted tokens
+ *   best_logprob[n]        sum over t < len of logp[t][a[t]]: thread i of 256 adds its frames t = i, i + 256, .. in
+ *                          ascending t, the 64 lanes of a wave meet in a butterfly (lane distance 32, 16, .., 1), the four
+ *                          wave sums are added ((w0 + w1) + w2) + w3
+ * Entries at or past out_len[n] are not written; an item with frame_lens[n] < 1 is skipped entirely (nothing of it is
+ * read or written, out_len[n] included).  1 <= N <= 65535 (one workgroup each), T_max, lp_ld <= 2^30.
+ *
+ * tmi_ctc_forward.  logp: element (n, t, c) at logp[n*lp_sn + t*lp_st + c]; labels int32 [N][L_max]; L = label_lens[n],
+ * T = frame_lens[n]; ext = [blank, l1, blank, l2, .., blank] with S = 2L + 1 states:
+ *   alpha_0(0) = lp[0][blank], alpha_0(1) = lp[0][l1], every other -inf
+ *   alpha_t(s) = lp[t][ext_s] + LSE(alpha_{t-1}(s), alpha_{t-1}(s-1), alpha_{t-1}(s-2))
+ *                the third term only if ext_s != blank && ext_s != ext_{s-2}
+ *   LSE(a0, a1, a2) = m + log((exp(a0 - m) + exp(a1 - m)) + exp(a2 - m)), m = the maximum, an absent term -inf
+ *   nll[n] = -LSE(alpha_{T-1}(S-1), alpha_{T-1}(S-2));  L = 0: -alpha_{T-1}(0)
+ * An item without a path (too few frames, T < 1) gives nll = +inf and infeasible[n] = 1 (else 0); with zero_infinity its
+ * nll is 0.  One workgroup per item, one thread per extended state: 1 <= L_max <= 511, 1 <= N <= 65535,
+ * 1 <= T_max <= 2^31 - 17, lp_sn >= T_max*lp_st, 0 <= blank < lp_st <= 2^30.
+ *
+ * tmi_ctc_viterbi.  The same recursion with max for LSE: the candidates are compared in the order stay (s), step (s-1),
+ * skip (s-2), the largest wins and a tie goes to the earliest in that order.  The end state is S-2 if its value is
+ * strictly larger than that of S-1, else S-1.  The path is traced back on the device:
+ *   tok_start[n*L_max + i] the first frame in state 2i + 1, tok_end[n*L_max + i] the last such frame plus 1  (i < L)
+ *   total[n]               the path's log-probability
+ *   states (may be NULL)   int32 [N][T_max]: the extended state of frame t < T
+ * An item without a path: total = -inf, bounds -1, states -1, infeasible[n] = 1.  Nothing past label_lens[n] or
+ * frame_lens[n] is written.  T_max <= 4096 here; workspace: tmi_ctc_workspace_bytes (the moves, 2 bits per frame and
+ * state; -1 outside the limits), any contents.
+ * TMI_ERR_INVALID (nothing is launched): a NULL or misaligned pointer, a size outside the limits above, a stride too
+ * small, blank outside the row, a flag that is not 0 / 1, a workspace too small. */
+int tmi_ctc_logsoftmax(const float* logits, int64_t ld, int64_t R, int64_t V, float* logp, int64_t lp_ld, int32_t* argmax,
+                       void* stream);
+int tmi_ctc_greedy(const int32_t* argmax, const float* logp, int64_t lp_ld, const int32_t* frame_lens, int32_t blank,
+                   int32_t* tokens, int32_t* out_len, int32_t* tok_start, int32_t* tok_end, float* best_logprob, int64_t N,
+                   int64_t T_max, void* stream);
+int tmi_ctc_forward(const float* logp, int64_t lp_sn, int64_t lp_st, const int32_t* labels, const int32_t* label_lens,
+                    const int32_t* frame_lens, int32_t blank, float* nll, int32_t* infeasible, int64_t N, int64_t L_max,
+                    int64_t T_max, int32_t zero_infinity, void* stream);
+int64_t tmi_ctc_workspace_bytes(int64_t N, int64_t L_max, int64_t T_max);
+int tmi_ctc_viterbi(const float* logp, int64_t lp_sn, int64_t lp_st, const int32_t* labels, const int32_t* label_lens,
+                    const int32_t* frame_lens, int32_t blank, int32_t* tok_start, int32_t* tok_end, float* total,
+                    int32_t* states, int32_t* infeasible, int64_t N, int64_t L_max, int64_t T_max, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Decoder token embedding + positional encoding (W:405-408) with the teacher-forcing
  * shift of W:559-563 folded in: id(b,t) = t == 0 ? start_id : labels[b, t-1].
  *   out[b,t,:] = table[id(b,t), :] + pe[t, :]

@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Inference job: CTC transcripts of padded clips from a Wav2Vec2ForCTC model (the reference's ``create_full_model("asr")``,
+speech_jobs/wav2vec2_dist.py V:940-1001, forward only).
+
+Loads weights (``--weights``: a ``save_checkpoint`` or ``save_weights`` file of a CTC model; ``--pretrained_encoder``: a
+``save_weights`` file of a pre-training model, whose base model is copied and whose heads are ignored; without either the
+model keeps its seeded initialisation), pads the ``--wav`` clips (16-bit PCM mono 16 kHz) to the longest of them - or,
+without one, takes ``--batch_size`` dummy clips of ``--seconds``, every second one cut to 60 % - builds the frame mask
+(``wav2vec2.frame_attention_mask``) and decodes greedily.  ``--labels FILE`` (one line of space-separated token ids per
+clip; an empty line: no labels) also scores the clips (``evaluate``) and aligns the labels to the frames (``align``).
+Prints one JSON line per clip: the token ids, with ``--timestamps`` their start and end times in seconds, the best path's
+log-probability, and with labels the nll, the edit distance of the transcript and the aligned times; then one summary line.
+There is no tokenizer: ids in, ids out.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def read_labels(path, n_clips):
+    rows = [[int(t) for t in line.split()] for line in open(path).read().splitlines()]
+    if len(rows) != n_clips:
+        raise SystemExit(f"--labels holds {len(rows)} lines for {n_clips} clips")
+    return rows
+
+
+def main(argv=None):
+    parser = argparse.ArgumentParser(description="Wav2Vec2 CTC transcripts of padded clips (greedy decode, loss, alignment)")
+    parser.add_argument("--model_size", default="base", choices=["tiny", "small", "base"])
+    parser.add_argument("--precision", choices=["bf16", "fp32"], default="bf16")
+    parser.add_argument("--weights", default=None, help="checkpoint of a CTC model to load")
+    parser.add_argument("--pretrained_encoder", default=None, help="save_weights file of a pre-training model: its base model is loaded")
+    parser.add_argument("--vocab_size", type=int, default=32)
+    parser.add_argument("--wav", action="append", default=[], help="16-bit PCM mono 16 kHz .wav file (repeatable)")
+    parser.add_argument("--batch_size", type=int, default=2, help="number of dummy clips when no --wav is given")
+    parser.add_argument("--seconds", type=float, default=2.0, help="length of the dummy clips")
+    parser.add_argument("--timestamps", action="store_true", help="print token start and end times")
+    parser.add_argument("--labels", default=None, help="file of token ids, one line per clip: evaluate and align")
+    args = parser.parse_args(argv)
+
+    import numpy as np
+    import torch
+    import tethys_speech_amd  # noqa: F401
+    from tethys_speech_amd import train, wav2vec2, whisper
+
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)
+    device = f"cuda:{local_rank}"
+    model = wav2vec2.create_full_model("asr", args.model_size, device=device, precision=args.precision,
+                                       vocab_size=args.vocab_size)
+    if args.pretrained_encoder:
+        wav2vec2.load_pretrained_encoder(model, args.pretrained_encoder)
+    if args.weights:
+        train.load_weights(model, args.weights)
+    if args.wav:
+        clips = [(p, whisper.read_wav(p)) for p in args.wav]
+    else:
+        n = max(1, int(args.seconds * 16000))
+        wave = whisper.dummy_waveform()[:n]
+        clips = [(f"dummy{i}", wave if i % 2 == 0 else wave[:max(1, (3 * n) // 5)]) for i in range(max(1, args.batch_size))]
+    lengths = [len(w) for _, w in clips]
+    T_in = max(lengths)
+    batch = np.zeros((len(clips), T_in), dtype=np.float32)
+    for row, (_, w) in zip(batch, clips):
+        row[:len(w)] = w
+    mask = wav2vec2.frame_attention_mask(model.config, lengths, T_in)
+    audio = torch.from_numpy(batch).to(device)
+    rows = read_labels(args.labels, len(clips)) if args.labels else None
+    torch.cuda.synchronize()
+    t0 = time.time()
+    dec = model.decode(audio, attention_mask=mask)
+    ev = al = None
+    if rows is not None:
+        L = max(len(r) for r in rows)
+        labels = torch.zeros(len(rows), L, dtype=torch.int64)
+        for i, r in enumerate(rows):
+            labels[i, :len(r)] = torch.tensor(r, dtype=torch.int64)
+        lens = [len(r) for r in rows]
+        ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True)
+        al = model.align(audio, labels, lens, attention_mask=mask)
+    torch.cuda.synchronize()
+    dt = time.time() - t0
+    frames = [int(x) for x in mask.sum(1).tolist()]
+    for i, (name, _) in enumerate(clips):
+        k = int(dec["lengths"][i])
+        line = {"clip": name, "frames": frames[i], "tokens": dec["sequences"][i, :k].tolist(),
+                "best_path_logprob": float(dec["best_path_logprob"][i])}
+        if args.timestamps:
+            line["start"] = [round(t, 4) for t in dec["token_start_times"][i, :k].tolist()]
+            line["end"] = [round(t, 4) for t in dec["token_end_times"][i, :k].tolist()]
+        if rows is not None:
+            n = len(rows[i])
+            line["labels"] = rows[i]
+            line["nll"] = float(ev["nll"][i])
+            line["infeasible"] = bool(ev["infeasible"][i])
+            line["edits"] = wav2vec2.edit_distance(np.asarray(line["tokens"]), np.asarray(rows[i]))
+            line["path_logprob"] = float(al["path_logprob"][i])
+            line["aligned_start"] = [round(t, 4) for t in al["token_start_times"][i, :n].tolist()]
+            line["aligned_end"] = [round(t, 4) for t in al["token_end_times"][i, :n].tolist()]
+        print(json.dumps(line), flush=True)
+    summary = {"clips": len(clips), "samples": T_in, "seconds": round(dt, 4)}
+    if ev is not None:
+        summary.update({k: ev[k] for k in ("loss", "nll_sum", "n_infeasible", "n_edits", "n_ref_tokens", "token_error_rate")})
+    print(json.dumps(summary), flush=True)
+
+
+if __name__ == "__main__":
+    main()

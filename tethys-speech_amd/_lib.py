@@ -164,6 +164,12 @@ SIGNATURES = {
                                c_i32, c_i32, c_i32, c_vp]),
     "tmi_dtw_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "tmi_dtw": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "tmi_ctc_logsoftmax": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),
+    "tmi_ctc_greedy": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+    "tmi_ctc_forward": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp]),
+    "tmi_ctc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "tmi_ctc_viterbi": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
+                                c_vp, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

@@ -489,6 +489,88 @@ def dtw(cost, rows, cols, tok_start, tok_end, total, workspace, path=None, path_
                             workspace.data_ptr(), workspace.numel() * 4, stream()), "tmi_dtw")
 
 
+def _ctc_logp(logp, what):
+    if logp.dtype != torch.float32 or logp.dim() != 3 or logp.stride(2) != 1 or logp.stride(0) < logp.shape[1] * logp.stride(1):
+        raise ValueError(f"{what}: logp must be float32 [N, T, V] with unit column stride")
+    return logp.shape
+
+
+def ctc_logsoftmax(logits, V, logp, argmax):
+    """Row-wise log-softmax and argmax over the first ``V`` columns (tmi_ctc_logsoftmax in include/tethys_mi.h): ``logits``
+    and ``logp`` fp32 [R, >= V] with unit column stride, ``argmax`` int32 [R]."""
+    R = logits.shape[0]
+    if (logits.dtype != torch.float32 or logp.dtype != torch.float32 or logits.dim() != 2 or logp.dim() != 2 or
+            logits.stride(1) != 1 or logp.stride(1) != 1 or logp.shape[0] != R):
+        raise ValueError("ctc_logsoftmax: logits and logp must be float32 [R, >= V] with unit column stride")
+    _i32_dev(argmax, R, "ctc_logsoftmax: argmax")
+    with _probe("ctc_logsoftmax", 8.0 * R * V):
+        check(lib().tmi_ctc_logsoftmax(logits.data_ptr(), logits.stride(0), R, int(V), logp.data_ptr(), logp.stride(0),
+                                       argmax.data_ptr(), stream()), "tmi_ctc_logsoftmax")
+
+
+def ctc_greedy(argmax, logp, frame_lens, blank, tokens, out_len, tok_start, tok_end, best_logprob):
+    """The greedy CTC collapse of every item (tmi_ctc_greedy): ``argmax`` int32 [N, T], ``logp`` fp32 [N, T, V] contiguous
+    in (t, v); ``tokens`` / ``tok_start`` / ``tok_end`` int32 [N, T], ``out_len`` int32 [N], ``best_logprob`` fp32 [N]."""
+    N, T, _ = _ctc_logp(logp, "ctc_greedy")
+    if logp.stride(0) != T * logp.stride(1):
+        raise ValueError("ctc_greedy: logp must be [N, T, lp_ld] without an item stride of its own")
+    for t, n, w in ((argmax, N * T, "argmax"), (frame_lens, N, "frame_lens"), (tokens, N * T, "tokens"), (out_len, N, "out_len"),
+                    (tok_start, N * T, "tok_start"), (tok_end, N * T, "tok_end")):
+        _i32_dev(t, n, "ctc_greedy: " + w)
+    _f32_flat(best_logprob, N, "ctc_greedy: best_logprob")
+    with _probe("ctc_greedy", 8.0 * N * T):
+        check(lib().tmi_ctc_greedy(argmax.data_ptr(), logp.data_ptr(), logp.stride(1), frame_lens.data_ptr(), int(blank),
+                                   tokens.data_ptr(), out_len.data_ptr(), tok_start.data_ptr(), tok_end.data_ptr(),
+                                   best_logprob.data_ptr(), N, T, stream()), "tmi_ctc_greedy")
+
+
+def ctc_forward(logp, labels, label_lens, frame_lens, blank, nll, infeasible, zero_infinity=False):
+    """The CTC negative log-likelihood of every item (tmi_ctc_forward): ``logp`` fp32 [N, T, V], ``labels`` int32
+    [N, L_max] contiguous, lengths int32 [N]; ``nll`` fp32 [N], ``infeasible`` int32 [N]."""
+    N, T, _ = _ctc_logp(logp, "ctc_forward")
+    if labels.dim() != 2 or labels.shape[0] != N:
+        raise ValueError("ctc_forward: labels must be int32 [N, L_max]")
+    L = labels.shape[1]
+    for t, n, w in ((labels, N * L, "labels"), (label_lens, N, "label_lens"), (frame_lens, N, "frame_lens"),
+                    (infeasible, N, "infeasible")):
+        _i32_dev(t, n, "ctc_forward: " + w)
+    _f32_flat(nll, N, "ctc_forward: nll")
+    with _probe("ctc_forward", 4.0 * N * T * (2 * L + 1)):
+        check(lib().tmi_ctc_forward(logp.data_ptr(), logp.stride(0), logp.stride(1), labels.data_ptr(), label_lens.data_ptr(),
+                                    frame_lens.data_ptr(), int(blank), nll.data_ptr(), infeasible.data_ptr(), N, L, T,
+                                    1 if zero_infinity else 0, stream()), "tmi_ctc_forward")
+
+
+def ctc_workspace_elems(N: int, L_max: int, T_max: int) -> int:
+    """int32 elements of tmi_ctc_viterbi's workspace (tmi_ctc_workspace_bytes / 4)."""
+    n = int(lib().tmi_ctc_workspace_bytes(N, L_max, T_max))
+    if n < 0:
+        raise ValueError(f"tmi_ctc_viterbi takes 1 <= N <= 65535 items of at most 511 labels x 4096 frames, got {N} x {L_max} x {T_max}")
+    return n // 4
+
+
+def ctc_viterbi(logp, labels, label_lens, frame_lens, blank, tok_start, tok_end, total, infeasible, workspace, states=None):
+    """The best CTC path of every item (tmi_ctc_viterbi): inputs as ``ctc_forward``; ``tok_start`` / ``tok_end`` int32
+    [N, L_max], ``total`` fp32 [N], ``infeasible`` int32 [N], ``states`` None or int32 [N, T]; ``workspace`` int32 of
+    ``ctc_workspace_elems`` entries, any contents."""
+    N, T, _ = _ctc_logp(logp, "ctc_viterbi")
+    if labels.dim() != 2 or labels.shape[0] != N:
+        raise ValueError("ctc_viterbi: labels must be int32 [N, L_max]")
+    L = labels.shape[1]
+    for t, n, w in ((labels, N * L, "labels"), (label_lens, N, "label_lens"), (frame_lens, N, "frame_lens"),
+                    (tok_start, N * L, "tok_start"), (tok_end, N * L, "tok_end"), (infeasible, N, "infeasible"),
+                    (workspace, ctc_workspace_elems(N, L, T), "workspace")):
+        _i32_dev(t, n, "ctc_viterbi: " + w)
+    if states is not None:
+        _i32_dev(states, N * T, "ctc_viterbi: states")
+    _f32_flat(total, N, "ctc_viterbi: total")
+    with _probe("ctc_viterbi", 4.0 * N * T * (2 * L + 1)):
+        check(lib().tmi_ctc_viterbi(logp.data_ptr(), logp.stride(0), logp.stride(1), labels.data_ptr(), label_lens.data_ptr(),
+                                    frame_lens.data_ptr(), int(blank), tok_start.data_ptr(), tok_end.data_ptr(),
+                                    total.data_ptr(), ptr(states), infeasible.data_ptr(), N, L, T, workspace.data_ptr(),
+                                    workspace.numel() * 4, stream()), "tmi_ctc_viterbi")
+
+
 def masked_mean_pool(x, mask, out, B, T, C):
     """out[b, c] = sum_t x[b, t, c] mask[b, t] / sum_t mask[b, t] (fp32 [B, C]); ``mask`` fp32 [B, T] or None: the plain mean."""
     if not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C or x.numel() != B * T * C:

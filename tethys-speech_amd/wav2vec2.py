@@ -17,6 +17,7 @@ positional Conv1D runs as one batched window-GEMM over a group-major repack.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from dataclasses import dataclass
@@ -52,6 +53,10 @@ class Wav2Vec2Config:  # V:24-128 (fields read by the pre-training path)
     hidden_dropout: float = 0.1       # V:69-71; applied only after enable_dropout (bf16 path), see blocks.py
     activation_dropout: float = 0.1
     attention_dropout: float = 0.1
+    vocab_size: int = 32              # V:104; the CTC head's columns (Wav2Vec2ForCTC)
+    ctc_blank_id: int = 0
+    ctc_loss_reduction: str = "sum"   # V:94-95
+    ctc_zero_infinity: bool = False
 
 
 # dropout site ids (KernelBlocks._site_seed; restated in oracle/dropout.py): V:296, V:779, V:560 (x2), then per
@@ -173,7 +178,13 @@ def check_evaluate_args(cfg: Wav2Vec2Config, audio, neg_indices, attention_mask=
 
 
 class W2VArena(Arena):
-    def __init__(self, cfg: Wav2Vec2Config, device):
+    """``head="pretraining"``: the base model, the quantiser and the two projection heads (V:826-865).  ``head="ctc"``: the
+    base model's parameters under the same names, then ``lm_head`` (V:940-975) - no quantiser, project_q or project_hid."""
+
+    def __init__(self, cfg: Wav2Vec2Config, device, head: str = "pretraining"):
+        if head not in ("pretraining", "ctc"):
+            raise ValueError('head must be "pretraining" or "ctc"')
+        pre = head == "pretraining"
         H, I = cfg.hidden_size, cfg.intermediate_size
         C, G = cfg.conv_dim[-1], cfg.num_conv_pos_embedding_groups
         spec: List[Tuple[str, Tuple[int, ...]]] = []
@@ -192,11 +203,12 @@ class W2VArena(Arena):
         spec.extend([("feature_projection.kernel", (C, H)), ("feature_projection.bias", (H,))])
         ln("feature_projection_layer_norm", H)
         gd = cfg.codevector_dim // cfg.num_codevector_groups
-        spec.extend([("quantizer.projection.kernel", (H, cfg.codevector_dim)), ("quantizer.projection.bias", (cfg.codevector_dim,)),
-                     ("quantizer.codevectors", (cfg.num_codevector_groups, cfg.num_codevectors_per_group, gd))])
-        spec.extend([("project_q.dense.kernel", (cfg.codevector_dim, cfg.proj_codevector_dim)),
-                     ("project_q.dense.bias", (cfg.proj_codevector_dim,))])
-        ln("project_q.layer_norm", cfg.proj_codevector_dim)
+        if pre:
+            spec.extend([("quantizer.projection.kernel", (H, cfg.codevector_dim)), ("quantizer.projection.bias", (cfg.codevector_dim,)),
+                         ("quantizer.codevectors", (cfg.num_codevector_groups, cfg.num_codevectors_per_group, gd))])
+            spec.extend([("project_q.dense.kernel", (cfg.codevector_dim, cfg.proj_codevector_dim)),
+                         ("project_q.dense.bias", (cfg.proj_codevector_dim,))])
+            ln("project_q.layer_norm", cfg.proj_codevector_dim)
         for i in range(cfg.num_hidden_layers):
             p = f"encoder.layers.{i}"
             ln(f"{p}.attention_layer_norm", H)
@@ -205,13 +217,18 @@ class W2VArena(Arena):
             ln(f"{p}.feed_forward_layer_norm", H)
             spec.extend([(f"{p}.feed_forward.intermediate_dense.kernel", (H, I)), (f"{p}.feed_forward.intermediate_dense.bias", (I,)),
                          (f"{p}.feed_forward.output_dense.kernel", (I, H)), (f"{p}.feed_forward.output_dense.bias", (H,))])
-        spec.extend([("project_hid.dense.kernel", (H, cfg.proj_codevector_dim)), ("project_hid.dense.bias", (cfg.proj_codevector_dim,))])
-        ln("project_hid.layer_norm", cfg.proj_codevector_dim)
+        if pre:
+            spec.extend([("project_hid.dense.kernel", (H, cfg.proj_codevector_dim)), ("project_hid.dense.bias", (cfg.proj_codevector_dim,))])
+            ln("project_hid.layer_norm", cfg.proj_codevector_dim)
+        else:
+            spec.extend([("lm_head.kernel", (H, cfg.vocab_size)), ("lm_head.bias", (cfg.vocab_size,))])
         super().__init__(spec, device)
 
 
 class Wav2Vec2ForPreTraining(KernelBlocks):
     """V:826-937: the pre-training step, and the forward pass alone of the model inside it (V:768-825, ``forward_infer``)."""
+
+    _arena_head = "pretraining"  # which heads follow the base model in the arena (W2VArena)
 
     def __init__(self, config: Wav2Vec2Config, device="cuda:0", precision: str = "bf16", seed: int = 1234):
         if precision not in ("fp32", "bf16"):
@@ -230,7 +247,7 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
             raise ValueError("the fused attention kernel is built for head_dim 64")
         if config.conv_dim[-1] % config.num_conv_pos_embedding_groups:
             raise ValueError("conv_dim must divide by the group count")
-        self.arena = W2VArena(config, self.device)
+        self.arena = W2VArena(config, self.device, self._arena_head)
         self.arena.init_keras_defaults(seed)
         self.ws: Dict[str, torch.Tensor] = {}
         self._ws_sets: Dict[tuple, Dict[str, torch.Tensor]] = {}
@@ -910,7 +927,12 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                 pooled = torch.empty(B, H, dtype=torch.float32, device=self.device)
                 ops.masked_mean_pool(x, mask_dev, pooled, B, T, H)
                 result["pooled_output"] = pooled
+            self._infer_head(x, inf, result)
         return result
+
+    def _infer_head(self, x, inf, result):
+        """What a model with a head of its own adds to ``forward_infer``'s outputs from the last hidden state ``x`` [B*T, H],
+        still inside the inference workspace (Wav2Vec2ForCTC: logits and log_probs).  The base model adds nothing."""
 
 
     # -- evaluation (forward only): the held-out contrastive loss, its accuracy and the code usage ------------------------
@@ -995,9 +1017,299 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
         return result
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# CTC inference (V:940-1001): the head, greedy decoding, the loss and forced alignment.  Forward only - CTC gradients and
+# fine-tuning are not built.
+CTC_MAX_LABELS = 511   # tmi_ctc_forward: one thread per extended state, 2 L + 1 <= 1023
+CTC_MAX_FRAMES = 4096  # tmi_ctc_viterbi: the moves of a walk-back piece are staged in LDS
+SAMPLE_RATE = 16000
+
+
+def frame_seconds(cfg: Wav2Vec2Config) -> float:
+    """Seconds per encoder frame: the product of the conv strides over the sample rate (20 ms for every reference size)."""
+    return float(np.prod(cfg.conv_stride)) / SAMPLE_RATE
+
+
+def check_ctc_args(cfg: Wav2Vec2Config, inputs_shape, labels=None, label_lengths=None, attention_mask=None):
+    """Host validation of ``Wav2Vec2ForCTC.decode`` / ``evaluate`` / ``align`` (no GPU needed; the kernels cannot see values
+    in device memory).  ``inputs_shape`` (B, T_in); ``labels`` None or integer [B, L_max] with every entry inside its row's
+    ``label_lengths`` in [0, vocab_size) and not the blank, L_max <= 511; ``label_lengths`` None (L_max everywhere) or B
+    integers in [0, L_max]; ``attention_mask`` None or [B, T] over frames (``frame_attention_mask``), values 0 or 1 only,
+    every row ones first and zeros behind them, at least one frame per row.
+    -> (B, T, frame_lens int32 [B] - the mask's row sums, or T -, the mask as float32 on the host or None, labels int32
+    [B, max(L_max, 1)] or None, label_lengths int32 [B] or None)."""
+    if len(inputs_shape) != 2 or int(inputs_shape[0]) < 1 or int(inputs_shape[1]) < 1:
+        raise ValueError("inputs must be [B, T_in]")
+    B, T_in = int(inputs_shape[0]), int(inputs_shape[1])
+    V, blank = cfg.vocab_size, cfg.ctc_blank_id
+    if not 2 <= V <= 64:
+        raise ValueError("the CTC head takes 2 <= vocab_size <= 64 (tmi_ctc_logsoftmax: one lane per column)")
+    if not 0 <= blank < V:
+        raise ValueError("ctc_blank_id must be in [0, vocab_size)")
+    T = frame_lengths(cfg, [T_in])[0]
+    mask, frame_lens = None, np.full(B, T, dtype=np.int32)
+    if attention_mask is not None:
+        mask = torch.as_tensor(attention_mask).detach().to("cpu")
+        if mask.dim() != 2 or tuple(mask.shape) != (B, T):
+            raise ValueError(f"attention_mask must be [B, T] over frames = [{B}, {T}] (frame_attention_mask), got {list(mask.shape)}")
+        mask = mask.to(torch.float32).contiguous()
+        if not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError("attention_mask must be binary here: a frame belongs to the clip or it does not")
+        frame_lens = mask.sum(dim=1).to(torch.int32).numpy()
+        if not bool((mask == (torch.arange(T)[None, :] < torch.from_numpy(frame_lens)[:, None]).to(torch.float32)).all()):
+            raise ValueError("attention_mask must be a prefix per row: ones on the clip's frames, zeros behind them")
+        if int(frame_lens.min()) < 1:
+            raise ValueError("attention_mask leaves a row without a frame")
+    lab = lens = None
+    if labels is None:
+        if label_lengths is not None:
+            raise ValueError("label_lengths come with labels")
+    else:
+        lab = torch.as_tensor(labels).detach().to("cpu")
+        if lab.dim() != 2 or lab.shape[0] != B or lab.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"labels must be integer [B, L_max] = [{B}, L_max]")
+        L_max = int(lab.shape[1])
+        if L_max > CTC_MAX_LABELS:
+            raise ValueError(f"at most {CTC_MAX_LABELS} labels per item (tmi_ctc_forward: one thread per extended state)")
+        if label_lengths is None:
+            lens = np.full(B, L_max, dtype=np.int32)
+        else:
+            lens = np.asarray(torch.as_tensor(label_lengths).detach().to("cpu").numpy()).astype(np.int64).reshape(-1)
+            if lens.shape[0] != B or (lens < 0).any() or (lens > L_max).any():
+                raise ValueError(f"label_lengths must be B = {B} integers in [0, L_max = {L_max}]")
+            lens = lens.astype(np.int32)
+        lab = lab.to(torch.int32).numpy()
+        inside = np.arange(L_max)[None, :] < lens[:, None]
+        if ((lab < 0) | (lab >= V))[inside].any():
+            raise ValueError(f"labels must be in [0, {V}) inside their length")
+        if (lab == blank)[inside].any():
+            raise ValueError(f"labels must not hold the blank ({blank}) inside their length")
+        if L_max == 0:
+            lab = np.zeros((B, 1), dtype=np.int32)  # (the kernels take L_max >= 1; every length is 0)
+        lab = np.ascontiguousarray(lab)
+    return B, T, frame_lens, mask, lab, lens
+
+
+def edit_distance(hyp: np.ndarray, ref: np.ndarray) -> int:
+    """Levenshtein distance of two integer sequences, one row of the table per hypothesis token, each row in numpy:
+    d[j] = min(up + 1, diagonal + (h != r_j), d[j-1] + 1), the last term as a running minimum of d[j] - j."""
+    hyp, ref = np.asarray(hyp), np.asarray(ref)
+    n = len(ref)
+    idx = np.arange(n + 1)
+    d = idx.copy()
+    for i, h in enumerate(hyp, 1):
+        cand = np.empty(n + 1, dtype=np.int64)
+        cand[0] = i
+        cand[1:] = np.minimum(d[1:] + 1, d[:-1] + (ref != h))
+        d = np.minimum.accumulate(cand - idx) + idx
+    return int(d[n])
+
+
+class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
+    """V:940-1001 at inference: the base model (stem, positional conv, projection, encoder - the blocks and the inference
+    workspace of ``Wav2Vec2ForPreTraining``) and a Dense head (V:972-975) over ``vocab_size`` symbols, with greedy CTC
+    decoding, the CTC loss and forced alignment on the kernels of csrc/ctc.hip.  Every public method runs under
+    ``torch.no_grad()`` on the inference workspace with dropout off, and reads or writes nothing of the training state.
+    The training entry points raise: CTC gradients are not built."""
+
+    _arena_head = "ctc"
+
+    def __init__(self, config: Wav2Vec2Config, device="cuda:0", precision: str = "bf16", seed: int = 1234):
+        if not 2 <= config.vocab_size <= 64:
+            raise ValueError("the CTC head takes 2 <= vocab_size <= 64 (tmi_ctc_logsoftmax: one lane per column)")
+        if not 0 <= config.ctc_blank_id < config.vocab_size:
+            raise ValueError("ctc_blank_id must be in [0, vocab_size)")
+        if config.ctc_loss_reduction not in ("sum", "mean"):
+            raise ValueError('ctc_loss_reduction must be "sum" or "mean"')
+        super().__init__(config, device=device, precision=precision, seed=seed)
+
+    def forward_backward(self, *a, **k):
+        raise NotImplementedError("CTC fine-tuning is not built")
+
+    def __call__(self, inputs, attention_mask=None, training=False, **kw):
+        """``model(inputs, attention_mask=None, training=False)`` is ``forward_infer``."""
+        if training:
+            raise NotImplementedError("CTC fine-tuning is not built")
+        return self.forward_infer(inputs, attention_mask=attention_mask, **kw)
+
+    # -- the head ----------------------------------------------------------------------------------------------------
+    def _ctc_buffers(self, inf):
+        """The head's buffers, added to the inference set on the first call."""
+        if "ctc_logits" in inf["ws"]:
+            return
+        B, V = inf["key"][0], self.config.vocab_size
+        R = B * inf["T"]
+        saved, self.ws = self.ws, inf["ws"]
+        try:
+            self._buf("ctc_logits", (R, V), torch.float32)
+            self._buf("ctc_logp", (R, V), torch.float32)
+            self._buf("ctc_argmax", (R,), torch.int32)
+        finally:
+            self.ws = saved
+
+    def _ctc_head(self, x, inf):
+        """V:972-975: logits = x . lm_head + bias as ONE tmi_gemm into fp32 (bf16 operands on the bf16 model: the logits are
+        never rounded to bf16), then tmi_ctc_logsoftmax.  -> (logits, log_probs fp32 [B*T, V], argmax int32 [B*T])."""
+        self._ctc_buffers(inf)
+        ws = inf["ws"]
+        self._dense_fwd(x, "lm_head.kernel", ws["ctc_logits"])
+        ops.ctc_logsoftmax(ws["ctc_logits"], self.config.vocab_size, ws["ctc_logp"], ws["ctc_argmax"])
+        return ws["ctc_logits"], ws["ctc_logp"], ws["ctc_argmax"]
+
+    def _infer_head(self, x, inf, result):
+        B, T, V = inf["key"][0], inf["T"], self.config.vocab_size
+        logits, logp, _ = self._ctc_head(x, inf)
+        result["logits"] = logits.view(B, T, V).clone()
+        result["log_probs"] = logp.view(B, T, V).clone()
+
+    @contextlib.contextmanager
+    def _ctc_pass(self, inputs, labels=None, label_lengths=None, attention_mask=None):
+        """The forward pass and the head of one batch, inside the inference workspace: yields what decode / evaluate /
+        align share."""
+        if not torch.is_tensor(inputs) or inputs.dim() != 2 or inputs.dtype != torch.float32:
+            raise TypeError("inputs must be float32 [B, T_in]")
+        cfg = self.config
+        B, T, frame_lens, mask, lab, lens = check_ctc_args(cfg, tuple(inputs.shape), labels, label_lengths, attention_mask)
+        audio = inputs.to(self.device).contiguous()
+        inf = self._infer_prepare(B, inputs.shape[1])
+        with self._inference(inf):
+            key_bias = None if mask is None else ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, as forward_infer
+            x, _ = self._infer_body(audio, inf, key_bias)
+            _, logp, amax = self._ctc_head(x, inf)
+            i32 = dict(dtype=torch.int32, device=self.device)
+            yield {"B": B, "T": T, "V": cfg.vocab_size, "logp": logp.view(B, T, cfg.vocab_size), "argmax": amax.view(B, T),
+                   "frame_lens": torch.from_numpy(frame_lens).to(self.device), "frame_lens_host": frame_lens,
+                   "labels": None if lab is None else torch.from_numpy(lab).to(self.device), "labels_host": lab,
+                   "label_lens": None if lens is None else torch.from_numpy(lens).to(self.device), "label_lens_host": lens,
+                   "L_max": 0 if labels is None else int(torch.as_tensor(labels).shape[1]), "i32": i32, "f32": dict(dtype=torch.float32, device=self.device)}
+
+    def _greedy(self, c):
+        B, T = c["B"], c["T"]
+        out = {n: torch.full((B, T), -1, **c["i32"]) for n in ("tokens", "start", "end")}
+        out["len"] = torch.zeros(B, **c["i32"])
+        out["best"] = torch.zeros(B, **c["f32"])
+        ops.ctc_greedy(c["argmax"], c["logp"], c["frame_lens"], self.config.ctc_blank_id, out["tokens"], out["len"],
+                       out["start"], out["end"], out["best"])
+        return out
+
+    def _times(self, frames):
+        return torch.where(frames >= 0, frames.to(torch.float64) * frame_seconds(self.config), -1.0)
+
+    @torch.no_grad()
+    def decode(self, inputs, attention_mask=None):
+        """Greedy CTC decoding: per frame the most probable symbol, runs of equal symbols collapsed, blanks dropped
+        (tmi_ctc_greedy).  -> ``sequences`` int32 [B, max length] padded with -1, ``lengths`` int32 [B],
+        ``token_start_frames`` / ``token_end_frames`` int32 (the first frame of a token's run and its last plus 1; -1 in the
+        padding), ``token_start_times`` / ``token_end_times`` float64 seconds (frames x ``frame_seconds``; -1 in the padding),
+        ``best_path_logprob`` fp32 [B]: the sum of the chosen symbols' log-probabilities over the clip's frames."""
+        with self._ctc_pass(inputs, attention_mask=attention_mask) as c:
+            g = self._greedy(c)
+            n = max(int(g["len"].max()), 0)  # (the one host read: the width of the result)
+            st, en = g["start"][:, :n].clone(), g["end"][:, :n].clone()
+            return {"sequences": g["tokens"][:, :n].clone(), "lengths": g["len"], "token_start_frames": st,
+                    "token_end_frames": en, "token_start_times": self._times(st), "token_end_times": self._times(en),
+                    "best_path_logprob": g["best"]}
+
+    @torch.no_grad()
+    def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False):
+        """The CTC loss of one batch and the error rate of its greedy transcript, forward only.  ``labels`` integer
+        [B, L_max] with ``label_lengths`` [B] (see ``check_ctc_args``).  Returns Python numbers, float64 on the host, so
+        that shards add up: ``nll_sum`` over the feasible items, ``n_items``, ``n_infeasible`` (items with fewer frames than
+        their labels need: nll = +inf); ``loss`` by ``ctc_loss_reduction`` as torch's ctc_loss - "sum": the sum of the
+        items' nll, "mean": the mean of nll / max(L, 1) - in which an infeasible item counts +inf, or 0 with
+        ``ctc_zero_infinity``; ``n_edits`` / ``n_ref_tokens`` / ``token_error_rate``: the Levenshtein distance of the greedy
+        transcript to the labels, summed over the items, over the number of labels.  ``return_items`` adds the device
+        tensors ``nll`` fp32 [B] (+inf where infeasible, whatever ``ctc_zero_infinity``), ``infeasible`` int32 [B],
+        ``sequences`` / ``lengths`` of the greedy transcript."""
+        cfg = self.config
+        with self._ctc_pass(inputs, labels, label_lengths, attention_mask) as c:
+            B = c["B"]
+            nll, bad = torch.zeros(B, **c["f32"]), torch.zeros(B, **c["i32"])
+            ops.ctc_forward(c["logp"], c["labels"], c["label_lens"], c["frame_lens"], cfg.ctc_blank_id, nll, bad, False)
+            g = self._greedy(c)
+            # one copy of what the host needs: the tokens and lengths of the transcript, nll and the flags
+            host = torch.cat([g["tokens"].reshape(-1), g["len"], bad, nll.view(torch.int32)]).cpu()
+            T = c["T"]
+            tok = host[:B * T].view(B, T).numpy()
+            hl, hbad = host[B * T:B * T + B].numpy(), host[B * T + B:B * T + 2 * B].numpy()
+            hnll = host[B * T + 2 * B:].view(torch.float32).double().numpy()
+            ok = hbad == 0
+            lens, lab = c["label_lens_host"], c["labels_host"]
+            nll_sum = float(hnll[ok].sum())
+            item = np.where(ok, hnll, 0.0 if cfg.ctc_zero_infinity else np.inf)
+            if cfg.ctc_loss_reduction == "mean":
+                loss = float((item / np.maximum(lens, 1)).mean())
+            else:
+                loss = float(item.sum())
+            n_edits = sum(edit_distance(tok[b, :hl[b]], lab[b, :lens[b]]) for b in range(B))
+            n_ref = int(lens.sum())
+            result = {"nll_sum": nll_sum, "n_items": float(B), "n_infeasible": float((~ok).sum()), "loss": loss,
+                      "n_edits": float(n_edits), "n_ref_tokens": float(n_ref),
+                      "token_error_rate": n_edits / n_ref if n_ref else float("nan")}
+            if return_items:
+                n = max(int(hl.max()), 0)
+                result.update(nll=nll, infeasible=bad, sequences=g["tokens"][:, :n].clone(), lengths=g["len"])
+        return result
+
+    @torch.no_grad()
+    def align(self, inputs, labels, label_lengths=None, attention_mask=None, return_states=False):
+        """Forced alignment: the most probable CTC path that spells ``labels`` (tmi_ctc_viterbi; the tie rule is in
+        include/tethys_mi.h).  -> ``token_start_frames`` / ``token_end_frames`` int32 [B, L_max] (the first frame a token's
+        state holds and the last plus 1; -1 past ``label_lengths`` and for an item without a path), ``token_start_times`` /
+        ``token_end_times`` float64 seconds, ``path_logprob`` fp32 [B] (-inf without a path), ``infeasible`` int32 [B];
+        ``return_states`` adds ``states`` int32 [B, T]: the extended state (2 i + 1: token i, even: a blank) of every frame,
+        -1 past the clip's frames.  At most 4096 frames."""
+        with self._ctc_pass(inputs, labels, label_lengths, attention_mask) as c:
+            B, T, L = c["B"], c["T"], c["labels"].shape[1]
+            if T > CTC_MAX_FRAMES:
+                raise ValueError(f"align takes at most {CTC_MAX_FRAMES} frames (tmi_ctc_viterbi), got {T}")
+            st, en = torch.full((B, L), -1, **c["i32"]), torch.full((B, L), -1, **c["i32"])
+            total, bad = torch.zeros(B, **c["f32"]), torch.zeros(B, **c["i32"])
+            states = torch.full((B, T), -1, **c["i32"]) if return_states else None
+            wsp = torch.empty(ops.ctc_workspace_elems(B, L, T), **c["i32"])
+            ops.ctc_viterbi(c["logp"], c["labels"], c["label_lens"], c["frame_lens"], self.config.ctc_blank_id, st, en, total,
+                            bad, wsp, states)
+            st, en = st[:, :c["L_max"]], en[:, :c["L_max"]]  # (L_max == 0: the kernels were given one unused column)
+            result = {"token_start_frames": st, "token_end_frames": en, "token_start_times": self._times(st),
+                      "token_end_times": self._times(en), "path_logprob": total, "infeasible": bad}
+            if return_states:
+                result["states"] = states
+        return result
+
+
+def load_pretrained_encoder(model, path):
+    """Copy into ``model`` (a Wav2Vec2ForCTC) every reference-keyed tensor of a ``train.save_weights`` file of a pre-training
+    model that the CTC model also has: the whole base model.  The head keeps its initialisation, the file's quantiser and
+    projection heads are ignored, the bf16 mirror is re-derived.  Raises if a shared name has another shape or the file
+    shares nothing.  -> the names copied."""
+    ck = torch.load(path, map_location="cpu")
+    if not isinstance(ck, dict) or "p" in ck:
+        raise ValueError("load_pretrained_encoder takes a save_weights file (reference-keyed tensors)")
+    views = model.arena.ref_views(model.arena.p)
+    shared = [k for k in views if k in ck and not k.startswith("lm_head.")]
+    if not shared:
+        raise ValueError("the file shares no parameter with the model")
+    for k in shared:
+        if tuple(ck[k].shape) != tuple(views[k].shape):
+            raise ValueError(f"{k}: the file has shape {tuple(ck[k].shape)}, the model {tuple(views[k].shape)}")
+    missing = [k for k in views if k not in ck and not k.startswith("lm_head.")]
+    if missing:
+        raise ValueError(f"the file lacks base-model parameters: {missing[:4]} ...")
+    if hasattr(model, "finish_late"):
+        model.finish_late()
+    for k in shared:
+        views[k].copy_(ck[k].to(torch.float32))
+    model.refresh_shadows()
+    return shared
+
+
 def create_full_model(model_type: str = "pretraining", model_size: str = "small", device="cuda:0",
-                      precision: str = "bf16", seed: int = 1234, **overrides) -> Wav2Vec2ForPreTraining:
-    """V:1157-1182; ``main`` hard-codes "pretraining" (V:1416), the only type on the hot path."""
-    if model_type != "pretraining":
-        raise NotImplementedError("only Wav2Vec2ForPreTraining is on the hot path (V:1416)")
-    return Wav2Vec2ForPreTraining(make_config(model_size, **overrides), device=device, precision=precision, seed=seed)
+                      precision: str = "bf16", seed: int = 1234, **overrides):
+    """V:1157-1182: "pretraining" -> Wav2Vec2ForPreTraining (``main`` hard-codes it, V:1416: the type on the hot path),
+    "asr" -> Wav2Vec2ForCTC (inference only).  The other two types of the reference are not built."""
+    cfg = make_config(model_size, **overrides)
+    if model_type == "pretraining":
+        return Wav2Vec2ForPreTraining(cfg, device=device, precision=precision, seed=seed)
+    if model_type == "asr":
+        return Wav2Vec2ForCTC(cfg, device=device, precision=precision, seed=seed)
+    raise NotImplementedError('only "pretraining" (Wav2Vec2ForPreTraining) and "asr" (Wav2Vec2ForCTC) are built')
