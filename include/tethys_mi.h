@@ -426,6 +426,36 @@ int tmi_ctc_viterbi(const float* logp, int64_t lp_sn, int64_t lp_st, const int32
                     int32_t* states, int32_t* infeasible, int64_t N, int64_t L_max, int64_t T_max, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* tmi_ctc_beam.  CTC prefix beam search over logp (element (n, t, c) at logp[n*lp_sn + t*lp_st + c], c < V), fp32
+ * throughout, -inf the additive zero, no atomics: the same call gives the same bits, and an item's results do not depend
+ * on the other items of the call.  LSE2(a, b) = m + log(exp(a - m) + exp(b - m)) with m = max(a, b), -inf when m is.
+ *   State.  A beam is a prefix y (non-blank tokens, possibly none) with pb (its paths that end in a blank) and pnb (those
+ *   that end in its last token e).  The start: one beam, y = (), pb = 0, pnb = -inf.  Beams are kept by descending score.
+ *   Frame t < T = min(frame_lens[n], T_max), lp = logp[n, t, :], for beam k of the current set, tot = LSE2(pb, pnb):
+ *     stay (candidate index k):          pb' = lp[blank] + tot;  pnb' = lp[e] + pnb, -inf for the empty prefix
+ *     extension by c != blank (index K + k*V + c):  v = lp[c] + (c == e ? pb : tot)
+ *       if the sequence y + c is itself a beam p of the current set, v is folded into p's stay candidate,
+ *       pnb'_p = LSE2(pnb'_p, v), and the extension is no candidate of its own (one extension at most folds into a beam);
+ *       otherwise it is a candidate with pb' = -inf, pnb' = v
+ *     a candidate's score is LSE2(pb', pnb') - for a pure extension v itself.  The next set: the up to K candidates of
+ *     largest finite score, among equal scores the lower candidate index first; a candidate whose score is -inf is never
+ *     kept, so a set may hold fewer than K beams (or none).
+ *   "Is a beam of the current set" is equality of the token sequences: a prefix that fell out of the set and was created
+ *   again is the same prefix (a hash filters, a walk of the two chains confirms).
+ *   tokens int32 [N][K][T_max]  rank r's sequence, dense, in frame order; nothing is written past its length
+ *   lengths int32 [N][K], scores fp32 [N][K]  the final LSE2(pb, pnb), descending; n_beams int32 [N]  the ranks filled;
+ *   a rank past it has length 0 and score -inf.  An item with T < 1 returns the start state: one empty beam, score 0.
+ * One workgroup per item, one wave per beam, one lane per symbol: 1 <= K <= 16, 2 <= V <= 64, V <= lp_st <= 2^30,
+ * lp_sn >= T_max*lp_st, 0 <= blank < V, 1 <= N <= 65535, 1 <= T_max <= 65536.  workspace: tmi_ctc_beam_workspace_bytes
+ * (the prefix trie, one (parent node, token) record per frame and rank; -1 outside the limits), 8-byte aligned, any
+ * contents.  Values in device memory are not trusted: a length is clamped to T_max, and no symbol is read from memory
+ * that this call did not write.  TMI_ERR_INVALID (nothing is launched): a NULL or misaligned pointer, a size outside
+ * the limits, a stride too small, blank outside the row, a workspace too small. */
+int64_t tmi_ctc_beam_workspace_bytes(int64_t N, int64_t K, int64_t T_max);
+int tmi_ctc_beam(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* frame_lens, int32_t blank,
+                 int32_t K, int32_t* tokens, int32_t* lengths, float* scores, int32_t* n_beams, int64_t N, int64_t T_max,
+                 void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Decoder token embedding + positional encoding (W:405-408) with the teacher-forcing
  * shift of W:559-563 folded in: id(b,t) = t == 0 ? start_id : labels[b, t-1].

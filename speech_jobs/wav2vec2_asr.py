@@ -8,6 +8,9 @@ model keeps its seeded initialisation), pads the ``--wav`` clips (16-bit PCM mon
 without one, takes ``--batch_size`` dummy clips of ``--seconds``, every second one cut to 60 % - builds the frame mask
 (``wav2vec2.frame_attention_mask``) and decodes greedily.  ``--labels FILE`` (one line of space-separated token ids per
 clip; an empty line: no labels) also scores the clips (``evaluate``) and aligns the labels to the frames (``align``).
+``--num_beams K`` (2..16) decodes by CTC prefix beam search instead (``decode(num_beams=K)``): the line then carries the best
+sequence, its score ``sequence_score`` and, with ``--nbest R``, the R best sequences and scores under ``nbest``; the
+timestamps are those of the best sequence's forced alignment, and with labels the edit distance is the best sequence's.
 Prints one JSON line per clip: the token ids, with ``--timestamps`` their start and end times in seconds, the best path's
 log-probability, and with labels the nll, the edit distance of the transcript and the aligned times; then one summary line.
 There is no tokenizer: ids in, ids out.
@@ -42,6 +45,8 @@ def main(argv=None):
     parser.add_argument("--seconds", type=float, default=2.0, help="length of the dummy clips")
     parser.add_argument("--timestamps", action="store_true", help="print token start and end times")
     parser.add_argument("--labels", default=None, help="file of token ids, one line per clip: evaluate and align")
+    parser.add_argument("--num_beams", type=int, default=None, help="CTC prefix beam search with this many beams (2..16)")
+    parser.add_argument("--nbest", type=int, default=1, help="with --num_beams: print this many sequences per clip")
     args = parser.parse_args(argv)
 
     import numpy as np
@@ -74,7 +79,15 @@ def main(argv=None):
     rows = read_labels(args.labels, len(clips)) if args.labels else None
     torch.cuda.synchronize()
     t0 = time.time()
-    dec = model.decode(audio, attention_mask=mask)
+    beam = args.num_beams is not None and args.num_beams > 1
+    if args.nbest != 1 and not beam:
+        raise SystemExit("--nbest comes with --num_beams >= 2")
+    if beam:
+        wav2vec2.check_ctc_beam_args(model.config, args.num_beams, args.nbest)
+        dec = model.decode(audio, attention_mask=mask, num_beams=args.num_beams, num_return_sequences=args.nbest,
+                           return_timestamps=args.timestamps)
+    else:
+        dec = model.decode(audio, attention_mask=mask)
     ev = al = None
     if rows is not None:
         L = max(len(r) for r in rows)
@@ -82,15 +95,25 @@ def main(argv=None):
         for i, r in enumerate(rows):
             labels[i, :len(r)] = torch.tensor(r, dtype=torch.int64)
         lens = [len(r) for r in rows]
-        ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True)
+        ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True,
+                            num_beams=args.num_beams if beam else None)
         al = model.align(audio, labels, lens, attention_mask=mask)
     torch.cuda.synchronize()
     dt = time.time() - t0
     frames = [int(x) for x in mask.sum(1).tolist()]
     for i, (name, _) in enumerate(clips):
-        k = int(dec["lengths"][i])
-        line = {"clip": name, "frames": frames[i], "tokens": dec["sequences"][i, :k].tolist(),
-                "best_path_logprob": float(dec["best_path_logprob"][i])}
+        if beam:
+            seqs, lens_, scores = (dec[n] if args.nbest > 1 else dec[n][:, None] for n in ("sequences", "lengths", "sequences_scores"))
+            k = int(lens_[i, 0])
+            line = {"clip": name, "frames": frames[i], "tokens": seqs[i, 0, :k].tolist(), "sequence_score": float(scores[i, 0]),
+                    "n_beams": int(dec["n_beams"][i])}
+            if args.nbest > 1:
+                line["nbest"] = [{"tokens": seqs[i, r, :int(lens_[i, r])].tolist(), "score": float(scores[i, r])}
+                                 for r in range(min(args.nbest, int(dec["n_beams"][i])))]
+        else:
+            k = int(dec["lengths"][i])
+            line = {"clip": name, "frames": frames[i], "tokens": dec["sequences"][i, :k].tolist(),
+                    "best_path_logprob": float(dec["best_path_logprob"][i])}
         if args.timestamps:
             line["start"] = [round(t, 4) for t in dec["token_start_times"][i, :k].tolist()]
             line["end"] = [round(t, 4) for t in dec["token_end_times"][i, :k].tolist()]

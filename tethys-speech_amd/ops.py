@@ -571,6 +571,30 @@ def ctc_viterbi(logp, labels, label_lens, frame_lens, blank, tok_start, tok_end,
                                     workspace.numel() * 4, stream()), "tmi_ctc_viterbi")
 
 
+def ctc_beam_workspace_elems(N: int, K: int, T_max: int) -> int:
+    """int32 elements of tmi_ctc_beam's workspace (tmi_ctc_beam_workspace_bytes / 4)."""
+    n = int(lib().tmi_ctc_beam_workspace_bytes(int(N), int(K), int(T_max)))
+    if n < 0:
+        raise ValueError(f"tmi_ctc_beam takes 1 <= N <= 65535 items, 1 <= K <= 16 beams and at most 65536 frames, got {N} x {K} x {T_max}")
+    return n // 4
+
+
+def ctc_beam(logp, frame_lens, blank, K, tokens, lengths, scores, n_beams, workspace):
+    """CTC prefix beam search of every item (tmi_ctc_beam in include/tethys_mi.h): ``logp`` fp32 [N, T, V] with 2 <= V <= 64,
+    ``frame_lens`` int32 [N]; ``tokens`` int32 [N, K, T], ``lengths`` int32 [N, K], ``scores`` fp32 [N, K], ``n_beams`` int32
+    [N]; ``workspace`` int32 of ``ctc_beam_workspace_elems`` entries, any contents."""
+    N, T, V = _ctc_logp(logp, "ctc_beam")
+    K = int(K)
+    for t, n, w in ((frame_lens, N, "frame_lens"), (tokens, N * K * T, "tokens"), (lengths, N * K, "lengths"),
+                    (n_beams, N, "n_beams"), (workspace, ctc_beam_workspace_elems(N, K, T), "workspace")):
+        _i32_dev(t, n, "ctc_beam: " + w)
+    _f32_flat(scores, N * K, "ctc_beam: scores")
+    with _probe("ctc_beam", 4.0 * N * T * V):
+        check(lib().tmi_ctc_beam(logp.data_ptr(), logp.stride(0), logp.stride(1), V, frame_lens.data_ptr(), int(blank), K,
+                                 tokens.data_ptr(), lengths.data_ptr(), scores.data_ptr(), n_beams.data_ptr(), N, T,
+                                 workspace.data_ptr(), workspace.numel() * 4, stream()), "tmi_ctc_beam")
+
+
 def masked_mean_pool(x, mask, out, B, T, C):
     """out[b, c] = sum_t x[b, t, c] mask[b, t] / sum_t mask[b, t] (fp32 [B, C]); ``mask`` fp32 [B, T] or None: the plain mean."""
     if not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C or x.numel() != B * T * C:

@@ -1022,6 +1022,7 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
 # fine-tuning are not built.
 CTC_MAX_LABELS = 511   # tmi_ctc_forward: one thread per extended state, 2 L + 1 <= 1023
 CTC_MAX_FRAMES = 4096  # tmi_ctc_viterbi: the moves of a walk-back piece are staged in LDS
+CTC_MAX_BEAMS = 16     # tmi_ctc_beam: one wave per beam
 SAMPLE_RATE = 16000
 
 
@@ -1088,6 +1089,22 @@ def check_ctc_args(cfg: Wav2Vec2Config, inputs_shape, labels=None, label_lengths
             lab = np.zeros((B, 1), dtype=np.int32)  # (the kernels take L_max >= 1; every length is 0)
         lab = np.ascontiguousarray(lab)
     return B, T, frame_lens, mask, lab, lens
+
+
+def check_ctc_beam_args(cfg: Wav2Vec2Config, num_beams=None, num_return_sequences=1):
+    """Host validation of the beam arguments of ``Wav2Vec2ForCTC.decode`` / ``evaluate`` (no GPU needed): ``num_beams`` None
+    or an integer in [1, 16] (None and 1: greedy decoding), ``num_return_sequences`` an integer with
+    1 <= num_return_sequences <= num_beams.  -> (K, R) as integers, K = 1 for the greedy path."""
+    def integer(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    if not 2 <= cfg.vocab_size <= 64 or not 0 <= cfg.ctc_blank_id < cfg.vocab_size:
+        raise ValueError("the CTC head takes 2 <= vocab_size <= 64 and ctc_blank_id in [0, vocab_size)")
+    K = 1 if num_beams is None else num_beams
+    if not integer(K) or not 1 <= K <= CTC_MAX_BEAMS:
+        raise ValueError(f"num_beams must be None or an integer in [1, {CTC_MAX_BEAMS}] (tmi_ctc_beam: one wave per beam)")
+    if not integer(num_return_sequences) or not 1 <= num_return_sequences <= K:
+        raise ValueError("num_return_sequences must be an integer with 1 <= num_return_sequences <= num_beams")
+    return int(K), int(num_return_sequences)
 
 
 def edit_distance(hyp: np.ndarray, ref: np.ndarray) -> int:
@@ -1195,13 +1212,41 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
     def _times(self, frames):
         return torch.where(frames >= 0, frames.to(torch.float64) * frame_seconds(self.config), -1.0)
 
+    def _beam(self, c, K):
+        """tmi_ctc_beam on the pass's log-probs -> tokens [B, K, T] (-1 past a length), len [B, K], scores [B, K], n [B]."""
+        B, T = c["B"], c["T"]
+        out = {"tokens": torch.full((B, K, T), -1, **c["i32"]), "len": torch.zeros((B, K), **c["i32"]),
+               "scores": torch.full((B, K), -math.inf, **c["f32"]), "n": torch.zeros(B, **c["i32"])}
+        wsp = torch.empty(ops.ctc_beam_workspace_elems(B, K, T), **c["i32"])
+        ops.ctc_beam(c["logp"], c["frame_lens"], self.config.ctc_blank_id, K, out["tokens"], out["len"], out["scores"],
+                     out["n"], wsp)
+        return out
+
+    def _check_beam_frames(self, inputs, what):
+        if torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.shape[1] >= 1:
+            T = frame_lengths(self.config, [int(inputs.shape[1])])[0]
+            if T > CTC_MAX_FRAMES:
+                raise ValueError(f"{what} with num_beams takes at most {CTC_MAX_FRAMES} frames, got {T}")
+
     @torch.no_grad()
-    def decode(self, inputs, attention_mask=None):
+    def decode(self, inputs, attention_mask=None, num_beams=None, num_return_sequences=1, return_timestamps=False):
         """Greedy CTC decoding: per frame the most probable symbol, runs of equal symbols collapsed, blanks dropped
         (tmi_ctc_greedy).  -> ``sequences`` int32 [B, max length] padded with -1, ``lengths`` int32 [B],
         ``token_start_frames`` / ``token_end_frames`` int32 (the first frame of a token's run and its last plus 1; -1 in the
         padding), ``token_start_times`` / ``token_end_times`` float64 seconds (frames x ``frame_seconds``; -1 in the padding),
-        ``best_path_logprob`` fp32 [B]: the sum of the chosen symbols' log-probabilities over the clip's frames."""
+        ``best_path_logprob`` fp32 [B]: the sum of the chosen symbols' log-probabilities over the clip's frames.
+
+        ``num_beams`` in [2, 16]: CTC prefix beam search (tmi_ctc_beam in include/tethys_mi.h) - the label sequences whose
+        paths together carry the most probability, not the best path.  With R = ``num_return_sequences`` <= num_beams
+        -> ``sequences`` int32 [B, R, max length] padded with -1, ``lengths`` int32 [B, R], ``sequences_scores`` fp32 [B, R]
+        (the log-probability the search kept for the sequence, descending; -inf past ``n_beams``), ``n_beams`` int32 [B] (the
+        ranks the search filled, of num_beams); R == 1 drops the rank dimension.  ``return_timestamps`` adds
+        ``token_start_frames`` / ``token_end_frames`` int32 [B, max best length] and the times of the BEST sequence of each
+        item: its forced alignment (tmi_ctc_viterbi on the same log-probs, the labels never leave the device).  At most
+        4096 frames; timestamps take a best sequence of at most 511 tokens.  ``num_beams`` None or 1 is the greedy path."""
+        K, R = check_ctc_beam_args(self.config, num_beams, num_return_sequences)
+        if K > 1:
+            return self._decode_beam(inputs, attention_mask, K, R, return_timestamps)
         with self._ctc_pass(inputs, attention_mask=attention_mask) as c:
             g = self._greedy(c)
             n = max(int(g["len"].max()), 0)  # (the one host read: the width of the result)
@@ -1210,8 +1255,34 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                     "token_end_frames": en, "token_start_times": self._times(st), "token_end_times": self._times(en),
                     "best_path_logprob": g["best"]}
 
+    def _decode_beam(self, inputs, attention_mask, K, R, return_timestamps):
+        self._check_beam_frames(inputs, "decode")
+        with self._ctc_pass(inputs, attention_mask=attention_mask) as c:
+            B, T = c["B"], c["T"]
+            bm = self._beam(c, K)
+            n = max(int(bm["len"][:, :R].max()), 0)  # (the one host read: the width of the result)
+            seqs, lens, scores = bm["tokens"][:, :R, :n].clone(), bm["len"][:, :R].clone(), bm["scores"][:, :R].clone()
+            if R == 1:
+                seqs, lens, scores = seqs[:, 0], lens[:, 0], scores[:, 0]
+            result = {"sequences": seqs, "lengths": lens, "sequences_scores": scores, "n_beams": bm["n"]}
+            if return_timestamps:
+                nb = max(int(bm["len"][:, 0].max()), 0)
+                if nb > CTC_MAX_LABELS:
+                    raise ValueError(f"timestamps take a best sequence of at most {CTC_MAX_LABELS} tokens (tmi_ctc_viterbi), got {nb}")
+                L = max(nb, 1)
+                lab = bm["tokens"][:, 0, :L].clamp_min(0).contiguous()  # (past a length: never read)
+                ll = bm["len"][:, 0].contiguous()
+                st, en = torch.full((B, L), -1, **c["i32"]), torch.full((B, L), -1, **c["i32"])
+                total, bad = torch.zeros(B, **c["f32"]), torch.zeros(B, **c["i32"])
+                wsp = torch.empty(ops.ctc_workspace_elems(B, L, T), **c["i32"])
+                ops.ctc_viterbi(c["logp"], lab, ll, c["frame_lens"], self.config.ctc_blank_id, st, en, total, bad, wsp)
+                st, en = st[:, :nb], en[:, :nb]
+                result.update(token_start_frames=st, token_end_frames=en, token_start_times=self._times(st),
+                              token_end_times=self._times(en))
+            return result
+
     @torch.no_grad()
-    def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False):
+    def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False, num_beams=None):
         """The CTC loss of one batch and the error rate of its greedy transcript, forward only.  ``labels`` integer
         [B, L_max] with ``label_lengths`` [B] (see ``check_ctc_args``).  Returns Python numbers, float64 on the host, so
         that shards add up: ``nll_sum`` over the feasible items, ``n_items``, ``n_infeasible`` (items with fewer frames than
@@ -1220,8 +1291,13 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         ``ctc_zero_infinity``; ``n_edits`` / ``n_ref_tokens`` / ``token_error_rate``: the Levenshtein distance of the greedy
         transcript to the labels, summed over the items, over the number of labels.  ``return_items`` adds the device
         tensors ``nll`` fp32 [B] (+inf where infeasible, whatever ``ctc_zero_infinity``), ``infeasible`` int32 [B],
-        ``sequences`` / ``lengths`` of the greedy transcript."""
+        ``sequences`` / ``lengths`` of the greedy transcript.  ``num_beams`` in [2, 16]: ``n_edits`` / ``token_error_rate`` are
+        those of the best sequence of the prefix beam search (``decode(num_beams=...)``) instead of the greedy transcript,
+        and ``return_items`` adds its ``beam_sequences`` / ``beam_lengths``; everything else is as without it."""
         cfg = self.config
+        K, _ = check_ctc_beam_args(cfg, num_beams)
+        if K > 1:
+            self._check_beam_frames(inputs, "evaluate")
         with self._ctc_pass(inputs, labels, label_lengths, attention_mask) as c:
             B = c["B"]
             nll, bad = torch.zeros(B, **c["f32"]), torch.zeros(B, **c["i32"])
@@ -1241,7 +1317,12 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                 loss = float((item / np.maximum(lens, 1)).mean())
             else:
                 loss = float(item.sum())
-            n_edits = sum(edit_distance(tok[b, :hl[b]], lab[b, :lens[b]]) for b in range(B))
+            hyp_tok, hyp_len = tok, hl
+            if K > 1:
+                bm = self._beam(c, K)
+                bhost = torch.cat([bm["tokens"][:, 0].reshape(-1), bm["len"][:, 0]]).cpu()
+                hyp_tok, hyp_len = bhost[:B * T].view(B, T).numpy(), bhost[B * T:].numpy()
+            n_edits = sum(edit_distance(hyp_tok[b, :hyp_len[b]], lab[b, :lens[b]]) for b in range(B))
             n_ref = int(lens.sum())
             result = {"nll_sum": nll_sum, "n_items": float(B), "n_infeasible": float((~ok).sum()), "loss": loss,
                       "n_edits": float(n_edits), "n_ref_tokens": float(n_ref),
@@ -1249,6 +1330,9 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             if return_items:
                 n = max(int(hl.max()), 0)
                 result.update(nll=nll, infeasible=bad, sequences=g["tokens"][:, :n].clone(), lengths=g["len"])
+                if K > 1:
+                    nbm = max(int(hyp_len.max()), 0)
+                    result.update(beam_sequences=bm["tokens"][:, 0, :nbm].clone(), beam_lengths=bm["len"][:, 0].clone())
         return result
 
     @torch.no_grad()
