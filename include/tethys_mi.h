@@ -426,6 +426,43 @@ int tmi_ctc_viterbi(const float* logp, int64_t lp_sn, int64_t lp_st, const int32
                     int32_t* states, int32_t* infeasible, int64_t N, int64_t L_max, int64_t T_max, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* tmi_ctc_posteriors (csrc/ctc_post.hip).  The forward-backward pass over the same lattice: alpha as tmi_ctc_forward, beta
+ * its mirror, and what the two give together.  fp32 throughout, -inf the additive zero, LSE3 exactly the LSE of
+ * tmi_ctc_forward, no atomics, no scratch besides gamma.  logp, labels, label_lens, frame_lens, blank as tmi_ctc_forward,
+ * with V columns; ext = [blank, l1, blank, .., lL, blank], S = 2L + 1, T = min(frame_lens[n], T_max), lp = logp[n].
+ *   alpha:  alpha_t(s) is the recursion of tmi_ctc_forward, in the same operation order.  nll[n] and infeasible[n] are bit
+ *           for bit what tmi_ctc_forward writes for the same arguments, zero_infinity included.  ll = -(the unclamped nll).
+ *   beta:   beta_{T-1}(s) = lp[T-1][ext_s] for s = S-1 and, if S > 1, s = S-2; -inf elsewhere.
+ *           beta_t(s) = lp[t][ext_s] + LSE3(beta_{t+1}(s), beta_{t+1}(s+1), beta_{t+1}(s+2)).
+ *           The second term applies only if s+1 < S.
+ *           The third term applies only if s+2 < S && ext_{s+2} != blank && ext_{s+2} != ext_s.
+ *   gamma:  gamma[n,t,s] = exp((alpha_t(s) - ll) + (beta_t(s) - lp[t][ext_s])): the two differences first, then their sum.
+ *           It is 0 whenever alpha_t(s) or beta_t(s) is -inf.  gamma is not clamped to 1.
+ *           Element (n, t, s) at gamma[(n*T_max + t)*(2*L_max + 1) + s]; the tensor is the call's scratch for alpha first.
+ *   occ:    occ[n,t,c] = sum over s ascending with ext_s == c of gamma[n,t,s], a running sum from 0.  The value is 0 for
+ *           a symbol that is not in ext.  Element (n, t, c) at occ[n*oc_sn + t*oc_st + c].
+ *   grad (may be NULL):  grad[n,t,c] = expf(lp[t][c]) - occ[n,t,c], at grad[n*gr_sn + t*gr_st + c].  This is
+ *           d nll[n] / d logits[n,t,c] for logits whose row-wise log-softmax is lp; per item and unscaled ("sum").
+ *   tok_frames:  tok_frames[n*L_max + i] = sum over t of gamma[n,t,2i+1], a running sum from 0 in descending t
+ *           (t = T-1, T-2, .., 0: the order of the beta pass).
+ *   tok_center:  tok_center[n*L_max + i] = (sum over t of t * gamma[n,t,2i+1]) / tok_frames[n,i], in frames.  The product
+ *           t * gamma is formed with t converted to fp32 and rounded before it is added.  The sum takes the same order as
+ *           tok_frames.
+ *   Written: gamma for t < T, s < S; occ / grad rows t < T, columns c < V; tok_* for i < L.  Everything else is left
+ *   untouched: rows past the clip, columns past V, states past S, tokens past L.
+ *   An item without a path (T < 1, or no finite path): nll / infeasible as tmi_ctc_forward; every gamma / occ / grad
+ *   element listed above is 0; tok_frames = 0, tok_center = -1.  With T < 1 only the tok_* entries exist.
+ * The same call gives the same bits; an item in a ragged batch gets the bits it gets alone.  A label length is clamped to
+ * [0, L_max], a frame length to T_max, and a symbol outside [0, V) is never dereferenced: its log-prob is -inf.
+ * 1 <= N <= 65535, 1 <= L_max <= 511, 1 <= T_max <= 4096, 2 <= V <= 64, 0 <= blank < V, V <= lp_st <= 2^30,
+ * lp_sn >= T_max*lp_st, and the same for oc_st / oc_sn and (grad given) gr_st / gr_sn; 4-byte aligned non-NULL pointers,
+ * grad excepted; zero_infinity 0 / 1.  Anything else: TMI_ERR_INVALID, nothing is launched. */
+int tmi_ctc_posteriors(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* labels,
+                       const int32_t* label_lens, const int32_t* frame_lens, int32_t blank, float* nll, int32_t* infeasible,
+                       float* gamma, float* occ, int64_t oc_sn, int64_t oc_st, float* grad, int64_t gr_sn, int64_t gr_st,
+                       float* tok_frames, float* tok_center, int64_t N, int64_t L_max, int64_t T_max, int32_t zero_infinity,
+                       void* stream);
+
 /* tmi_ctc_beam.  CTC prefix beam search over logp (element (n, t, c) at logp[n*lp_sn + t*lp_st + c], c < V), fp32
  * throughout, -inf the additive zero, no atomics: the same call gives the same bits, and an item's results do not depend
  * on the other items of the call.  LSE2(a, b) = m + log(exp(a - m) + exp(b - m)) with m = max(a, b), -inf when m is.

@@ -7,7 +7,9 @@ Loads weights (``--weights``: a ``save_checkpoint`` or ``save_weights`` file of 
 model keeps its seeded initialisation), pads the ``--wav`` clips (16-bit PCM mono 16 kHz) to the longest of them - or,
 without one, takes ``--batch_size`` dummy clips of ``--seconds``, every second one cut to 60 % - builds the frame mask
 (``wav2vec2.frame_attention_mask``) and decodes greedily.  ``--labels FILE`` (one line of space-separated token ids per
-clip; an empty line: no labels) also scores the clips (``evaluate``) and aligns the labels to the frames (``align``).
+clip; an empty line: no labels) also scores the clips (``evaluate``) and aligns the labels to the frames (``align``);
+``--posteriors`` adds, after the aligned times, each token's expected number of frames and its centre time under ALL paths
+that spell the labels (``posteriors``: ``expected_frames``, ``center_time``), where ``align`` gives the best path's.
 ``--num_beams K`` (2..16) decodes by CTC prefix beam search instead (``decode(num_beams=K)``): the line then carries the best
 sequence, its score ``sequence_score`` and, with ``--nbest R``, the R best sequences and scores under ``nbest``; the
 timestamps are those of the best sequence's forced alignment, and with labels the edit distance is the best sequence's.
@@ -45,6 +47,8 @@ def main(argv=None):
     parser.add_argument("--seconds", type=float, default=2.0, help="length of the dummy clips")
     parser.add_argument("--timestamps", action="store_true", help="print token start and end times")
     parser.add_argument("--labels", default=None, help="file of token ids, one line per clip: evaluate and align")
+    parser.add_argument("--posteriors", action="store_true",
+                        help="with --labels: each token's expected frames and centre time over all paths (forward-backward)")
     parser.add_argument("--num_beams", type=int, default=None, help="CTC prefix beam search with this many beams (2..16)")
     parser.add_argument("--nbest", type=int, default=1, help="with --num_beams: print this many sequences per clip")
     args = parser.parse_args(argv)
@@ -88,7 +92,9 @@ def main(argv=None):
                            return_timestamps=args.timestamps)
     else:
         dec = model.decode(audio, attention_mask=mask)
-    ev = al = None
+    if args.posteriors and rows is None:
+        raise SystemExit("--posteriors comes with --labels")
+    ev = al = post = None
     if rows is not None:
         L = max(len(r) for r in rows)
         labels = torch.zeros(len(rows), L, dtype=torch.int64)
@@ -98,6 +104,8 @@ def main(argv=None):
         ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True,
                             num_beams=args.num_beams if beam else None)
         al = model.align(audio, labels, lens, attention_mask=mask)
+        if args.posteriors:
+            post = model.posteriors(audio, labels, lens, attention_mask=mask)
     torch.cuda.synchronize()
     dt = time.time() - t0
     frames = [int(x) for x in mask.sum(1).tolist()]
@@ -126,6 +134,9 @@ def main(argv=None):
             line["path_logprob"] = float(al["path_logprob"][i])
             line["aligned_start"] = [round(t, 4) for t in al["token_start_times"][i, :n].tolist()]
             line["aligned_end"] = [round(t, 4) for t in al["token_end_times"][i, :n].tolist()]
+            if post is not None:
+                line["expected_frames"] = [round(t, 3) for t in post["token_expected_frames"][i, :n].tolist()]
+                line["center_time"] = [round(t, 4) for t in post["token_center_times"][i, :n].tolist()]
         print(json.dumps(line), flush=True)
     summary = {"clips": len(clips), "samples": T_in, "seconds": round(dt, 4)}
     if ev is not None:

@@ -170,6 +170,8 @@ SIGNATURES = {
     "tmi_ctc_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "tmi_ctc_viterbi": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64,
                                 c_vp, c_i64, c_vp]),
+    "tmi_ctc_posteriors": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                   c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_vp]),
     "tmi_ctc_beam_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "tmi_ctc_beam": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                              c_vp]),

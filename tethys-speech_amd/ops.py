@@ -571,6 +571,34 @@ def ctc_viterbi(logp, labels, label_lens, frame_lens, blank, tok_start, tok_end,
                                     workspace.numel() * 4, stream()), "tmi_ctc_viterbi")
 
 
+def ctc_posteriors(logp, labels, label_lens, frame_lens, blank, nll, infeasible, gamma, occ, tok_frames, tok_center, grad=None,
+                   zero_infinity=False):
+    """The CTC forward-backward pass of every item (tmi_ctc_posteriors in include/tethys_mi.h): inputs as ``ctc_forward``
+    with 2 <= V <= 64; ``nll`` fp32 [N], ``infeasible`` int32 [N], ``gamma`` fp32 [N, T, 2 L_max + 1] contiguous (the state
+    posteriors; the call's scratch for alpha first), ``occ`` and optionally ``grad`` fp32 [N, T, V] with unit column stride
+    (the symbol posteriors and d nll / d logits), ``tok_frames`` / ``tok_center`` fp32 [N, L_max].  At most 4096 frames."""
+    N, T, V = _ctc_logp(logp, "ctc_posteriors")
+    if labels.dim() != 2 or labels.shape[0] != N:
+        raise ValueError("ctc_posteriors: labels must be int32 [N, L_max]")
+    L = labels.shape[1]
+    for t, n, w in ((labels, N * L, "labels"), (label_lens, N, "label_lens"), (frame_lens, N, "frame_lens"),
+                    (infeasible, N, "infeasible")):
+        _i32_dev(t, n, "ctc_posteriors: " + w)
+    for t, n, w in ((nll, N, "nll"), (gamma, N * T * (2 * L + 1), "gamma"), (tok_frames, N * L, "tok_frames"),
+                    (tok_center, N * L, "tok_center")):
+        _f32_flat(t, n, "ctc_posteriors: " + w)
+    for t, w in ((occ, "occ"),) + (() if grad is None else ((grad, "grad"),)):
+        if tuple(_ctc_logp(t, "ctc_posteriors: " + w)) != (N, T, V):
+            raise ValueError(f"ctc_posteriors: {w} must be float32 [N, T, V] as logp")
+    with _probe("ctc_posteriors", 4.0 * N * T * (3 * (2 * L + 1) + 3 * V)):
+        check(lib().tmi_ctc_posteriors(logp.data_ptr(), logp.stride(0), logp.stride(1), V, labels.data_ptr(),
+                                       label_lens.data_ptr(), frame_lens.data_ptr(), int(blank), nll.data_ptr(),
+                                       infeasible.data_ptr(), gamma.data_ptr(), occ.data_ptr(), occ.stride(0), occ.stride(1),
+                                       ptr(grad), 0 if grad is None else grad.stride(0), 0 if grad is None else grad.stride(1),
+                                       tok_frames.data_ptr(), tok_center.data_ptr(), N, L, T, 1 if zero_infinity else 0,
+                                       stream()), "tmi_ctc_posteriors")
+
+
 def ctc_beam_workspace_elems(N: int, K: int, T_max: int) -> int:
     """int32 elements of tmi_ctc_beam's workspace (tmi_ctc_beam_workspace_bytes / 4)."""
     n = int(lib().tmi_ctc_beam_workspace_bytes(int(N), int(K), int(T_max)))

@@ -1032,8 +1032,8 @@ def frame_seconds(cfg: Wav2Vec2Config) -> float:
 
 
 def check_ctc_args(cfg: Wav2Vec2Config, inputs_shape, labels=None, label_lengths=None, attention_mask=None):
-    """Host validation of ``Wav2Vec2ForCTC.decode`` / ``evaluate`` / ``align`` (no GPU needed; the kernels cannot see values
-    in device memory).  ``inputs_shape`` (B, T_in); ``labels`` None or integer [B, L_max] with every entry inside its row's
+    """Host validation of ``Wav2Vec2ForCTC.decode`` / ``evaluate`` / ``align`` / ``posteriors`` (no GPU needed; the kernels
+    cannot see values in device memory).  ``inputs_shape`` (B, T_in); ``labels`` None or integer [B, L_max] with every entry inside its row's
     ``label_lengths`` in [0, vocab_size) and not the blank, L_max <= 511; ``label_lengths`` None (L_max everywhere) or B
     integers in [0, L_max]; ``attention_mask`` None or [B, T] over frames (``frame_attention_mask``), values 0 or 1 only,
     every row ones first and zeros behind them, at least one frame per row.
@@ -1125,7 +1125,8 @@ def edit_distance(hyp: np.ndarray, ref: np.ndarray) -> int:
 class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
     """V:940-1001 at inference: the base model (stem, positional conv, projection, encoder - the blocks and the inference
     workspace of ``Wav2Vec2ForPreTraining``) and a Dense head (V:972-975) over ``vocab_size`` symbols, with greedy CTC
-    decoding, the CTC loss and forced alignment on the kernels of csrc/ctc.hip.  Every public method runs under
+    decoding, the CTC loss and forced alignment on the kernels of csrc/ctc.hip, and the forward-backward posteriors of
+    csrc/ctc_post.hip.  Every public method runs under
     ``torch.no_grad()`` on the inference workspace with dropout off, and reads or writes nothing of the training state.
     The training entry points raise: CTC gradients are not built."""
 
@@ -1358,6 +1359,43 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                       "token_end_times": self._times(en), "path_logprob": total, "infeasible": bad}
             if return_states:
                 result["states"] = states
+        return result
+
+    @torch.no_grad()
+    def posteriors(self, inputs, labels, label_lengths=None, attention_mask=None, return_logit_grad=False,
+                   return_states=False):
+        """The CTC forward-backward pass over ALL paths that spell ``labels`` (tmi_ctc_posteriors in include/tethys_mi.h),
+        where ``align`` returns the single best one.  -> ``nll`` fp32 [B] (+inf where infeasible, whatever
+        ``ctc_zero_infinity``, as ``evaluate(return_items=True)``), ``infeasible`` int32 [B], ``symbol_posteriors`` fp32
+        [B, T, V] (the probability that frame t emits symbol c; zeros past a clip's frames), ``token_expected_frames`` fp32
+        [B, L_max] (the expected number of frames of each token; -1 past ``label_lengths``, 0 for an item without a path),
+        ``token_center_frames`` fp32 [B, L_max] (the posterior mean frame of each token; -1 in the padding and for items
+        without a path), ``token_center_times`` float64 seconds (centre x ``frame_seconds``, the convention of the start
+        times; -1 likewise).  ``return_logit_grad`` adds ``logit_grad`` fp32 [B, T, V]: the gradient of the sum of the
+        items' nll with respect to ``logits`` (softmax - posterior; zero past a clip and for infeasible items) - a result
+        for inspection, nothing of the training state is read or written.  ``return_states`` adds ``state_posteriors`` fp32
+        [B, T, 2 L_max + 1] over the extended states (zeros past a clip's frames and an item's states).  At most 4096
+        frames."""
+        if torch.is_tensor(inputs) and inputs.dim() == 2 and inputs.shape[1] >= 1:   # (before the pass: nothing runs)
+            T = frame_lengths(self.config, [int(inputs.shape[1])])[0]
+            if T > CTC_MAX_FRAMES:
+                raise ValueError(f"posteriors takes at most {CTC_MAX_FRAMES} frames (tmi_ctc_posteriors), got {T}")
+        with self._ctc_pass(inputs, labels, label_lengths, attention_mask) as c:
+            B, T, V, L = c["B"], c["T"], c["V"], c["labels"].shape[1]
+            nll, bad = torch.zeros(B, **c["f32"]), torch.zeros(B, **c["i32"])
+            gamma = torch.zeros((B, T, 2 * L + 1), **c["f32"])   # (what the kernel leaves unwritten is pre-filled)
+            occ = torch.zeros((B, T, V), **c["f32"])
+            grad = torch.zeros((B, T, V), **c["f32"]) if return_logit_grad else None
+            frames, center = torch.full((B, L), -1.0, **c["f32"]), torch.full((B, L), -1.0, **c["f32"])
+            ops.ctc_posteriors(c["logp"], c["labels"], c["label_lens"], c["frame_lens"], self.config.ctc_blank_id, nll, bad,
+                               gamma, occ, frames, center, grad, False)
+            frames, center = frames[:, :c["L_max"]], center[:, :c["L_max"]]  # (L_max == 0: one unused column, as align)
+            result = {"nll": nll, "infeasible": bad, "symbol_posteriors": occ, "token_expected_frames": frames,
+                      "token_center_frames": center, "token_center_times": self._times(center)}
+            if return_logit_grad:
+                result["logit_grad"] = grad
+            if return_states:
+                result["state_posteriors"] = gamma[:, :, :2 * c["L_max"] + 1]
         return result
 
 
