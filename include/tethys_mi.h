@@ -636,6 +636,58 @@ int tmi_lm_head_sample(const void* x, int64_t x_ld, int32_t x_dtype, const float
                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Decode constraints (whisper.py generate: repetition_penalty, no_repeat_ngram_size, suppress_tokens,
+ * begin_suppress_tokens): per decoded row r two bit sets over the vocabulary, arrays of uint32 words, W = ceil(V / 32)
+ * words a row at row stride bits_ld >= W; column n is bit n & 31 of word n >> 5.
+ *   seen[r]:   the tokens the penalty applies to;     banned[r]: the tokens the row cannot emit.
+ * With z[n] the LM-head logit exactly as tmi_lm_head_argmax / _topk / _sample compute it, for n < V
+ *   z'[n] = -inf                         if banned bit n
+ *         = z[n] / penalty  (z[n] > 0)   if seen bit n      (fp32, correctly rounded)
+ *         = z[n] * penalty  (z[n] <= 0)  if seen bit n
+ *         = z[n]                         otherwise
+ * and the _c entry points are the originals' rules with z' in place of z - in every mode the edit comes BEFORE the
+ * temperature: tmi_lm_head_argmax_c is argmax z' (same tie rule); tmi_lm_head_topk_c has s = z' * inv_temperature; in
+ * tmi_lm_head_sample_c s = z' / temperature, suppress_id is one more ban and the candidates are ranked on z'.  The
+ * logsumexp runs over the columns that are not banned; a banned column's log-probability is -inf and it is never drawn.
+ * A row whose every column is banned: argmax writes column 0; top-k writes columns 0 .. N-1 with log-probability -inf
+ * and lse -inf (never NaN); sample writes pad_id with log-probability 0.
+ * The _c entry points take the originals' arguments and then seen, banned (either may be NULL: an empty set; other-
+ * wise 4-byte aligned), bits_ld and penalty (finite, > 0; 1: none).  With both sets NULL the call IS the original (the
+ * same kernel, the same bits).  Workspaces: the originals', same sizes, left zero - an original and its _c form can
+ * alternate on one workspace.
+ *
+ * tmi_decode_constraints builds both sets for M rows from the rows' prefixes, one launch per decoding step:
+ *   prefix [M, ld] int32, columns [0, t) of each row are read (1 <= t <= ld) and nothing past them;
+ *   seen[r]   = { prefix[r, j] : j < t };
+ *   banned[r] = static_banned (W words, the same for every row; NULL: empty)
+ *               + { prefix[r, j + ngram - 1] : ngram >= 1, j + ngram - 1 <= t - 1,
+ *                   prefix[r, j : j + ngram - 1] == prefix[r, t - ngram + 1 : t] }
+ *     - the tokens that would complete an n-gram the prefix already holds; ngram 1: every token seen; ngram 0: none;
+ *     nothing while t < ngram - 1.
+ * A token id outside [0, V) is never used as an index and sets no bit.  All W words of both rows are written (the caller
+ * never clears them), bits at or above V in the last word are 0, words [W, bits_ld) are left untouched.  The result is
+ * the same bits in every run.  M <= 65535, V <= 65536, t <= 65536, ngram >= 0; anything else is TMI_ERR_INVALID and
+ * launches nothing.
+ */
+int tmi_decode_constraints(const int32_t* prefix, int64_t ld, int64_t M, int64_t t, int64_t V,
+                           const uint32_t* static_banned, int64_t ngram, uint32_t* seen, uint32_t* banned, int64_t bits_ld,
+                           void* stream);
+int tmi_lm_head_argmax_c(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                         const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, int32_t* ids,
+                         int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace, int64_t workspace_bytes,
+                         const uint32_t* seen, const uint32_t* banned, int64_t bits_ld, float penalty, void* stream);
+int tmi_lm_head_topk_c(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                       const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, float inv_temperature,
+                       int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace, int64_t workspace_bytes,
+                       const uint32_t* seen, const uint32_t* banned, int64_t bits_ld, float penalty, void* stream);
+int tmi_lm_head_sample_c(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                         const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, float temperature,
+                         int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id, int32_t eos_id, int32_t pad_id,
+                         int32_t* finished, int32_t* ids, int64_t ids_ld, float* logprob, int32_t* n_finished,
+                         void* workspace, int64_t workspace_bytes, const uint32_t* seen, const uint32_t* banned,
+                         int64_t bits_ld, float penalty, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * One step of beam search's bookkeeping (the rule of whisper.py generate / INTEGRATION.md), one workgroup per batch item
  * b of B; row r = b * K + k is beam k (1 <= K <= 8).  Step t (finalize = 0; 2K <= N <= 16):
  *   candidates (k, cand_ids[r * N + j], sums[r] + cand_lp[r * N + j]) (fp32 add), ranked by score desc then (k, id) asc;

@@ -10,6 +10,13 @@ the reference's seeded 30 s dummy clip into log-mel features on the GPU, and dec
 with the decoder start token; beam search adds "rank" and "score"), then one timing line.  No tokenizer ships
 with the project, so the output is token ids.
 
+``--repetition_penalty``, ``--no_repeat_ngram_size``, ``--suppress_tokens 1,2,3``, ``--begin_suppress_tokens`` and
+``--prompt_ids`` are ``generate``'s decode constraints and decoder prompt, in every mode: the logit of a token already
+in the transcript is divided (or, when negative, multiplied) by the penalty, a token that would repeat an n-gram cannot be
+emitted, the suppressed ids never appear (the begin-suppressed ones not as the first token), and the prompt's tokens
+follow the start token in the printed ids ("n_tokens" counts them; ``--max_length`` still counts generated tokens and is
+capped so that both fit the decoder).
+
 ``--save_cross_attentions PATH`` writes, after decoding, the cross-attention weights of each clip's (best) transcript to
 an ``.npz``: one more forward pass over [start, tokens] with ``output_attentions=("cross",)`` - under the reference's
 inverted decoder mask every decoding step recomputes the whole prefix, so this pass is the last step's computation -
@@ -52,6 +59,15 @@ def main(argv=None):
     parser.add_argument("--timestamps", action="store_true",
                         help="after each transcript, one '[start -> end] id' line per token (seconds; DTW over the "
                              "cross-attention weights); caps --max_length at 447")
+    id_list = lambda text: [int(v) for v in text.split(",") if v.strip()]  # noqa: E731
+    parser.add_argument("--repetition_penalty", type=float, default=None,
+                        help="logits of tokens already in the transcript: / this when positive, * this otherwise (1: off)")
+    parser.add_argument("--no_repeat_ngram_size", type=int, default=0, help="no n-gram of this size appears twice (0: off)")
+    parser.add_argument("--suppress_tokens", type=id_list, default=[], metavar="1,2,3", help="ids that are never emitted")
+    parser.add_argument("--begin_suppress_tokens", type=id_list, default=[], metavar="1,2,3",
+                        help="ids that are not emitted as the first token")
+    parser.add_argument("--prompt_ids", type=id_list, default=[], metavar="1,2,3",
+                        help="decoder prompt: these ids follow the start token")
     args = parser.parse_args(argv)
     if args.do_sample and args.num_beams > 1:
         parser.error("--do_sample does not go with --num_beams > 1")
@@ -68,6 +84,14 @@ def main(argv=None):
     model = whisper.create_whisper_model(args.model_type, device=device, precision=args.precision)
     if args.timestamps:
         args.max_length = min(args.max_length, model.config.max_target_positions - 1)
+    if args.prompt_ids:
+        room = model.config.max_target_positions - (1 if args.timestamps else 0) - len(args.prompt_ids)
+        args.max_length = max(0, min(args.max_length, room))
+    cons = dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                suppress_tokens=args.suppress_tokens, begin_suppress_tokens=args.begin_suppress_tokens,
+                prompt_ids=args.prompt_ids or None)
+    whisper.check_constraint_args(model.config, args.max_length, args.num_beams, return_token_timestamps=args.timestamps,
+                                  **cons)
     beam = args.num_beams > 1
     sample = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                   min_length=args.min_length, seed=args.seed) if args.do_sample else None
@@ -127,7 +151,7 @@ def main(argv=None):
         if args.save_cross_attentions or args.timestamps:
             feats_all = fe(wave)
         if sample:
-            out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample)
+            out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample, **cons)
             seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
             lines = stamps(feats_all, seqs, lens, wave.shape[1], range(len(items))) if args.timestamps else {}
             for j, ((name, _), row, sc, n) in enumerate(zip(items, seqs, scores, lens)):
@@ -140,7 +164,7 @@ def main(argv=None):
                 save_cross(name, feats_all[j] if args.save_cross_attentions else None, row[:1 + int(n)].tolist())
             continue
         if not beam:
-            ids = model.generate(fe(wave), max_length=args.max_length).cpu()
+            ids = model.generate(fe(wave), max_length=args.max_length, **cons).cpu()
             lines = stamps(feats_all, ids, None, wave.shape[1], range(len(items))) if args.timestamps else {}
             for j, ((name, _), row) in enumerate(zip(items, ids)):
                 n_tok += row.numel() - 1
@@ -152,7 +176,8 @@ def main(argv=None):
             continue
         R = args.num_return_sequences
         out = model.generate(fe(wave), max_length=args.max_length, num_beams=args.num_beams,
-                             length_penalty=args.length_penalty, num_return_sequences=R, return_dict_in_generate=True)
+                             length_penalty=args.length_penalty, num_return_sequences=R, return_dict_in_generate=True,
+                             **cons)
         seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
         lines = stamps(feats_all, seqs, lens, wave.shape[1], range(len(seqs))) if args.timestamps else {}
         for i, row in enumerate(seqs):

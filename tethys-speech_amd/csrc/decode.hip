@@ -31,6 +31,36 @@ __device__ __forceinline__ uint32_t am_order(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// Decode constraints (tmi_lm_head_*_c; the rule is include/tethys_mi.h's "Decode constraints"): two bit sets per row,
+// column n at bit n & 31 of word n >> 5.  A thread of the epilogue owns 8 consecutive columns from a multiple of 8, so its
+// bits are one byte of one word of each set.  C = false compiles all of it away: the unconstrained kernels are unchanged.
+struct am_cons {
+  const uint32_t* seen;
+  const uint32_t* banned;
+  int64_t bits_ld;
+  float penalty;
+};
+template <bool C>
+__device__ __forceinline__ void am_cons_bits(const am_cons& cs, int r, int c0, int V, uint32_t& sb, uint32_t& bb) {
+  sb = 0, bb = 0;
+  if constexpr (C) {
+    if (c0 < V) {  // (a word at or past ceil(V / 32) is never read)
+      const int64_t o = (int64_t)r * cs.bits_ld + (c0 >> 5);
+      if (cs.seen) sb = (cs.seen[o] >> (c0 & 31)) & 0xffu;
+      if (cs.banned) bb = (cs.banned[o] >> (c0 & 31)) & 0xffu;
+    }
+  }
+}
+// z -> z': -inf when banned, z / penalty (z > 0) or z * penalty (z <= 0) when seen
+template <bool C>
+__device__ __forceinline__ float am_cons_logit(float z, uint32_t sb, uint32_t bb, int c, float penalty) {
+  if constexpr (C) {
+    if ((bb >> c) & 1u) return -INFINITY;
+    if ((sb >> c) & 1u) return z > 0.f ? __fdiv_rn(z, penalty) : z * penalty;
+  }
+  return z;
+}
+
 template <typename TW> struct am_rows;
 // 8 consecutive columns of one weight row, in registers
 template <> struct am_rows<bf16_t> {
@@ -176,11 +206,12 @@ __device__ __forceinline__ void am_head_tile(float* am_lds, const void* __restri
 }
 
 // grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128) floats
-template <typename TW, int MT>
-__global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
+template <typename TW, int MT, bool C>
+__device__ __forceinline__ void lm_head_argmax_body(
     const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
     float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, int32_t* __restrict__ ids, int64_t ids_ld,
-    int eos_id, int32_t* __restrict__ eos_count, uint64_t* __restrict__ slots, uint32_t* __restrict__ counter) {
+    int eos_id, int32_t* __restrict__ eos_count, uint64_t* __restrict__ slots, uint32_t* __restrict__ counter,
+    const am_cons cs) {
   extern __shared__ __attribute__((aligned(16))) float am_lds[];
   __shared__ int am_last, am_eos;
   const int tid = threadIdx.x;
@@ -195,11 +226,14 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
     uint64_t best = 0;  // 0 = no candidate (every real key is larger: its ~column half is nonzero or its value half is)
     if (m < rows) {
       const int c0 = blockIdx.x * AM_COLS + g * 8;
+      uint32_t sb, bb;
+      am_cons_bits<C>(cs, row0 + m, c0, V, sb, bb);
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const int col = c0 + c;
         const int o = m * AM_COLS + g * 8 + c;
-        const float v = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
+        const float z = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
+        const float v = am_cons_logit<C>(z, sb, bb, c, cs.penalty);
         const uint64_t key = ((uint64_t)am_order(v) << 32) | (uint64_t)(~(uint32_t)col);
         if (col < V && key > best) best = key;
       }
@@ -242,9 +276,44 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
 }
 
 template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, int32_t* __restrict__ ids, int64_t ids_ld,
+    int eos_id, int32_t* __restrict__ eos_count, uint64_t* __restrict__ slots, uint32_t* __restrict__ counter) {
+  lm_head_argmax_body<TW, MT, false>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, ids, ids_ld, eos_id, eos_count,
+                                     slots, counter, am_cons{nullptr, nullptr, 0, 1.f});
+}
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_c_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, int32_t* __restrict__ ids, int64_t ids_ld,
+    int eos_id, int32_t* __restrict__ eos_count, uint64_t* __restrict__ slots, uint32_t* __restrict__ counter,
+    const uint32_t* __restrict__ seen, const uint32_t* __restrict__ banned, int64_t bits_ld, float penalty) {
+  lm_head_argmax_body<TW, MT, true>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, ids, ids_ld, eos_id, eos_count,
+                                    slots, counter, am_cons{seen, banned, bits_ld, penalty});
+}
+
+template <typename TW, int MT>
 int am_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
               const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, int32_t* ids, int64_t ids_ld,
-              int eos_id, int32_t* eos_count, uint64_t* slots, uint32_t* counter) {
+              int eos_id, int32_t* eos_count, uint64_t* slots, uint32_t* counter, const am_cons* cs) {
+  if (cs) {
+    auto kern = lm_head_argmax_c_kernel<TW, MT>;
+    static size_t opted = 65536;  // (as below)
+    if (lds > opted) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+          hipSuccess) {
+        (void)hipGetLastError();
+        tmi_set_error("tmi_lm_head_argmax_c: the LDS size could not be granted");
+        return TMI_ERR_LAUNCH;
+      }
+      opted = lds;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
+                       reinterpret_cast<const TW*>(w), w_ld, M, d, V, ids, ids_ld, eos_id, eos_count, slots, counter,
+                       cs->seen, cs->banned, cs->bits_ld, cs->penalty);
+    return tmi_check_launch("tmi_lm_head_argmax_c");
+  }
   auto kern = lm_head_argmax_kernel<TW, MT>;
   // above 64 KiB of dynamic LDS (16 rows of d > 1024) the kernel has to opt in, up to what it needs (160 KiB per CU on
   // gfx950, its few static bytes included)
@@ -266,11 +335,11 @@ int am_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld,
 template <typename TW>
 int am_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
                 const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, int32_t* ids,
-                int64_t ids_ld, int eos_id, int32_t* eos_count, uint64_t* slots, uint32_t* counter) {
+                int64_t ids_ld, int eos_id, int32_t* eos_count, uint64_t* slots, uint32_t* counter, const am_cons* cs) {
 #define AM_CASE(n)                                                                                                  \
   case n:                                                                                                           \
     return am_launch<TW, n>(grid, lds, s, x, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, ids, ids_ld, eos_id, \
-                            eos_count, slots, counter);
+                            eos_count, slots, counter, cs);
   switch (MT) {
     AM_CASE(1) AM_CASE(2) AM_CASE(4) AM_CASE(8) AM_CASE(16)
   }
@@ -319,12 +388,12 @@ __device__ __forceinline__ uint64_t tk_wave_max(uint64_t v) {
 }
 
 // grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128, 4 * TK_CAP * 2) floats
-template <typename TW, int MT>
-__global__ __launch_bounds__(AM_THREADS) void lm_head_topk_kernel(
+template <typename TW, int MT, bool C>
+__device__ __forceinline__ void lm_head_topk_body(
     const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
     float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float inv_t, int N, int32_t* __restrict__ out_ids,
     float* __restrict__ out_lp, float* __restrict__ out_lse, uint32_t* __restrict__ counters, float2* __restrict__ part,
-    uint64_t* __restrict__ keys) {
+    uint64_t* __restrict__ keys, const am_cons cs) {
   extern __shared__ __attribute__((aligned(16))) float am_lds[];
   __shared__ int tk_last;
   __shared__ int tk_n[4];
@@ -344,20 +413,28 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_topk_kernel(
       float s[8];
       uint64_t k8[8];
       float mx = -INFINITY;
+      uint32_t sb, bb;
+      am_cons_bits<C>(cs, r, c0, V, sb, bb);
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const int o = m * AM_COLS + g * 8 + c;
         const float z = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
-        s[c] = z * inv_t;
+        s[c] = am_cons_logit<C>(z, sb, bb, c, cs.penalty) * inv_t;
         const bool ok = c0 + c < V;
+        // (a banned column keeps its key, value -inf: it ranks below every other column and is outside the logsumexp)
         k8[c] = ok ? (((uint64_t)am_order(s[c]) << 32) | (uint64_t)(~(uint32_t)(c0 + c))) : 0;
-        if (ok) mx = fmaxf(mx, s[c]);
+        if (ok && !((bb >> c) & 1u)) mx = fmaxf(mx, s[c]);
       }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
       float se = 0.f;
 #pragma unroll
-      for (int c = 0; c < 8; ++c) se += (c0 + c < V) ? expf(s[c] - mx) : 0.f;
+      for (int c = 0; c < 8; ++c) {
+        if constexpr (C)
+          se += (c0 + c < V && !((bb >> c) & 1u) && mx > -INFINITY) ? expf(s[c] - mx) : 0.f;
+        else
+          se += (c0 + c < V) ? expf(s[c] - mx) : 0.f;
+      }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) se += __shfl_xor(se, o, 64);  // (xor pairs: both lanes add the same two values)
       if (g == 0) part[(int64_t)r * nwg + blockIdx.x] = make_float2(mx, se);
@@ -463,7 +540,11 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_topk_kernel(
       for (int i = 0; i < c; ++i) rank += lk[i] > key;
       if (rank < N) {
         out_ids[(int64_t)r * N + rank] = (int32_t)(~(uint32_t)key);
-        out_lp[(int64_t)r * N + rank] = tk_unorder((uint32_t)(key >> 32)) - lse;
+        const float sv = tk_unorder((uint32_t)(key >> 32));
+        if constexpr (C)  // (a banned column: -inf, also in a row whose every column is banned, where lse is -inf too)
+          out_lp[(int64_t)r * N + rank] = sv == -INFINITY ? -INFINITY : sv - lse;
+        else
+          out_lp[(int64_t)r * N + rank] = sv - lse;
       }
     }
     for (int64_t j = lane; j < (int64_t)nwg * N; j += 64) list[j] = 0;
@@ -475,9 +556,47 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_topk_kernel(
 }
 
 template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_topk_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float inv_t, int N, int32_t* __restrict__ out_ids,
+    float* __restrict__ out_lp, float* __restrict__ out_lse, uint32_t* __restrict__ counters, float2* __restrict__ part,
+    uint64_t* __restrict__ keys) {
+  lm_head_topk_body<TW, MT, false>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse,
+                                   counters, part, keys, am_cons{nullptr, nullptr, 0, 1.f});
+}
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_topk_c_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float inv_t, int N, int32_t* __restrict__ out_ids,
+    float* __restrict__ out_lp, float* __restrict__ out_lse, uint32_t* __restrict__ counters, float2* __restrict__ part,
+    uint64_t* __restrict__ keys, const uint32_t* __restrict__ seen, const uint32_t* __restrict__ banned, int64_t bits_ld,
+    float penalty) {
+  lm_head_topk_body<TW, MT, true>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse,
+                                  counters, part, keys, am_cons{seen, banned, bits_ld, penalty});
+}
+
+template <typename TW, int MT>
 int tk_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
               const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, float inv_t, int N,
-              int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys) {
+              int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys,
+              const am_cons* cs) {
+  if (cs) {
+    auto kern = lm_head_topk_c_kernel<TW, MT>;
+    static size_t opted = 65536;  // (as am_launch)
+    if (lds > opted) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+          hipSuccess) {
+        (void)hipGetLastError();
+        tmi_set_error("tmi_lm_head_topk_c: the LDS size could not be granted");
+        return TMI_ERR_LAUNCH;
+      }
+      opted = lds;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
+                       reinterpret_cast<const TW*>(w), w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse, counters, part,
+                       keys, cs->seen, cs->banned, cs->bits_ld, cs->penalty);
+    return tmi_check_launch("tmi_lm_head_topk_c");
+  }
   auto kern = lm_head_topk_kernel<TW, MT>;
   static size_t opted = 65536;  // (as am_launch)
   if (lds > opted) {
@@ -497,11 +616,12 @@ int tk_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld,
 template <typename TW>
 int tk_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
                 const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, float inv_t, int N,
-                int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys) {
+                int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys,
+                const am_cons* cs) {
 #define TK_CASE(n)                                                                                                     \
   case n:                                                                                                              \
     return tk_launch<TW, n>(grid, lds, s, x, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, inv_t, N, out_ids,      \
-                            out_lp, out_lse, counters, part, keys);
+                            out_lp, out_lse, counters, part, keys, cs);
   switch (MT) {
     TK_CASE(1) TK_CASE(2) TK_CASE(4) TK_CASE(8) TK_CASE(16)
   }
@@ -544,13 +664,13 @@ __device__ __forceinline__ float sm_neglog_u(uint32_t n) {
 }
 
 // grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128, 512) floats
-template <typename TW, int MT>
-__global__ __launch_bounds__(AM_THREADS) void lm_head_sample_kernel(
+template <typename TW, int MT, bool C>
+__device__ __forceinline__ void lm_head_sample_body(
     const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
     float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float temperature, int top_k, float top_p,
     uint32_t stream_key, int suppress_id, int eos_id, int pad_id, int32_t* __restrict__ finished, int32_t* __restrict__ ids,
     int64_t ids_ld, float* __restrict__ out_lp, int32_t* __restrict__ n_finished, uint32_t* __restrict__ counters,
-    float2* __restrict__ part, uint64_t* __restrict__ keys) {
+    float2* __restrict__ part, uint64_t* __restrict__ keys, const am_cons cs) {
   extern __shared__ __attribute__((aligned(16))) float am_lds[];
   __shared__ int sm_last, sm_count;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -571,12 +691,15 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_sample_kernel(
       uint64_t k8[8];
       bool ok[8];
       float mx = -INFINITY;
+      uint32_t sb, bb;
+      am_cons_bits<C>(cs, r, c0, V, sb, bb);
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const int o = m * AM_COLS + g * 8 + c;
-        const float z = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
+        const float z = am_cons_logit<C>(
+            ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o], sb, bb, c, cs.penalty);
         s[c] = __fdiv_rn(z, temperature);
-        ok[c] = c0 + c < V && c0 + c != suppress_id;
+        ok[c] = c0 + c < V && c0 + c != suppress_id && !((bb >> c) & 1u);  // (a banned column: one more suppressed id)
         k8[c] = ok[c] ? sm_key(z, c0 + c) : 0;
         if (ok[c]) mx = fmaxf(mx, s[c]);
       }
@@ -799,8 +922,50 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_sample_kernel(
   }
 }
 
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_sample_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float temperature, int top_k, float top_p,
+    uint32_t stream_key, int suppress_id, int eos_id, int pad_id, int32_t* __restrict__ finished, int32_t* __restrict__ ids,
+    int64_t ids_ld, float* __restrict__ out_lp, int32_t* __restrict__ n_finished, uint32_t* __restrict__ counters,
+    float2* __restrict__ part, uint64_t* __restrict__ keys) {
+  lm_head_sample_body<TW, MT, false>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, temperature, top_k, top_p,
+                                     stream_key, suppress_id, eos_id, pad_id, finished, ids, ids_ld, out_lp, n_finished,
+                                     counters, part, keys, am_cons{nullptr, nullptr, 0, 1.f});
+}
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_sample_c_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, float temperature, int top_k, float top_p,
+    uint32_t stream_key, int suppress_id, int eos_id, int pad_id, int32_t* __restrict__ finished, int32_t* __restrict__ ids,
+    int64_t ids_ld, float* __restrict__ out_lp, int32_t* __restrict__ n_finished, uint32_t* __restrict__ counters,
+    float2* __restrict__ part, uint64_t* __restrict__ keys, const uint32_t* __restrict__ seen,
+    const uint32_t* __restrict__ banned, int64_t bits_ld, float penalty) {
+  lm_head_sample_body<TW, MT, true>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, temperature, top_k, top_p,
+                                    stream_key, suppress_id, eos_id, pad_id, finished, ids, ids_ld, out_lp, n_finished,
+                                    counters, part, keys, am_cons{seen, banned, bits_ld, penalty});
+}
+
 template <typename TW, int MT, typename... A>
-int sm_launch(dim3 grid, size_t lds, hipStream_t s, A... a) {
+int sm_launch_c(dim3 grid, size_t lds, hipStream_t s, const am_cons* cs, A... a) {
+  auto kern = lm_head_sample_c_kernel<TW, MT>;
+  static size_t opted = 65536;  // (as am_launch)
+  if (lds > opted) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+        hipSuccess) {
+      (void)hipGetLastError();
+      tmi_set_error("tmi_lm_head_sample_c: the LDS size could not be granted");
+      return TMI_ERR_LAUNCH;
+    }
+    opted = lds;
+  }
+  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, a..., cs->seen, cs->banned, cs->bits_ld, cs->penalty);
+  return tmi_check_launch("tmi_lm_head_sample_c");
+}
+
+template <typename TW, int MT, typename... A>
+int sm_launch(dim3 grid, size_t lds, hipStream_t s, const am_cons* cs, A... a) {
+  if (cs) return sm_launch_c<TW, MT>(grid, lds, s, cs, a...);
   auto kern = lm_head_sample_kernel<TW, MT>;
   static size_t opted = 65536;  // (as am_launch)
   if (lds > opted) {
@@ -817,13 +982,13 @@ int sm_launch(dim3 grid, size_t lds, hipStream_t s, A... a) {
 }
 
 template <typename TW, typename... A>
-int sm_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, A... a) {
+int sm_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const am_cons* cs, A... a) {
   switch (MT) {
-    case 1: return sm_launch<TW, 1>(grid, lds, s, a...);
-    case 2: return sm_launch<TW, 2>(grid, lds, s, a...);
-    case 4: return sm_launch<TW, 4>(grid, lds, s, a...);
-    case 8: return sm_launch<TW, 8>(grid, lds, s, a...);
-    case 16: return sm_launch<TW, 16>(grid, lds, s, a...);
+    case 1: return sm_launch<TW, 1>(grid, lds, s, cs, a...);
+    case 2: return sm_launch<TW, 2>(grid, lds, s, cs, a...);
+    case 4: return sm_launch<TW, 4>(grid, lds, s, cs, a...);
+    case 8: return sm_launch<TW, 8>(grid, lds, s, cs, a...);
+    case 16: return sm_launch<TW, 16>(grid, lds, s, cs, a...);
   }
   return TMI_ERR_INVALID;
 }
@@ -832,17 +997,30 @@ inline bool am_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15
 
 }  // namespace
 
-static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                   int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
-                                   int64_t workspace_bytes, void* stream) {
+// The constraint arguments of the _c entry points -> the kernels' form, or false.  Both sets NULL is "no constraint": the
+// unconstrained instantiation runs (cs stays null), which is what gives such a call the originals' bits.
+static bool am_cons_args(const uint32_t* seen, const uint32_t* banned, int64_t bits_ld, float penalty, int64_t V, am_cons& c,
+                         const am_cons*& cs) {
+  cs = nullptr;
+  if (!(penalty > 0.f && penalty < INFINITY)) return false;
+  if (!seen && !banned) return true;
+  if (bits_ld < (V + 31) / 32 || ((reinterpret_cast<uintptr_t>(seen) | reinterpret_cast<uintptr_t>(banned)) & 3)) return false;
+  c = am_cons{seen, banned, bits_ld, penalty};
+  cs = &c;
+  return true;
+}
+
+static int am_run(const char* bad, const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, int32_t* ids,
+                  int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace, int64_t workspace_bytes, void* stream,
+                  const am_cons* cs) {
   const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
   const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
   const int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
   if (!x || !w || !ids || !workspace || !dt_ok || M < 1 || M > (int64_t)16 * 65535 || d < 1 || V < 1 || V >= INT32_MAX ||
       w_ld < V || (w_ld & 7) || !am_al16(w) || x_ld < d || ids_ld < 1 || (gamma == nullptr) != (beta == nullptr) ||
       workspace_bytes < 8 * (M + 1) || (reinterpret_cast<uintptr_t>(workspace) & 7) || lds_floats * 4 > 160 * 1024 - 256) {
-    tmi_set_error("tmi_lm_head_argmax: bad argument");
+    tmi_set_error(bad);
     return TMI_ERR_INVALID;
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -853,9 +1031,16 @@ static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype,
   const int xb = x_dtype == TMI_BF16;
   if (w_dtype == TMI_BF16)
     return am_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V, ids, ids_ld,
-                               eos_id, eos_count, slots, counter);
+                               eos_id, eos_count, slots, counter, cs);
   return am_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V, ids, ids_ld,
-                            eos_id, eos_count, slots, counter);
+                            eos_id, eos_count, slots, counter, cs);
+}
+static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                   int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
+                                   int64_t workspace_bytes, void* stream) {
+  return am_run("tmi_lm_head_argmax: bad argument", x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids, ids_ld,
+                eos_id, eos_count, workspace, workspace_bytes, stream, nullptr);
 }
 extern "C" int tmi_lm_head_argmax(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
@@ -864,11 +1049,34 @@ extern "C" int tmi_lm_head_argmax(const void* x, int64_t x_ld, int32_t x_dtype, 
   return tmi_plan_run<tmi_lm_head_argmax_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids, ids_ld,
                                                eos_id, eos_count, workspace, workspace_bytes, stream);
 }
+static int tmi_lm_head_argmax_c_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                     float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                     int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
+                                     int64_t workspace_bytes, const uint32_t* seen, const uint32_t* banned, int64_t bits_ld,
+                                     float penalty, void* stream) {
+  am_cons c;
+  const am_cons* cs;
+  if (!am_cons_args(seen, banned, bits_ld, penalty, V, c, cs)) {
+    tmi_set_error("tmi_lm_head_argmax_c: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  return am_run("tmi_lm_head_argmax_c: bad argument", x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids,
+                ids_ld, eos_id, eos_count, workspace, workspace_bytes, stream, cs);
+}
+extern "C" int tmi_lm_head_argmax_c(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                    float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                    int32_t* ids, int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace,
+                                    int64_t workspace_bytes, const uint32_t* seen, const uint32_t* banned, int64_t bits_ld,
+                                    float penalty, void* stream) {
+  return tmi_plan_run<tmi_lm_head_argmax_c_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, ids, ids_ld,
+                                                 eos_id, eos_count, workspace, workspace_bytes, seen, banned, bits_ld,
+                                                 penalty, stream);
+}
 
-static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                 float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                 float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
-                                 void* workspace, int64_t workspace_bytes, void* stream) {
+static int tk_run(const char* bad, const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                  float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace,
+                  int64_t workspace_bytes, void* stream, const am_cons* cs) {
   const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
   const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
   int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
@@ -880,7 +1088,7 @@ static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, c
       x_ld < d || (gamma == nullptr) != (beta == nullptr) || !(inv_temperature > 0.f && inv_temperature < INFINITY) ||
       workspace_bytes < 8 * M * (1 + nwg * (N + 1)) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
       lds_floats * 4 > 160 * 1024 - 256) {
-    tmi_set_error("tmi_lm_head_topk: bad argument");
+    tmi_set_error(bad);
     return TMI_ERR_INVALID;
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -893,9 +1101,16 @@ static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, c
   const int xb = x_dtype == TMI_BF16;
   if (w_dtype == TMI_BF16)
     return tk_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
-                               inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys);
+                               inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys, cs);
   return tk_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
-                            inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys);
+                            inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys, cs);
+}
+static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                 float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                 float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  return tk_run("tmi_lm_head_topk: bad argument", x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V,
+                inv_temperature, N, ids, logprobs, lse, workspace, workspace_bytes, stream, nullptr);
 }
 extern "C" int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                 float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
@@ -904,6 +1119,29 @@ extern "C" int tmi_lm_head_topk(const void* x, int64_t x_ld, int32_t x_dtype, co
   return tmi_plan_run<tmi_lm_head_topk_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature, N,
                                              ids, logprobs, lse, workspace, workspace_bytes, stream);
 }
+static int tmi_lm_head_topk_c_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                   float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
+                                   void* workspace, int64_t workspace_bytes, const uint32_t* seen, const uint32_t* banned,
+                                   int64_t bits_ld, float penalty, void* stream) {
+  am_cons c;
+  const am_cons* cs;
+  if (!am_cons_args(seen, banned, bits_ld, penalty, V, c, cs)) {
+    tmi_set_error("tmi_lm_head_topk_c: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  return tk_run("tmi_lm_head_topk_c: bad argument", x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V,
+                inv_temperature, N, ids, logprobs, lse, workspace, workspace_bytes, stream, cs);
+}
+extern "C" int tmi_lm_head_topk_c(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                  float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse,
+                                  void* workspace, int64_t workspace_bytes, const uint32_t* seen, const uint32_t* banned,
+                                  int64_t bits_ld, float penalty, void* stream) {
+  return tmi_plan_run<tmi_lm_head_topk_c_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, inv_temperature,
+                                               N, ids, logprobs, lse, workspace, workspace_bytes, seen, banned, bits_ld,
+                                               penalty, stream);
+}
 
 extern "C" int64_t tmi_lm_head_sample_workspace_bytes(int64_t M, int64_t V, int64_t top_k) {
   if (M < 1 || V < 1 || top_k < 0 || top_k > SM_MAXK) return -1;
@@ -911,12 +1149,11 @@ extern "C" int64_t tmi_lm_head_sample_workspace_bytes(int64_t M, int64_t V, int6
   return 8 * M * (1 + nwg * (1 + (top_k > 0 ? top_k : 2))) + 8;
 }
 
-static int tmi_lm_head_sample_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
-                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
-                                   float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id,
-                                   int32_t eos_id, int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld,
-                                   float* logprob, int32_t* n_finished, void* workspace, int64_t workspace_bytes,
-                                   void* stream) {
+static int sm_run(const char* bad, const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                  float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id, int32_t eos_id,
+                  int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld, float* logprob, int32_t* n_finished,
+                  void* workspace, int64_t workspace_bytes, void* stream, const am_cons* cs) {
   const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
   const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
   int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
@@ -929,7 +1166,7 @@ static int tmi_lm_head_sample_impl(const void* x, int64_t x_ld, int32_t x_dtype,
       (w_ld & 7) || !am_al16(w) || x_ld < d || ids_ld < 1 || (gamma == nullptr) != (beta == nullptr) ||
       workspace_bytes < tmi_lm_head_sample_workspace_bytes(M, V, top_k) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
       lds_floats * 4 > 160 * 1024 - 256) {
-    tmi_set_error("tmi_lm_head_sample: bad argument");
+    tmi_set_error(bad);
     return TMI_ERR_INVALID;
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -942,12 +1179,22 @@ static int tmi_lm_head_sample_impl(const void* x, int64_t x_ld, int32_t x_dtype,
   const int xb = x_dtype == TMI_BF16;
   const uint32_t skey = tmi_stream_key(seed, 0);
   if (w_dtype == TMI_BF16)
-    return sm_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const bf16_t*>(w), w_ld,
+    return sm_dispatch<bf16_t>(MT, grid, lds, s, cs, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const bf16_t*>(w), w_ld,
                                (int)M, (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id,
                                (int)pad_id, finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
-  return sm_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const float*>(w), w_ld, (int)M,
-                            (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id, (int)pad_id,
-                            finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
+  return sm_dispatch<float>(MT, grid, lds, s, cs, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const float*>(w), w_ld,
+                            (int)M, (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id,
+                            (int)pad_id, finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
+}
+static int tmi_lm_head_sample_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                   float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id,
+                                   int32_t eos_id, int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld,
+                                   float* logprob, int32_t* n_finished, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  return sm_run("tmi_lm_head_sample: bad argument", x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, temperature,
+                top_k, top_p, seed, suppress_id, eos_id, pad_id, finished, ids, ids_ld, logprob, n_finished, workspace,
+                workspace_bytes, stream, nullptr);
 }
 extern "C" int tmi_lm_head_sample(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
@@ -958,4 +1205,95 @@ extern "C" int tmi_lm_head_sample(const void* x, int64_t x_ld, int32_t x_dtype, 
   return tmi_plan_run<tmi_lm_head_sample_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, temperature,
                                                top_k, top_p, seed, suppress_id, eos_id, pad_id, finished, ids, ids_ld,
                                                logprob, n_finished, workspace, workspace_bytes, stream);
+}
+static int tmi_lm_head_sample_c_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                     float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                     float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id,
+                                     int32_t eos_id, int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld,
+                                     float* logprob, int32_t* n_finished, void* workspace, int64_t workspace_bytes,
+                                     const uint32_t* seen, const uint32_t* banned, int64_t bits_ld, float penalty,
+                                     void* stream) {
+  am_cons c;
+  const am_cons* cs;
+  if (!am_cons_args(seen, banned, bits_ld, penalty, V, c, cs)) {
+    tmi_set_error("tmi_lm_head_sample_c: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  return sm_run("tmi_lm_head_sample_c: bad argument", x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V,
+                temperature, top_k, top_p, seed, suppress_id, eos_id, pad_id, finished, ids, ids_ld, logprob, n_finished,
+                workspace, workspace_bytes, stream, cs);
+}
+extern "C" int tmi_lm_head_sample_c(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                    float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                                    float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id,
+                                    int32_t eos_id, int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld,
+                                    float* logprob, int32_t* n_finished, void* workspace, int64_t workspace_bytes,
+                                    const uint32_t* seen, const uint32_t* banned, int64_t bits_ld, float penalty,
+                                    void* stream) {
+  return tmi_plan_run<tmi_lm_head_sample_c_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, temperature,
+                                                 top_k, top_p, seed, suppress_id, eos_id, pad_id, finished, ids, ids_ld,
+                                                 logprob, n_finished, workspace, workspace_bytes, seen, banned, bits_ld,
+                                                 penalty, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// tmi_decode_constraints: the two bit sets of the _c LM heads for M rows, from the rows' current prefixes; the rule is
+// include/tethys_mi.h's.  One workgroup per row, both sets built in LDS (8 KiB each at V = 65536) with LDS atomic ORs - an
+// OR does not depend on the order, so the words are the same in every run - and written out once, every one of the W
+// words: the caller never clears them.  The work is a few hundred loads; the cost is the launch.
+namespace {
+constexpr int CN_THREADS = 256;
+constexpr int CN_MAXV = 65536;
+
+__global__ __launch_bounds__(CN_THREADS) void decode_constraints_kernel(
+    const int32_t* __restrict__ prefix, int64_t ld, int t, int V, int W, const uint32_t* __restrict__ static_banned, int ngram,
+    uint32_t* __restrict__ seen, uint32_t* __restrict__ banned, int64_t bits_ld) {
+  __shared__ uint32_t s_seen[CN_MAXV / 32], s_ban[CN_MAXV / 32];
+  const int tid = threadIdx.x;
+  const int32_t* p = prefix + (int64_t)blockIdx.x * ld;
+  for (int i = tid; i < W; i += CN_THREADS) {
+    s_seen[i] = 0;
+    s_ban[i] = static_banned ? static_banned[i] : 0;
+  }
+  __syncthreads();
+  for (int j = tid; j < t; j += CN_THREADS) {
+    const uint32_t x = (uint32_t)p[j];
+    if (x < (uint32_t)V) atomicOr(&s_seen[x >> 5], 1u << (x & 31));  // (an id outside [0, V) sets no bit)
+  }
+  const int g = ngram - 1;  // the length of the context: the last g tokens of the prefix
+  if (ngram >= 1 && g <= t) {
+    for (int j = tid; j + g < t; j += CN_THREADS) {  // (the token after the match is column j + g <= t - 1)
+      bool same = true;
+      for (int i = 0; i < g && same; ++i) same = p[j + i] == p[t - g + i];
+      const uint32_t x = (uint32_t)p[j + g];
+      if (same && x < (uint32_t)V) atomicOr(&s_ban[x >> 5], 1u << (x & 31));
+    }
+  }
+  __syncthreads();
+  const uint32_t last = (V & 31) ? ((1u << (V & 31)) - 1u) : 0xffffffffu;  // bits at or above V stay 0
+  for (int i = tid; i < W; i += CN_THREADS) {
+    const uint32_t mask = i == W - 1 ? last : 0xffffffffu;
+    seen[(int64_t)blockIdx.x * bits_ld + i] = s_seen[i] & mask;
+    banned[(int64_t)blockIdx.x * bits_ld + i] = s_ban[i] & mask;
+  }
+}
+}  // namespace
+
+static int tmi_decode_constraints_impl(const int32_t* prefix, int64_t ld, int64_t M, int64_t t, int64_t V,
+                                       const uint32_t* static_banned, int64_t ngram, uint32_t* seen, uint32_t* banned,
+                                       int64_t bits_ld, void* stream) {
+  const int64_t W = (V + 31) / 32;
+  if (!prefix || !seen || !banned || M < 1 || M > 65535 || V < 1 || V > CN_MAXV || t < 1 || t > 65536 || t > ld || ngram < 0 ||
+      ngram > INT32_MAX || bits_ld < W) {
+    tmi_set_error("tmi_decode_constraints: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(decode_constraints_kernel, dim3((unsigned)M), dim3(CN_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     prefix, ld, (int)t, (int)V, (int)W, static_banned, (int)ngram, seen, banned, bits_ld);
+  return tmi_check_launch("tmi_decode_constraints");
+}
+extern "C" int tmi_decode_constraints(const int32_t* prefix, int64_t ld, int64_t M, int64_t t, int64_t V,
+                                      const uint32_t* static_banned, int64_t ngram, uint32_t* seen, uint32_t* banned,
+                                      int64_t bits_ld, void* stream) {
+  return tmi_plan_run<tmi_decode_constraints_impl>(prefix, ld, M, t, V, static_banned, ngram, seen, banned, bits_ld, stream);
 }

@@ -778,6 +778,83 @@ def lm_head_sample(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished,
                                        workspace.numel() * workspace.element_size(), stream()), "tmi_lm_head_sample")
 
 
+def constraint_words(V: int) -> int:
+    """uint32 words per row of a decode-constraint bit set over V columns (column n: bit n & 31 of word n >> 5)."""
+    return (int(V) + 31) // 32
+
+
+def _bits(t, rows, V, what):
+    if t is None:
+        return None, 0
+    if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] < rows or t.stride(1) != 1 or t.shape[1] < constraint_words(V):
+        raise ValueError(f"{what} must be an int32 [>= {rows}, >= {constraint_words(V)}] bit set with unit column stride")
+    return t, t.stride(0)
+
+
+def _cons_args(seen, banned, rows, V):
+    seen, ld_s = _bits(seen, rows, V, "seen")
+    banned, ld_b = _bits(banned, rows, V, "banned")
+    if seen is not None and banned is not None and ld_s != ld_b:
+        raise ValueError("seen and banned must share their row stride")
+    return ptr(seen), ptr(banned), ld_s or ld_b
+
+
+def decode_constraints(prefix, ld, M, t, V, seen, banned, ngram=0, static_banned=None):
+    """The two bit sets of the constrained LM heads for M rows (tmi_decode_constraints; the rule is include/tethys_mi.h's):
+    ``seen[r]`` = the tokens in prefix[r, :t], ``banned[r]`` = ``static_banned`` plus the tokens that would complete an
+    ``ngram``-gram the prefix already holds (0: none).  ``prefix`` int32 with row stride ``ld``; ``seen`` and ``banned``
+    int32 [M, >= constraint_words(V)] of one row stride, every word of [:, :constraint_words(V)] written;
+    ``static_banned`` int32 [constraint_words(V)] or None."""
+    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
+    if sp is None or bp is None:
+        raise ValueError("decode_constraints writes both seen and banned")
+    if static_banned is not None and (static_banned.dtype != torch.int32 or not static_banned.is_contiguous()
+                                      or static_banned.numel() < constraint_words(V)):
+        raise ValueError(f"static_banned must be a contiguous int32 tensor of >= {constraint_words(V)} words")
+    check(lib().tmi_decode_constraints(prefix.data_ptr(), ld, M, t, V, ptr(static_banned), int(ngram), sp, bp, bits_ld,
+                                       stream()), "tmi_decode_constraints")
+
+
+def lm_head_argmax_c(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, seen=None, banned=None, penalty=1.0, gamma=None,
+                     beta=None, eps=1e-5, eos_id=-1, eos_count=None):
+    """``lm_head_argmax`` over the constrained logits z' (include/tethys_mi.h, "Decode constraints"): a column whose bit
+    is set in ``banned[r]`` is -inf, one set in ``seen[r]`` is divided (z > 0) or multiplied (z <= 0) by ``penalty``.
+    ``seen`` / ``banned``: int32 [M, >= constraint_words(V)] bit sets or None (empty); the workspace is lm_head_argmax's."""
+    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
+    with _probe("lm_head_argmax_c", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_argmax_c(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M,
+                                         d, V, ids.data_ptr(), ids_ld, eos_id, ptr(eos_count), workspace.data_ptr(),
+                                         workspace.numel() * workspace.element_size(), sp, bp, bits_ld, float(penalty),
+                                         stream()), "tmi_lm_head_argmax_c")
+
+
+def lm_head_topk_c(x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, seen=None, banned=None, penalty=1.0, gamma=None,
+                   beta=None, eps=1e-5, temperature=1.0, lse=None):
+    """``lm_head_topk`` over the constrained logits z' (as ``lm_head_argmax_c``): s = z' / temperature, the logsumexp over
+    the columns that are not banned, a banned column's log-probability -inf; the workspace is lm_head_topk's."""
+    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
+    with _probe("lm_head_topk_c", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_topk_c(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
+                                       V, 1.0 / float(temperature), N, ids.data_ptr(), logprobs.data_ptr(), ptr(lse),
+                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), sp, bp, bits_ld,
+                                       float(penalty), stream()), "tmi_lm_head_topk_c")
+
+
+def lm_head_sample_c(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace, seen=None, banned=None,
+                     penalty=1.0, temperature=1.0, top_k=50, top_p=1.0, seed=0, suppress_id=-1, eos_id=-1, pad_id=0,
+                     logprob=None, gamma=None, beta=None, eps=1e-5):
+    """``lm_head_sample`` over the constrained logits z' (as ``lm_head_argmax_c``): a banned column is one more
+    suppressed id and the candidates are ranked on z'; the workspace is lm_head_sample's."""
+    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
+    with _probe("lm_head_sample_c", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_sample_c(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M,
+                                         d, V, float(temperature), int(top_k), float(top_p),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, suppress_id, eos_id, pad_id, finished.data_ptr(),
+                                         ids.data_ptr(), ids_ld, ptr(logprob), n_finished.data_ptr(), workspace.data_ptr(),
+                                         workspace.numel() * workspace.element_size(), sp, bp, bits_ld, float(penalty),
+                                         stream()), "tmi_lm_head_sample_c")
+
+
 def beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping, pool_ids, pool_scores,
               pool_len, pool_cnt, done, done_count, finalize=False):
     """One step of beam search's bookkeeping on the device (tmi_beam_step; the rule is whisper.generate's): candidates

@@ -18,8 +18,10 @@ reference's training-mode sites (W:160, W:205, W:342, W:411) on the bf16 path wi
 
 Beam search (``generate(num_beams=K)``, 2 <= K <= 8; the reference leaves it a ``pass`` at W:696-698).  Row r = b*K + k
 is beam k of batch item b.  Step t (1-based) reads prefix columns [0, t) and writes column t.  lp_r(v) =
-log_softmax(z_r / temperature)[v] over the V real columns (temperature as at W:678; top_k, top_p, min_length and
-repetition_penalty are accepted and ignored, as in greedy).
+log_softmax(z_r / temperature)[v] over the V real columns (temperature as at W:678; top_k, top_p and min_length are
+accepted and ignored, as in greedy); with decode constraints z_r is the constrained logit z' of include/tethys_mi.h, the
+softmax runs over the columns that are not banned, and with a prompt of P tokens every prefix is P longer while t, the
+scores and t**length_penalty keep counting generated tokens.
   Start: running sums s_{b,0} = 0, s_{b,k>0} = -inf; every beam holds [decoder_start_token_id].
   Per step, for each item not done: the candidates (k, v, s_k + lp_k(v)) ordered by score desc, then k*V + v asc; the
     first 2K are kept (each row's top 2K of lp_k suffices).  Walk the ranks j = 0 .. 2K-1: an EOS candidate at j < K is
@@ -1015,7 +1017,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
     def generate(self, input_features, max_length=None, min_length=None, num_beams=None, temperature=1.0, top_k=None,
                  top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None, length_penalty=1.0,
                  early_stopping=False, num_return_sequences=1, return_dict_in_generate=False, do_sample=False, seed=0,
-                 return_token_timestamps=False):
+                 return_token_timestamps=False, no_repeat_ngram_size=None, suppress_tokens=None, begin_suppress_tokens=None,
+                 prompt_ids=None):
         """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.  ``num_beams`` of 2 to
         8: beam search (``_generate_beam``; the reference accepts num_beams at W:637 and leaves it as a ``pass`` at
         W:696-698); None or 1: the greedy path below, unchanged.
@@ -1038,15 +1041,37 @@ class WhisperForConditionalGeneration(KernelBlocks):
         ``return_dict_in_generate`` adds - with the outputs of ``align`` for the returned sequences (over "lengths" where
         the mode reports them) added: one more encoder pass and one teacher-forced decoder pass per distinct length.
         Aligning token n needs position n of the decoder, so ``max_length`` is then at most max_target_positions - 1 (and
-        defaults to it).  False: nothing changes."""
+        defaults to it).  False: nothing changes.
+
+        Decode constraints and prompts (every mode; the rule is include/tethys_mi.h's "Decode constraints", applied to the
+        logits BEFORE the temperature; ``check_constraint_args`` states the bounds).  ``repetition_penalty`` p (None or 1:
+        off): the logit of every token already in the row - start token, prompt and generated tokens alike - is divided
+        by p when positive and multiplied by p otherwise.  ``no_repeat_ngram_size`` n (None or 0: off): a token that would
+        complete an n-gram the row already holds cannot be emitted.  ``suppress_tokens``: ids that can never be emitted;
+        ``begin_suppress_tokens``: ids that cannot be the first generated token.  ``prompt_ids`` int [P] or [B, P], P >= 1:
+        these tokens follow the start token (in beam search every beam of an item starts from them).  The result is then
+        ids [B, 1 + P + n]; "lengths" counts prompt plus generated tokens (sequences[b, 1 : 1 + lengths[b]] stays the row's
+        tokens), while "token_logprobs" [B, n], "sequences_scores", the beam length penalty, ``max_length`` and
+        ``min_length`` count generated tokens only, with P + max_length <= max_target_positions.  Per step there is one
+        tmi_decode_constraints launch on the step's prefixes (so beams may reorder freely) and the _c form of the mode's
+        LM head.  With every one of these at its default the call takes the path it took without them: the same kernels
+        and launches, no other buffer."""
         cfg = self.config
+        cons = check_constraint_args(cfg, max_length, num_beams, repetition_penalty=repetition_penalty,
+                                     no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens,
+                                     begin_suppress_tokens=begin_suppress_tokens, prompt_ids=prompt_ids,
+                                     eos_token_id=eos_token_id, return_token_timestamps=return_token_timestamps)
+        if cons is not None:
+            max_length = cons["max_length"]
         if return_token_timestamps:
             max_length = check_timestamp_length(cfg, max_length)
             out = self.generate(input_features, max_length=max_length, min_length=min_length, num_beams=num_beams,
                                 temperature=temperature, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty,
                                 attention_mask=attention_mask, eos_token_id=eos_token_id, length_penalty=length_penalty,
                                 early_stopping=early_stopping, num_return_sequences=num_return_sequences,
-                                return_dict_in_generate=True, do_sample=do_sample, seed=seed)
+                                return_dict_in_generate=True, do_sample=do_sample, seed=seed,
+                                no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens,
+                                begin_suppress_tokens=begin_suppress_tokens, prompt_ids=prompt_ids)
             if not isinstance(out, dict):  # (the greedy path has no dict form of its own)
                 out = {"sequences": out}
             out.update(self.align(input_features, out["sequences"], out.get("lengths")))
@@ -1055,18 +1080,20 @@ class WhisperForConditionalGeneration(KernelBlocks):
             max_length, top_k, top_p, min_length = sample_args(cfg, max_length, num_beams, temperature, top_k, top_p, min_length)
             eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
             return self._generate_sample(input_features, max_length, float(temperature), top_k, top_p, min_length, eos,
-                                         int(seed), bool(return_dict_in_generate))
+                                         int(seed), bool(return_dict_in_generate), cons)
         if num_beams is not None and int(num_beams) > 1:  # (ahead of check_generate_args: it still raises for num_beams > 1)
             max_length = check_beam_args(cfg, max_length, num_beams, temperature, length_penalty, num_return_sequences)
             eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
             return self._generate_beam(input_features, max_length, int(num_beams), float(temperature), eos,
                                        float(length_penalty), bool(early_stopping), int(num_return_sequences),
-                                       bool(return_dict_in_generate))
+                                       bool(return_dict_in_generate), cons)
         max_length = check_generate_args(cfg, max_length, num_beams, temperature)
         features = self._check_features(input_features)
         B = features.shape[0]
         eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
         dev = self.device
+        if cons is not None:
+            return self._generate_greedy_c(features, max_length, eos, cons)
         ids = torch.empty(B, 1 + max_length, dtype=torch.int32, device=dev)
         if max_length == 0:
             ids.fill_(cfg.decoder_start_token_id)
@@ -1106,7 +1133,88 @@ class WhisperForConditionalGeneration(KernelBlocks):
         torch.cuda.current_stream(dev).synchronize()
         return ids[:, :1 + n].clone()
 
-    def _generate_sample(self, features, max_length, temperature, top_k, top_p, min_length, eos, seed, return_dict):
+    def _constraint_state(self, cons, rows: int, K: int = 1):
+        """The device side of ``cons`` (check_constraint_args) for ``rows`` decoded rows, K rows per batch item: the prompt
+        as int32 [rows, P] (or None), and ``apply(prefix, ld, t, first)`` -> the keyword arguments of the step's _c LM
+        head, after one tmi_decode_constraints launch on the rows' prefixes of length t (``first``: the first generated
+        step, where begin_suppress_tokens are banned too).  Without an active constraint (a prompt alone) ``apply`` is
+        None and the mode keeps its unconstrained LM head."""
+        dev, V = self.device, self.config.vocab_size
+        prompt = None
+        if cons["P"]:
+            pr = torch.from_numpy(cons["prompt"]).to(dev)
+            if pr.dim() == 1:
+                pr = pr[None, :].expand(rows // K, -1)
+            elif pr.shape[0] != rows // K:
+                raise ValueError(f"prompt_ids has {pr.shape[0]} rows for a batch of {rows // K}")
+            prompt = pr.repeat_interleave(K, dim=0).contiguous()
+        if not cons["active"]:
+            return prompt, None
+        W = ops.constraint_words(V)
+        sets = torch.empty(2, rows, W, dtype=torch.int32, device=dev)
+        words = lambda ids: torch.from_numpy(token_bitset(ids, V)).to(dev) if ids else None  # noqa: E731
+        static, static_first = words(cons["suppress"]), words(sorted(set(cons["suppress"]) | set(cons["begin"])))
+        penalty, ngram = cons["penalty"], cons["ngram"]
+
+        def apply(prefix, ld, t, first):
+            ops.decode_constraints(prefix, ld, rows, t, V, sets[0], sets[1], ngram=ngram,
+                                   static_banned=static_first if first else static)
+            return dict(seen=sets[0], banned=sets[1], penalty=penalty)
+
+        return prompt, apply
+
+    def _generate_greedy_c(self, features, max_length, eos, cons):
+        """Greedy decoding with decode constraints and / or a prompt (``generate``'s docstring): the greedy path with the
+        prompt behind the start token, one tmi_decode_constraints launch per step and tmi_lm_head_argmax_c as the choice.
+        Generated step s (1-based) reads the prefix columns [0, P + s) and writes column P + s.  -> ids [B, 1 + P + n]."""
+        cfg = self.config
+        B, dev, P = features.shape[0], self.device, cons["P"]
+        L1 = 1 + P + max_length
+        ids = torch.empty(B, L1, dtype=torch.int32, device=dev)
+        ids[:, 0] = cfg.decoder_start_token_id
+        prompt, apply = self._constraint_state(cons, B)
+        if P:
+            ids[:, 1:1 + P] = prompt
+        if max_length == 0:
+            return ids
+        inf = self._infer_prepare(B, features.shape[2])
+        counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
+        host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
+        events = [torch.cuda.Event(), torch.cuda.Event()]
+        with self._inference(inf):
+            ws, d, T, V = self.ws, cfg.d_model, inf["T"], cfg.vocab_size
+            enc_out = self._encode_infer(features, inf)
+            self._cross_kv_infer(enc_out)
+            lab_flat = ws["labels"]
+            wl, ldw = self.W("lm_head.kernel")
+            gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
+            main = self._main or torch.cuda.current_stream(dev)
+
+            def step(s):
+                t = P + s
+                lab = lab_flat[:B * t].view(B, t)
+                if t > 1:
+                    lab[:, :t - 1].copy_(ids[:, 1:t])
+                h = self._decode_infer(lab, B, t, T)
+                kw = dict(gamma=gamma, beta=beta, eps=cfg.layer_norm_eps, eos_id=eos, eos_count=counts[s:])
+                if apply is None:
+                    ops.lm_head_argmax(h[t - 1:], t * d, wl, ldw, B, d, V, ids[:, t:], L1, ws["argmax_ws"], **kw)
+                else:
+                    ops.lm_head_argmax_c(h[t - 1:], t * d, wl, ldw, B, d, V, ids[:, t:], L1, ws["argmax_ws"],
+                                         **apply(ids, L1, t, s == 1), **kw)
+                host[s:s + 1].copy_(counts[s:s + 1], non_blocking=True)
+                events[s & 1].record(main)
+
+            def read_eos(s):
+                events[s & 1].synchronize()
+                return int(host[s])
+
+            n = greedy_loop(max_length, B, step, read_eos if eos >= 0 else None)
+        torch.cuda.current_stream(dev).synchronize()
+        return ids[:, :1 + P + n].clone()
+
+    def _generate_sample(self, features, max_length, temperature, top_k, top_p, min_length, eos, seed, return_dict,
+                         cons=None):
         """Sampled decoding: the greedy loop with tmi_lm_head_sample as the choice rule (include/tethys_mi.h states it:
         top_k >= 1 keeps the top_k largest scores and their top_p nucleus and draws by inverse CDF, top_k == 0 draws from
         the whole vocabulary by Gumbel-max).  Step t (1-based) draws with the seed (seed + t * 0x9E3779B97F4A7C15) mod
@@ -1116,13 +1224,20 @@ class WhisperForConditionalGeneration(KernelBlocks):
         one step late) or after max_length steps.  -> ids [B, 1 + n], or with ``return_dict`` {"sequences",
         "token_logprobs" [B, n] (log-softmax of logits / temperature at the token: the uncut distribution),
         "sequences_scores" [B] (their sum up to and including the row's EOS), "lengths" [B] (tokens up to and including
-        EOS)}."""
+        EOS)}.  ``cons`` (check_constraint_args; None: none): a prompt of P tokens behind the start token and / or decode
+        constraints - step t then reads the prefix columns [0, P + t) and writes column P + t, ids are [B, 1 + P + n],
+        "lengths" counts the prompt too, everything else above (the step seeds, min_length, the log-probabilities) still
+        counts generated tokens."""
         cfg = self.config
         features = self._check_features(features)
         B, dev = features.shape[0], self.device
         start, pad, V = cfg.decoder_start_token_id, cfg.pad_token_id, cfg.vocab_size
-        ids = torch.empty(B, 1 + max_length, dtype=torch.int32, device=dev)
+        P = cons["P"] if cons is not None else 0
+        prompt, apply = self._constraint_state(cons, B) if cons is not None else (None, None)
+        ids = torch.empty(B, 1 + P + max_length, dtype=torch.int32, device=dev)
         ids[:, 0] = start
+        if P:
+            ids[:, 1:1 + P] = prompt
         lps = torch.zeros(1 + max_length, B, device=dev)  # (a step's log-probabilities are one contiguous row)
         n = 0
         if max_length > 0:
@@ -1140,18 +1255,22 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 wl, ldw = self.W("lm_head.kernel")
                 gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
                 main = self._main or torch.cuda.current_stream(dev)
-                L1 = 1 + max_length
+                L1 = 1 + P + max_length
 
                 def step(t):
-                    lab = lab_flat[:B * t].view(B, t)
-                    if t > 1:
-                        lab[:, :t - 1].copy_(ids[:, 1:t])
-                    h = self._decode_infer(lab, B, t, T)
-                    ops.lm_head_sample(h[t - 1:], t * d, wl, ldw, B, d, V, ids[:, t:], L1, finished, counts[t:],
-                                       ws["sample_ws"], temperature=temperature, top_k=top_k, top_p=top_p,
-                                       seed=sample_step_seed(seed, t), suppress_id=eos if t <= min_length else -1,
-                                       eos_id=eos, pad_id=pad, logprob=lps[t], gamma=gamma, beta=beta,
-                                       eps=cfg.layer_norm_eps)
+                    tp = P + t  # the prefix length: start token, prompt, t - 1 generated tokens
+                    lab = lab_flat[:B * tp].view(B, tp)
+                    if tp > 1:
+                        lab[:, :tp - 1].copy_(ids[:, 1:tp])
+                    h = self._decode_infer(lab, B, tp, T)
+                    head, kw = ops.lm_head_sample, {}
+                    if apply is not None:
+                        head, kw = ops.lm_head_sample_c, apply(ids, L1, tp, t == 1)
+                    head(h[tp - 1:], tp * d, wl, ldw, B, d, V, ids[:, tp:], L1, finished, counts[t:],
+                         ws["sample_ws"], temperature=temperature, top_k=top_k, top_p=top_p,
+                         seed=sample_step_seed(seed, t), suppress_id=eos if t <= min_length else -1,
+                         eos_id=eos, pad_id=pad, logprob=lps[t], gamma=gamma, beta=beta,
+                         eps=cfg.layer_norm_eps, **kw)
                     host[t:t + 1].copy_(counts[t:t + 1], non_blocking=True)
                     events[t & 1].record(main)
 
@@ -1161,34 +1280,47 @@ class WhisperForConditionalGeneration(KernelBlocks):
 
                 n = greedy_loop(max_length, B, step, read_finished if eos >= 0 else None)
             torch.cuda.current_stream(dev).synchronize()
-        seq = ids[:, :1 + n].clone()
+        seq = ids[:, :1 + P + n].clone()
         if not return_dict:
             return seq
         tok_lp = lps[1:1 + n].t().contiguous()
-        is_eos = (seq[:, 1:] == eos) if eos >= 0 else torch.zeros(B, n, dtype=torch.bool, device=dev)
+        is_eos = (seq[:, 1 + P:] == eos) if eos >= 0 else torch.zeros(B, n, dtype=torch.bool, device=dev)
         first = torch.where(is_eos.any(dim=1), is_eos.int().argmax(dim=1) + 1, n) if n else torch.zeros(B, dtype=torch.int64, device=dev)
         return {"sequences": seq, "token_logprobs": tok_lp, "sequences_scores": tok_lp.sum(dim=1),
-                "lengths": first.to(torch.int32)}
+                "lengths": (first + P).to(torch.int32)}
 
-    def _generate_beam(self, features, max_length, K, temperature, eos, length_penalty, early_stopping, R, return_dict):
+    def _generate_beam(self, features, max_length, K, temperature, eos, length_penalty, early_stopping, R, return_dict,
+                       cons=None):
         """Beam search; the rule is the module docstring's "Beam search".  The encoder and the cross-attention k|v run once
         on the B items, the k|v rows are then repeated for the K beams of each item; every step runs the decoder over the
         B*K prefixes, tmi_lm_head_topk (N = 2K candidates per row: final LayerNorm, LM head, log-softmax and top-N in one
         launch) and tmi_beam_step (one workgroup per item: the walk, the pool, the next prefixes in a second buffer, the
         done flags and count).  The done count is read one step late (``greedy_loop``); the only other host work is
-        queueing.  Finalize (the live beams of the items not done, offered to the pools) is a mode of tmi_beam_step."""
+        queueing.  Finalize (the live beams of the items not done, offered to the pools) is a mode of tmi_beam_step.
+        ``cons`` (check_constraint_args; None: none): every beam starts from [start, prompt] (P tokens), step t works on
+        prefixes of length P + t, the scores and the length penalty t ** length_penalty count generated tokens, the
+        lengths count the prompt too; with an active constraint the candidates come from tmi_lm_head_topk_c on the sets
+        tmi_decode_constraints builds from the step's own prefix rows."""
         cfg = self.config
         features = self._check_features(features)
         B, dev = features.shape[0], self.device
-        BK, N, L1, V = B * K, 2 * K, 1 + max_length, cfg.vocab_size
+        P = cons["P"] if cons is not None else 0
+        BK, N, L1, V = B * K, 2 * K, 1 + P + max_length, cfg.vocab_size
         start, pad = cfg.decoder_start_token_id, cfg.pad_token_id
+        prompt, apply = self._constraint_state(cons, BK, K) if cons is not None else (None, None)
         if max_length == 0:
-            seq = torch.full((B * R, 1), start, dtype=torch.int32, device=dev)
+            seq = torch.full((B * R, 1 + P), start, dtype=torch.int32, device=dev)
+            if P:
+                seq[:, 1:] = prompt.view(B, K, P)[:, :R].reshape(B * R, P)
             zeros = torch.zeros(B * R, device=dev)
-            return {"sequences": seq, "sequences_scores": zeros, "lengths": zeros.int()} if return_dict else seq
+            if return_dict:
+                return {"sequences": seq, "sequences_scores": zeros, "lengths": torch.full((B * R,), P, dtype=torch.int32, device=dev)}
+            return seq
         inf = self._infer_prepare(B, features.shape[2], K)
         i32 = dict(dtype=torch.int32, device=dev)
         prefix = torch.full((2, BK, L1), start, **i32)  # double-buffered prefixes; every entry a valid token id
+        if P:
+            prefix[:, :, 1:1 + P] = prompt
         sums = torch.zeros(B, K, device=dev)
         sums[:, 1:] = float("-inf")
         sums = sums.view(BK)
@@ -1213,13 +1345,17 @@ class WhisperForConditionalGeneration(KernelBlocks):
 
             def step(t):
                 cur, nxt = prefix[t & 1], prefix[(t + 1) & 1]
-                lab = lab_flat[:BK * t].view(BK, t)
-                if t > 1:
-                    lab[:, :t - 1].copy_(cur[:, 1:t])
-                h = self._decode_infer(lab, BK, t, T)
-                ops.lm_head_topk(h[t - 1:], t * d, wl, ldw, BK, d, V, N, cand_ids, cand_lp, ws["topk_ws"], gamma=gamma,
-                                 beta=beta, eps=cfg.layer_norm_eps, temperature=temperature)
-                ops.beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, L1, t, eos, len_pow(t), early_stopping, pool_ids,
+                tp = P + t  # the prefix length: start token, prompt, t - 1 generated tokens
+                lab = lab_flat[:BK * tp].view(BK, tp)
+                if tp > 1:
+                    lab[:, :tp - 1].copy_(cur[:, 1:tp])
+                h = self._decode_infer(lab, BK, tp, T)
+                head, kw = ops.lm_head_topk, {}
+                if apply is not None:
+                    head, kw = ops.lm_head_topk_c, apply(cur, L1, tp, t == 1)
+                head(h[tp - 1:], tp * d, wl, ldw, BK, d, V, N, cand_ids, cand_lp, ws["topk_ws"], gamma=gamma,
+                     beta=beta, eps=cfg.layer_norm_eps, temperature=temperature, **kw)
+                ops.beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, L1, tp, eos, len_pow(t), early_stopping, pool_ids,
                               pool_scores, pool_len, pool_cnt, done, n_done)
                 host[t:t + 1].copy_(n_done, non_blocking=True)
                 events[t & 1].record(main)
@@ -1229,7 +1365,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 return int(host[t])
 
             n = greedy_loop(max_length, B, step, read_done if eos >= 0 else None)
-            ops.beam_step(None, None, N, B, K, sums, prefix[(n + 1) & 1], None, L1, n, eos, len_pow(n), early_stopping,
+            ops.beam_step(None, None, N, B, K, sums, prefix[(n + 1) & 1], None, L1, P + n, eos, len_pow(n), early_stopping,
                           pool_ids, pool_scores, pool_len, pool_cnt, done, n_done, finalize=True)
         lengths = pool_len[:, :R].reshape(B * R)
         n_out = int(lengths.max())
@@ -1756,6 +1892,83 @@ def check_beam_args(cfg: WhisperConfig, max_length=None, num_beams=2, temperatur
     return max_length
 
 
+CONSTRAINT_MAX_VOCAB = 65536  # tmi_decode_constraints'
+
+
+def token_bitset(ids, V: int) -> np.ndarray:
+    """The ids as a decode-constraint bit set over V columns: int32 words, column n at bit n & 31 of word n >> 5."""
+    words = np.zeros((int(V) + 31) // 32, dtype=np.uint32)
+    for v in ids:
+        words[int(v) >> 5] |= np.uint32(1) << np.uint32(int(v) & 31)
+    return words.view(np.int32)
+
+
+def check_constraint_args(cfg: WhisperConfig, max_length=None, num_beams=None, repetition_penalty=None,
+                          no_repeat_ngram_size=None, suppress_tokens=None, begin_suppress_tokens=None, prompt_ids=None,
+                          eos_token_id=None, return_token_timestamps=False):
+    """``generate``'s decode constraints and prompt, checked on the host before the encoder runs.  -> None when every
+    one of them is at its default (penalty None or 1, n-gram size None or 0, no suppressed id, no prompt), else {"penalty",
+    "ngram", "suppress", "begin" (sorted id lists), "prompt" (int32 numpy [P] or [B, P], or None), "P", "max_length",
+    "active" (False for a prompt alone)}.  Raises ValueError unless: the penalty is finite and > 0; the n-gram size is in
+    [0, max_target_positions]; every id is in [0, vocab_size); the prompt is [P] or [B, P] with P >= 1; P + max_length <=
+    max_target_positions (one less with token timestamps; max_length None: the largest that fits); vocab_size <= 65536;
+    and no row can run out of columns: vocab_size - |suppress + begin_suppress + {eos}| - (P + max_length if n-gram bans
+    are on else 0) >= 2 * num_beams in beam search (tmi_lm_head_topk_c's candidates per row), >= 1 otherwise."""
+    penalty = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    if not (math.isfinite(penalty) and penalty > 0.0):
+        raise ValueError("repetition_penalty must be finite and > 0 (None or 1: off)")
+    ngram = 0 if no_repeat_ngram_size is None else int(no_repeat_ngram_size)
+    if isinstance(no_repeat_ngram_size, bool) or (no_repeat_ngram_size is not None and ngram != no_repeat_ngram_size):
+        raise ValueError("no_repeat_ngram_size must be an integer")
+    if not 0 <= ngram <= cfg.max_target_positions:
+        raise ValueError(f"no_repeat_ngram_size must be in [0, {cfg.max_target_positions}] (None or 0: off)")
+    V = cfg.vocab_size
+
+    def id_list(ids, what):
+        if ids is None:
+            return []
+        arr = np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids)
+        if arr.size == 0:
+            return []
+        if arr.ndim != 1 or arr.dtype.kind not in "iu":
+            raise ValueError(f"{what} must be a list of integer token ids")
+        if arr.min() < 0 or arr.max() >= V:
+            raise ValueError(f"{what}: every id must be in [0, {V})")
+        return sorted(set(int(v) for v in arr))
+
+    suppress, begin = id_list(suppress_tokens, "suppress_tokens"), id_list(begin_suppress_tokens, "begin_suppress_tokens")
+    prompt, P = None, 0
+    if prompt_ids is not None:
+        prompt = np.asarray(prompt_ids.cpu() if isinstance(prompt_ids, torch.Tensor) else prompt_ids)
+        if prompt.ndim not in (1, 2) or prompt.shape[-1] < 1 or prompt.dtype.kind not in "iu":
+            raise ValueError("prompt_ids must be integer token ids, [P] or [B, P] with P >= 1")
+        if prompt.min() < 0 or prompt.max() >= V:
+            raise ValueError(f"prompt_ids: every id must be in [0, {V})")
+        prompt, P = np.ascontiguousarray(prompt.astype(np.int32)), int(prompt.shape[-1])
+    active = penalty != 1.0 or ngram > 0 or bool(suppress) or bool(begin)
+    if not active and prompt is None:
+        return None
+    top = cfg.max_target_positions - (1 if return_token_timestamps else 0)
+    if P > top:
+        raise ValueError(f"prompt_ids: {P} tokens leave no decoder position (at most {top})")
+    max_length = top - P if max_length is None else int(max_length)
+    if max_length < 0 or P + max_length > top:
+        raise ValueError(f"with a prompt of {P} tokens max_length must be in [0, {top - P}]")
+    if active:
+        if V > CONSTRAINT_MAX_VOCAB:
+            raise ValueError(f"decode constraints take vocab_size <= {CONSTRAINT_MAX_VOCAB}")
+        eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+        fixed = set(suppress) | set(begin) | ({eos} if 0 <= eos < V else set())
+        free = V - len(fixed) - (P + max_length if ngram > 0 else 0)
+        K = 1 if num_beams is None else int(num_beams)
+        need = 2 * K if K > 1 else 1
+        if free < need:
+            raise ValueError(f"the constraints can leave a row with {free} columns to choose from; {need} are needed "
+                             "(vocab_size minus the suppressed ids, EOS and, with n-gram bans, one id per position)")
+    return {"penalty": penalty, "ngram": ngram, "suppress": suppress, "begin": begin, "prompt": prompt, "P": P,
+            "max_length": max_length, "active": active}
+
+
 SAMPLE_MAX_TOP_K = 64  # tmi_lm_head_sample's
 
 
@@ -1843,7 +2056,8 @@ def dummy_waveform(seed: int = DUMMY_AUDIO_SEED) -> np.ndarray:
 
 
 def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beams=1, length_penalty=1.0, do_sample=False,
-                     temperature=1.0, top_k=None, top_p=None, seed=0, return_timestamps=False):
+                     temperature=1.0, top_k=None, top_p=None, seed=0, return_timestamps=False, repetition_penalty=None,
+                     no_repeat_ngram_size=None, suppress_tokens=None, begin_suppress_tokens=None, prompt_ids=None):
     """W:962-986: waveform -> log-mel (frontend.LogMelFrontend, channels-first: the layout the encoder reads; the reference
     feeds [frames, 80] un-transposed) -> ``model.generate`` -> ``tokenizer.decode(ids)``, or the ids
     (int32 numpy array, start token first) without a tokenizer.  ``audio``: a waveform (1-D tensor or array, 16 kHz), a
@@ -1852,7 +2066,9 @@ def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beam
     ``seed`` (``generate(do_sample=True)``).  ``return_timestamps=True``: -> {"text" (with a tokenizer) or "ids",
     "token_start_times", "token_end_times" (fp32 numpy arrays, seconds, one entry per token after the start token)} from
     ``model.align`` with the clip's own number of encoder frames; ``max_length`` is then capped at
-    max_target_positions - 1."""
+    max_target_positions - 1.  ``repetition_penalty``, ``no_repeat_ngram_size``, ``suppress_tokens``,
+    ``begin_suppress_tokens`` and ``prompt_ids`` ([P]) are ``generate``'s; with a prompt the returned ids hold it behind the
+    start token and ``max_length`` is capped so that prompt and transcript fit the decoder's positions."""
     from .frontend import LogMelFrontend
     if audio is None:
         wav = dummy_waveform()
@@ -1867,14 +2083,20 @@ def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beam
     feats = fe(wav)
     if return_timestamps:
         max_length = min(int(max_length), model.config.max_target_positions - 1)
+    cons = {k: v for k, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size),
+                              ("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens),
+                              ("prompt_ids", prompt_ids)) if v is not None}
+    if prompt_ids is not None:
+        room = model.config.max_target_positions - (1 if return_timestamps else 0) - int(np.asarray(prompt_ids).shape[-1])
+        max_length = max(0, min(int(max_length), room))
     if do_sample:
         ids = model.generate(feats, max_length=max_length, num_beams=num_beams, do_sample=True, temperature=temperature,
-                             top_k=top_k, top_p=top_p, seed=seed, return_dict_in_generate=bool(return_timestamps))
+                             top_k=top_k, top_p=top_p, seed=seed, return_dict_in_generate=bool(return_timestamps), **cons)
     elif num_beams is not None and int(num_beams) > 1:
         ids = model.generate(feats, max_length=max_length, num_beams=num_beams, length_penalty=length_penalty,
-                             return_dict_in_generate=bool(return_timestamps))
+                             return_dict_in_generate=bool(return_timestamps), **cons)
     else:
-        ids = model.generate(feats, max_length=max_length)
+        ids = model.generate(feats, max_length=max_length, **cons)
     if return_timestamps:
         out = ids if isinstance(ids, dict) else {"sequences": ids}
         seqs = out["sequences"][:1]

@@ -11,7 +11,14 @@ against tmi_lm_head_argmax at equal M (8 and 40, d 768 and 1280), both measured 
 and tmi_lm_head_sample at M = 8 in both modes beside tmi_lm_head_argmax (M = 8) and tmi_lm_head_topk (M = 8, N = 16),
 all measured in this run.
 
-usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2] [--num_beams 1] [--do_sample [--top_k K] [--top_p P]]"""
+--constrained: decode constraints, all in ONE run (a JSON file, --out): the three constrained LM heads
+(tmi_lm_head_argmax_c / _topk_c / _sample_c, sets with 100 seen and 93 banned columns a row) against their originals at
+equal M, original and constrained alternating, every pair repeated (median, and the repeats' own spread);
+tmi_decode_constraints alone; and greedy, beam-4 and sampled ``generate`` with and without no_repeat_ngram_size 3,
+repetition_penalty 1.2 and 90 suppressed ids, alternating too.
+
+usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2] [--num_beams 1] [--do_sample [--top_k K] [--top_p P]]
+       python tools/generate_bench.py --constrained [--steps 448] [--batch 8] [--reps 3] [--out profiles/r19_generate_constrained.json]"""
 import argparse
 import json
 import os
@@ -19,6 +26,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import tethys_speech_amd  # noqa: E402,F401
 from tethys_speech_amd import ops, whisper  # noqa: E402
@@ -37,30 +45,47 @@ def timed_us(fn, iters=50, warm=5):
     return e0.elapsed_time(e1) * 1e3 / iters
 
 
-def argmax_alone(dev, d, M=8, V=51865, Vp=51904, topk_n=0, sample=None):
+def constraint_sets(dev, M, V=51865, n_seen=100, n_banned=93, seed=0):
+    """Bit sets as a decoding step has them: ``n_seen`` seen and ``n_banned`` banned columns a row."""
+    g = torch.Generator().manual_seed(seed)
+    sets = []
+    for n in (n_seen, n_banned):
+        rows = [whisper.token_bitset(torch.randperm(V, generator=g)[:n].tolist(), V) for _ in range(M)]
+        sets.append(torch.from_numpy(np.stack(rows)).to(dev))
+    return sets
+
+
+def argmax_alone(dev, d, M=8, V=51865, Vp=51904, topk_n=0, sample=None, constrained=False):
     """tmi_lm_head_argmax (topk_n = 0), tmi_lm_head_topk with N = topk_n, or tmi_lm_head_sample with ``sample`` =
-    (top_k, top_p), alone on M rows."""
+    (top_k, top_p), alone on M rows; ``constrained``: the _c entry point on ``constraint_sets`` with penalty 1.2."""
     g = torch.Generator(device=dev).manual_seed(d)
     x = torch.randn(M, d, device=dev, generator=g).to(torch.bfloat16)
     w = (torch.randn(d, Vp, device=dev, generator=g) * 0.03).to(torch.bfloat16)
     gamma, beta = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+    cons = {}
+    if constrained:
+        seen, banned = constraint_sets(dev, M, V)
+        cons = dict(seen=seen, banned=banned, penalty=1.2)
     if sample is not None:
         ids, lp = torch.empty(M, dtype=torch.int32, device=dev), torch.empty(M, device=dev)
         fin, cnt = torch.zeros(M, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
         ws = torch.zeros(ops.lm_head_sample_workspace_elems(M, V, sample[0]), dtype=torch.int64, device=dev)
-        call = lambda: ops.lm_head_sample(x, d, w, Vp, M, d, V, ids, 1, fin, cnt, ws, temperature=0.8,  # noqa: E731
-                                          top_k=sample[0], top_p=sample[1], seed=1, logprob=lp, gamma=gamma, beta=beta)
+        head = ops.lm_head_sample_c if constrained else ops.lm_head_sample
+        call = lambda: head(x, d, w, Vp, M, d, V, ids, 1, fin, cnt, ws, temperature=0.8,  # noqa: E731
+                            top_k=sample[0], top_p=sample[1], seed=1, logprob=lp, gamma=gamma, beta=beta, **cons)
     elif topk_n:
         ids = torch.empty(M, topk_n, dtype=torch.int32, device=dev)
         lp = torch.empty(M, topk_n, device=dev)
         ws = torch.zeros(ops.lm_head_topk_workspace_elems(M, V, topk_n), dtype=torch.int64, device=dev)
-        call = lambda: ops.lm_head_topk(x, d, w, Vp, M, d, V, topk_n, ids, lp, ws, gamma=gamma, beta=beta)  # noqa: E731
+        head = ops.lm_head_topk_c if constrained else ops.lm_head_topk
+        call = lambda: head(x, d, w, Vp, M, d, V, topk_n, ids, lp, ws, gamma=gamma, beta=beta, **cons)  # noqa: E731
     else:
         ids = torch.empty(M, dtype=torch.int32, device=dev)
         cnt = torch.empty(1, dtype=torch.int32, device=dev)
         ws = torch.zeros(M + 1, dtype=torch.int64, device=dev)
-        call = lambda: ops.lm_head_argmax(x, d, w, Vp, M, d, V, ids, 1, ws, gamma=gamma, beta=beta, eos_id=2,  # noqa: E731
-                                          eos_count=cnt)
+        head = ops.lm_head_argmax_c if constrained else ops.lm_head_argmax
+        call = lambda: head(x, d, w, Vp, M, d, V, ids, 1, ws, gamma=gamma, beta=beta, eos_id=2,  # noqa: E731
+                            eos_count=cnt, **cons)
     eager = timed_us(call)  # per call from Python: host-bound (ctypes + wrapper) at this size
     # device time: n back-to-back launches captured once and replayed (no host in between)
     n = 20
@@ -74,8 +99,86 @@ def argmax_alone(dev, d, M=8, V=51865, Vp=51904, topk_n=0, sample=None):
     return {"us": round(us, 2), "GBps": round(d * Vp * 2 / (us * 1e-6) / 1e9, 1), "us_eager_call": round(eager, 2)}
 
 
+def graph_us(call, n=20):
+    """Device time of one ``call``: n launches captured once, the replay timed."""
+    call()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        for _ in range(n):
+            call()
+    return timed_us(graph.replay, iters=10, warm=2) / n
+
+
+def _stats(vals):
+    vals = sorted(vals)
+    med = vals[len(vals) // 2]
+    return {"median": round(med, 3), "min": round(vals[0], 3), "max": round(vals[-1], 3),
+            "spread": round((vals[-1] - vals[0]) / med, 4)}
+
+
+def constrained_report(args):
+    """The --constrained run: see the module docstring."""
+    dev, B, reps = "cuda:0", args.batch, max(3, args.reps)
+    out = {"what": "tools/generate_bench.py --constrained on one MI355X, one process: originals and constrained forms "
+                   "alternating, every figure the median of the repeats with their min, max and (max - min) / median",
+           "batch": B, "steps": args.steps, "reps": reps, "precision": "bf16"}
+    heads = {}
+    for M in (B, 4 * B):
+        for name, kw in (("argmax", {}), ("topk_N8", dict(topk_n=8)), ("sample_k50_p0.9", dict(sample=(50, 0.9)))):
+            runs = {"original": [], "constrained": []}
+            for _ in range(reps):
+                for which in ("original", "constrained"):
+                    runs[which].append(argmax_alone(dev, 768, M, constrained=which == "constrained", **kw)["us"])
+            o, c = _stats(runs["original"]), _stats(runs["constrained"])
+            heads[f"M{M}_d768_{name}"] = {"original_us": o, "constrained_us": c,
+                                          "constrained_over_original": round(c["median"] / o["median"], 4)}
+    out["lm_head"] = heads
+    V = 51865
+    static = torch.from_numpy(whisper.token_bitset(range(1, 91), V)).to(dev)
+    builder = {}
+    for M in (B, 4 * B):
+        for t in (1, 224, 448):
+            prefix = torch.randint(0, V, (M, 449), dtype=torch.int32, device=dev)
+            sets = torch.empty(2, M, ops.constraint_words(V), dtype=torch.int32, device=dev)
+            call = lambda: ops.decode_constraints(prefix, 449, M, t, V, sets[0], sets[1], ngram=3, static_banned=static)  # noqa: E731
+            builder[f"M{M}_t{t}"] = _stats([graph_us(call) for _ in range(reps)])
+    out["decode_constraints_us"] = builder
+    model = whisper.create_whisper_model("small", device=dev, precision="bf16")
+    feats = torch.randn(B, 80, 3000, generator=torch.Generator().manual_seed(0)).to(dev)
+    cons = dict(no_repeat_ngram_size=3, repetition_penalty=1.2, suppress_tokens=list(range(1, 91)))
+    gen = {}
+    for name, mode in (("greedy", {}), ("beam_K4", dict(num_beams=4)),
+                       ("sample_k50_p0.9", dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.8, seed=1))):
+        runs = {"plain": [], "constrained": []}
+        for kw in ({}, cons):
+            model.generate(feats, max_length=4, eos_token_id=-1, **mode, **kw)  # warm-up: workspace, kernels
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for which, kw in (("plain", {}), ("constrained", cons)):
+                t0 = time.perf_counter()
+                ids = model.generate(feats, max_length=args.steps, eos_token_id=-1, **mode, **kw)
+                torch.cuda.synchronize()
+                runs[which].append((time.perf_counter() - t0) * 1e3 / args.steps)
+                assert ids.shape[1] == 1 + args.steps, ids.shape
+        p, c = _stats(runs["plain"]), _stats(runs["constrained"])
+        gen[name] = {"plain_per_step_ms": p, "constrained_per_step_ms": c,
+                     "constrained_over_plain": round(c["median"] / p["median"], 4),
+                     "added_per_step_us": round((c["median"] - p["median"]) * 1e3, 1)}
+    out["generate"] = gen
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"wrote": args.out, "generate": {k: v["constrained_over_plain"] for k, v in gen.items()},
+                      "lm_head": {k: v["constrained_over_original"] for k, v in heads.items()}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--constrained", action="store_true")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                  "r19_generate_constrained.json"))
     ap.add_argument("--steps", type=int, default=448)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=2)
@@ -84,6 +187,8 @@ def main():
     ap.add_argument("--top_k", type=int, default=50)
     ap.add_argument("--top_p", type=float, default=0.9)
     args = ap.parse_args()
+    if args.constrained:
+        return constrained_report(args)
     K = args.num_beams
     beam = dict(num_beams=K) if K > 1 else {}
     if args.do_sample:
