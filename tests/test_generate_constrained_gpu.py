@@ -210,6 +210,39 @@ def test_defaults_take_the_unconstrained_path(dev, monkeypatch):
         assert calls[head] == 6 and not new & set(calls)
 
 
+def test_zero_and_one_step_forms_of_every_mode(dev, monkeypatch):
+    """The forms that never enter, or barely enter, the step loop: ``max_length=0`` returns [start, prompt...] per row
+    without one call into ``ops``, and one step behind a prompt of two appends one column and leaves the prompt alone."""
+    ops, whisper, _ = _mods()
+    _, params, feats, _ = _setup(T_IN)
+    model = _model(dev, "bf16", params)
+    f = feats.to(dev)
+    B = f.shape[0]
+    calls = _counting(ops, monkeypatch)
+    for mode, Rr, keys in ((dict(), 1, None),  # (the greedy path has no dict form: it returns the ids either way)
+                           (dict(num_beams=2, num_return_sequences=2), 2, {"sequences", "sequences_scores", "lengths"}),
+                           (dict(do_sample=True, top_k=8, seed=1), 1,
+                            {"sequences", "token_logprobs", "sequences_scores", "lengths"})):
+        for prompt in ([], [9, 8]):
+            P, rows = len(prompt), B * Rr
+            want = torch.tensor([[START] + prompt] * rows, dtype=torch.int32)
+            calls.clear()
+            ids = model.generate(f, max_length=0, prompt_ids=prompt or None, **mode)
+            out = model.generate(f, max_length=0, prompt_ids=prompt or None, return_dict_in_generate=True, **mode)
+            assert not calls, (mode, prompt, calls)
+            assert ids.dtype == torch.int32 and torch.equal(ids.cpu(), want), (mode, prompt, ids)
+            if keys is None:
+                assert torch.equal(out.cpu(), want)
+                continue
+            assert set(out) == keys and out["sequences"].dtype == torch.int32 and torch.equal(out["sequences"].cpu(), want)
+            assert out["lengths"].dtype == torch.int32 and out["lengths"].cpu().tolist() == [P] * rows
+            assert out["sequences_scores"].cpu().tolist() == [0.0] * rows
+            if "token_logprobs" in keys:
+                assert tuple(out["token_logprobs"].shape) == (B, 0)
+        one = model.generate(f, max_length=1, prompt_ids=[9, 8], eos_token_id=-1, **mode)
+        assert tuple(one.shape) == (B * Rr, 1 + 2 + 1) and torch.equal(one[:, :3].cpu(), want), (mode, one)
+
+
 def test_token_timestamps_cover_prompt_and_transcript(dev):
     _, whisper, _ = _mods()
     _, params, feats, _ = _setup(T_IN)

@@ -46,8 +46,6 @@ constexpr int DT_TMAX = 4096;  // columns: the path (<= DT_SMAX + DT_TMAX - 1 ce
 constexpr int DT_PF = 8;       // diagonals per cost prefetch
 constexpr int DT_CHUNK = 8192; // move words staged in LDS per piece of the walk back (>= 32 rows at DT_TMAX)
 
-inline bool al_al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 __device__ __forceinline__ void cx(float& a, float& b) {  // a <- min, b <- max
   const float lo = fminf(a, b), hi = fmaxf(a, b);
   a = lo, b = hi;
@@ -323,8 +321,8 @@ static int tmi_align_cost_impl(const void* probs, int32_t probs_dtype, int64_t p
                                int32_t accumulate, void* stream) {
   const bool dt_ok = probs_dtype == TMI_F32 || probs_dtype == TMI_BF16;
   const int64_t lim = (int64_t)1 << 30;
-  if (!probs || !rows || !cols || !head_weight || !cost || !dt_ok || !al_al(probs, probs_dtype == TMI_BF16 ? 2 : 4) ||
-      !al_al(rows, 4) || !al_al(cols, 4) || !al_al(head_weight, 4) || !al_al(cost, 4) || N < 1 || N > 65535 || H < 1 ||
+  if (!probs || !rows || !cols || !head_weight || !cost || !dt_ok || !tmi_aligned(probs, probs_dtype == TMI_BF16 ? 2 : 4) ||
+      !tmi_aligned(rows, 4) || !tmi_aligned(cols, 4) || !tmi_aligned(head_weight, 4) || !tmi_aligned(cost, 4) || N < 1 || N > 65535 || H < 1 ||
       H > AC_HMAX || S < 1 || S > lim || T < 1 || T > lim || medfilt_width < 1 || medfilt_width > AC_WMAX ||
       !(medfilt_width & 1) || T <= medfilt_width / 2 || p_sq < T || p_sq > lim || p_sbh < S * p_sq || c_ss < T || c_ss > lim ||
       c_sn < S * c_ss || (normalize != 0 && normalize != 1) || (accumulate != 0 && accumulate != 1)) {
@@ -360,8 +358,8 @@ static int tmi_dtw_impl(const float* cost, int64_t c_sn, int64_t c_ss, const int
                         int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream) {
   const int64_t need = tmi_dtw_workspace_bytes(N, S_max, T_max);
   if (!cost || !rows || !cols || !tok_start || !tok_end || !total || !workspace || (path != nullptr) != (path_len != nullptr) ||
-      !al_al(cost, 4) || !al_al(rows, 4) || !al_al(cols, 4) || !al_al(tok_start, 4) || !al_al(tok_end, 4) || !al_al(total, 4) ||
-      !al_al(path, 4) || !al_al(path_len, 4) || !al_al(workspace, 4) || need < 0 || workspace_bytes < need || c_ss < T_max ||
+      !tmi_aligned(cost, 4) || !tmi_aligned(rows, 4) || !tmi_aligned(cols, 4) || !tmi_aligned(tok_start, 4) || !tmi_aligned(tok_end, 4) || !tmi_aligned(total, 4) ||
+      !tmi_aligned(path, 4) || !tmi_aligned(path_len, 4) || !tmi_aligned(workspace, 4) || need < 0 || workspace_bytes < need || c_ss < T_max ||
       c_ss > ((int64_t)1 << 30) || c_sn < S_max * c_ss) {
     tmi_set_error("tmi_dtw: bad argument (non-NULL pointers, path and path_len together; 1 <= N <= 65535, 1 <= S_max <= 1024 "
                   "rows, 1 <= T_max <= 4096 columns; c_ss >= T_max, c_sn >= S_max c_ss; workspace of tmi_dtw_workspace_bytes)");

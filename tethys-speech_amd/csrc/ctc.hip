@@ -38,8 +38,6 @@ constexpr int CT_TMAX = 4096;    // Viterbi: frames (the moves of CT_ROWS * 16 f
 constexpr int CT_PF = 8;         // frames per log-prob prefetch
 constexpr int CT_ROWS = 8;       // word rows per piece of the walk back
 
-inline bool ct_al(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 __global__ __launch_bounds__(LS_ROWS * TMI_WAVE) void ctc_logsoftmax_kernel(const float* __restrict__ x, int64_t ld,
                                                                            int R, int V, float* __restrict__ y,
                                                                            int64_t lp_ld, int32_t* __restrict__ amax) {
@@ -108,12 +106,6 @@ __global__ __launch_bounds__(GR_THREADS) void ctc_greedy_kernel(const int32_t* _
     out_len[n] = base;
     best[n] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
   }
-}
-
-__device__ __forceinline__ float lse3(float a0, float a1, float a2) {
-  const float m = fmaxf(a0, fmaxf(a1, a2));
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf((expf(a0 - m) + expf(a1 - m)) + expf(a2 - m));
 }
 
 // The walk back of the max semiring; every thread of the workgroup calls it, thread 0 walks.
@@ -259,8 +251,8 @@ __global__ __launch_bounds__(1024) void ctc_kernel(const float* __restrict__ log
 bool ctc_common_ok(const float* logp, int64_t lp_sn, int64_t lp_st, const int32_t* labels, const int32_t* label_lens,
                    const int32_t* frame_lens, int32_t blank, const void* out, const int32_t* infeasible, int64_t N,
                    int64_t L_max, int64_t T_max, int64_t t_lim) {
-  return logp && labels && label_lens && frame_lens && out && infeasible && ct_al(logp) && ct_al(labels) &&
-         ct_al(label_lens) && ct_al(frame_lens) && ct_al(out) && ct_al(infeasible) && N >= 1 && N <= 65535 && L_max >= 1 &&
+  return logp && labels && label_lens && frame_lens && out && infeasible && tmi_aligned(logp, 4) && tmi_aligned(labels, 4) &&
+         tmi_aligned(label_lens, 4) && tmi_aligned(frame_lens, 4) && tmi_aligned(out, 4) && tmi_aligned(infeasible, 4) && N >= 1 && N <= 65535 && L_max >= 1 &&
          L_max <= CT_LMAX && T_max >= 1 && T_max <= t_lim && lp_st >= 1 && lp_st <= ((int64_t)1 << 30) &&
          lp_sn >= T_max * lp_st && blank >= 0 && blank < lp_st;
 }
@@ -272,7 +264,7 @@ unsigned ctc_threads(int64_t L_max) { return (unsigned)((2 * L_max + 1 + TMI_WAV
 static int tmi_ctc_logsoftmax_impl(const float* logits, int64_t ld, int64_t R, int64_t V, float* logp, int64_t lp_ld,
                                    int32_t* argmax, void* stream) {
   const int64_t lim = (int64_t)1 << 30;
-  if (!logits || !logp || !argmax || !ct_al(logits) || !ct_al(logp) || !ct_al(argmax) || R < 1 || R > lim || V < 2 || V > 64 ||
+  if (!logits || !logp || !argmax || !tmi_aligned(logits, 4) || !tmi_aligned(logp, 4) || !tmi_aligned(argmax, 4) || R < 1 || R > lim || V < 2 || V > 64 ||
       ld < V || ld > lim || lp_ld < V || lp_ld > lim) {
     tmi_set_error("tmi_ctc_logsoftmax: bad argument (non-NULL 4-byte aligned pointers; 1 <= R <= 2^30 rows; 2 <= V <= 64 "
                   "columns, one lane each; ld >= V, lp_ld >= V)");
@@ -291,9 +283,9 @@ extern "C" int tmi_ctc_logsoftmax(const float* logits, int64_t ld, int64_t R, in
 static int tmi_ctc_greedy_impl(const int32_t* argmax, const float* logp, int64_t lp_ld, const int32_t* frame_lens,
                                int32_t blank, int32_t* tokens, int32_t* out_len, int32_t* tok_start, int32_t* tok_end,
                                float* best_logprob, int64_t N, int64_t T_max, void* stream) {
-  if (!argmax || !logp || !frame_lens || !tokens || !out_len || !tok_start || !tok_end || !best_logprob || !ct_al(argmax) ||
-      !ct_al(logp) || !ct_al(frame_lens) || !ct_al(tokens) || !ct_al(out_len) || !ct_al(tok_start) || !ct_al(tok_end) ||
-      !ct_al(best_logprob) || N < 1 || N > 65535 || T_max < 1 || T_max > ((int64_t)1 << 30) || lp_ld < 1 ||
+  if (!argmax || !logp || !frame_lens || !tokens || !out_len || !tok_start || !tok_end || !best_logprob || !tmi_aligned(argmax, 4) ||
+      !tmi_aligned(logp, 4) || !tmi_aligned(frame_lens, 4) || !tmi_aligned(tokens, 4) || !tmi_aligned(out_len, 4) || !tmi_aligned(tok_start, 4) || !tmi_aligned(tok_end, 4) ||
+      !tmi_aligned(best_logprob, 4) || N < 1 || N > 65535 || T_max < 1 || T_max > ((int64_t)1 << 30) || lp_ld < 1 ||
       lp_ld > ((int64_t)1 << 30) || blank < 0) {
     tmi_set_error("tmi_ctc_greedy: bad argument (non-NULL 4-byte aligned pointers; 1 <= N <= 65535 items, one workgroup "
                   "each; 1 <= T_max <= 2^30 frames; 1 <= lp_ld <= 2^30; blank >= 0)");
@@ -347,7 +339,7 @@ static int tmi_ctc_viterbi_impl(const float* logp, int64_t lp_sn, int64_t lp_st,
                                 int64_t T_max, void* workspace, int64_t workspace_bytes, void* stream) {
   const int64_t need = tmi_ctc_workspace_bytes(N, L_max, T_max);
   if (!ctc_common_ok(logp, lp_sn, lp_st, labels, label_lens, frame_lens, blank, total, infeasible, N, L_max, T_max, CT_TMAX) ||
-      !tok_start || !tok_end || !workspace || !ct_al(tok_start) || !ct_al(tok_end) || !ct_al(states) || !ct_al(workspace) ||
+      !tok_start || !tok_end || !workspace || !tmi_aligned(tok_start, 4) || !tmi_aligned(tok_end, 4) || !tmi_aligned(states, 4) || !tmi_aligned(workspace, 4) ||
       need < 0 || workspace_bytes < need) {
     tmi_set_error("tmi_ctc_viterbi: bad argument (non-NULL 4-byte aligned pointers, states may be NULL; 1 <= N <= 65535 items, "
                   "one workgroup each; 1 <= L_max <= 511 labels; 1 <= T_max <= 4096 frames; 1 <= lp_st <= 2^30, lp_sn >= T_max "

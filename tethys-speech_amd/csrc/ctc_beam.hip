@@ -35,8 +35,6 @@ constexpr int CB_TMAX = 65536;    // frames (trie node ids 1 + t K + r stay far 
 constexpr int CB_PF = 4;          // frames per log-prob prefetch
 constexpr uint32_t CB_MUL = 0x9E3779B1u;
 
-inline bool cb_al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 struct CbBeam {
   float pb, pnb;
   int last, len, node, par;
@@ -245,9 +243,9 @@ static int tmi_ctc_beam_impl(const float* logp, int64_t lp_sn, int64_t lp_st, in
                              int32_t blank, int32_t K, int32_t* tokens, int32_t* lengths, float* scores, int32_t* n_beams,
                              int64_t N, int64_t T_max, void* workspace, int64_t workspace_bytes, void* stream) {
   const int64_t need = tmi_ctc_beam_workspace_bytes(N, K, T_max);
-  if (!logp || !frame_lens || !tokens || !lengths || !scores || !n_beams || !workspace || !cb_al(logp, 4) ||
-      !cb_al(frame_lens, 4) || !cb_al(tokens, 4) || !cb_al(lengths, 4) || !cb_al(scores, 4) || !cb_al(n_beams, 4) ||
-      !cb_al(workspace, 8) || need < 0 || workspace_bytes < need || V < 2 || V > CB_VMAX || lp_st < V ||
+  if (!logp || !frame_lens || !tokens || !lengths || !scores || !n_beams || !workspace || !tmi_aligned(logp, 4) ||
+      !tmi_aligned(frame_lens, 4) || !tmi_aligned(tokens, 4) || !tmi_aligned(lengths, 4) || !tmi_aligned(scores, 4) || !tmi_aligned(n_beams, 4) ||
+      !tmi_aligned(workspace, 8) || need < 0 || workspace_bytes < need || V < 2 || V > CB_VMAX || lp_st < V ||
       lp_st > ((int64_t)1 << 30) || lp_sn < T_max * lp_st || blank < 0 || blank >= V) {
     tmi_set_error("tmi_ctc_beam: bad argument (non-NULL 4-byte aligned pointers, the workspace 8-byte aligned; 1 <= N <= 65535 "
                   "items, one workgroup each; 1 <= K <= 16 beams, one wave each; 2 <= V <= 64 symbols, one lane each; "

@@ -3,8 +3,8 @@
 // the gamma tensor itself: the same call gives the same bits, and an item gets the bits it gets alone.  Two launches.
 //
 // ctc_post_kernel - one workgroup per item, thread s owns extended state s of [blank, l1, blank, .., blank], as
-//   ctc.hip's ctc_kernel.  The alpha pass IS that kernel's sum semiring, operation for operation (lse3 below is a copy of
-//   ctc.hip's): states s - 1 and s - 2 of frame t - 1 arrive by __shfl_up, lanes 62 and 63 of every wave leave theirs in a
+//   ctc.hip's ctc_kernel.  The alpha pass IS that kernel's sum semiring, operation for operation (the same lse3 of
+//   tmi_common.h): states s - 1 and s - 2 of frame t - 1 arrive by __shfl_up, lanes 62 and 63 of every wave leave theirs in a
 //   two-slot LDS pair (s_bnd, slot t & 1), one barrier per frame, the thread's own column of logp prefetched CT_PF frames
 //   ahead.  alpha_t(s) is stored to gamma[n][t][s].  ll = LSE3(alpha_{T-1}(S-1), alpha_{T-1}(S-2), -inf) is computed by
 //   every thread from the two values in LDS, so nll / infeasible are bit for bit tmi_ctc_forward's.
@@ -39,14 +39,6 @@ constexpr int CT_TMAX = 4096;  // frames (the limit of tmi_ctc_viterbi: the call
 constexpr int CT_PF = 8;       // frames per prefetch
 constexpr int CT_WAVES = 1024 / TMI_WAVE;
 constexpr int OC_ROWS = 4;     // occupancy: frames (waves) per workgroup
-
-inline bool cp_al(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
-__device__ __forceinline__ float lse3(float a0, float a1, float a2) {
-  const float m = fmaxf(a0, fmaxf(a1, a2));
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf((expf(a0 - m) + expf(a1 - m)) + expf(a2 - m));
-}
 
 __global__ __launch_bounds__(1024) void ctc_post_kernel(const float* __restrict__ logp, int64_t lp_sn, int64_t lp_st, int V,
                                                         const int32_t* __restrict__ labels,
@@ -251,8 +243,8 @@ static int tmi_ctc_posteriors_impl(const float* logp, int64_t lp_sn, int64_t lp_
   const int64_t lim = (int64_t)1 << 30;
   const bool sizes = N >= 1 && N <= 65535 && L_max >= 1 && L_max <= CT_LMAX && T_max >= 1 && T_max <= CT_TMAX && V >= 2 && V <= 64;
   const bool ptrs = logp && labels && label_lens && frame_lens && nll && infeasible && gamma && occ && tok_frames && tok_center &&
-                    cp_al(logp) && cp_al(labels) && cp_al(label_lens) && cp_al(frame_lens) && cp_al(nll) && cp_al(infeasible) &&
-                    cp_al(gamma) && cp_al(occ) && cp_al(grad) && cp_al(tok_frames) && cp_al(tok_center);
+                    tmi_aligned(logp, 4) && tmi_aligned(labels, 4) && tmi_aligned(label_lens, 4) && tmi_aligned(frame_lens, 4) && tmi_aligned(nll, 4) && tmi_aligned(infeasible, 4) &&
+                    tmi_aligned(gamma, 4) && tmi_aligned(occ, 4) && tmi_aligned(grad, 4) && tmi_aligned(tok_frames, 4) && tmi_aligned(tok_center, 4);
   const bool strides = sizes && blank >= 0 && blank < V && lp_st >= V && lp_st <= lim && lp_sn >= T_max * lp_st && oc_st >= V &&
                        oc_st <= lim && oc_sn >= T_max * oc_st &&
                        (grad == nullptr || (gr_st >= V && gr_st <= lim && gr_sn >= T_max * gr_st));

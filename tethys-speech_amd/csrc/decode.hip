@@ -18,18 +18,14 @@
 // first.  The last workgroup to finish (an agent-scope completion counter) publishes the ids and the EOS count and puts the
 // slots and the counter back to zero: the workspace is clean again for the next launch, with no memset per step.
 #include "tmi_common.h"
+#include <string>
+#include <type_traits>
 
 namespace {
 
 constexpr int AM_THREADS = 256;
 constexpr int AM_COLS = 128;      // columns per workgroup: 16 column groups of 8
 constexpr int AM_KSLICES = 16;    // row slices per workgroup
-
-// order-preserving map of an fp32 value onto uint32 (-0 folded onto +0 first: tf.argmax sees them equal)
-__device__ __forceinline__ uint32_t am_order(float v) {
-  const uint32_t u = __float_as_uint(v + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // Decode constraints (tmi_lm_head_*_c; the rule is include/tethys_mi.h's "Decode constraints"): two bit sets per row,
 // column n at bit n & 31 of word n >> 5.  A thread of the epilogue owns 8 consecutive columns from a multiple of 8, so its
@@ -293,60 +289,6 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_argmax_c_kernel(
                                     slots, counter, am_cons{seen, banned, bits_ld, penalty});
 }
 
-template <typename TW, int MT>
-int am_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
-              const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, int32_t* ids, int64_t ids_ld,
-              int eos_id, int32_t* eos_count, uint64_t* slots, uint32_t* counter, const am_cons* cs) {
-  if (cs) {
-    auto kern = lm_head_argmax_c_kernel<TW, MT>;
-    static size_t opted = 65536;  // (as below)
-    if (lds > opted) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess) {
-        (void)hipGetLastError();
-        tmi_set_error("tmi_lm_head_argmax_c: the LDS size could not be granted");
-        return TMI_ERR_LAUNCH;
-      }
-      opted = lds;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
-                       reinterpret_cast<const TW*>(w), w_ld, M, d, V, ids, ids_ld, eos_id, eos_count, slots, counter,
-                       cs->seen, cs->banned, cs->bits_ld, cs->penalty);
-    return tmi_check_launch("tmi_lm_head_argmax_c");
-  }
-  auto kern = lm_head_argmax_kernel<TW, MT>;
-  // above 64 KiB of dynamic LDS (16 rows of d > 1024) the kernel has to opt in, up to what it needs (160 KiB per CU on
-  // gfx950, its few static bytes included)
-  static size_t opted = 65536;
-  if (lds > opted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      tmi_set_error("tmi_lm_head_argmax: the LDS size could not be granted");
-      return TMI_ERR_LAUNCH;
-    }
-    opted = lds;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
-                     reinterpret_cast<const TW*>(w), w_ld, M, d, V, ids, ids_ld, eos_id, eos_count, slots, counter);
-  return tmi_check_launch("tmi_lm_head_argmax");
-}
-
-template <typename TW>
-int am_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
-                const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, int32_t* ids,
-                int64_t ids_ld, int eos_id, int32_t* eos_count, uint64_t* slots, uint32_t* counter, const am_cons* cs) {
-#define AM_CASE(n)                                                                                                  \
-  case n:                                                                                                           \
-    return am_launch<TW, n>(grid, lds, s, x, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, ids, ids_ld, eos_id, \
-                            eos_count, slots, counter, cs);
-  switch (MT) {
-    AM_CASE(1) AM_CASE(2) AM_CASE(4) AM_CASE(8) AM_CASE(16)
-  }
-#undef AM_CASE
-  return TMI_ERR_INVALID;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // Beam search's LM head: tmi_lm_head_topk.  The argmax kernel's body (am_head_tile) with a top-N epilogue: per row, the
 // logsumexp of s = z * inv_temperature over the V real columns and the N largest s (ties: smaller column first), written
@@ -365,17 +307,6 @@ constexpr int TK_HEADS = 8;    // list heads per lane: ceil(V / 128) <= 512
 
 __device__ __forceinline__ float tk_unorder(uint32_t u) {
   return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-
-// (max, sum exp(x - max)) pairs: b folded into a
-__device__ __forceinline__ void tk_fold(float& am, float& as, float bm, float bs) {
-  if (bm == -INFINITY) return;
-  if (bm > am) {
-    as = as * expf(am - bm) + bs;
-    am = bm;
-  } else {
-    as = as + bs * expf(bm - am);
-  }
 }
 
 __device__ __forceinline__ uint64_t tk_wave_max(uint64_t v) {
@@ -483,7 +414,7 @@ __device__ __forceinline__ void lm_head_topk_body(
     for (int wg = lane; wg < nwg; wg += 64) {
       float2* p = part + (int64_t)r * nwg + wg;
       const float2 v = *p;
-      tk_fold(am, as, v.x, v.y);
+      lse_fold(am, as, v.x, v.y);
       *p = make_float2(0.f, 0.f);
     }
 #pragma unroll
@@ -491,10 +422,10 @@ __device__ __forceinline__ void lm_head_topk_body(
       const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
       if (lane & o) {  // the lower lane's pair first, in both lanes
         float lm = om, ls = os;
-        tk_fold(lm, ls, am, as);
+        lse_fold(lm, ls, am, as);
         am = lm, as = ls;
       } else {
-        tk_fold(am, as, om, os);
+        lse_fold(am, as, om, os);
       }
     }
     const float lse = am + logf(as);
@@ -573,60 +504,6 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_topk_c_kernel(
     float penalty) {
   lm_head_topk_body<TW, MT, true>(xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse,
                                   counters, part, keys, am_cons{seen, banned, bits_ld, penalty});
-}
-
-template <typename TW, int MT>
-int tk_launch(dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
-              const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, float inv_t, int N,
-              int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys,
-              const am_cons* cs) {
-  if (cs) {
-    auto kern = lm_head_topk_c_kernel<TW, MT>;
-    static size_t opted = 65536;  // (as am_launch)
-    if (lds > opted) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-          hipSuccess) {
-        (void)hipGetLastError();
-        tmi_set_error("tmi_lm_head_topk_c: the LDS size could not be granted");
-        return TMI_ERR_LAUNCH;
-      }
-      opted = lds;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
-                       reinterpret_cast<const TW*>(w), w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse, counters, part,
-                       keys, cs->seen, cs->banned, cs->bits_ld, cs->penalty);
-    return tmi_check_launch("tmi_lm_head_topk_c");
-  }
-  auto kern = lm_head_topk_kernel<TW, MT>;
-  static size_t opted = 65536;  // (as am_launch)
-  if (lds > opted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      tmi_set_error("tmi_lm_head_topk: the LDS size could not be granted");
-      return TMI_ERR_LAUNCH;
-    }
-    opted = lds;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, x, x_ld, x_bf16, gamma, beta, eps,
-                     reinterpret_cast<const TW*>(w), w_ld, M, d, V, inv_t, N, out_ids, out_lp, out_lse, counters, part, keys);
-  return tmi_check_launch("tmi_lm_head_topk");
-}
-
-template <typename TW>
-int tk_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const void* x, int64_t x_ld, int x_bf16, const float* gamma,
-                const float* beta, float eps, const void* w, int64_t w_ld, int M, int d, int V, float inv_t, int N,
-                int32_t* out_ids, float* out_lp, float* out_lse, uint32_t* counters, float2* part, uint64_t* keys,
-                const am_cons* cs) {
-#define TK_CASE(n)                                                                                                     \
-  case n:                                                                                                              \
-    return tk_launch<TW, n>(grid, lds, s, x, x_ld, x_bf16, gamma, beta, eps, w, w_ld, M, d, V, inv_t, N, out_ids,      \
-                            out_lp, out_lse, counters, part, keys, cs);
-  switch (MT) {
-    TK_CASE(1) TK_CASE(2) TK_CASE(4) TK_CASE(8) TK_CASE(16)
-  }
-#undef TK_CASE
-  return TMI_ERR_INVALID;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -788,7 +665,7 @@ __device__ __forceinline__ void lm_head_sample_body(
     for (int wg = lane; wg < nwg; wg += 64) {
       float2* p = part + (int64_t)r * nwg + wg;
       const float2 v = *p;
-      tk_fold(am, as, v.x, v.y);
+      lse_fold(am, as, v.x, v.y);
       *p = make_float2(0.f, 0.f);
     }
 #pragma unroll
@@ -796,10 +673,10 @@ __device__ __forceinline__ void lm_head_sample_body(
       const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
       if (lane & o) {  // the lower lane's pair first, in both lanes
         float lm = om, ls = os;
-        tk_fold(lm, ls, am, as);
+        lse_fold(lm, ls, am, as);
         am = lm, as = ls;
       } else {
-        tk_fold(am, as, om, os);
+        lse_fold(am, as, om, os);
       }
     }
     const float lse = am + logf(as);
@@ -946,54 +823,72 @@ __global__ __launch_bounds__(AM_THREADS) void lm_head_sample_c_kernel(
                                     counters, part, keys, am_cons{seen, banned, bits_ld, penalty});
 }
 
-template <typename TW, int MT, typename... A>
-int sm_launch_c(dim3 grid, size_t lds, hipStream_t s, const am_cons* cs, A... a) {
-  auto kern = lm_head_sample_c_kernel<TW, MT>;
-  static size_t opted = 65536;  // (as am_launch)
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side: the one launch path of the six kernels above.
+
+// What shapes a launch of any of them: the row tile, am_head_tile's LDS and the workgroups per row tile.
+struct am_geom {
+  int MT;              // rows per workgroup
+  int64_t lds_floats;  // max(d * MT, 4 * MT * 128); a head whose epilogue needs more raises it
+  int64_t nwg;         // ceil(V / 128)
+};
+
+// One instantiation's launch as entry point `name`.  Above 64 KiB of dynamic LDS (16 rows of d > 1024) a kernel has to opt
+// in, up to what it needs (160 KiB per CU on gfx950, its few static bytes included); `opted` is this instantiation's own.
+template <auto Kern, typename... A>
+int am_launch_one(const char* name, dim3 grid, size_t lds, hipStream_t s, A... a) {
+  static size_t opted = 65536;
   if (lds > opted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
         hipSuccess) {
       (void)hipGetLastError();
-      tmi_set_error("tmi_lm_head_sample_c: the LDS size could not be granted");
+      tmi_set_error((std::string(name) + ": the LDS size could not be granted").c_str());
       return TMI_ERR_LAUNCH;
     }
     opted = lds;
   }
-  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, a..., cs->seen, cs->banned, cs->bits_ld, cs->penalty);
-  return tmi_check_launch("tmi_lm_head_sample_c");
+  hipLaunchKernelGGL(Kern, grid, dim3(AM_THREADS), lds, s, a...);
+  return tmi_check_launch(name);
 }
 
-template <typename TW, int MT, typename... A>
-int sm_launch(dim3 grid, size_t lds, hipStream_t s, const am_cons* cs, A... a) {
-  if (cs) return sm_launch_c<TW, MT>(grid, lds, s, cs, a...);
-  auto kern = lm_head_sample_kernel<TW, MT>;
-  static size_t opted = 65536;  // (as am_launch)
-  if (lds > opted) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      tmi_set_error("tmi_lm_head_sample: the LDS size could not be granted");
-      return TMI_ERR_LAUNCH;
+// A head's launch: KernC with the constraint's four arguments behind `a` when there is one, Kern otherwise.
+template <auto Kern, auto KernC, typename... A>
+int am_launch(const char* name, const char* name_c, const am_geom& g, int64_t M, void* stream, const am_cons* cs, A... a) {
+  const dim3 grid((unsigned)g.nwg, (unsigned)((M + g.MT - 1) / g.MT));
+  const size_t lds = (size_t)g.lds_floats * 4;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (cs) return am_launch_one<KernC>(name_c, grid, lds, s, a..., cs->seen, cs->banned, cs->bits_ld, cs->penalty);
+  return am_launch_one<Kern>(name, grid, lds, s, a...);
+}
+
+// f(am_tag<TW>, integral_constant<MT>) for the weights' dtype and the row tile of a call
+template <typename TW> struct am_tag { using type = TW; };
+template <typename F>
+int am_dispatch(int32_t w_dtype, int MT, F f) {
+  auto tile = [&](auto tw) -> int {
+    switch (MT) {
+      case 1: return f(tw, std::integral_constant<int, 1>{});
+      case 2: return f(tw, std::integral_constant<int, 2>{});
+      case 4: return f(tw, std::integral_constant<int, 4>{});
+      case 8: return f(tw, std::integral_constant<int, 8>{});
+      case 16: return f(tw, std::integral_constant<int, 16>{});
     }
-    opted = lds;
-  }
-  hipLaunchKernelGGL(kern, grid, dim3(AM_THREADS), lds, s, a...);
-  return tmi_check_launch("tmi_lm_head_sample");
+    return TMI_ERR_INVALID;
+  };
+  return w_dtype == TMI_BF16 ? tile(am_tag<bf16_t>{}) : tile(am_tag<float>{});
 }
 
-template <typename TW, typename... A>
-int sm_dispatch(int MT, dim3 grid, size_t lds, hipStream_t s, const am_cons* cs, A... a) {
-  switch (MT) {
-    case 1: return sm_launch<TW, 1>(grid, lds, s, cs, a...);
-    case 2: return sm_launch<TW, 2>(grid, lds, s, cs, a...);
-    case 4: return sm_launch<TW, 4>(grid, lds, s, cs, a...);
-    case 8: return sm_launch<TW, 8>(grid, lds, s, cs, a...);
-    case 16: return sm_launch<TW, 16>(grid, lds, s, cs, a...);
-  }
-  return TMI_ERR_INVALID;
+// What the three heads ask of the arguments they share -> g; false: a bad argument.
+bool am_args(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, const void* w, int64_t w_ld,
+             int32_t w_dtype, int64_t M, int64_t d, int64_t V, const void* workspace, am_geom& g) {
+  const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
+  g.MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
+  g.lds_floats = d * g.MT > 4 * g.MT * AM_COLS ? d * g.MT : 4 * g.MT * AM_COLS;
+  g.nwg = (V + AM_COLS - 1) / AM_COLS;
+  return x && w && workspace && dt_ok && M >= 1 && M <= (int64_t)16 * 65535 && d >= 1 && V >= 1 && w_ld >= V && !(w_ld & 7) &&
+         tmi_aligned(w, 16) && x_ld >= d && (gamma == nullptr) == (beta == nullptr) && tmi_aligned(workspace, 8) &&
+         g.lds_floats * 4 <= 160 * 1024 - 256;
 }
-
-inline bool am_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -1014,26 +909,21 @@ static int am_run(const char* bad, const void* x, int64_t x_ld, int32_t x_dtype,
                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V, int32_t* ids,
                   int64_t ids_ld, int32_t eos_id, int32_t* eos_count, void* workspace, int64_t workspace_bytes, void* stream,
                   const am_cons* cs) {
-  const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
-  const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
-  const int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
-  if (!x || !w || !ids || !workspace || !dt_ok || M < 1 || M > (int64_t)16 * 65535 || d < 1 || V < 1 || V >= INT32_MAX ||
-      w_ld < V || (w_ld & 7) || !am_al16(w) || x_ld < d || ids_ld < 1 || (gamma == nullptr) != (beta == nullptr) ||
-      workspace_bytes < 8 * (M + 1) || (reinterpret_cast<uintptr_t>(workspace) & 7) || lds_floats * 4 > 160 * 1024 - 256) {
+  am_geom g;
+  if (!am_args(x, x_ld, x_dtype, gamma, beta, w, w_ld, w_dtype, M, d, V, workspace, g) || !ids || V >= INT32_MAX ||
+      ids_ld < 1 || workspace_bytes < 8 * (M + 1)) {
     tmi_set_error(bad);
     return TMI_ERR_INVALID;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint64_t* slots = reinterpret_cast<uint64_t*>(workspace);
   uint32_t* counter = reinterpret_cast<uint32_t*>(slots + M);
-  const dim3 grid((unsigned)((V + AM_COLS - 1) / AM_COLS), (unsigned)((M + MT - 1) / MT));
-  const size_t lds = (size_t)lds_floats * 4;
   const int xb = x_dtype == TMI_BF16;
-  if (w_dtype == TMI_BF16)
-    return am_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V, ids, ids_ld,
-                               eos_id, eos_count, slots, counter, cs);
-  return am_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V, ids, ids_ld,
-                            eos_id, eos_count, slots, counter, cs);
+  return am_dispatch(w_dtype, g.MT, [&](auto tw, auto mt) {
+    using TW = typename decltype(tw)::type;
+    return am_launch<lm_head_argmax_kernel<TW, mt()>, lm_head_argmax_c_kernel<TW, mt()>>(
+        "tmi_lm_head_argmax", "tmi_lm_head_argmax_c", g, M, stream, cs, x, x_ld, xb, gamma, beta, eps,
+        reinterpret_cast<const TW*>(w), w_ld, (int)M, (int)d, (int)V, ids, ids_ld, eos_id, eos_count, slots, counter);
+  });
 }
 static int tmi_lm_head_argmax_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                    float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
@@ -1077,33 +967,27 @@ static int tk_run(const char* bad, const void* x, int64_t x_ld, int32_t x_dtype,
                   float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
                   float inv_temperature, int64_t N, int32_t* ids, float* logprobs, float* lse, void* workspace,
                   int64_t workspace_bytes, void* stream, const am_cons* cs) {
-  const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
-  const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
-  int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
-  if (lds_floats < 4 * TK_CAP * 2) lds_floats = 4 * TK_CAP * 2;
-  const int64_t nwg = (V + AM_COLS - 1) / AM_COLS;
-  const bool sizes_ok = M >= 1 && M <= (int64_t)16 * 65535 && d >= 1 && V >= 1 && nwg <= 64 * TK_HEADS && N >= 1 &&
-                        N <= 16 && N <= V;
-  if (!x || !w || !ids || !logprobs || !workspace || !dt_ok || !sizes_ok || w_ld < V || (w_ld & 7) || !am_al16(w) ||
-      x_ld < d || (gamma == nullptr) != (beta == nullptr) || !(inv_temperature > 0.f && inv_temperature < INFINITY) ||
-      workspace_bytes < 8 * M * (1 + nwg * (N + 1)) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
-      lds_floats * 4 > 160 * 1024 - 256) {
+  am_geom g;
+  const bool shared_ok = am_args(x, x_ld, x_dtype, gamma, beta, w, w_ld, w_dtype, M, d, V, workspace, g);
+  const int64_t nwg = g.nwg;
+  if (!shared_ok || !ids || !logprobs || nwg > 64 * TK_HEADS || N < 1 || N > 16 || N > V ||
+      !(inv_temperature > 0.f && inv_temperature < INFINITY) || workspace_bytes < 8 * M * (1 + nwg * (N + 1))) {
     tmi_set_error(bad);
     return TMI_ERR_INVALID;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (g.lds_floats < 4 * TK_CAP * 2) g.lds_floats = 4 * TK_CAP * 2;  // (the gathered keys of the epilogue's four waves)
   char* base = reinterpret_cast<char*>(workspace);
   uint32_t* counters = reinterpret_cast<uint32_t*>(base);  // (one per row tile; 8 * M bytes reserved)
   float2* part = reinterpret_cast<float2*>(base + 8 * M);
   uint64_t* keys = reinterpret_cast<uint64_t*>(base + 8 * M + 8 * M * nwg);
-  const dim3 grid((unsigned)nwg, (unsigned)((M + MT - 1) / MT));
-  const size_t lds = (size_t)lds_floats * 4;
   const int xb = x_dtype == TMI_BF16;
-  if (w_dtype == TMI_BF16)
-    return tk_dispatch<bf16_t>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
-                               inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys, cs);
-  return tk_dispatch<float>(MT, grid, lds, s, x, x_ld, xb, gamma, beta, eps, w, w_ld, (int)M, (int)d, (int)V,
-                            inv_temperature, (int)N, ids, logprobs, lse, counters, part, keys, cs);
+  return am_dispatch(w_dtype, g.MT, [&](auto tw, auto mt) {
+    using TW = typename decltype(tw)::type;
+    return am_launch<lm_head_topk_kernel<TW, mt()>, lm_head_topk_c_kernel<TW, mt()>>(
+        "tmi_lm_head_topk", "tmi_lm_head_topk_c", g, M, stream, cs, x, x_ld, xb, gamma, beta, eps,
+        reinterpret_cast<const TW*>(w), w_ld, (int)M, (int)d, (int)V, inv_temperature, (int)N, ids, logprobs, lse, counters,
+        part, keys);
+  });
 }
 static int tmi_lm_head_topk_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                  float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
@@ -1154,37 +1038,30 @@ static int sm_run(const char* bad, const void* x, int64_t x_ld, int32_t x_dtype,
                   float temperature, int64_t top_k, float top_p, uint64_t seed, int32_t suppress_id, int32_t eos_id,
                   int32_t pad_id, int32_t* finished, int32_t* ids, int64_t ids_ld, float* logprob, int32_t* n_finished,
                   void* workspace, int64_t workspace_bytes, void* stream, const am_cons* cs) {
-  const bool dt_ok = (x_dtype == TMI_F32 || x_dtype == TMI_BF16) && (w_dtype == TMI_F32 || w_dtype == TMI_BF16);
-  const int MT = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : M <= 8 ? 8 : 16;
-  int64_t lds_floats = d * MT > 4 * MT * AM_COLS ? d * MT : 4 * MT * AM_COLS;
-  if (lds_floats < 512) lds_floats = 512;
-  const int64_t nwg = (V + AM_COLS - 1) / AM_COLS;
-  const bool sizes_ok = M >= 1 && M <= (int64_t)16 * 65535 && d >= 1 && V >= 1 && nwg <= 64 * TK_HEADS;
+  am_geom g;
+  const bool shared_ok = am_args(x, x_ld, x_dtype, gamma, beta, w, w_ld, w_dtype, M, d, V, workspace, g);
+  const int64_t nwg = g.nwg;
   const bool rule_ok = temperature > 0.f && temperature < INFINITY && top_k >= 0 && top_k <= SM_MAXK && top_p > 0.f &&
                        top_p <= 1.f && (top_k > 0 || top_p == 1.f);
-  if (!x || !w || !ids || !finished || !n_finished || !workspace || !dt_ok || !sizes_ok || !rule_ok || w_ld < V ||
-      (w_ld & 7) || !am_al16(w) || x_ld < d || ids_ld < 1 || (gamma == nullptr) != (beta == nullptr) ||
-      workspace_bytes < tmi_lm_head_sample_workspace_bytes(M, V, top_k) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
-      lds_floats * 4 > 160 * 1024 - 256) {
+  if (!shared_ok || !ids || !finished || !n_finished || nwg > 64 * TK_HEADS || !rule_ok || ids_ld < 1 ||
+      workspace_bytes < tmi_lm_head_sample_workspace_bytes(M, V, top_k)) {
     tmi_set_error(bad);
     return TMI_ERR_INVALID;
   }
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (g.lds_floats < 512) g.lds_floats = 512;  // (the epilogue's four waves: 64 lists and 64 probabilities each)
   char* base = reinterpret_cast<char*>(workspace);
   uint32_t* counters = reinterpret_cast<uint32_t*>(base);  // (one per row tile, then the tiles' own at [M]; 8 * M + 8 bytes)
   float2* part = reinterpret_cast<float2*>(base + 8 * M + 8);
   uint64_t* keys = reinterpret_cast<uint64_t*>(base + 8 * M + 8 + 8 * M * nwg);
-  const dim3 grid((unsigned)nwg, (unsigned)((M + MT - 1) / MT));
-  const size_t lds = (size_t)lds_floats * 4;
   const int xb = x_dtype == TMI_BF16;
   const uint32_t skey = tmi_stream_key(seed, 0);
-  if (w_dtype == TMI_BF16)
-    return sm_dispatch<bf16_t>(MT, grid, lds, s, cs, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const bf16_t*>(w), w_ld,
-                               (int)M, (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id,
-                               (int)pad_id, finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
-  return sm_dispatch<float>(MT, grid, lds, s, cs, x, x_ld, xb, gamma, beta, eps, reinterpret_cast<const float*>(w), w_ld,
-                            (int)M, (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id, (int)eos_id,
-                            (int)pad_id, finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
+  return am_dispatch(w_dtype, g.MT, [&](auto tw, auto mt) {
+    using TW = typename decltype(tw)::type;
+    return am_launch<lm_head_sample_kernel<TW, mt()>, lm_head_sample_c_kernel<TW, mt()>>(
+        "tmi_lm_head_sample", "tmi_lm_head_sample_c", g, M, stream, cs, x, x_ld, xb, gamma, beta, eps,
+        reinterpret_cast<const TW*>(w), w_ld, (int)M, (int)d, (int)V, temperature, (int)top_k, top_p, skey, (int)suppress_id,
+        (int)eos_id, (int)pad_id, finished, ids, ids_ld, logprob, n_finished, counters, part, keys);
+  });
 }
 static int tmi_lm_head_sample_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
                                    float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,

@@ -37,22 +37,6 @@ struct LpState {  // tmi_logprob_state_bytes(M) = 32 * M
 };
 static_assert(sizeof(LpState) == 32, "state layout");
 
-__device__ __forceinline__ uint32_t lp_order(float v) {  // decode.hip's am_order
-  const uint32_t u = __float_as_uint(v + 0.0f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// (am, as) <- (am, as) followed by (bm, bs): decode.hip's tk_fold
-__device__ __forceinline__ void lp_fold(float& am, float& as, float bm, float bs) {
-  if (bm == -INFINITY) return;
-  if (bm > am) {
-    as = as * expf(am - bm) + bs;
-    am = bm;
-  } else {
-    as = as + bs * expf(bm - am);
-  }
-}
-
 template <typename T> struct lp_vec;
 template <> struct lp_vec<bf16_t> {
   static constexpr int N = 8;
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(LP_THREADS) void lp_fold_kernel(
       z[c] = ok ? v.get(c) : -INFINITY;
       if (ok) {
         vm = fmaxf(vm, z[c]);
-        const uint64_t key = ((uint64_t)lp_order(z[c]) << 32) | (uint64_t)(~(uint32_t)(col0 + j + c));
+        const uint64_t key = ((uint64_t)am_order(z[c]) << 32) | (uint64_t)(~(uint32_t)(col0 + j + c));
         if (key > best) best = key;
       }
     }
@@ -118,10 +102,10 @@ __global__ __launch_bounds__(LP_THREADS) void lp_fold_kernel(
     const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
     if (lane & o) {
       float lm = om, ls = os;
-      lp_fold(lm, ls, am, as);
+      lse_fold(lm, ls, am, as);
       am = lm, as = ls;
     } else {
-      lp_fold(am, as, om, os);
+      lse_fold(am, as, om, os);
     }
     const uint32_t lo = __shfl_xor((uint32_t)best, o, 64), hi = __shfl_xor((uint32_t)(best >> 32), o, 64);
     const uint64_t ob = ((uint64_t)hi << 32) | lo;
@@ -148,7 +132,7 @@ __global__ __launch_bounds__(LP_THREADS) void lp_fold_kernel(
     st.m = am, st.s = as, st.best = best, st.zt = zt, st.zts = zts;
   } else {
     st = state[row];
-    lp_fold(st.m, st.s, am, as);        // the earlier chunks first
+    lse_fold(st.m, st.s, am, as);        // the earlier chunks first
     if (best > st.best) st.best = best;  // (keys of different columns are never equal: strictly greater value, or an equal one at a smaller column - which an earlier chunk holds)
     if (here) st.zt = zt, st.zts = zts;
   }
@@ -178,8 +162,6 @@ __global__ __launch_bounds__(LP_THREADS) void lp_fold_kernel(
   argmax[row] = (int32_t)(~(uint32_t)st.best);
 }
 
-inline bool lp_al(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int64_t tmi_logprob_state_bytes(int64_t M) { return M < 1 ? -1 : (int64_t)sizeof(LpState) * M; }
@@ -192,11 +174,11 @@ static int tmi_logprob_fold_impl(const void* chunk, int64_t ld, int32_t dtype, i
   const bool dt_ok = dtype == TMI_F32 || dtype == TMI_BF16;
   const int64_t vec = dtype == TMI_BF16 ? 8 : 4;
   const bool lm = x != nullptr || w != nullptr;
-  const bool lm_ok = !lm || (x && w && d >= 1 && d <= (1 << 20) && x_ld >= d && w_sk != 0 && w_sn != 0 && lp_al(x, 2) && lp_al(w, 2));
-  const bool out_ok = !last || (lse && logprob && argmax && lp_al(lse, 4) && lp_al(logprob, 4) && lp_al(argmax, 4));
-  if (!chunk || !targets || !lp_al(targets, 4) || !state || !dt_ok || !lm_ok || !out_ok || M < 1 || M > (1 << 30) || V < 1 || V > (1 << 30) ||
-      col0 < 0 || col0 >= V || ncols < 1 || ncols > ld || ld > (1 << 30) || (ld % vec) != 0 || !lp_al(chunk, 16) ||
-      !lp_al(state, 8) || state_bytes < (int64_t)sizeof(LpState) * M || (first != 0 && first != 1) || (last != 0 && last != 1) ||
+  const bool lm_ok = !lm || (x && w && d >= 1 && d <= (1 << 20) && x_ld >= d && w_sk != 0 && w_sn != 0 && tmi_aligned(x, 2) && tmi_aligned(w, 2));
+  const bool out_ok = !last || (lse && logprob && argmax && tmi_aligned(lse, 4) && tmi_aligned(logprob, 4) && tmi_aligned(argmax, 4));
+  if (!chunk || !targets || !tmi_aligned(targets, 4) || !state || !dt_ok || !lm_ok || !out_ok || M < 1 || M > (1 << 30) || V < 1 || V > (1 << 30) ||
+      col0 < 0 || col0 >= V || ncols < 1 || ncols > ld || ld > (1 << 30) || (ld % vec) != 0 || !tmi_aligned(chunk, 16) ||
+      !tmi_aligned(state, 8) || state_bytes < (int64_t)sizeof(LpState) * M || (first != 0 && first != 1) || (last != 0 && last != 1) ||
       (first && col0 != 0) || (!first && col0 == 0) || (last && col0 + ncols < V) || (!last && col0 + ncols >= V)) {
     tmi_set_error("tmi_logprob_fold: bad argument");
     return TMI_ERR_INVALID;
@@ -347,8 +329,8 @@ static int tmi_contrastive_score_impl(const void* h, const void* q, int64_t ld, 
   const bool dt_ok = dtype == TMI_F32 || dtype == TMI_BF16;
   const int64_t vec = dtype == TMI_BF16 ? 8 : 4;
   const int64_t lim = (int64_t)1 << 30;
-  if (!h || !q || !neg || !row_loss || !row_correct || !dt_ok || !lp_al(h, 16) || !lp_al(q, 16) || !lp_al(neg, 4) ||
-      !lp_al(mask, 4) || !lp_al(row_loss, 4) || !lp_al(row_correct, 4) || B < 1 || T < 1 || Nn < 1 || pd < 1 || B > lim ||
+  if (!h || !q || !neg || !row_loss || !row_correct || !dt_ok || !tmi_aligned(h, 16) || !tmi_aligned(q, 16) || !tmi_aligned(neg, 4) ||
+      !tmi_aligned(mask, 4) || !tmi_aligned(row_loss, 4) || !tmi_aligned(row_correct, 4) || B < 1 || T < 1 || Nn < 1 || pd < 1 || B > lim ||
       T > lim || Nn > lim || pd > lim || ld > lim || B * T > lim || (pd % vec) != 0 || ld < pd || (ld % vec) != 0 ||
       neg_sb < 0 || neg_st < 0 || !(temperature > 0.f)) {
     tmi_set_error("tmi_contrastive_score: bad argument");
@@ -378,7 +360,7 @@ extern "C" int tmi_contrastive_score(const void* h, const void* q, int64_t ld, i
 
 static int tmi_vq_count_impl(const int32_t* idx, const float* mask, int64_t* counts, int64_t rows, int64_t G, int64_t Nc,
                              void* stream) {
-  if (!idx || !counts || !lp_al(idx, 4) || !lp_al(mask, 4) || !lp_al(counts, 8) || rows < 1 || rows > ((int64_t)1 << 30) ||
+  if (!idx || !counts || !tmi_aligned(idx, 4) || !tmi_aligned(mask, 4) || !tmi_aligned(counts, 8) || rows < 1 || rows > ((int64_t)1 << 30) ||
       G < 1 || Nc < 1 || G > 8192 || Nc > 8192 || G * Nc > 8192) {
     tmi_set_error("tmi_vq_count: bad argument");
     return TMI_ERR_INVALID;

@@ -257,3 +257,31 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
   __syncthreads();
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
+
+// ---- helpers the decoding, scoring and CTC kernels share
+// order-preserving map of an fp32 value onto uint32 (-0 folded onto +0 first: tf.argmax sees them equal)
+__device__ __forceinline__ uint32_t am_order(float v) {
+  const uint32_t u = __float_as_uint(v + 0.0f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// (max, sum exp(x - max)) pairs: b folded into a, (am, as) <- (am, as) followed by (bm, bs)
+__device__ __forceinline__ void lse_fold(float& am, float& as, float bm, float bs) {
+  if (bm == -INFINITY) return;
+  if (bm > am) {
+    as = as * expf(am - bm) + bs;
+    am = bm;
+  } else {
+    as = as + bs * expf(bm - am);
+  }
+}
+
+// log(exp(a0) + exp(a1) + exp(a2)) in that order; -inf is the additive zero (the CTC sum semiring)
+__device__ __forceinline__ float lse3(float a0, float a1, float a2) {
+  const float m = fmaxf(a0, fmaxf(a1, a2));
+  if (m == -INFINITY) return -INFINITY;
+  return m + logf((expf(a0 - m) + expf(a1 - m)) + expf(a2 - m));
+}
+
+// host side: is p a multiple of `bytes` (a power of two)?
+inline bool tmi_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }

@@ -726,20 +726,40 @@ def xent_fwd_bwd_weighted(logits, ld, labels, row_w, inv_wsum, row_loss, B, S, V
                                                  V, loss_scale, dt(logits), stream()), "tmi_linear_xent_weighted")
 
 
+def _lm_head_argmax(cons, x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma, beta, eps, eos_id, eos_count):
+    """The one marshalling of tmi_lm_head_argmax and, with ``cons`` = (seen, banned, penalty), of tmi_lm_head_argmax_c: the
+    _c entry point takes the same arguments with the constraint's four in front of the stream."""
+    c = cons is not None
+    tail = _cons_tail(cons, M, V) if c else ()
+    with _probe("lm_head_argmax_c" if c else "lm_head_argmax", float(d) * w_ld * w.element_size()):
+        check((lib().tmi_lm_head_argmax_c if c else lib().tmi_lm_head_argmax)(
+            x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d, V, ids.data_ptr(), ids_ld,
+            eos_id, ptr(eos_count), workspace.data_ptr(), workspace.numel() * workspace.element_size(), *tail, stream()),
+            "tmi_lm_head_argmax_c" if c else "tmi_lm_head_argmax")
+
+
 def lm_head_argmax(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma=None, beta=None, eps=1e-5, eos_id=-1,
                    eos_count=None):
     """ids[r * ids_ld] = argmax_{n < V} (LayerNorm(x[r]) . w)[n] for M rows of x (row stride x_ld), w the LM head in its
     stored [d, w_ld] layout (fp32 arena or bf16 mirror); eos_count[0] = how many of them equal eos_id.  ``workspace``: an
     int64 tensor of >= M + 1 elements, zero before the first call (tmi_lm_head_argmax leaves it zero)."""
-    with _probe("lm_head_argmax", float(d) * w_ld * w.element_size()):
-        check(lib().tmi_lm_head_argmax(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
-                                       V, ids.data_ptr(), ids_ld, eos_id, ptr(eos_count), workspace.data_ptr(),
-                                       workspace.numel() * workspace.element_size(), stream()), "tmi_lm_head_argmax")
+    _lm_head_argmax(None, x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma, beta, eps, eos_id, eos_count)
 
 
 def lm_head_topk_workspace_elems(M, V, N):
     """int64 elements of tmi_lm_head_topk's workspace: 8 * M * (1 + ceil(V / 128) * (N + 1)) bytes."""
     return M * (1 + (V + 127) // 128 * (N + 1))
+
+
+def _lm_head_topk(cons, x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma, beta, eps, temperature, lse):
+    """The one marshalling of tmi_lm_head_topk / tmi_lm_head_topk_c (as ``_lm_head_argmax``)."""
+    c = cons is not None
+    tail = _cons_tail(cons, M, V) if c else ()
+    with _probe("lm_head_topk_c" if c else "lm_head_topk", float(d) * w_ld * w.element_size()):
+        check((lib().tmi_lm_head_topk_c if c else lib().tmi_lm_head_topk)(
+            x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d, V, 1.0 / float(temperature), N,
+            ids.data_ptr(), logprobs.data_ptr(), ptr(lse), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+            *tail, stream()), "tmi_lm_head_topk_c" if c else "tmi_lm_head_topk")
 
 
 def lm_head_topk(x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma=None, beta=None, eps=1e-5,
@@ -748,11 +768,7 @@ def lm_head_topk(x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma=N
     columns of s (ties: the smaller column first), logprobs[r, :N] their s - logsumexp(s) (fp32), lse[r] the logsumexp.
     ``ids`` int32 and ``logprobs`` fp32 are contiguous [M, N].  ``workspace``: an int64 tensor of at least
     ``lm_head_topk_workspace_elems(M, V, N)`` elements, zero before the first call (tmi_lm_head_topk leaves it zero)."""
-    with _probe("lm_head_topk", float(d) * w_ld * w.element_size()):
-        check(lib().tmi_lm_head_topk(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
-                                     V, 1.0 / float(temperature), N, ids.data_ptr(), logprobs.data_ptr(), ptr(lse),
-                                     workspace.data_ptr(), workspace.numel() * workspace.element_size(), stream()),
-              "tmi_lm_head_topk")
+    _lm_head_topk(None, x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma, beta, eps, temperature, lse)
 
 
 def lm_head_sample_workspace_elems(M, V, top_k):
@@ -763,6 +779,20 @@ def lm_head_sample_workspace_elems(M, V, top_k):
     return n // 8
 
 
+def _lm_head_sample(cons, x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace, temperature, top_k, top_p,
+                    seed, suppress_id, eos_id, pad_id, logprob, gamma, beta, eps):
+    """The one marshalling of tmi_lm_head_sample / tmi_lm_head_sample_c (as ``_lm_head_argmax``)."""
+    c = cons is not None
+    tail = _cons_tail(cons, M, V) if c else ()
+    with _probe("lm_head_sample_c" if c else "lm_head_sample", float(d) * w_ld * w.element_size()):
+        check((lib().tmi_lm_head_sample_c if c else lib().tmi_lm_head_sample)(
+            x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d, V, float(temperature),
+            int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, suppress_id, eos_id, pad_id, finished.data_ptr(),
+            ids.data_ptr(), ids_ld, ptr(logprob), n_finished.data_ptr(), workspace.data_ptr(),
+            workspace.numel() * workspace.element_size(), *tail, stream()),
+            "tmi_lm_head_sample_c" if c else "tmi_lm_head_sample")
+
+
 def lm_head_sample(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace, temperature=1.0, top_k=50,
                    top_p=1.0, seed=0, suppress_id=-1, eos_id=-1, pad_id=0, logprob=None, gamma=None, beta=None, eps=1e-5):
     """One sampled token per row of M rows of x (row stride x_ld): ids[r * ids_ld] drawn from softmax((LayerNorm(x[r]) . w)
@@ -770,12 +800,8 @@ def lm_head_sample(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished,
     Gumbel-max), logprob[r] = its log-probability under the uncut distribution; the rule is include/tethys_mi.h's.
     ``finished`` int32 [M] in and out, ``n_finished`` int32 [1]; ``workspace``: an int64 tensor of at least
     ``lm_head_sample_workspace_elems(M, V, top_k)`` elements, zero before the first call (left zero by every call)."""
-    with _probe("lm_head_sample", float(d) * w_ld * w.element_size()):
-        check(lib().tmi_lm_head_sample(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
-                                       V, float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                       suppress_id, eos_id, pad_id, finished.data_ptr(), ids.data_ptr(), ids_ld,
-                                       ptr(logprob), n_finished.data_ptr(), workspace.data_ptr(),
-                                       workspace.numel() * workspace.element_size(), stream()), "tmi_lm_head_sample")
+    _lm_head_sample(None, x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace, temperature, top_k, top_p,
+                    seed, suppress_id, eos_id, pad_id, logprob, gamma, beta, eps)
 
 
 def constraint_words(V: int) -> int:
@@ -799,6 +825,11 @@ def _cons_args(seen, banned, rows, V):
     return ptr(seen), ptr(banned), ld_s or ld_b
 
 
+def _cons_tail(cons, rows, V):
+    """``cons`` = (seen, banned, penalty) -> the four trailing arguments of a _c LM head."""
+    return (*_cons_args(cons[0], cons[1], rows, V), float(cons[2]))
+
+
 def decode_constraints(prefix, ld, M, t, V, seen, banned, ngram=0, static_banned=None):
     """The two bit sets of the constrained LM heads for M rows (tmi_decode_constraints; the rule is include/tethys_mi.h's):
     ``seen[r]`` = the tokens in prefix[r, :t], ``banned[r]`` = ``static_banned`` plus the tokens that would complete an
@@ -820,24 +851,16 @@ def lm_head_argmax_c(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, seen=Non
     """``lm_head_argmax`` over the constrained logits z' (include/tethys_mi.h, "Decode constraints"): a column whose bit
     is set in ``banned[r]`` is -inf, one set in ``seen[r]`` is divided (z > 0) or multiplied (z <= 0) by ``penalty``.
     ``seen`` / ``banned``: int32 [M, >= constraint_words(V)] bit sets or None (empty); the workspace is lm_head_argmax's."""
-    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
-    with _probe("lm_head_argmax_c", float(d) * w_ld * w.element_size()):
-        check(lib().tmi_lm_head_argmax_c(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M,
-                                         d, V, ids.data_ptr(), ids_ld, eos_id, ptr(eos_count), workspace.data_ptr(),
-                                         workspace.numel() * workspace.element_size(), sp, bp, bits_ld, float(penalty),
-                                         stream()), "tmi_lm_head_argmax_c")
+    _lm_head_argmax((seen, banned, penalty), x, x_ld, w, w_ld, M, d, V, ids, ids_ld, workspace, gamma, beta, eps, eos_id,
+                    eos_count)
 
 
 def lm_head_topk_c(x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, seen=None, banned=None, penalty=1.0, gamma=None,
                    beta=None, eps=1e-5, temperature=1.0, lse=None):
     """``lm_head_topk`` over the constrained logits z' (as ``lm_head_argmax_c``): s = z' / temperature, the logsumexp over
     the columns that are not banned, a banned column's log-probability -inf; the workspace is lm_head_topk's."""
-    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
-    with _probe("lm_head_topk_c", float(d) * w_ld * w.element_size()):
-        check(lib().tmi_lm_head_topk_c(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d,
-                                       V, 1.0 / float(temperature), N, ids.data_ptr(), logprobs.data_ptr(), ptr(lse),
-                                       workspace.data_ptr(), workspace.numel() * workspace.element_size(), sp, bp, bits_ld,
-                                       float(penalty), stream()), "tmi_lm_head_topk_c")
+    _lm_head_topk((seen, banned, penalty), x, x_ld, w, w_ld, M, d, V, N, ids, logprobs, workspace, gamma, beta, eps,
+                  temperature, lse)
 
 
 def lm_head_sample_c(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace, seen=None, banned=None,
@@ -845,14 +868,8 @@ def lm_head_sample_c(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finishe
                      logprob=None, gamma=None, beta=None, eps=1e-5):
     """``lm_head_sample`` over the constrained logits z' (as ``lm_head_argmax_c``): a banned column is one more
     suppressed id and the candidates are ranked on z'; the workspace is lm_head_sample's."""
-    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
-    with _probe("lm_head_sample_c", float(d) * w_ld * w.element_size()):
-        check(lib().tmi_lm_head_sample_c(x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M,
-                                         d, V, float(temperature), int(top_k), float(top_p),
-                                         int(seed) & 0xFFFFFFFFFFFFFFFF, suppress_id, eos_id, pad_id, finished.data_ptr(),
-                                         ids.data_ptr(), ids_ld, ptr(logprob), n_finished.data_ptr(), workspace.data_ptr(),
-                                         workspace.numel() * workspace.element_size(), sp, bp, bits_ld, float(penalty),
-                                         stream()), "tmi_lm_head_sample_c")
+    _lm_head_sample((seen, banned, penalty), x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finished, workspace,
+                    temperature, top_k, top_p, seed, suppress_id, eos_id, pad_id, logprob, gamma, beta, eps)
 
 
 def beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping, pool_ids, pool_scores,

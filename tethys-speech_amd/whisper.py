@@ -1021,7 +1021,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
                  prompt_ids=None):
         """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.  ``num_beams`` of 2 to
         8: beam search (``_generate_beam``; the reference accepts num_beams at W:637 and leaves it as a ``pass`` at
-        W:696-698); None or 1: the greedy path below, unchanged.
+        W:696-698); None or 1: greedy (``_generate_greedy``).  Every mode runs the one step loop of ``_decode_steps``.
 
         As in the reference: the encoder runs once; every step runs the WHOLE decoder over the whole prefix (under the
         inverted mask of W:416-418 appending a token changes every earlier position's state from layer 1 up, so there is
@@ -1031,7 +1031,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
         head (W:675 reads a key WhisperModel does not return), ``max_length`` above max_target_positions raises up front
         instead of overrunning the positional table (W:383).  ``eos_token_id`` (not in the reference's signature):
         overrides config.eos_token_id; -1 disables the stop.  ``do_sample=True``: sampled decoding (``_generate_sample``),
-        the one mode in which temperature, top_k, top_p and min_length take effect; False: nothing below changes.
+        the one mode in which temperature, top_k, top_p and min_length take effect.
 
         Per step: the embedding of [start, tokens so far] (tmi_embed_fwd), the decoder over the prefix, and
         tmi_lm_head_argmax on the B last rows (final LayerNorm, LM head and argmax in one launch).  The EOS count of a step
@@ -1076,69 +1076,31 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 out = {"sequences": out}
             out.update(self.align(input_features, out["sequences"], out.get("lengths")))
             return out
+        beam = not do_sample and num_beams is not None and int(num_beams) > 1
         if do_sample:
             max_length, top_k, top_p, min_length = sample_args(cfg, max_length, num_beams, temperature, top_k, top_p, min_length)
-            eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
-            return self._generate_sample(input_features, max_length, float(temperature), top_k, top_p, min_length, eos,
-                                         int(seed), bool(return_dict_in_generate), cons)
-        if num_beams is not None and int(num_beams) > 1:  # (ahead of check_generate_args: it still raises for num_beams > 1)
+        elif beam:  # (ahead of check_generate_args: it still raises for num_beams > 1)
             max_length = check_beam_args(cfg, max_length, num_beams, temperature, length_penalty, num_return_sequences)
-            eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
-            return self._generate_beam(input_features, max_length, int(num_beams), float(temperature), eos,
-                                       float(length_penalty), bool(early_stopping), int(num_return_sequences),
-                                       bool(return_dict_in_generate), cons)
-        max_length = check_generate_args(cfg, max_length, num_beams, temperature)
-        features = self._check_features(input_features)
-        B = features.shape[0]
+        else:
+            max_length = check_generate_args(cfg, max_length, num_beams, temperature)
         eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
-        dev = self.device
-        if cons is not None:
-            return self._generate_greedy_c(features, max_length, eos, cons)
-        ids = torch.empty(B, 1 + max_length, dtype=torch.int32, device=dev)
-        if max_length == 0:
-            ids.fill_(cfg.decoder_start_token_id)
-            return ids
-        inf = self._infer_prepare(B, features.shape[2])
-        counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
-        host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
-        events = [torch.cuda.Event(), torch.cuda.Event()]
-        with self._inference(inf):
-            ws, d, T = self.ws, cfg.d_model, inf["T"]
-            ids[:, 0] = cfg.decoder_start_token_id
-            enc_out = self._encode_infer(features, inf)
-            self._cross_kv_infer(enc_out)
-            lab_flat = ws["labels"]
-            wl, ldw = self.W("lm_head.kernel")
-            gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
-            main = self._main or torch.cuda.current_stream(dev)
-            L1 = 1 + max_length
-
-            def step(t):
-                """Decoding step t (1-based): the prefix is columns [0, t) of ids, the token lands in column t."""
-                lab = lab_flat[:B * t].view(B, t)
-                if t > 1:
-                    lab[:, :t - 1].copy_(ids[:, 1:t])  # (index relayout only: the embedding shift reads rows of stride t)
-                h = self._decode_infer(lab, B, t, T)
-                col = ids[:, t:]
-                ops.lm_head_argmax(h[t - 1:], t * d, wl, ldw, B, d, cfg.vocab_size, col, L1, ws["argmax_ws"], gamma=gamma,
-                                   beta=beta, eps=cfg.layer_norm_eps, eos_id=eos, eos_count=counts[t:])
-                host[t:t + 1].copy_(counts[t:t + 1], non_blocking=True)
-                events[t & 1].record(main)
-
-            def read_eos(t):
-                events[t & 1].synchronize()
-                return int(host[t])
-
-            n = greedy_loop(max_length, B, step, read_eos if eos >= 0 else None)
-        torch.cuda.current_stream(dev).synchronize()
-        return ids[:, :1 + n].clone()
+        features = self._check_features(input_features)
+        if do_sample:
+            return self._generate_sample(features, max_length, float(temperature), top_k, top_p, min_length, eos, int(seed),
+                                         bool(return_dict_in_generate), cons)
+        if beam:
+            return self._generate_beam(features, max_length, int(num_beams), float(temperature), eos, float(length_penalty),
+                                       bool(early_stopping), int(num_return_sequences), bool(return_dict_in_generate), cons)
+        return self._generate_greedy(features, max_length, eos, cons)
 
     def _constraint_state(self, cons, rows: int, K: int = 1):
-        """The device side of ``cons`` (check_constraint_args) for ``rows`` decoded rows, K rows per batch item: the prompt
-        as int32 [rows, P] (or None), and ``apply(prefix, ld, t, first)`` -> the keyword arguments of the step's _c LM
-        head, after one tmi_decode_constraints launch on the rows' prefixes of length t (``first``: the first generated
-        step, where begin_suppress_tokens are banned too).  Without an active constraint (a prompt alone) ``apply`` is
-        None and the mode keeps its unconstrained LM head."""
+        """The device side of ``cons`` (check_constraint_args; None: nothing, -> (0, None, None)) for ``rows`` decoded rows, K
+        rows per batch item: the prompt's length P, the prompt as int32 [rows, P] (or None), and ``apply(prefix, ld, t,
+        first)`` -> the keyword arguments of the step's _c LM head, after one tmi_decode_constraints launch on the rows'
+        prefixes of length t (``first``: the first generated step, where begin_suppress_tokens are banned too).  Without an
+        active constraint (a prompt alone) ``apply`` is None and the mode keeps its unconstrained LM head."""
+        if cons is None:
+            return 0, None, None
         dev, V = self.device, self.config.vocab_size
         prompt = None
         if cons["P"]:
@@ -1149,7 +1111,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 raise ValueError(f"prompt_ids has {pr.shape[0]} rows for a batch of {rows // K}")
             prompt = pr.repeat_interleave(K, dim=0).contiguous()
         if not cons["active"]:
-            return prompt, None
+            return cons["P"], prompt, None
         W = ops.constraint_words(V)
         sets = torch.empty(2, rows, W, dtype=torch.int32, device=dev)
         words = lambda ids: torch.from_numpy(token_bitset(ids, V)).to(dev) if ids else None  # noqa: E731
@@ -1161,56 +1123,91 @@ class WhisperForConditionalGeneration(KernelBlocks):
                                    static_banned=static_first if first else static)
             return dict(seen=sets[0], banned=sets[1], penalty=penalty)
 
-        return prompt, apply
+        return cons["P"], prompt, apply
 
-    def _generate_greedy_c(self, features, max_length, eos, cons):
-        """Greedy decoding with decode constraints and / or a prompt (``generate``'s docstring): the greedy path with the
-        prompt behind the start token, one tmi_decode_constraints launch per step and tmi_lm_head_argmax_c as the choice.
-        Generated step s (1-based) reads the prefix columns [0, P + s) and writes column P + s.  -> ids [B, 1 + P + n]."""
+    def _decode_steps(self, features, K, P, max_length, eos, apply, prefix_of, heads, head, prepare=None, finish=None):
+        """The step loop every decoding mode shares -> n, the number of generated steps to keep (``greedy_loop``).
+
+        ``features`` [B, n_mels, T_in] as ``_check_features`` returns them; K decoder rows per item (beams; otherwise 1); P
+        prompt tokens behind the start token; ``max_length`` >= 1.  The encoder and the cross-attention k|v run once on the
+        B items (the k|v rows then repeated for the K rows of each item).  Generated step t = 1, 2, .. works on prefixes of
+        length tp = P + t and queues
+          - the relayout of ``prefix_of(t)``, the mode's int32 prefix rows [B*K, 1 + P + max_length] of that step, into the
+            decoder's labels, and the decoder over the tp positions;
+          - ``head(t, tp, cur, lm_head, shared, kw)``, the mode's own part.  It calls ``lm_head(*shared, <its own
+            arguments>, **kw)`` once: the LM head on the B*K last positions - ``heads[0]``, or behind the step's
+            tmi_decode_constraints launch on ``cur`` its _c form ``heads[1]`` when a constraint is active (``apply`` of
+            ``_constraint_state``; None, also for a prompt alone: heads[0]); ``shared`` and ``kw`` are the arguments
+            every head takes (the final LayerNorm's and the constraint's among them).  It queues whatever follows the
+            head, and returns the step's one-element device count (rows at EOS, rows finished, items done);
+          - the count's copy to pinned memory and an event.
+        The count is read one step late (``greedy_loop``), so the device never idles on the host's check, and the extra
+        queued step's column is dropped; ``eos`` < 0: never read.  ``prepare(inf)`` adds a mode's scratch to the inference
+        set before the scope opens; ``finish(n)`` queues what follows the last step inside it.  Ends synchronized."""
         cfg = self.config
-        B, dev, P = features.shape[0], self.device, cons["P"]
-        L1 = 1 + P + max_length
-        ids = torch.empty(B, L1, dtype=torch.int32, device=dev)
-        ids[:, 0] = cfg.decoder_start_token_id
-        prompt, apply = self._constraint_state(cons, B)
-        if P:
-            ids[:, 1:1 + P] = prompt
-        if max_length == 0:
-            return ids
-        inf = self._infer_prepare(B, features.shape[2])
-        counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
+        B, dev = features.shape[0], self.device
+        rows, L1 = B * K, 1 + P + max_length
+        inf = self._infer_prepare(B, features.shape[2], K)
+        if prepare is not None:
+            prepare(inf)
         host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
         events = [torch.cuda.Event(), torch.cuda.Event()]
         with self._inference(inf):
             ws, d, T, V = self.ws, cfg.d_model, inf["T"], cfg.vocab_size
             enc_out = self._encode_infer(features, inf)
             self._cross_kv_infer(enc_out)
+            if K > 1 and cfg.decoder_layers:
+                _repeat_rows_per_item(ws["kvc_all"].view(rows, T, -1), B, K)
             lab_flat = ws["labels"]
             wl, ldw = self.W("lm_head.kernel")
-            gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
+            ln = dict(gamma=self.arena.param("decoder.layer_norm.gamma"), beta=self.arena.param("decoder.layer_norm.beta"),
+                      eps=cfg.layer_norm_eps)
             main = self._main or torch.cuda.current_stream(dev)
+            lm_head = heads[0] if apply is None else heads[1]
 
-            def step(s):
-                t = P + s
-                lab = lab_flat[:B * t].view(B, t)
-                if t > 1:
-                    lab[:, :t - 1].copy_(ids[:, 1:t])
-                h = self._decode_infer(lab, B, t, T)
-                kw = dict(gamma=gamma, beta=beta, eps=cfg.layer_norm_eps, eos_id=eos, eos_count=counts[s:])
-                if apply is None:
-                    ops.lm_head_argmax(h[t - 1:], t * d, wl, ldw, B, d, V, ids[:, t:], L1, ws["argmax_ws"], **kw)
-                else:
-                    ops.lm_head_argmax_c(h[t - 1:], t * d, wl, ldw, B, d, V, ids[:, t:], L1, ws["argmax_ws"],
-                                         **apply(ids, L1, t, s == 1), **kw)
-                host[s:s + 1].copy_(counts[s:s + 1], non_blocking=True)
-                events[s & 1].record(main)
+            def step(t):
+                tp, cur = P + t, prefix_of(t)
+                lab = lab_flat[:rows * tp].view(rows, tp)
+                if tp > 1:
+                    lab[:, :tp - 1].copy_(cur[:, 1:tp])  # (index relayout only: the embedding shift reads rows of stride tp)
+                h = self._decode_infer(lab, rows, tp, T)
+                kw = ln if apply is None else dict(ln, **apply(cur, L1, tp, t == 1))
+                count = head(t, tp, cur, lm_head, (h[tp - 1:], tp * d, wl, ldw, rows, d, V), kw)
+                host[t:t + 1].copy_(count, non_blocking=True)
+                events[t & 1].record(main)
 
-            def read_eos(s):
-                events[s & 1].synchronize()
-                return int(host[s])
+            def read_count(t):
+                events[t & 1].synchronize()
+                return int(host[t])
 
-            n = greedy_loop(max_length, B, step, read_eos if eos >= 0 else None)
+            n = greedy_loop(max_length, B, step, read_count if eos >= 0 else None)
+            if finish is not None:
+                finish(n)
         torch.cuda.current_stream(dev).synchronize()
+        return n
+
+    def _generate_greedy(self, features, max_length, eos, cons):
+        """Greedy decoding (``generate``'s docstring) -> ids [B, 1 + P + n]: tmi_lm_head_argmax as the choice, the count of
+        rows at EOS as the stop.  Generated step t (1-based) reads the prefix columns [0, P + t) and writes column P + t.
+        ``cons`` (check_constraint_args; None: none): a prompt of P tokens behind the start token and / or decode
+        constraints - one tmi_decode_constraints launch per step and tmi_lm_head_argmax_c."""
+        B, dev = features.shape[0], self.device
+        P, prompt, apply = self._constraint_state(cons, B)
+        L1 = 1 + P + max_length
+        ids = torch.empty(B, L1, dtype=torch.int32, device=dev)
+        ids[:, 0] = self.config.decoder_start_token_id
+        if P:
+            ids[:, 1:1 + P] = prompt
+        if max_length == 0:
+            return ids
+        counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
+
+        def head(t, tp, cur, lm_head, shared, kw):
+            lm_head(*shared, ids[:, tp:], L1, self.ws["argmax_ws"], eos_id=eos, eos_count=counts[t:], **kw)
+            return counts[t:t + 1]
+
+        n = self._decode_steps(features, 1, P, max_length, eos, apply, lambda t: ids,
+                               (ops.lm_head_argmax, ops.lm_head_argmax_c), head)
         return ids[:, :1 + P + n].clone()
 
     def _generate_sample(self, features, max_length, temperature, top_k, top_p, min_length, eos, seed, return_dict,
@@ -1229,57 +1226,28 @@ class WhisperForConditionalGeneration(KernelBlocks):
         "lengths" counts the prompt too, everything else above (the step seeds, min_length, the log-probabilities) still
         counts generated tokens."""
         cfg = self.config
-        features = self._check_features(features)
         B, dev = features.shape[0], self.device
-        start, pad, V = cfg.decoder_start_token_id, cfg.pad_token_id, cfg.vocab_size
-        P = cons["P"] if cons is not None else 0
-        prompt, apply = self._constraint_state(cons, B) if cons is not None else (None, None)
-        ids = torch.empty(B, 1 + P + max_length, dtype=torch.int32, device=dev)
-        ids[:, 0] = start
+        P, prompt, apply = self._constraint_state(cons, B)
+        L1 = 1 + P + max_length
+        ids = torch.empty(B, L1, dtype=torch.int32, device=dev)
+        ids[:, 0] = cfg.decoder_start_token_id
         if P:
             ids[:, 1:1 + P] = prompt
         lps = torch.zeros(1 + max_length, B, device=dev)  # (a step's log-probabilities are one contiguous row)
         n = 0
         if max_length > 0:
-            inf = self._infer_prepare(B, features.shape[2])
-            self._sample_workspace(inf, B, top_k)
             finished = torch.zeros(B, dtype=torch.int32, device=dev)
             counts = torch.zeros(1 + max_length, dtype=torch.int32, device=dev)
-            host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
-            events = [torch.cuda.Event(), torch.cuda.Event()]
-            with self._inference(inf):
-                ws, d, T = self.ws, cfg.d_model, inf["T"]
-                enc_out = self._encode_infer(features, inf)
-                self._cross_kv_infer(enc_out)
-                lab_flat = ws["labels"]
-                wl, ldw = self.W("lm_head.kernel")
-                gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
-                main = self._main or torch.cuda.current_stream(dev)
-                L1 = 1 + P + max_length
 
-                def step(t):
-                    tp = P + t  # the prefix length: start token, prompt, t - 1 generated tokens
-                    lab = lab_flat[:B * tp].view(B, tp)
-                    if tp > 1:
-                        lab[:, :tp - 1].copy_(ids[:, 1:tp])
-                    h = self._decode_infer(lab, B, tp, T)
-                    head, kw = ops.lm_head_sample, {}
-                    if apply is not None:
-                        head, kw = ops.lm_head_sample_c, apply(ids, L1, tp, t == 1)
-                    head(h[tp - 1:], tp * d, wl, ldw, B, d, V, ids[:, tp:], L1, finished, counts[t:],
-                         ws["sample_ws"], temperature=temperature, top_k=top_k, top_p=top_p,
-                         seed=sample_step_seed(seed, t), suppress_id=eos if t <= min_length else -1,
-                         eos_id=eos, pad_id=pad, logprob=lps[t], gamma=gamma, beta=beta,
-                         eps=cfg.layer_norm_eps, **kw)
-                    host[t:t + 1].copy_(counts[t:t + 1], non_blocking=True)
-                    events[t & 1].record(main)
+            def head(t, tp, cur, lm_head, shared, kw):
+                lm_head(*shared, ids[:, tp:], L1, finished, counts[t:], self.ws["sample_ws"], temperature=temperature,
+                        top_k=top_k, top_p=top_p, seed=sample_step_seed(seed, t), suppress_id=eos if t <= min_length else -1,
+                        eos_id=eos, pad_id=cfg.pad_token_id, logprob=lps[t], **kw)
+                return counts[t:t + 1]
 
-                def read_finished(t):
-                    events[t & 1].synchronize()
-                    return int(host[t])
-
-                n = greedy_loop(max_length, B, step, read_finished if eos >= 0 else None)
-            torch.cuda.current_stream(dev).synchronize()
+            n = self._decode_steps(features, 1, P, max_length, eos, apply, lambda t: ids,
+                                   (ops.lm_head_sample, ops.lm_head_sample_c), head,
+                                   prepare=lambda inf: self._sample_workspace(inf, B, top_k))
         seq = ids[:, :1 + P + n].clone()
         if not return_dict:
             return seq
@@ -1302,12 +1270,11 @@ class WhisperForConditionalGeneration(KernelBlocks):
         lengths count the prompt too; with an active constraint the candidates come from tmi_lm_head_topk_c on the sets
         tmi_decode_constraints builds from the step's own prefix rows."""
         cfg = self.config
-        features = self._check_features(features)
         B, dev = features.shape[0], self.device
-        P = cons["P"] if cons is not None else 0
-        BK, N, L1, V = B * K, 2 * K, 1 + P + max_length, cfg.vocab_size
+        BK, N = B * K, 2 * K
+        P, prompt, apply = self._constraint_state(cons, BK, K)
+        L1 = 1 + P + max_length
         start, pad = cfg.decoder_start_token_id, cfg.pad_token_id
-        prompt, apply = self._constraint_state(cons, BK, K) if cons is not None else (None, None)
         if max_length == 0:
             seq = torch.full((B * R, 1 + P), start, dtype=torch.int32, device=dev)
             if P:
@@ -1316,7 +1283,6 @@ class WhisperForConditionalGeneration(KernelBlocks):
             if return_dict:
                 return {"sequences": seq, "sequences_scores": zeros, "lengths": torch.full((B * R,), P, dtype=torch.int32, device=dev)}
             return seq
-        inf = self._infer_prepare(B, features.shape[2], K)
         i32 = dict(dtype=torch.int32, device=dev)
         prefix = torch.full((2, BK, L1), start, **i32)  # double-buffered prefixes; every entry a valid token id
         if P:
@@ -1329,44 +1295,21 @@ class WhisperForConditionalGeneration(KernelBlocks):
         pool_len = torch.zeros(B, K, **i32)
         pool_cnt, done, n_done = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(1, **i32)
         cand_ids, cand_lp = torch.empty(BK, N, **i32), torch.empty(BK, N, device=dev)
-        host = torch.zeros(1 + max_length, dtype=torch.int32, pin_memory=True)
-        events = [torch.cuda.Event(), torch.cuda.Event()]
         len_pow = lambda n: float(np.float32(float(n) ** length_penalty))  # noqa: E731
-        with self._inference(inf):
-            ws, d, T = self.ws, cfg.d_model, inf["T"]
-            enc_out = self._encode_infer(features, inf)
-            self._cross_kv_infer(enc_out)
-            if cfg.decoder_layers:
-                _repeat_rows_per_item(ws["kvc_all"].view(BK, T, -1), B, K)
-            lab_flat = ws["labels"]
-            wl, ldw = self.W("lm_head.kernel")
-            gamma, beta = self.arena.param("decoder.layer_norm.gamma"), self.arena.param("decoder.layer_norm.beta")
-            main = self._main or torch.cuda.current_stream(dev)
+        pool = (pool_ids, pool_scores, pool_len, pool_cnt, done, n_done)
 
-            def step(t):
-                cur, nxt = prefix[t & 1], prefix[(t + 1) & 1]
-                tp = P + t  # the prefix length: start token, prompt, t - 1 generated tokens
-                lab = lab_flat[:BK * tp].view(BK, tp)
-                if tp > 1:
-                    lab[:, :tp - 1].copy_(cur[:, 1:tp])
-                h = self._decode_infer(lab, BK, tp, T)
-                head, kw = ops.lm_head_topk, {}
-                if apply is not None:
-                    head, kw = ops.lm_head_topk_c, apply(cur, L1, tp, t == 1)
-                head(h[tp - 1:], tp * d, wl, ldw, BK, d, V, N, cand_ids, cand_lp, ws["topk_ws"], gamma=gamma,
-                     beta=beta, eps=cfg.layer_norm_eps, temperature=temperature, **kw)
-                ops.beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, L1, tp, eos, len_pow(t), early_stopping, pool_ids,
-                              pool_scores, pool_len, pool_cnt, done, n_done)
-                host[t:t + 1].copy_(n_done, non_blocking=True)
-                events[t & 1].record(main)
+        def head(t, tp, cur, lm_head, shared, kw):
+            lm_head(*shared, N, cand_ids, cand_lp, self.ws["topk_ws"], temperature=temperature, **kw)
+            ops.beam_step(cand_ids, cand_lp, N, B, K, sums, cur, prefix[(t + 1) & 1], L1, tp, eos, len_pow(t), early_stopping,
+                          *pool)
+            return n_done
 
-            def read_done(t):
-                events[t & 1].synchronize()
-                return int(host[t])
-
-            n = greedy_loop(max_length, B, step, read_done if eos >= 0 else None)
+        def finalize(n):
             ops.beam_step(None, None, N, B, K, sums, prefix[(n + 1) & 1], None, L1, P + n, eos, len_pow(n), early_stopping,
-                          pool_ids, pool_scores, pool_len, pool_cnt, done, n_done, finalize=True)
+                          *pool, finalize=True)
+
+        self._decode_steps(features, K, P, max_length, eos, apply, lambda t: prefix[t & 1],
+                           (ops.lm_head_topk, ops.lm_head_topk_c), head, finish=finalize)
         lengths = pool_len[:, :R].reshape(B * R)
         n_out = int(lengths.max())
         seq = pool_ids[:, :R, :1 + n_out].reshape(B * R, 1 + n_out)
