@@ -493,6 +493,33 @@ int tmi_ctc_beam(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, con
                  int32_t K, int32_t* tokens, int32_t* lengths, float* scores, int32_t* n_beams, int64_t N, int64_t T_max,
                  void* workspace, int64_t workspace_bytes, void* stream);
 
+/* tmi_ctc_beam_lm.  tmi_ctc_beam with an n-gram language model and a length bonus in the ranking, applied while the search
+ * runs (shallow fusion): everything above holds - pb, pnb, the fold, the tie rule, the limits, the workspace - and this:
+ *   The table.  lm fp32, dense, row-major, V^lm_order entries, 1 <= lm_order <= 4, V^lm_order <= 2^24.  lm[ctx*V + c] is
+ *   log P(c | the previous lm_order - 1 tokens); ctx reads those tokens as base-V digits, the most recent one last.  A
+ *   context slot before the start of the sequence holds `blank` (never a token, so its index is free to mean "nothing
+ *   yet"): the start context is blank*(1 + V + ... + V^(lm_order-2)), and after an extension by c
+ *   ctx' = (ctx*V + c) mod V^(lm_order-1) - always 0 for lm_order 1.  Column `blank` is never read, nor a row with a blank
+ *   behind a non-blank.  Entries are finite or -inf; a -inf entry is a forbidden transition: that extension is no
+ *   candidate and is not folded.
+ *   The beam state.  Every beam carries g in fp32, 0 at the start state.  An extension of beam k by c gets
+ *   g' = g_k + fmaf(lm_alpha, lm[ctx_k*V + c], lm_beta) (one fma, one add; lm_alpha >= 0, both weights finite); a stay
+ *   candidate keeps g_k.  The fold adds CTC mass only: g is a function of the token sequence alone, computed by the same
+ *   operations in the same order whichever parent created the beam, so the beam that is folded into already holds
+ *   exactly the g the extension would have got.
+ *   Ranking.  A candidate ranks by LSE2(pb', pnb') + g (one fp32 add) where tmi_ctc_beam ranks by LSE2(pb', pnb'); a
+ *   candidate whose CTC score is -inf is never kept.
+ *   scores fp32 [N][K]  the final LSE2(pb, pnb) + g, descending; ctc_scores [N][K]  LSE2(pb, pnb); lm_scores [N][K]  g.
+ *   A rank past n_beams holds -inf, -inf and 0.
+ * Not built: an end-of-sequence term, word-level models, lexicons beyond -inf entries, backoff structures.
+ * TMI_ERR_INVALID (nothing is launched): what tmi_ctc_beam refuses; lm, ctc_scores or lm_scores NULL or not 4-byte
+ * aligned; lm_order outside 1..4; V^lm_order > 2^24; lm_alpha negative or not finite; lm_beta not finite.  The table's
+ * values are not checked on the device (Wav2Vec2's check_ctc_lm_args does it on the host). */
+int tmi_ctc_beam_lm(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* frame_lens, int32_t blank,
+                    int32_t K, const float* lm, int32_t lm_order, float lm_alpha, float lm_beta, int32_t* tokens,
+                    int32_t* lengths, float* scores, float* ctc_scores, float* lm_scores, int32_t* n_beams, int64_t N,
+                    int64_t T_max, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Decoder token embedding + positional encoding (W:405-408) with the teacher-forcing
  * shift of W:559-563 folded in: id(b,t) = t == 0 ? start_id : labels[b, t-1].

@@ -13,6 +13,11 @@ that spell the labels (``posteriors``: ``expected_frames``, ``center_time``), wh
 ``--num_beams K`` (2..16) decodes by CTC prefix beam search instead (``decode(num_beams=K)``): the line then carries the best
 sequence, its score ``sequence_score`` and, with ``--nbest R``, the R best sequences and scores under ``nbest``; the
 timestamps are those of the best sequence's forced alignment, and with labels the edit distance is the best sequence's.
+``--lm PATH.npy`` (with ``--num_beams``; ``--lm_alpha``, ``--lm_beta``) fuses an n-gram table of log-probabilities, shape
+[vocab_size] * order, into the search (``decode(lm=...)``): ``sequence_score`` is then the fused score, and the line and
+every ``nbest`` entry also carry ``ctc_score`` and ``lm_score``.  ``--build_lm LABELS_FILE --lm_order N --lm_out PATH.npy``
+builds such a table from a file of label lines (``wav2vec2.ngram_lm_table``, add-one smoothing), writes it and exits:
+no model is created and no GPU is needed.
 Prints one JSON line per clip: the token ids, with ``--timestamps`` their start and end times in seconds, the best path's
 log-probability, and with labels the nll, the edit distance of the transcript and the aligned times; then one summary line.
 There is no tokenizer: ids in, ids out.
@@ -51,9 +56,29 @@ def main(argv=None):
                         help="with --labels: each token's expected frames and centre time over all paths (forward-backward)")
     parser.add_argument("--num_beams", type=int, default=None, help="CTC prefix beam search with this many beams (2..16)")
     parser.add_argument("--nbest", type=int, default=1, help="with --num_beams: print this many sequences per clip")
+    parser.add_argument("--lm", default=None, help="with --num_beams: .npy n-gram table [vocab_size] * order fused into the search")
+    parser.add_argument("--lm_alpha", type=float, default=0.5, help="weight of the table's log-probabilities")
+    parser.add_argument("--lm_beta", type=float, default=0.0, help="bonus per token")
+    parser.add_argument("--build_lm", default=None, help="file of token ids, one line per sequence: build a table and exit")
+    parser.add_argument("--lm_order", type=int, default=2, help="with --build_lm: the order of the table (1..4)")
+    parser.add_argument("--lm_out", default=None, help="with --build_lm: where the .npy table goes")
     args = parser.parse_args(argv)
 
     import numpy as np
+    if args.build_lm:
+        if not args.lm_out:
+            raise SystemExit("--build_lm comes with --lm_out")
+        import tethys_speech_amd  # noqa: F401
+        from tethys_speech_amd import wav2vec2 as w2v
+        cfg = w2v.make_config(args.model_size, vocab_size=args.vocab_size)
+        rows = [[int(t) for t in line.split()] for line in open(args.build_lm).read().splitlines()]
+        width = max([len(r) for r in rows] + [1])
+        table = w2v.ngram_lm_table([r + [0] * (width - len(r)) for r in rows], [len(r) for r in rows], args.lm_order,
+                                   cfg.vocab_size, cfg.ctc_blank_id)
+        np.save(args.lm_out, table)
+        print(json.dumps({"lm": args.lm_out, "order": args.lm_order, "vocab_size": cfg.vocab_size, "sequences": len(rows),
+                          "tokens": sum(len(r) for r in rows)}), flush=True)
+        return
     import torch
     import tethys_speech_amd  # noqa: F401
     from tethys_speech_amd import train, wav2vec2, whisper
@@ -86,10 +111,13 @@ def main(argv=None):
     beam = args.num_beams is not None and args.num_beams > 1
     if args.nbest != 1 and not beam:
         raise SystemExit("--nbest comes with --num_beams >= 2")
+    if args.lm and not beam:
+        raise SystemExit("--lm comes with --num_beams >= 2")
+    lm_kw = dict(lm=np.load(args.lm), lm_alpha=args.lm_alpha, lm_beta=args.lm_beta) if args.lm else {}
     if beam:
         wav2vec2.check_ctc_beam_args(model.config, args.num_beams, args.nbest)
         dec = model.decode(audio, attention_mask=mask, num_beams=args.num_beams, num_return_sequences=args.nbest,
-                           return_timestamps=args.timestamps)
+                           return_timestamps=args.timestamps, **lm_kw)
     else:
         dec = model.decode(audio, attention_mask=mask)
     if args.posteriors and rows is None:
@@ -102,7 +130,7 @@ def main(argv=None):
             labels[i, :len(r)] = torch.tensor(r, dtype=torch.int64)
         lens = [len(r) for r in rows]
         ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True,
-                            num_beams=args.num_beams if beam else None)
+                            num_beams=args.num_beams if beam else None, **lm_kw)
         al = model.align(audio, labels, lens, attention_mask=mask)
         if args.posteriors:
             post = model.posteriors(audio, labels, lens, attention_mask=mask)
@@ -118,6 +146,11 @@ def main(argv=None):
             if args.nbest > 1:
                 line["nbest"] = [{"tokens": seqs[i, r, :int(lens_[i, r])].tolist(), "score": float(scores[i, r])}
                                  for r in range(min(args.nbest, int(dec["n_beams"][i])))]
+            if args.lm:
+                ctc, lms = (dec[n] if args.nbest > 1 else dec[n][:, None] for n in ("ctc_scores", "lm_scores"))
+                line.update(ctc_score=float(ctc[i, 0]), lm_score=float(lms[i, 0]))
+                for r, entry in enumerate(line.get("nbest", [])):
+                    entry.update(ctc_score=float(ctc[i, r]), lm_score=float(lms[i, r]))
         else:
             k = int(dec["lengths"][i])
             line = {"clip": name, "frames": frames[i], "tokens": dec["sequences"][i, :k].tolist(),

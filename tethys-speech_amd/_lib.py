@@ -183,6 +183,8 @@ SIGNATURES = {
     "tmi_ctc_beam_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "tmi_ctc_beam": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64,
                              c_vp]),
+    "tmi_ctc_beam_lm": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp,
+                                c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

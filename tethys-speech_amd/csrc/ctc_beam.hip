@@ -24,6 +24,14 @@
 //      never kept.  Wave r then loads rank r's record and stores its node (parent node, token) if the frame created it.
 //      The maxima are DPP row rotations and scalar reads, no LDS traffic.
 // After the last frame lane 0 of wave r walks rank r's chain back into tokens[n][r][len-1 .. 0].
+//
+// tmi_ctc_beam_lm is the same kernel with the compile-time flag LM set (tmi_ctc_beam is the instantiation without it: the
+// record, the loads and the arithmetic it had).  A beam then also carries g (the weighted LM terms of its tokens, summed in
+// token order) and ctx (its last order - 1 tokens as base-V digits, the row of the table its extensions read).  Lane c of
+// wave k loads lm[ctx V + c] at the top of the frame, before the shuffles and the fold search, so the one row per wave
+// (coalesced, L2 resident) is in flight while those run.  An extension whose entry is -inf is dropped before the fold
+// search; the others rank by v + (g + fmaf(alpha, entry, beta)), a stay candidate by its score + g.  A fold adds CTC mass
+// only: g is a function of the token sequence, so the beam folded into holds the g the extension would have got.
 #include "tmi_common.h"
 #include <math.h>
 
@@ -40,6 +48,24 @@ struct CbBeam {
   int last, len, node, par;
   uint32_t hash;
   int pad;
+};
+struct CbBeamLm {
+  float pb, pnb;
+  int last, len, node, par;
+  uint32_t hash;
+  int ctx;  // the last order - 1 tokens, base V, the most recent one last; blank where the sequence has not begun
+  float g;  // sum over the tokens of fmaf(alpha, lm entry, beta), in token order
+  int pad;
+};
+template <bool LM> struct CbRec { using type = CbBeam; };
+template <> struct CbRec<true> { using type = CbBeamLm; };
+
+// What the fused form takes besides tmi_ctc_beam's arguments; the plain instantiation never reads it.
+struct CbLmArgs {
+  const float* lm;
+  int ctx0, ctx_mod;  // the start context; V^(order-1)
+  float alpha, beta;
+  float *ctc_scores, *lm_scores;
 };
 
 __device__ __forceinline__ float cb_lse2(float a, float b) {
@@ -101,12 +127,15 @@ __device__ __forceinline__ bool cb_same(const int2* trie, int a, int b, int last
   return true;
 }
 
+template <bool LM>
 __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float* __restrict__ logp, int64_t lp_sn, int64_t lp_st,
                                                                     int V, const int32_t* __restrict__ frame_lens, int blank,
                                                                     int K, int32_t* __restrict__ tokens,
                                                                     int32_t* __restrict__ lengths, float* __restrict__ scores,
-                                                                    int32_t* __restrict__ n_beams, int T_max, int2* trie_ws) {
-  __shared__ CbBeam s_beam[2][CB_KMAX];
+                                                                    int32_t* __restrict__ n_beams, int T_max, int2* trie_ws,
+                                                                    CbLmArgs la) {
+  using Rec = typename CbRec<LM>::type;
+  __shared__ Rec s_beam[2][CB_KMAX];
   __shared__ float s_fold[CB_KMAX];
   __shared__ uint64_t s_head[2][CB_KMAX];
   const int n = blockIdx.x;
@@ -121,7 +150,14 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
   float pb = 0.f, pnb = -INFINITY;
   int last = -1, len = 0, node = 0, par = 0, nb = 1;
   uint32_t hash = 0u;
-  if (threadIdx.x == 0) s_beam[0][0] = CbBeam{pb, pnb, last, len, node, par, hash, 0};
+  int ctx = 0;
+  float g = 0.f;
+  if constexpr (LM) {
+    ctx = la.ctx0;
+    if (threadIdx.x == 0) s_beam[0][0] = Rec{pb, pnb, last, len, node, par, hash, ctx, g, 0};
+  } else {
+    if (threadIdx.x == 0) s_beam[0][0] = Rec{pb, pnb, last, len, node, par, hash, 0};
+  }
   if (threadIdx.x < CB_KMAX) s_fold[threadIdx.x] = -INFINITY;
   __syncthreads();
 
@@ -140,22 +176,26 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
       if (t >= T) break;  // (uniform)
       const int rd = t & 1, wr = rd ^ 1;
       const bool live = k < nb;
+      const bool ext = c != blank;
+      float lmv = 0.f;
+      if constexpr (LM) {
+        if (live && sym && ext) lmv = la.lm[ctx * V + c];  // (ctx < V^(order-1): inside the table)
+      }
       const float lpc = cur[j];
       const float lp_blank = __shfl(lpc, blank, 64);
       const float lp_e = __shfl(lpc, len > 0 ? last : 0, 64);
       const float tot = cb_lse2(pb, pnb);
       float n_pb = -INFINITY, n_pnb = -INFINITY, sc = -INFINITY;
-      const bool ext = c != blank;
       const uint32_t h_ext = hash * CB_MUL + (uint32_t)c + 1u;
       if (live && sym) {
         if (!ext) {
           n_pb = lp_blank + tot;
           n_pnb = len > 0 ? lp_e + pnb : -INFINITY;
-        } else {
+        } else if (!LM || lmv != -INFINITY) {  // (a -inf entry: no candidate, nothing folded)
           const float v = lpc + ((len > 0 && c == last) ? pb : tot);
           int tgt = -1;
           for (int p = 0; p < nb; ++p) {
-            const CbBeam& b = s_beam[rd][p];
+            const Rec& b = s_beam[rd][p];
             if (b.last == c && b.len == len + 1 && b.hash == h_ext && cb_same(trie, b.par, node, last, par)) {
               tgt = p;
               break;
@@ -178,6 +218,11 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
         }
         sc = cb_lse2(n_pb, n_pnb);
       }
+      float g_c = g;
+      if constexpr (LM) {
+        if (ext) g_c = g + fmaf(la.alpha, lmv, la.beta);
+        sc = sc == -INFINITY ? sc : sc + g_c;  // (the rank; the CTC score itself stays in n_pb, n_pnb)
+      }
       uint64_t key = cb_key(sc, ((ext ? 1u : 0u) << 10) | ((uint32_t)k << 6) | (uint32_t)c);
       uint64_t best = cb_wave_max(key);
       if (c == 0) s_head[0][k] = best;
@@ -190,8 +235,13 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
         const uint32_t code = 0xFFFFFFFFu - (uint32_t)w;
         if ((int)((code >> 6) & 15u) == k) {  // (uniform over the wave)
           if ((int)(code & 63u) == c) {
-            s_beam[wr][r] = ext ? CbBeam{n_pb, n_pnb, c, len + 1, 1 + t * K + r, node, h_ext, 0}
-                                : CbBeam{n_pb, n_pnb, last, len, node, par, hash, 0};
+            if constexpr (LM) {
+              s_beam[wr][r] = ext ? Rec{n_pb, n_pnb, c, len + 1, 1 + t * K + r, node, h_ext, (ctx * V + c) % la.ctx_mod, g_c, 0}
+                                  : Rec{n_pb, n_pnb, last, len, node, par, hash, ctx, g, 0};
+            } else {
+              s_beam[wr][r] = ext ? Rec{n_pb, n_pnb, c, len + 1, 1 + t * K + r, node, h_ext, 0}
+                                  : Rec{n_pb, n_pnb, last, len, node, par, hash, 0};
+            }
             key = 0ull;
           }
           best = cb_wave_max(key);
@@ -202,8 +252,9 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
       }
       nb = nb_new;
       if (k < nb) {
-        const CbBeam& b = s_beam[wr][k];
+        const Rec& b = s_beam[wr][k];
         pb = b.pb, pnb = b.pnb, last = b.last, len = b.len, node = b.node, par = b.par, hash = b.hash;
+        if constexpr (LM) ctx = b.ctx, g = b.g;
         if (c == 0 && node == 1 + t * K + k) trie[node - 1] = make_int2(par, last);  // created in this frame
       }
     }
@@ -216,7 +267,14 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
     const int64_t o = (int64_t)n * K + k;
     if (k < nb) {
       lengths[o] = len;
-      scores[o] = cb_lse2(pb, pnb);
+      const float ctc = cb_lse2(pb, pnb);
+      if constexpr (LM) {
+        scores[o] = ctc + g;
+        la.ctc_scores[o] = ctc;
+        la.lm_scores[o] = g;
+      } else {
+        scores[o] = ctc;
+      }
       int32_t* row = tokens + o * T_max;
       int a = node;
       for (int pos = len - 1; pos >= 0 && a >= 1; --pos) {
@@ -227,6 +285,10 @@ __global__ __launch_bounds__(CB_KMAX* TMI_WAVE) void ctc_beam_kernel(const float
     } else {
       lengths[o] = 0;
       scores[o] = -INFINITY;
+      if constexpr (LM) {
+        la.ctc_scores[o] = -INFINITY;
+        la.lm_scores[o] = 0.f;
+      }
     }
     if (k == 0) n_beams[n] = nb;
   }
@@ -239,23 +301,30 @@ extern "C" int64_t tmi_ctc_beam_workspace_bytes(int64_t N, int64_t K, int64_t T_
   return N * K * T_max * (int64_t)sizeof(int2);
 }
 
+static bool cb_bad_args(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* frame_lens, int32_t blank,
+                        int32_t K, int32_t* tokens, int32_t* lengths, float* scores, int32_t* n_beams, int64_t N, int64_t T_max,
+                        void* workspace, int64_t workspace_bytes) {
+  const int64_t need = tmi_ctc_beam_workspace_bytes(N, K, T_max);
+  return !logp || !frame_lens || !tokens || !lengths || !scores || !n_beams || !workspace || !tmi_aligned(logp, 4) ||
+         !tmi_aligned(frame_lens, 4) || !tmi_aligned(tokens, 4) || !tmi_aligned(lengths, 4) || !tmi_aligned(scores, 4) ||
+         !tmi_aligned(n_beams, 4) || !tmi_aligned(workspace, 8) || need < 0 || workspace_bytes < need || V < 2 || V > CB_VMAX ||
+         lp_st < V || lp_st > ((int64_t)1 << 30) || lp_sn < T_max * lp_st || blank < 0 || blank >= V;
+}
+
 static int tmi_ctc_beam_impl(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* frame_lens,
                              int32_t blank, int32_t K, int32_t* tokens, int32_t* lengths, float* scores, int32_t* n_beams,
                              int64_t N, int64_t T_max, void* workspace, int64_t workspace_bytes, void* stream) {
-  const int64_t need = tmi_ctc_beam_workspace_bytes(N, K, T_max);
-  if (!logp || !frame_lens || !tokens || !lengths || !scores || !n_beams || !workspace || !tmi_aligned(logp, 4) ||
-      !tmi_aligned(frame_lens, 4) || !tmi_aligned(tokens, 4) || !tmi_aligned(lengths, 4) || !tmi_aligned(scores, 4) || !tmi_aligned(n_beams, 4) ||
-      !tmi_aligned(workspace, 8) || need < 0 || workspace_bytes < need || V < 2 || V > CB_VMAX || lp_st < V ||
-      lp_st > ((int64_t)1 << 30) || lp_sn < T_max * lp_st || blank < 0 || blank >= V) {
+  if (cb_bad_args(logp, lp_sn, lp_st, V, frame_lens, blank, K, tokens, lengths, scores, n_beams, N, T_max, workspace,
+                  workspace_bytes)) {
     tmi_set_error("tmi_ctc_beam: bad argument (non-NULL 4-byte aligned pointers, the workspace 8-byte aligned; 1 <= N <= 65535 "
                   "items, one workgroup each; 1 <= K <= 16 beams, one wave each; 2 <= V <= 64 symbols, one lane each; "
                   "1 <= T_max <= 65536 frames; V <= lp_st <= 2^30, lp_sn >= T_max lp_st; 0 <= blank < V; workspace of "
                   "tmi_ctc_beam_workspace_bytes)");
     return TMI_ERR_INVALID;
   }
-  hipLaunchKernelGGL(ctc_beam_kernel, dim3((unsigned)N), dim3((unsigned)K * TMI_WAVE), 0, reinterpret_cast<hipStream_t>(stream),
-                     logp, lp_sn, lp_st, (int)V, frame_lens, (int)blank, (int)K, tokens, lengths, scores, n_beams, (int)T_max,
-                     reinterpret_cast<int2*>(workspace));
+  hipLaunchKernelGGL(ctc_beam_kernel<false>, dim3((unsigned)N), dim3((unsigned)K * TMI_WAVE), 0,
+                     reinterpret_cast<hipStream_t>(stream), logp, lp_sn, lp_st, (int)V, frame_lens, (int)blank, (int)K, tokens,
+                     lengths, scores, n_beams, (int)T_max, reinterpret_cast<int2*>(workspace), CbLmArgs{});
   return tmi_check_launch("tmi_ctc_beam");
 }
 
@@ -264,4 +333,44 @@ extern "C" int tmi_ctc_beam(const float* logp, int64_t lp_sn, int64_t lp_st, int
                             int64_t T_max, void* workspace, int64_t workspace_bytes, void* stream) {
   return tmi_plan_run<tmi_ctc_beam_impl>(logp, lp_sn, lp_st, V, frame_lens, blank, K, tokens, lengths, scores, n_beams, N, T_max,
                                          workspace, workspace_bytes, stream);
+}
+
+static int tmi_ctc_beam_lm_impl(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* frame_lens,
+                                int32_t blank, int32_t K, const float* lm, int32_t lm_order, float lm_alpha, float lm_beta,
+                                int32_t* tokens, int32_t* lengths, float* scores, float* ctc_scores, float* lm_scores,
+                                int32_t* n_beams, int64_t N, int64_t T_max, void* workspace, int64_t workspace_bytes,
+                                void* stream) {
+  bool bad = cb_bad_args(logp, lp_sn, lp_st, V, frame_lens, blank, K, tokens, lengths, scores, n_beams, N, T_max, workspace,
+                         workspace_bytes) ||
+             !lm || !ctc_scores || !lm_scores || !tmi_aligned(lm, 4) || !tmi_aligned(ctc_scores, 4) ||
+             !tmi_aligned(lm_scores, 4) || lm_order < 1 || lm_order > 4 || !isfinite(lm_alpha) || lm_alpha < 0.f ||
+             !isfinite(lm_beta);
+  int64_t ctx_mod = 1, ctx0 = 0;  // V^(order-1); blank (1 + V + ... + V^(order-2))
+  if (!bad) {
+    for (int i = 1; i < lm_order; ++i) {
+      ctx0 = ctx0 * V + blank;
+      ctx_mod *= V;
+    }
+    bad = ctx_mod * V > ((int64_t)1 << 24);
+  }
+  if (bad) {
+    tmi_set_error("tmi_ctc_beam_lm: bad argument (tmi_ctc_beam's limits; lm, ctc_scores and lm_scores non-NULL and 4-byte "
+                  "aligned; 1 <= lm_order <= 4 with V^lm_order <= 2^24 table entries; lm_alpha >= 0 and lm_beta finite)");
+    return TMI_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(ctc_beam_kernel<true>, dim3((unsigned)N), dim3((unsigned)K * TMI_WAVE), 0,
+                     reinterpret_cast<hipStream_t>(stream), logp, lp_sn, lp_st, (int)V, frame_lens, (int)blank, (int)K, tokens,
+                     lengths, scores, n_beams, (int)T_max, reinterpret_cast<int2*>(workspace),
+                     CbLmArgs{lm, (int)ctx0, (int)ctx_mod, lm_alpha, lm_beta, ctc_scores, lm_scores});
+  return tmi_check_launch("tmi_ctc_beam_lm");
+}
+
+extern "C" int tmi_ctc_beam_lm(const float* logp, int64_t lp_sn, int64_t lp_st, int64_t V, const int32_t* frame_lens,
+                               int32_t blank, int32_t K, const float* lm, int32_t lm_order, float lm_alpha, float lm_beta,
+                               int32_t* tokens, int32_t* lengths, float* scores, float* ctc_scores, float* lm_scores,
+                               int32_t* n_beams, int64_t N, int64_t T_max, void* workspace, int64_t workspace_bytes,
+                               void* stream) {
+  return tmi_plan_run<tmi_ctc_beam_lm_impl>(logp, lp_sn, lp_st, V, frame_lens, blank, K, lm, lm_order, lm_alpha, lm_beta, tokens,
+                                            lengths, scores, ctc_scores, lm_scores, n_beams, N, T_max, workspace,
+                                            workspace_bytes, stream);
 }

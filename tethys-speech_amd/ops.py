@@ -623,6 +623,31 @@ def ctc_beam(logp, frame_lens, blank, K, tokens, lengths, scores, n_beams, works
                                  workspace.data_ptr(), workspace.numel() * 4, stream()), "tmi_ctc_beam")
 
 
+def ctc_beam_lm(logp, frame_lens, blank, K, lm, lm_order, lm_alpha, lm_beta, tokens, lengths, scores, ctc_scores, lm_scores,
+                n_beams, workspace):
+    """``ctc_beam`` with an n-gram table in the ranking (tmi_ctc_beam_lm in include/tethys_mi.h): ``lm`` fp32, contiguous,
+    V^lm_order entries on the device (finite or -inf: ``wav2vec2.check_ctc_lm_args``), 1 <= lm_order <= 4; ``scores`` the
+    fused score, ``ctc_scores`` and ``lm_scores`` fp32 [N, K] its two terms."""
+    N, T, V = _ctc_logp(logp, "ctc_beam_lm")
+    K, lm_order = int(K), int(lm_order)
+    if not 1 <= lm_order <= 4 or V ** lm_order > 1 << 24:
+        raise ValueError(f"ctc_beam_lm: 1 <= lm_order <= 4 and V^lm_order <= 2^24, got order {lm_order} at V = {V}")
+    for t, n, w in ((frame_lens, N, "frame_lens"), (tokens, N * K * T, "tokens"), (lengths, N * K, "lengths"),
+                    (n_beams, N, "n_beams"), (workspace, ctc_beam_workspace_elems(N, K, T), "workspace")):
+        _i32_dev(t, n, "ctc_beam_lm: " + w)
+    for t, n, w in ((scores, N * K, "scores"), (ctc_scores, N * K, "ctc_scores"), (lm_scores, N * K, "lm_scores"),
+                    (lm, V ** lm_order, "lm")):
+        _f32_flat(t, n, "ctc_beam_lm: " + w)
+    if lm.device != logp.device:
+        raise ValueError("ctc_beam_lm: lm must be on the device of logp")
+    with _probe("ctc_beam_lm", 4.0 * N * T * V):
+        check(lib().tmi_ctc_beam_lm(logp.data_ptr(), logp.stride(0), logp.stride(1), V, frame_lens.data_ptr(), int(blank), K,
+                                    lm.data_ptr(), lm_order, float(lm_alpha), float(lm_beta), tokens.data_ptr(),
+                                    lengths.data_ptr(), scores.data_ptr(), ctc_scores.data_ptr(), lm_scores.data_ptr(),
+                                    n_beams.data_ptr(), N, T, workspace.data_ptr(), workspace.numel() * 4, stream()),
+              "tmi_ctc_beam_lm")
+
+
 def masked_mean_pool(x, mask, out, B, T, C):
     """out[b, c] = sum_t x[b, t, c] mask[b, t] / sum_t mask[b, t] (fp32 [B, C]); ``mask`` fp32 [B, T] or None: the plain mean."""
     if not x.is_contiguous() or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != B * C or x.numel() != B * T * C:

@@ -1107,6 +1107,80 @@ def check_ctc_beam_args(cfg: Wav2Vec2Config, num_beams=None, num_return_sequence
     return int(K), int(num_return_sequences)
 
 
+CTC_LM_MAX_ORDER = 4          # tmi_ctc_beam_lm: a dense table of V^order entries ...
+CTC_LM_MAX_ENTRIES = 1 << 24  # ... of at most this many
+
+
+def check_ctc_lm_args(cfg: Wav2Vec2Config, lm, lm_alpha=0.5, lm_beta=0.0, num_beams=None):
+    """Host validation of the language-model arguments of ``Wav2Vec2ForCTC.decode`` / ``evaluate`` (no GPU needed; the
+    kernel cannot check the table's values).  ``lm`` None (then nothing else is looked at), or a float tensor or array of
+    shape [V] * order, or flat with V^order entries, 1 <= order <= 4 and V^order <= 2^24: ``lm[..., c]`` is log P(c | the
+    previous order - 1 tokens), most recent last, ``ctc_blank_id`` in a context slot before the sequence's start (tmi_ctc_beam_lm in
+    include/tethys_mi.h).  Entries finite or -inf (a forbidden transition), never NaN or +inf; ``lm_alpha`` >= 0 and
+    ``lm_beta`` finite numbers; a table comes with ``num_beams`` >= 2 - the greedy path has no ranking to fuse it into.
+    -> None, or (the table as a contiguous float32 CPU tensor [V^order], order, alpha, beta)."""
+    if lm is None:
+        return None
+    K, _ = check_ctc_beam_args(cfg, num_beams)
+    if K < 2:
+        raise ValueError("lm comes with num_beams >= 2: greedy decoding has no ranking to fuse a language model into")
+    V = cfg.vocab_size
+    table = torch.as_tensor(lm).detach().to("cpu")
+    if not table.dtype.is_floating_point:
+        raise ValueError("lm must be a float tensor or array")
+    n = table.numel()
+    if table.dim() == 1:
+        order = next((o for o in range(1, CTC_LM_MAX_ORDER + 1) if V ** o == n), None)
+    else:
+        order = table.dim() if all(int(s) == V for s in table.shape) else None
+    if order is None or not 1 <= order <= CTC_LM_MAX_ORDER or V ** order > CTC_LM_MAX_ENTRIES:
+        raise ValueError(f"lm must have shape [V] * order or V^order entries flat, V = {V}, 1 <= order <= {CTC_LM_MAX_ORDER}, "
+                         f"V^order <= 2^24; got {list(table.shape)}")
+    table = table.to(torch.float32).contiguous().view(-1)
+    if bool(torch.isnan(table).any()) or bool((table == math.inf).any()):
+        raise ValueError("lm entries must be finite or -inf (a forbidden transition), never NaN or +inf")
+    for name, v in (("lm_alpha", lm_alpha), ("lm_beta", lm_beta)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not abs(float(v)) <= float(np.finfo(np.float32).max):
+            raise ValueError(f"{name} must be a finite number (in float32)")
+    if float(lm_alpha) < 0:
+        raise ValueError("lm_alpha must be >= 0")
+    return table, order, float(lm_alpha), float(lm_beta)
+
+
+def ngram_lm_table(sequences, lengths, order, vocab_size, blank, add_k=1.0):
+    """A dense n-gram table for ``decode(lm=...)`` from label sequences: ``sequences`` integer [N, L_max] (or a list of
+    rows), ``lengths`` N integers.  Every token of every sequence counts once in the row of its ``order - 1`` predecessors,
+    slots before the sequence's start holding ``blank``; counts in float64, then add-k smoothing over the non-blank
+    columns: P(c | ctx) = (n(ctx, c) + add_k) / (n(ctx) + add_k (V - 1)), so every row sums to 1 over them (a row
+    without counts is uniform; with add_k = 0 an unseen transition is -inf, and so is a whole row that was never seen).
+    Column ``blank`` holds -inf.  -> float32 numpy [V] * order of log-probabilities."""
+    V, order = int(vocab_size), int(order)
+    if not 2 <= V <= 64 or not 0 <= blank < V or not 1 <= order <= CTC_LM_MAX_ORDER or V ** order > CTC_LM_MAX_ENTRIES:
+        raise ValueError("ngram_lm_table: 2 <= vocab_size <= 64, blank inside it, 1 <= order <= 4, V^order <= 2^24")
+    if not add_k >= 0 or not math.isfinite(add_k):
+        raise ValueError("ngram_lm_table: add_k must be finite and >= 0")
+    lengths = [int(n) for n in lengths]
+    if len(lengths) != len(sequences):
+        raise ValueError("ngram_lm_table: one length per sequence")
+    mod = V ** (order - 1)
+    counts = np.zeros((mod, V), dtype=np.float64)
+    for row, n in zip(sequences, lengths):
+        row = [int(t) for t in list(row)[:n]]
+        if len(row) != n or n < 0 or any(not 0 <= t < V or t == blank for t in row):
+            raise ValueError("ngram_lm_table: tokens must be in [0, vocab_size) and not the blank inside their length")
+        ctx = blank * sum(V ** i for i in range(order - 1))
+        for t in row:
+            counts[ctx, t] += 1.0
+            ctx = (ctx * V + t) % mod
+    cols = np.arange(V) != blank
+    num = counts + add_k
+    den = counts[:, cols].sum(axis=1, keepdims=True) + add_k * (V - 1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        table = np.where(den > 0, np.log(num) - np.log(den), -np.inf)
+    table[:, blank] = -np.inf
+    return table.astype(np.float32).reshape((V,) * order)
+
+
 def edit_distance(hyp: np.ndarray, ref: np.ndarray) -> int:
     """Levenshtein distance of two integer sequences, one row of the table per hypothesis token, each row in numpy:
     d[j] = min(up + 1, diagonal + (h != r_j), d[j-1] + 1), the last term as a running minimum of d[j] - j."""
@@ -1213,14 +1287,22 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
     def _times(self, frames):
         return torch.where(frames >= 0, frames.to(torch.float64) * frame_seconds(self.config), -1.0)
 
-    def _beam(self, c, K):
-        """tmi_ctc_beam on the pass's log-probs -> tokens [B, K, T] (-1 past a length), len [B, K], scores [B, K], n [B]."""
+    def _beam(self, c, K, lm=None):
+        """tmi_ctc_beam on the pass's log-probs -> tokens [B, K, T] (-1 past a length), len [B, K], scores [B, K], n [B].
+        ``lm`` (what ``check_ctc_lm_args`` returned): tmi_ctc_beam_lm instead, the table moved to the device here, once per
+        call; ``scores`` is then the fused score, and ``ctc`` / ``lm`` [B, K] are its two terms."""
         B, T = c["B"], c["T"]
         out = {"tokens": torch.full((B, K, T), -1, **c["i32"]), "len": torch.zeros((B, K), **c["i32"]),
                "scores": torch.full((B, K), -math.inf, **c["f32"]), "n": torch.zeros(B, **c["i32"])}
         wsp = torch.empty(ops.ctc_beam_workspace_elems(B, K, T), **c["i32"])
-        ops.ctc_beam(c["logp"], c["frame_lens"], self.config.ctc_blank_id, K, out["tokens"], out["len"], out["scores"],
-                     out["n"], wsp)
+        if lm is None:
+            ops.ctc_beam(c["logp"], c["frame_lens"], self.config.ctc_blank_id, K, out["tokens"], out["len"], out["scores"],
+                         out["n"], wsp)
+            return out
+        table, order, alpha, beta = lm
+        out["ctc"], out["lm"] = torch.full((B, K), -math.inf, **c["f32"]), torch.zeros((B, K), **c["f32"])
+        ops.ctc_beam_lm(c["logp"], c["frame_lens"], self.config.ctc_blank_id, K, table.to(self.device), order, alpha, beta,
+                        out["tokens"], out["len"], out["scores"], out["ctc"], out["lm"], out["n"], wsp)
         return out
 
     def _check_beam_frames(self, inputs, what):
@@ -1230,7 +1312,8 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                 raise ValueError(f"{what} with num_beams takes at most {CTC_MAX_FRAMES} frames, got {T}")
 
     @torch.no_grad()
-    def decode(self, inputs, attention_mask=None, num_beams=None, num_return_sequences=1, return_timestamps=False):
+    def decode(self, inputs, attention_mask=None, num_beams=None, num_return_sequences=1, return_timestamps=False,
+               lm=None, lm_alpha=0.5, lm_beta=0.0):
         """Greedy CTC decoding: per frame the most probable symbol, runs of equal symbols collapsed, blanks dropped
         (tmi_ctc_greedy).  -> ``sequences`` int32 [B, max length] padded with -1, ``lengths`` int32 [B],
         ``token_start_frames`` / ``token_end_frames`` int32 (the first frame of a token's run and its last plus 1; -1 in the
@@ -1244,10 +1327,20 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         ranks the search filled, of num_beams); R == 1 drops the rank dimension.  ``return_timestamps`` adds
         ``token_start_frames`` / ``token_end_frames`` int32 [B, max best length] and the times of the BEST sequence of each
         item: its forced alignment (tmi_ctc_viterbi on the same log-probs, the labels never leave the device).  At most
-        4096 frames; timestamps take a best sequence of at most 511 tokens.  ``num_beams`` None or 1 is the greedy path."""
+        4096 frames; timestamps take a best sequence of at most 511 tokens.  ``num_beams`` None or 1 is the greedy path.
+
+        ``lm`` (with ``num_beams`` >= 2; see ``check_ctc_lm_args``, ``ngram_lm_table`` builds one): an n-gram table of
+        log-probabilities fused into the ranking WHILE the search runs (tmi_ctc_beam_lm in include/tethys_mi.h), which
+        rescoring an n-best list cannot do - a prefix the model prefers is pruned by then.  A beam ranks by its CTC
+        log-probability + ``lm_alpha`` x the table's log-probabilities of its tokens + ``lm_beta`` x its length; -inf
+        entries forbid a transition.  ``sequences_scores`` is then this fused score and the result adds ``ctc_scores`` and
+        ``lm_scores``, its two terms, shaped like it; timestamps are those of the fused search's best sequence.  Not built:
+        an end-of-sequence term, word-level models, lexicons beyond -inf entries, backoff structures.  ``lm`` None is the
+        search without a model: the same kernel and launches as before."""
         K, R = check_ctc_beam_args(self.config, num_beams, num_return_sequences)
+        lm = check_ctc_lm_args(self.config, lm, lm_alpha, lm_beta, num_beams)
         if K > 1:
-            return self._decode_beam(inputs, attention_mask, K, R, return_timestamps)
+            return self._decode_beam(inputs, attention_mask, K, R, return_timestamps, lm)
         with self._ctc_pass(inputs, attention_mask=attention_mask) as c:
             g = self._greedy(c)
             n = max(int(g["len"].max()), 0)  # (the one host read: the width of the result)
@@ -1256,16 +1349,20 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                     "token_end_frames": en, "token_start_times": self._times(st), "token_end_times": self._times(en),
                     "best_path_logprob": g["best"]}
 
-    def _decode_beam(self, inputs, attention_mask, K, R, return_timestamps):
+    def _decode_beam(self, inputs, attention_mask, K, R, return_timestamps, lm=None):
         self._check_beam_frames(inputs, "decode")
         with self._ctc_pass(inputs, attention_mask=attention_mask) as c:
             B, T = c["B"], c["T"]
-            bm = self._beam(c, K)
+            bm = self._beam(c, K, lm)
             n = max(int(bm["len"][:, :R].max()), 0)  # (the one host read: the width of the result)
             seqs, lens, scores = bm["tokens"][:, :R, :n].clone(), bm["len"][:, :R].clone(), bm["scores"][:, :R].clone()
             if R == 1:
                 seqs, lens, scores = seqs[:, 0], lens[:, 0], scores[:, 0]
             result = {"sequences": seqs, "lengths": lens, "sequences_scores": scores, "n_beams": bm["n"]}
+            if lm is not None:
+                for name, key in (("ctc_scores", "ctc"), ("lm_scores", "lm")):
+                    part = bm[key][:, :R].clone()
+                    result[name] = part[:, 0] if R == 1 else part
             if return_timestamps:
                 nb = max(int(bm["len"][:, 0].max()), 0)
                 if nb > CTC_MAX_LABELS:
@@ -1283,7 +1380,8 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             return result
 
     @torch.no_grad()
-    def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False, num_beams=None):
+    def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False, num_beams=None,
+                 lm=None, lm_alpha=0.5, lm_beta=0.0):
         """The CTC loss of one batch and the error rate of its greedy transcript, forward only.  ``labels`` integer
         [B, L_max] with ``label_lengths`` [B] (see ``check_ctc_args``).  Returns Python numbers, float64 on the host, so
         that shards add up: ``nll_sum`` over the feasible items, ``n_items``, ``n_infeasible`` (items with fewer frames than
@@ -1294,9 +1392,11 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         tensors ``nll`` fp32 [B] (+inf where infeasible, whatever ``ctc_zero_infinity``), ``infeasible`` int32 [B],
         ``sequences`` / ``lengths`` of the greedy transcript.  ``num_beams`` in [2, 16]: ``n_edits`` / ``token_error_rate`` are
         those of the best sequence of the prefix beam search (``decode(num_beams=...)``) instead of the greedy transcript,
-        and ``return_items`` adds its ``beam_sequences`` / ``beam_lengths``; everything else is as without it."""
+        and ``return_items`` adds its ``beam_sequences`` / ``beam_lengths``; everything else is as without it.  ``lm`` /
+        ``lm_alpha`` / ``lm_beta`` (with ``num_beams`` >= 2) as in ``decode``: the best sequence is the fused search's."""
         cfg = self.config
         K, _ = check_ctc_beam_args(cfg, num_beams)
+        lm = check_ctc_lm_args(cfg, lm, lm_alpha, lm_beta, num_beams)
         if K > 1:
             self._check_beam_frames(inputs, "evaluate")
         with self._ctc_pass(inputs, labels, label_lengths, attention_mask) as c:
@@ -1320,7 +1420,7 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                 loss = float(item.sum())
             hyp_tok, hyp_len = tok, hl
             if K > 1:
-                bm = self._beam(c, K)
+                bm = self._beam(c, K, lm)
                 bhost = torch.cat([bm["tokens"][:, 0].reshape(-1), bm["len"][:, 0]]).cpu()
                 hyp_tok, hyp_len = bhost[:B * T].view(B, T).numpy(), bhost[B * T:].numpy()
             n_edits = sum(edit_distance(hyp_tok[b, :hyp_len[b]], lab[b, :lens[b]]) for b in range(B))
