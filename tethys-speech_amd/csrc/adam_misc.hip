@@ -648,14 +648,26 @@ static int tmi_feat_to_channels_last_impl(const float* feats, void* out, int64_t
   const int64_t Tp = T + pad_left + pad_right;
   dim3 grid((unsigned)((Tp + 63) / 64), (unsigned)B);
   const size_t lds = (size_t)64 * (C + 1) * sizeof(float);
+  // C = 256 needs 64 * 257 * 4 = 65792 bytes: above the 64 KiB a kernel gets without opting in (160 KiB per CU on gfx950)
+  constexpr int FEAT_MAX_LDS = 64 * (256 + 1) * (int)sizeof(float);
+  if (dtype != TMI_BF16 && dtype != TMI_F32) return TMI_ERR_UNSUPPORTED;
+  if (lds > 65536) {  // (only the widest inputs pay for the opt-in; the models' C = 80 and C = 1 never reach it)
+    static const hipError_t attr_bf = hipFuncSetAttribute(reinterpret_cast<const void*>(feat_cl_kernel<bf16_t>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, FEAT_MAX_LDS);
+    static const hipError_t attr_f32 = hipFuncSetAttribute(reinterpret_cast<const void*>(feat_cl_kernel<float>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, FEAT_MAX_LDS);
+    if ((dtype == TMI_BF16 ? attr_bf : attr_f32) != hipSuccess) {
+      (void)hipGetLastError();
+      tmi_set_error("tmi_feat_to_channels_last: cannot raise the dynamic LDS limit");
+      return TMI_ERR_LAUNCH;
+    }
+  }
   if (dtype == TMI_BF16)
     hipLaunchKernelGGL(feat_cl_kernel<bf16_t>, grid, dim3(256), lds, s, feats, (bf16_t*)out, (int)C, T, Tp,
                        (int)pad_left);
-  else if (dtype == TMI_F32)
+  else
     hipLaunchKernelGGL(feat_cl_kernel<float>, grid, dim3(256), lds, s, feats, (float*)out, (int)C, T, Tp,
                        (int)pad_left);
-  else
-    return TMI_ERR_UNSUPPORTED;
   return tmi_check_launch("tmi_feat_to_channels_last");
 }
 extern "C" int tmi_feat_to_channels_last(const float* feats, void* out, int64_t B, int64_t C, int64_t T,
