@@ -29,6 +29,7 @@ extern "C" {
 #define TMI_ERR_INVALID (-1)   /* bad argument (shape, alignment, dtype combination) */
 #define TMI_ERR_LAUNCH (-2)    /* hipLaunchKernel reported an error */
 #define TMI_ERR_UNSUPPORTED (-3)
+#define TMI_ERR_CALLBACK (-4)  /* tmi_plan_replay: a callback node returned non-zero; the nodes after it were not issued */
 
 #define TMI_F32 0
 #define TMI_BF16 1
@@ -209,10 +210,12 @@ int tmi_gelu_bwd_batched(const void* dy, const void* u, void* dx, int64_t n, int
  * Ordering between streams is part of the plan: the host reports each event record / stream wait it makes while recording
  * (tmi_plan_note_event_record / tmi_plan_note_stream_wait, raw hipEvent_t / hipStream_t handles that must outlive the
  * plan) and the replay repeats them with hipEventRecord / hipStreamWaitEvent.  tmi_plan_note_callback records a host
- * function called in sequence (what a step does between launches that is not this library's: an RCCL collective).
+ * function called in sequence (what a step does between launches that is not this library's: an RCCL collective);
+ * it returns 0 to go on, and anything else ends the replay at once: no later node is issued and tmi_plan_replay
+ * returns TMI_ERR_CALLBACK (a failed exchange must not be followed by the Adam updates on unreduced gradients).
  * Memory operations of a step go through tmi_memset_async / tmi_memset2d_async / tmi_memcpy_async (device to device)
- * so that they are recorded too.  tmi_plan_size: what = 0 nodes, 1 launches.  One recorder per thread; a plan is
- * replayed by one thread at a time.
+ * so that they are recorded too.  tmi_plan_size: what = 0 nodes, 1 launches, 2 event-record nodes, 3 stream-wait
+ * nodes, 4 callback nodes (-1 for anything else).  One recorder per thread; a plan is replayed by one thread at a time.
  */
 typedef struct tmi_plan tmi_plan;
 int tmi_plan_create(tmi_plan** out);
@@ -223,7 +226,7 @@ int tmi_plan_replay(tmi_plan* plan, uint64_t seed_delta, int64_t step_delta);
 int64_t tmi_plan_size(const tmi_plan* plan, int32_t what);
 int tmi_plan_note_event_record(void* event, void* stream);
 int tmi_plan_note_stream_wait(void* stream, void* event);
-int tmi_plan_note_callback(void (*fn)(void));
+int tmi_plan_note_callback(int (*fn)(void));
 int tmi_memset_async(void* dst, int32_t value, int64_t bytes, void* stream);
 int tmi_memset2d_async(void* dst, int64_t pitch_bytes, int32_t value, int64_t width_bytes, int64_t rows, void* stream);
 int tmi_memcpy_async(void* dst, const void* src, int64_t bytes, void* stream);

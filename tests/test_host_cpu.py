@@ -540,3 +540,76 @@ def test_launch_plan_callback_nodes_replay_in_order_and_raise():
     fail[0] = False
     bad.replay()
     assert later == [1, 1]
+
+
+def test_launch_plan_size_counts_each_kind_of_node():
+    """tmi_plan_size(plan, 2 / 3 / 4): event-record, stream-wait and callback nodes (``LaunchPlan.records`` / ``.waits`` /
+    ``.callback_nodes``).  No GPU: a callback-only plan, plus two hand-made notes (the library only stores the handles
+    until a replay, and this plan is never replayed)."""
+    import ctypes as C
+    from tethys_speech_amd import plan as P
+    from tethys_speech_amd._lib import lib
+    pl = P.LaunchPlan()
+    assert (pl.nodes, pl.launches, pl.records, pl.waits, pl.callback_nodes) == (0, 0, 0, 0, 0)
+    with pl.recording():
+        for _ in range(3):
+            P.host_call(lambda: None)
+    assert pl.callback_nodes == pl.nodes == pl.callbacks == 3
+    assert pl.records == 0 and pl.waits == 0 and pl.launches == 0
+    assert lib().tmi_plan_size(pl._h, 5) == -1 and lib().tmi_plan_size(pl._h, -1) == -1
+    mixed = P.LaunchPlan()
+    with mixed.recording():
+        P.host_call(lambda: None)
+        lib().tmi_plan_note_event_record(C.c_void_p(8), C.c_void_p(16))
+        lib().tmi_plan_note_stream_wait(C.c_void_p(16), C.c_void_p(8))
+        lib().tmi_plan_note_stream_wait(C.c_void_p(16), C.c_void_p(8))
+    assert (mixed.nodes, mixed.launches, mixed.records, mixed.waits, mixed.callback_nodes) == (4, 0, 1, 2, 1)
+
+
+def test_launch_plan_failed_callback_ends_the_replay_in_the_library():
+    """The test above only sees that later PYTHON callbacks return early (``LaunchPlan.add_callback`` checks a flag).  The
+    replay loop itself must stop: a raw C callback noted straight through tmi_plan_note_callback, which knows nothing of
+    that flag, stands for the launch closures behind a failed collective (the Adam updates on unreduced gradients).  It
+    must not be called at all by the failing replay."""
+    import ctypes as C
+    from tethys_speech_amd import plan as P
+    from tethys_speech_amd._lib import lib
+    fail, raw_calls = [False], []
+
+    def maybe():
+        if fail[0]:
+            raise RuntimeError("collective failed")
+
+    @C.CFUNCTYPE(C.c_int)
+    def raw():
+        raw_calls.append(1)
+        return 0
+
+    pl = P.LaunchPlan()
+    with pl.recording():
+        P.host_call(maybe)
+        assert lib().tmi_plan_note_callback(C.cast(raw, C.c_void_p)) == 0
+    assert pl.callback_nodes == pl.nodes == 2 and raw_calls == []   # (noting a callback does not call it)
+    pl.replay()
+    assert raw_calls == [1]
+    fail[0] = True
+    with pytest.raises(RuntimeError, match="collective failed"):
+        pl.replay()
+    assert raw_calls == [1], "tmi_plan_replay went on issuing nodes after a callback node failed"
+    fail[0] = False
+    pl.replay()
+    assert raw_calls == [1, 1]
+
+    # a callback that fails without a Python exception behind it: the library's own error, distinct from a launch error
+    @C.CFUNCTYPE(C.c_int)
+    def refuses():
+        return 7
+
+    pl2 = P.LaunchPlan()
+    with pl2.recording():
+        lib().tmi_plan_note_callback(C.cast(refuses, C.c_void_p))
+        lib().tmi_plan_note_callback(C.cast(raw, C.c_void_p))
+    assert lib().tmi_plan_replay(pl2._h, 0, 0) == -4   # TMI_ERR_CALLBACK
+    assert raw_calls == [1, 1]
+    with pytest.raises(Exception, match="callback"):
+        pl2.replay()

@@ -257,15 +257,20 @@ class KernelBlocks:
         self._late_ev = pend
 
     def _wait_late(self, key=None):
-        """Order the main stream behind the pending late slice ``key`` (behind all of them without a key); no-op when
-        nothing is pending.  Called before the first main-stream access to what a slice updates; ``finish_late`` is the
-        same thing for callers outside a step."""
-        pend = self.__dict__.get("_late_pending")
-        if not pend:
+        """Order the main stream behind the late slice ``key`` (behind all of them without a key).  Called before the first
+        main-stream access to what a slice updates; ``finish_late`` is the same thing for callers outside a step.
+        The wait is issued whenever the slice's persistent event exists, pending or not: a step that a launch plan
+        records right after something drained the slices (a checkpoint, an empty batch) must still contain the wait,
+        because every replay launches the slice again.  (A wait on an event that has completed is free, ``_inference``.)
+        ``_late_pending`` / ``_late_ev`` only say whether a slice may still be running."""
+        done = self.__dict__.get("_late_done")
+        if not done:
             return
+        pend = self.__dict__.get("_late_pending") or {}
         main = self._main or torch.cuda.current_stream(self.device)
-        for k in ([key] if key is not None else list(pend)):
-            ev = pend.pop(k, None)
+        for k in ([key] if key is not None else list(done)):
+            pend.pop(k, None)
+            ev = done.get(k)
             if ev is not None:
                 main.wait_event(ev)
         if not pend:

@@ -19,7 +19,7 @@
 // through tmi_plan_note_event_record / tmi_plan_note_stream_wait (the host code's own event objects: the handles stay
 // valid because the host keeps them alive with the plan).  Anything else the step does on the host between launches
 // (an RCCL collective issued through torch.distributed) is a callback node: the recorded function pointer is called in
-// its place in the sequence.
+// its place in the sequence; a callback that returns non-zero ends the replay there (nothing after it is issued).
 #include "tmi_common.h"
 #include <functional>
 #include <vector>
@@ -86,7 +86,12 @@ extern "C" int tmi_plan_end(tmi_plan* p) {
 
 extern "C" int64_t tmi_plan_size(const tmi_plan* p, int32_t what) {
   if (!p) return -1;
-  return what == 0 ? (int64_t)p->nodes.size() : (int64_t)p->launches;
+  if (what == 0) return (int64_t)p->nodes.size();
+  if (what == 1) return (int64_t)p->launches;
+  if (what < 2 || what > 4) return -1;
+  int64_t n = 0;  // 2 event records, 3 stream waits, 4 callbacks: node kinds 1, 2, 3
+  for (const auto& node : p->nodes) n += node.kind == what - 1;
+  return n;
 }
 
 extern "C" int tmi_plan_note_event_record(void* event, void* stream) {
@@ -99,7 +104,7 @@ extern "C" int tmi_plan_note_stream_wait(void* stream, void* event) {
   return TMI_OK;
 }
 
-extern "C" int tmi_plan_note_callback(void (*fn)(void)) {
+extern "C" int tmi_plan_note_callback(int (*fn)(void)) {
   if (g_rec && g_depth == 0) g_rec->nodes.push_back(tmi_plan::Node{3, nullptr, reinterpret_cast<void*>(fn), nullptr});
   return TMI_OK;
 }
@@ -120,13 +125,14 @@ extern "C" int tmi_plan_replay(tmi_plan* p, uint64_t seed_delta, int64_t step_de
     } else if (n.kind == 2) {
       if (hipStreamWaitEvent(reinterpret_cast<hipStream_t>(n.a), reinterpret_cast<hipEvent_t>(n.b), 0) != hipSuccess) rc = TMI_ERR_LAUNCH;
     } else {
-      reinterpret_cast<void (*)(void)>(n.a)();
+      if (reinterpret_cast<int (*)(void)>(n.a)() != 0) rc = TMI_ERR_CALLBACK;
     }
     if (rc != TMI_OK) break;
   }
   g_seed_delta = 0;
   g_step_delta = 0;
   if (rc == TMI_ERR_LAUNCH) tmi_set_error("tmi_plan_replay: a recorded event / stream call failed");
+  if (rc == TMI_ERR_CALLBACK) tmi_set_error("tmi_plan_replay: a callback node failed; the rest of the plan was not issued");
   return rc;
 }
 

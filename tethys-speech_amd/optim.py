@@ -226,7 +226,9 @@ class Adam:
 
     @staticmethod
     def invalidate_row_flags(model, off=None):
-        """m / v of the embedding tables (of the one at ``off``) were written by something else than the row-sparse kernel."""
+        """m / v of the embedding tables (of the one at ``off``) were written by something else than the row-sparse kernel.
+        A recorded launch plan holds the ADDRESS of the flag tensors dropped here: ``adam_row_epoch`` is part of the state
+        ``plan.PlannedStep`` compares before every replay, so such a plan is recorded again instead of replayed."""
         a = model.arena
         store = a.__dict__.setdefault("adam_row_flags", {})
         if off is None:
@@ -234,6 +236,7 @@ class Adam:
         else:
             store.pop(off, None)
         a.adam_state_dirty = True
+        a.adam_row_epoch = a.__dict__.get("adam_row_epoch", 0) + 1
 
     def apply_gradients_clipped(self, model, chunks, sumsq, nseg, clip_global=0.0, clip_each=0.0, grad_scale=1.0,
                                 zero_grad=False, late_row=None):

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import weakref
 
 import torch
 
@@ -34,7 +35,7 @@ from ._lib import check, lib
 SEED_STEP = 0x9E3779B97F4A7C15  # KernelBlocks._site_seed: the per-step stride of every dropout site's seed
 
 _recording = None   # the LaunchPlan recording on this thread (one at a time: tmi_plan_begin refuses a second)
-_CALLBACK = C.CFUNCTYPE(None)
+_CALLBACK = C.CFUNCTYPE(C.c_int)   # int (*)(void): non-zero ends the replay at this node (tmi_plan_note_callback)
 
 
 def host_call(fn):
@@ -88,12 +89,14 @@ class LaunchPlan:
 
         def node():
             if self._error is not None:
-                return       # a previous node of this replay failed: issue nothing more (the caller raises after the replay)
+                return 1     # a previous node of this replay failed: issue nothing more (the caller raises after the replay)
             try:
                 with ctx():
                     fn()
             except BaseException as e:   # (an exception cannot cross the C frames of the replay loop)
                 self._error = e
+                return 1     # tmi_plan_replay stops here: no launch behind a failed exchange (the Adam updates least of all)
+            return 0
 
         cb = _CALLBACK(node)
         self._keep.append(cb)
@@ -151,6 +154,20 @@ class LaunchPlan:
     def launches(self):
         return int(lib().tmi_plan_size(self._h, 1))
 
+    @property
+    def records(self):
+        """Event-record nodes."""
+        return int(lib().tmi_plan_size(self._h, 2))
+
+    @property
+    def waits(self):
+        """Stream-wait nodes."""
+        return int(lib().tmi_plan_size(self._h, 3))
+
+    @property
+    def callback_nodes(self):
+        return int(lib().tmi_plan_size(self._h, 4))
+
 
 class PlannedStep:
     """``step(*inputs) -> loss`` for ONE replica, replayed from a launch plan.
@@ -158,18 +175,67 @@ class PlannedStep:
     ``eager(*inputs)`` is the step as the host code issues it (``train.distributed_train_step`` / ``wav2vec2_train_step``
     bound to their strategy, model and optimizer); it must return a fresh device tensor derived from ``loss_buffer()``,
     the model's own (static) loss scalar.  Per input signature (shapes + dtypes): the first ``warm`` calls run eagerly
-    (workspaces, streams and the steady state of the early / late Adam slices come into being), the next call runs
-    eagerly on STATIC copies of the inputs while the plan records it, every later call copies its inputs into those
-    buffers and replays.  ``finish(loss_tensor)`` turns the static loss scalar into the step's return value (clone +
-    the strategy's reduce).  Python-side counters the eager step advances are advanced here too (``model._drop_step``,
-    ``optimizer.iterations``); everything else the step leaves behind on the host (event bookkeeping, the ``g_clean``
-    flag) is the same after every steady-state step, which is what makes the recording replayable."""
+    (workspaces, streams and the early / late Adam slices come into being), the next call runs eagerly on STATIC copies
+    of the inputs while the plan records it, every later call copies its inputs into those buffers and replays.
+    ``finish(loss_tensor)`` turns the static loss scalar into the step's return value (clone + the strategy's reduce).
+    Python-side counters the eager step advances are advanced here too (``model._drop_step``, ``optimizer.iterations``).
 
-    def __init__(self, eager, model, optimizer, loss_buffer, finish=None, warm=2):
-        self.eager, self.model, self.opt = eager, model, optimizer
+    A plan copies by value everything else the step read on the host while it was recorded, so every replay is preceded
+    by a comparison of that state with the state now (``_fingerprint``): the optimizer's hyper-parameters and
+    ``row_sparse``, the dropout rates and base seed, the row-activity flag tensors of the row-sparse Adam
+    (``Adam.invalidate_row_flags`` frees them: a replay would write through the stale address), ``strategy.exchange_off``.
+    When any of them differs the plan of that signature is dropped (``_drop``), the next call runs eagerly and the one
+    after it records again.  ``arena.g_clean`` is treated apart: a plan is only ever recorded with a clean gradient arena
+    (it contains no fill pass), and a call that finds gradients left in the arena - a bare ``model.forward_backward``
+    between two steps - runs that one step eagerly, fill included, and keeps the plan.  ``invalidate()`` drops every plan
+    at once (``train.load_checkpoint`` calls it through ``model._planned_steps``)."""
+
+    def __init__(self, eager, model, optimizer, loss_buffer, finish=None, warm=2, strategy=None):
+        self.eager, self.model, self.opt, self.strategy = eager, model, optimizer, strategy
         self.loss_buffer, self.finish, self.warm = loss_buffer, finish or (lambda t: t.clone()), warm
         self._by_sig = {}
         self.replays = 0
+        self.rerecords = 0   # plans dropped because the state they had copied changed
+        try:
+            model.__dict__.setdefault("_planned_steps", weakref.WeakSet()).add(self)
+        except (AttributeError, TypeError):
+            pass
+
+    def _fingerprint(self):
+        o, m = self.opt, self.model
+        a = getattr(m, "arena", None)
+        flags = getattr(a, "adam_row_flags", None) or {}
+        return (o.learning_rate, o.beta_1, o.beta_2, o.epsilon, o.weight_decay, getattr(o, "eps_mode", 0),
+                getattr(o, "row_sparse", None),
+                getattr(m, "_drop_p", 0.0), getattr(m, "_drop_attn_p", 0.0), getattr(m, "_drop_act_p", 0.0),
+                getattr(m, "_drop_base", 0),
+                getattr(a, "adam_row_epoch", 0), tuple((k, t.data_ptr()) for k, t in flags.items()),
+                getattr(self.strategy, "exchange_off", None))
+
+    def _g_clean(self):
+        return bool(getattr(getattr(self.model, "arena", None), "g_clean", True))
+
+    def _drop(self, st):
+        """Forget the plan of one signature (its events, static inputs and workspace reference go with it).  What it has in
+        flight may still be running on the model's other streams: the current stream, on which the freed buffers are
+        handed out again, is ordered behind them first.  One eager call, then the next one records."""
+        m = self.model
+        if torch.cuda.is_available() and getattr(m, "device", None) is not None and m.device.type == "cuda":
+            cur = torch.cuda.current_stream(m.device)
+            for s_ in (m.gradient_streams() if hasattr(m, "gradient_streams") else []):
+                cur.wait_stream(s_)
+        for k in ("plan", "static", "loss", "ws", "state", "drop0", "it0"):
+            st.pop(k, None)
+        st["plan"] = None
+        st["seen"] = max(self.warm - 1, 0)
+
+    def invalidate(self):
+        """Drop every recorded plan: the caller changed something a plan had copied (restored a checkpoint in place, ...).
+        The fingerprint catches the cases listed in the class docstring by itself; this is for everything else."""
+        for st in self._by_sig.values():
+            if st.get("plan") is not None:
+                self._drop(st)
+                self.rerecords += 1
 
     def __call__(self, *inputs):
         from . import ops
@@ -177,10 +243,15 @@ class PlannedStep:
         st = self._by_sig.get(sig)
         if st is None:
             st = self._by_sig[sig] = {"seen": 0, "plan": None}
+        if st["plan"] is not None and st["state"] != self._fingerprint():
+            self._drop(st)
+            self.rerecords += 1
         if st["plan"] is None:
             if st["seen"] < self.warm or any(t.numel() == 0 for t in inputs):
                 st["seen"] += 1
                 return self.eager(*inputs)
+            if not self._g_clean():
+                return self.eager(*inputs)   # (gradients left in the arena: this step fills first; record the next one)
             # record: a real step, on static input buffers
             st["static"] = [torch.empty_like(t) for t in inputs]
             for s_, t in zip(st["static"], inputs):
@@ -191,8 +262,11 @@ class PlannedStep:
                 out = self.eager(*st["static"])
             st["loss"] = self.loss_buffer()
             st["ws"] = getattr(self.model, "ws", None)  # the workspace set whose addresses the plan bakes in
+            st["state"] = self._fingerprint()           # (after the step: it may have created the row-activity flags)
             st["plan"] = plan
             return out
+        if not self._g_clean():
+            return self.eager(*inputs)       # the plan has no fill pass: this one step from Python, the plan stays
         for s_, t in zip(st["static"], inputs):
             ops.copy(s_, t.contiguous())
         m = self.model

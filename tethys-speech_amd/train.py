@@ -123,7 +123,7 @@ def planned_step(strategy, model, optimizer, kind="whisper", pipelined=True):
         return eager
     from .plan import PlannedStep
     ps = PlannedStep(eager, model, optimizer, loss_buffer=lambda: model.ws["loss"],
-                     finish=lambda t: strategy.reduce_sum(t.clone()))
+                     finish=lambda t: strategy.reduce_sum(t.clone()), strategy=strategy)
     if kind == "whisper":
         # (a bool / integer mask becomes float32 OUTSIDE the plan: a torch kernel inside a recording is lost on replay)
         step = lambda f, l, *m: ps(f, l, *(t if t.dtype == torch.float32 else t.to(torch.float32) for t in m))
@@ -472,6 +472,8 @@ def load_checkpoint(model, optimizer, path, dataset=None):
     a.p.copy_(ck["p"]); a.m.copy_(ck["m"]); a.v.copy_(ck["v"])
     optimizer.iterations = int(ck["iterations"])
     optimizer.invalidate_row_flags(model)  # the loaded m / v are not the ones the row-activity flags were kept for
+    for ps in list(model.__dict__.get("_planned_steps", ())):
+        ps.invalidate()  # (plans recorded on this model: the state fingerprint would catch the dropped flags by itself)
     model._drop_step = int(ck.get("drop_step", optimizer.iterations))
     if dataset is not None and ck.get("data_pos") is not None:
         dataset._pos = int(ck["data_pos"])
