@@ -718,6 +718,53 @@ int tmi_lm_head_sample_c(const void* x, int64_t x_ld, int32_t x_dtype, const flo
                          int64_t bits_ld, float penalty, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Timestamp rules (whisper.py generate, segment_timestamps): Whisper's timestamp tokens are the ids [tb, V), id tb + u
+ * standing for u * 0.02 s, and a row is decoded under the grammar  <|t0|> text <|t1|><|t1|> text <|t2|> ..  The grammar is
+ * more bans, OR-ed into the banned set of "Decode constraints" AFTER tmi_decode_constraints wrote it and before the step's
+ * _c LM head reads it: two launches per step, tmi_timestamp_rules (rules a - f) then tmi_lm_head_timestamp_gate (rule g).
+ * The row's generated tokens are g[0..n) = prefix[r, 1 + P : t], n = t - 1 - P (behind the start token and the P prompt
+ * tokens).  isT(x): tb <= x < V (an id outside [0, V) is no timestamp and is never used as an index); "below": the
+ * columns [0, tb), EOS and the specials among them.
+ *   last = n >= 1 && isT(g[n-1]);   pen = n < 2 || isT(g[n-2]);   tl = the last g[j] with isT, or none.
+ *   a. no_timestamps_id (>= 0) and every timestamp id > tb + max_ts are banned, always.
+ *   b. n == 0: every below column is banned (EOS too), and every timestamp id > tb + max_initial (max_initial < 0: no cap).
+ *   c. last && pen: every timestamp id is banned (after an opening timestamp or a closing/opening pair: text or EOS).
+ *   d. last && !pen: every below column except eos_id is banned (after a closing timestamp: a timestamp or EOS).
+ *   e. tl exists, last && !pen: the timestamp ids < tl are banned (the next segment may open where this one closed).
+ *   f. tl exists, otherwise: the timestamp ids <= tl are banned.
+ *   g. with z' the logit of "Decode constraints" under the set after a - f (so before the temperature),
+ *        lse_ts = log sum exp z' over the timestamp columns not banned, max_below = max z' over the below columns not banned;
+ *        lse_ts > max_below (fp32, strict; -inf on both sides is false, never NaN): every below column is banned.
+ *
+ * tmi_timestamp_rules: a - f for M rows in one launch.  prefix [M, ld] int32, columns [0, t) read (1 + P <= t <= ld);
+ * banned [M, bits_ld] is read and written: bits are only added, only bits < V, a word with nothing to add is not
+ * written and words [W, bits_ld) are never touched.  max_ts >= 0 and max_initial count timestamp units.  The result is
+ * the same bits in every run.  Limits as tmi_decode_constraints (M <= 65535, V <= 65536, t <= 65536), 0 <= tb <= V,
+ * no_timestamps_id and eos_id < V (negative: none); anything else is TMI_ERR_INVALID and launches nothing.
+ *
+ * tmi_lm_head_timestamp_gate: g for M rows in one launch that streams the LM head once: x .. V and seen, banned, bits_ld,
+ * penalty as for tmi_lm_head_argmax_c (seen may be NULL; banned is required and written), z' by the same device code in
+ * the same accumulation order as the _c kernels, so a column's z' here is bit for bit the z' the step's head then sees.
+ * Per workgroup (max_below) and (max_ts, sum exp) partials meet in `workspace` and are folded in a fixed column order,
+ * as tmi_lm_head_topk folds its lse: bit-reproducible.  fired[r] (int32 [M]) = 1 where the rule fired, else 0; where it
+ * fired the below columns are OR-ed into banned[r], nothing else of banned changes, seen is not written.
+ * Ordering: every workgroup of the launch reads the row's banned words, so they are rewritten inside the SAME launch by
+ * the last workgroup of the row's 16-row tile to arrive, after every partial of that tile is in (the completion counter
+ * that tmi_lm_head_topk uses to clean its workspace); there is no second launch.
+ * `workspace`: >= tmi_lm_head_timestamp_gate_workspace_bytes(M, V) = 16 * M * (1 + ceil(V / 128)) bytes (-1 for sizes the
+ * kernel refuses), 16-byte aligned, ZERO before the first call and left zero by every call; one buffer per stream.
+ * V <= 65536, 0 <= tb <= V, the LDS bound of tmi_lm_head_argmax; anything else is TMI_ERR_INVALID and launches nothing.
+ */
+int tmi_timestamp_rules(const int32_t* prefix, int64_t ld, int64_t M, int64_t t, int64_t P, int64_t V, int64_t tb,
+                        int32_t no_timestamps_id, int32_t eos_id, int64_t max_initial, int64_t max_ts, uint32_t* banned,
+                        int64_t bits_ld, void* stream);
+int64_t tmi_lm_head_timestamp_gate_workspace_bytes(int64_t M, int64_t V);
+int tmi_lm_head_timestamp_gate(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta, float eps,
+                               const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d, int64_t V,
+                               const uint32_t* seen, uint32_t* banned, int64_t bits_ld, float penalty, int64_t tb,
+                               int32_t* fired, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * One step of beam search's bookkeeping (the rule of whisper.py generate / INTEGRATION.md), one workgroup per batch item
  * b of B; row r = b * K + k is beam k (1 <= K <= 8).  Step t (finalize = 0; 2K <= N <= 16):
  *   candidates (k, cand_ids[r * N + j], sums[r] + cand_lp[r * N + j]) (fp32 add), ranked by score desc then (k, id) asc;

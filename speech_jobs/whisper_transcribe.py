@@ -68,6 +68,16 @@ def main(argv=None):
                         help="ids that are not emitted as the first token")
     parser.add_argument("--prompt_ids", type=id_list, default=[], metavar="1,2,3",
                         help="decoder prompt: these ids follow the start token")
+    parser.add_argument("--segment_timestamps", action="store_true",
+                        help="decode under Whisper's timestamp-token grammar; every result carries its segments "
+                             "(start / end in units of 0.02 s and the text ids)")
+    parser.add_argument("--long", action="store_true",
+                        help="long-form transcription: walk each clip in 30 s windows by its timestamp tokens "
+                             "(whisper.transcribe_long) and print its segments in seconds; implies the timestamp grammar")
+    parser.add_argument("--max_initial_timestamp", type=float, default=1.0,
+                        help="with --segment_timestamps / --long: the first timestamp of a window is at most this (seconds)")
+    parser.add_argument("--no_condition_on_previous_text", action="store_true",
+                        help="with --long: do not prompt a window with the text of the windows before it")
     args = parser.parse_args(argv)
     if args.do_sample and args.num_beams > 1:
         parser.error("--do_sample does not go with --num_beams > 1")
@@ -92,6 +102,12 @@ def main(argv=None):
                 prompt_ids=args.prompt_ids or None)
     whisper.check_constraint_args(model.config, args.max_length, args.num_beams, return_token_timestamps=args.timestamps,
                                   **cons)
+    ts = dict(segment_timestamps=True, max_initial_timestamp=args.max_initial_timestamp) \
+        if args.segment_timestamps or args.long else {}
+    if ts:
+        whisper.check_timestamp_rule_args(model.config, suppress_tokens=args.suppress_tokens,
+                                          min_length=args.min_length if args.do_sample else None, **ts)
+    seg = lambda out, r: {"segments": out["segments"][r]} if ts else {}  # noqa: E731
     beam = args.num_beams > 1
     sample = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
                   min_length=args.min_length, seed=args.seed) if args.do_sample else None
@@ -113,6 +129,22 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.time()
     n_tok = 0
+    if args.long:
+        for name, wav in clips:
+            res = whisper.transcribe_long(
+                model, wav, condition_on_previous_text=not args.no_condition_on_previous_text,
+                max_initial_timestamp=args.max_initial_timestamp, max_length=args.max_length, num_beams=args.num_beams,
+                length_penalty=args.length_penalty, do_sample=args.do_sample, temperature=args.temperature,
+                top_k=args.top_k, top_p=args.top_p, seed=args.seed, **cons)
+            n_tok += len(res["ids"])
+            print(json.dumps({"clip": name, "n_windows": res["n_windows"], "n_tokens": len(res["ids"]),
+                              "segments": [{"start": round(s["start"], 2), "end": round(s["end"], 2), "ids": s["ids"]}
+                                           for s in res["segments"]]}), flush=True)
+        torch.cuda.synchronize()
+        dt = time.time() - t0
+        print(json.dumps({"clips": len(clips), "seconds": round(dt, 4), "tokens": n_tok,
+                          "tokens_per_s": round(n_tok / dt, 1) if dt > 0 else None}), flush=True)
+        return
     # clips of one length are decoded as one batch (the dummy clips, or wav files of equal length)
     groups = {}
     for name, wav in clips:
@@ -151,24 +183,26 @@ def main(argv=None):
         if args.save_cross_attentions or args.timestamps:
             feats_all = fe(wave)
         if sample:
-            out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample, **cons)
+            out = model.generate(fe(wave), max_length=args.max_length, return_dict_in_generate=True, **sample, **cons, **ts)
             seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
             lines = stamps(feats_all, seqs, lens, wave.shape[1], range(len(items))) if args.timestamps else {}
             for j, ((name, _), row, sc, n) in enumerate(zip(items, seqs, scores, lens)):
                 n_tok += int(n)
-                print(json.dumps({"clip": name, "ids": row[:1 + int(n)].tolist(), "n_tokens": int(n), "logprob": float(sc)}),
-                      flush=True)
+                print(json.dumps({"clip": name, "ids": row[:1 + int(n)].tolist(), "n_tokens": int(n), "logprob": float(sc),
+                                  **seg(out, j)}), flush=True)
                 if lines.get(j):
                     print(lines[j], flush=True)
             for j, ((name, _), row, n) in enumerate(zip(items, seqs, lens)):
                 save_cross(name, feats_all[j] if args.save_cross_attentions else None, row[:1 + int(n)].tolist())
             continue
         if not beam:
-            ids = model.generate(fe(wave), max_length=args.max_length, **cons).cpu()
+            out = model.generate(fe(wave), max_length=args.max_length, **cons, **ts)
+            ids = (out["sequences"] if ts else out).cpu()
             lines = stamps(feats_all, ids, None, wave.shape[1], range(len(items))) if args.timestamps else {}
             for j, ((name, _), row) in enumerate(zip(items, ids)):
                 n_tok += row.numel() - 1
-                print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1)}), flush=True)
+                print(json.dumps({"clip": name, "ids": row.tolist(), "n_tokens": int(row.numel() - 1), **seg(out, j)}),
+                      flush=True)
                 if lines.get(j):
                     print(lines[j], flush=True)
             for j, ((name, _), row) in enumerate(zip(items, ids)):
@@ -177,14 +211,14 @@ def main(argv=None):
         R = args.num_return_sequences
         out = model.generate(fe(wave), max_length=args.max_length, num_beams=args.num_beams,
                              length_penalty=args.length_penalty, num_return_sequences=R, return_dict_in_generate=True,
-                             **cons)
+                             **cons, **ts)
         seqs, scores, lens = out["sequences"].cpu(), out["sequences_scores"].cpu(), out["lengths"].cpu()
         lines = stamps(feats_all, seqs, lens, wave.shape[1], range(len(seqs))) if args.timestamps else {}
         for i, row in enumerate(seqs):
             n = int(lens[i])
             n_tok += n
             print(json.dumps({"clip": items[i // R][0], "rank": i % R, "ids": row[:1 + n].tolist(), "n_tokens": n,
-                              "score": float(scores[i])}), flush=True)
+                              "score": float(scores[i]), **seg(out, i)}), flush=True)
             if lines.get(i):
                 print(lines[i], flush=True)
             if i % R == 0:  # (the best hypothesis of the clip)

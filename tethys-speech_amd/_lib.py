@@ -158,6 +158,11 @@ SIGNATURES = {
     "tmi_lm_head_sample_c": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_f32,
                                      c_i64, c_f32, C.c_uint64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64,
                                      c_vp, c_vp, c_i64, c_f32, c_vp]),
+    "tmi_timestamp_rules": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_vp, c_i64,
+                                    c_vp]),
+    "tmi_lm_head_timestamp_gate_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "tmi_lm_head_timestamp_gate": (c_i32, [c_vp, c_i64, c_i32, c_vp, c_vp, c_f32, c_vp, c_i64, c_i32, c_i64, c_i64, c_i64,
+                                           c_vp, c_vp, c_i64, c_f32, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "tmi_beam_step": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_f32, c_i32, c_vp,
                               c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "tmi_logprob_state_bytes": (c_i64, [c_i64]),

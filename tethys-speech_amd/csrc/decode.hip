@@ -1174,3 +1174,232 @@ extern "C" int tmi_decode_constraints(const int32_t* prefix, int64_t ld, int64_t
                                       int64_t bits_ld, void* stream) {
   return tmi_plan_run<tmi_decode_constraints_impl>(prefix, ld, M, t, V, static_banned, ngram, seen, banned, bits_ld, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Whisper's timestamp-token grammar; the rules are include/tethys_mi.h's "Timestamp rules" (a - g).
+//
+// tmi_timestamp_rules: rules a - f, one workgroup per row.  The row's state (n, last, pen, tl) comes from one scan of the
+// generated tokens (the last timestamp by a max over positions: wave shuffles, then the four waves through LDS); every ban
+// of a - f is then one of at most three column ranges - the below columns [0, tb) less EOS, the timestamps [tb, lo_hi) and
+// the timestamps [hi_lo, V) - plus the one no-timestamps bit, so a thread ORs the ranges' share of a word into the word it
+// owns with a plain load and store.  A word with nothing to add is not written.
+namespace {
+__device__ __forceinline__ uint32_t ts_range_word(int i, int lo, int hi) {  // bits of [lo, hi) in word i
+  const int a = max(lo, 32 * i) - 32 * i, b = min(hi, 32 * i + 32) - 32 * i;
+  if (a >= b) return 0u;
+  return (b == 32 ? 0xffffffffu : (1u << b) - 1u) & ~((1u << a) - 1u);
+}
+
+__global__ __launch_bounds__(CN_THREADS) void timestamp_rules_kernel(
+    const int32_t* __restrict__ prefix, int64_t ld, int t, int P, int V, int W, int tb, int no_ts, int eos, int max_initial,
+    int max_ts, uint32_t* __restrict__ banned, int64_t bits_ld) {
+  __shared__ int s_best[CN_THREADS / 64];
+  const int tid = threadIdx.x;
+  const int32_t* g = prefix + (int64_t)blockIdx.x * ld + 1 + P;
+  const int n = t - 1 - P;
+  auto is_ts = [&](int32_t x) { return x >= tb && x < V; };  // (an id outside [0, V) is no timestamp: never an index)
+  int best = -1;
+  for (int j = tid; j < n; j += CN_THREADS)
+    if (is_ts(g[j])) best = j;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+  if ((tid & 63) == 0) s_best[tid >> 6] = best;
+  __syncthreads();
+  best = max(max(s_best[0], s_best[1]), max(s_best[2], s_best[3]));
+  const bool last = n >= 1 && is_ts(g[n - 1]);
+  const bool pen = n < 2 || is_ts(g[n - 2]);
+  const bool closed = last && !pen;  // a closing timestamp: rules d and e
+  // the below columns [0, below_hi), less EOS when a closing timestamp precedes (b, d)
+  const int below_hi = (n == 0 || closed) ? tb : 0;
+  const int keep = closed ? eos : -1;
+  // the timestamps [tb, lo_hi) (c, e, f) and [hi_lo, V) (a, b)
+  int lo_hi = tb;
+  if (best >= 0) lo_hi = closed ? g[best] : g[best] + 1;
+  if (last && pen) lo_hi = V;
+  int hi_lo = tb + max_ts + 1;
+  if (n == 0 && max_initial >= 0) hi_lo = min(hi_lo, tb + max_initial + 1);
+  uint32_t* row = banned + (int64_t)blockIdx.x * bits_ld;
+  for (int i = tid; i < W; i += CN_THREADS) {
+    uint32_t m = ts_range_word(i, 0, below_hi);
+    if (keep >= 0 && (keep >> 5) == i && keep < below_hi) m &= ~(1u << (keep & 31));
+    m |= ts_range_word(i, tb, min(lo_hi, V)) | ts_range_word(i, min(hi_lo, V), V);
+    if (no_ts >= 0 && (no_ts >> 5) == i) m |= 1u << (no_ts & 31);
+    if (m) row[i] |= m;
+  }
+}
+}  // namespace
+
+static int tmi_timestamp_rules_impl(const int32_t* prefix, int64_t ld, int64_t M, int64_t t, int64_t P, int64_t V, int64_t tb,
+                                    int32_t no_timestamps_id, int32_t eos_id, int64_t max_initial, int64_t max_ts,
+                                    uint32_t* banned, int64_t bits_ld, void* stream) {
+  const int64_t W = (V + 31) / 32;
+  if (!prefix || !banned || (reinterpret_cast<uintptr_t>(banned) & 3) || M < 1 || M > 65535 || V < 1 || V > CN_MAXV || t < 1 ||
+      t > 65536 || t > ld || P < 0 || 1 + P > t || tb < 0 || tb > V || no_timestamps_id >= V || eos_id >= V || max_ts < 0 ||
+      bits_ld < W) {
+    tmi_set_error("tmi_timestamp_rules: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  const int no_ts = no_timestamps_id < 0 ? -1 : no_timestamps_id, eos = eos_id < 0 ? -1 : eos_id;
+  const int mi = max_initial < 0 ? -1 : (int)(max_initial < V ? max_initial : V);  // (a cap at or past V bans nothing)
+  const int mt = (int)(max_ts < V ? max_ts : V);
+  hipLaunchKernelGGL(timestamp_rules_kernel, dim3((unsigned)M), dim3(CN_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     prefix, ld, (int)t, (int)P, (int)V, (int)W, (int)tb, no_ts, eos, mi, mt, banned, bits_ld);
+  return tmi_check_launch("tmi_timestamp_rules");
+}
+extern "C" int tmi_timestamp_rules(const int32_t* prefix, int64_t ld, int64_t M, int64_t t, int64_t P, int64_t V, int64_t tb,
+                                   int32_t no_timestamps_id, int32_t eos_id, int64_t max_initial, int64_t max_ts,
+                                   uint32_t* banned, int64_t bits_ld, void* stream) {
+  return tmi_plan_run<tmi_timestamp_rules_impl>(prefix, ld, M, t, P, V, tb, no_timestamps_id, eos_id, max_initial, max_ts,
+                                                banned, bits_ld, stream);
+}
+
+// tmi_lm_head_timestamp_gate: rule g.  The LM-head body of the kernels above (am_head_tile) and their z' (am_cons_bits,
+// am_cons_logit), with a reduction as the epilogue: per workgroup and row the max of z' over its below columns and the
+// (max, sum exp) pair over its timestamp columns, banned columns left out of both (16 lanes of 8 columns, a fixed butterfly),
+// stored in the row's slot for this workgroup - a plain 16-byte store.  The last workgroup of a row tile (one completion
+// counter per tile, the top-k kernel's pattern) works one wave per row: lane w folds slots w, w + 64, .. in order, a
+// butterfly that pairs the lower lane first finishes the logsumexp, so the bits do not depend on the arrival order; it
+// writes fired[r], puts the slots back to zero and - only now, when every workgroup that reads the row's banned words has
+// delivered its partial - ORs the below columns into banned[r] where the rule fired.
+namespace {
+// grid (ceil(V / 128), ceil(M / MT)); dynamic LDS max(d * MT, 4 * MT * 128) floats
+template <typename TW, int MT>
+__global__ __launch_bounds__(AM_THREADS) void lm_head_timestamp_gate_kernel(
+    const void* __restrict__ xv, int64_t x_ld, int x_bf16, const float* __restrict__ gamma, const float* __restrict__ beta,
+    float eps, const TW* __restrict__ w, int64_t w_ld, int M, int d, int V, const uint32_t* seen, uint32_t* banned,
+    int64_t bits_ld, float penalty, int tb, int32_t* __restrict__ fired, uint32_t* __restrict__ counters,
+    f32x4* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) float am_lds[];
+  __shared__ int tg_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row0 = blockIdx.y * MT;
+  const int rows = min(MT, M - row0);
+  const int nwg = gridDim.x;
+  am_head_tile<TW, MT>(am_lds, xv, x_ld, x_bf16, gamma, beta, eps, w, w_ld, d, V, row0, rows);
+  const float* red = am_lds;
+  const am_cons cs{seen, banned, bits_ld, penalty};
+
+  // ---- per row (16 lanes of 8 columns): max z' below tb, (max, sum exp) of z' from tb up
+  {
+    const int m = tid >> 4, g = tid & 15;
+    if (m < rows) {
+      const int r = row0 + m;
+      const int c0 = blockIdx.x * AM_COLS + g * 8;
+      uint32_t sb, bb;
+      am_cons_bits<true>(cs, r, c0, V, sb, bb);
+      float v[8];
+      float mb = -INFINITY, mt = -INFINITY;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int o = m * AM_COLS + g * 8 + c;
+        const float z = ((red[o] + red[MT * AM_COLS + o]) + red[2 * MT * AM_COLS + o]) + red[3 * MT * AM_COLS + o];
+        v[c] = am_cons_logit<true>(z, sb, bb, c, cs.penalty);
+        const bool ok = c0 + c < V && !((bb >> c) & 1u);
+        if (ok && c0 + c < tb) mb = fmaxf(mb, v[c]);
+        if (ok && c0 + c >= tb) mt = fmaxf(mt, v[c]);
+      }
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        mb = fmaxf(mb, __shfl_xor(mb, o, 64));
+        mt = fmaxf(mt, __shfl_xor(mt, o, 64));
+      }
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < 8; ++c)
+        se += (c0 + c < V && c0 + c >= tb && !((bb >> c) & 1u) && mt > -INFINITY) ? expf(v[c] - mt) : 0.f;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) se += __shfl_xor(se, o, 64);  // (xor pairs: both lanes add the same two values)
+      if (g == 0) part[(int64_t)r * nwg + blockIdx.x] = f32x4{mb, mt, se, 0.f};
+    }
+  }
+
+  // ---- completion: the last workgroup of the row tile folds, publishes and cleans up
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t prev = __hip_atomic_fetch_add(counters + blockIdx.y, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    tg_last = prev == (uint32_t)nwg - 1;
+  }
+  __syncthreads();
+  if (!tg_last) return;
+  __threadfence();
+  for (int m = wave; m < rows; m += 4) {
+    const int r = row0 + m;
+    float below = -INFINITY, am = -INFINITY, as = 0.f;
+    f32x4* slot = part + (int64_t)r * nwg;
+    f32x4 pv[TK_HEADS];  // (ceil(V / 128) <= 512 slots: at most 8 a lane, all loads in flight before the first fold)
+#pragma unroll
+    for (int i = 0; i < TK_HEADS; ++i) {
+      const int wg = lane + 64 * i;
+      pv[i] = wg < nwg ? slot[wg] : f32x4{-INFINITY, -INFINITY, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < TK_HEADS; ++i) {
+      below = fmaxf(below, pv[i][0]);
+      lse_fold(am, as, pv[i][1], pv[i][2]);
+      if (lane + 64 * i < nwg) slot[lane + 64 * i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      below = fmaxf(below, __shfl_xor(below, o, 64));
+      const float om = __shfl_xor(am, o, 64), os = __shfl_xor(as, o, 64);
+      if (lane & o) {  // the lower lane's pair first, in both lanes
+        float lm = om, ls = os;
+        lse_fold(lm, ls, am, as);
+        am = lm, as = ls;
+      } else {
+        lse_fold(am, as, om, os);
+      }
+    }
+    const float lse = am == -INFINITY ? -INFINITY : am + logf(as);
+    const bool fire = lse > below;  // (strict, fp32; -inf on both sides does not fire)
+    if (lane == 0) fired[r] = fire ? 1 : 0;
+    if (fire) {
+      uint32_t* row = banned + (int64_t)r * bits_ld;
+      const int full = tb >> 5;
+      for (int i = lane; i < full; i += 64) row[i] = 0xffffffffu;
+      if (lane == 0 && (tb & 31)) row[full] |= (1u << (tb & 31)) - 1u;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) __hip_atomic_store(counters + blockIdx.y, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+}  // namespace
+
+extern "C" int64_t tmi_lm_head_timestamp_gate_workspace_bytes(int64_t M, int64_t V) {
+  if (M < 1 || V < 1 || V > CN_MAXV) return -1;
+  return 16 * M * (1 + (V + AM_COLS - 1) / AM_COLS);
+}
+
+static int tmi_lm_head_timestamp_gate_impl(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                           float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d,
+                                           int64_t V, const uint32_t* seen, uint32_t* banned, int64_t bits_ld, float penalty,
+                                           int64_t tb, int32_t* fired, void* workspace, int64_t workspace_bytes, void* stream) {
+  am_geom g;
+  const bool shared_ok = am_args(x, x_ld, x_dtype, gamma, beta, w, w_ld, w_dtype, M, d, V, workspace, g);
+  if (!shared_ok || !banned || !fired || V > CN_MAXV || tb < 0 || tb > V || !(penalty > 0.f && penalty < INFINITY) ||
+      bits_ld < (V + 31) / 32 || ((reinterpret_cast<uintptr_t>(seen) | reinterpret_cast<uintptr_t>(banned)) & 3) ||
+      !tmi_aligned(workspace, 16) || workspace_bytes < tmi_lm_head_timestamp_gate_workspace_bytes(M, V)) {
+    tmi_set_error("tmi_lm_head_timestamp_gate: bad argument");
+    return TMI_ERR_INVALID;
+  }
+  char* base = reinterpret_cast<char*>(workspace);
+  uint32_t* counters = reinterpret_cast<uint32_t*>(base);  // (one per row tile; 16 * M bytes reserved)
+  f32x4* part = reinterpret_cast<f32x4*>(base + 16 * M);
+  const int xb = x_dtype == TMI_BF16;
+  const dim3 grid((unsigned)g.nwg, (unsigned)((M + g.MT - 1) / g.MT));
+  return am_dispatch(w_dtype, g.MT, [&](auto tw, auto mt) {
+    using TW = typename decltype(tw)::type;
+    return am_launch_one<lm_head_timestamp_gate_kernel<TW, mt()>>(
+        "tmi_lm_head_timestamp_gate", grid, (size_t)g.lds_floats * 4, reinterpret_cast<hipStream_t>(stream), x, x_ld, xb, gamma,
+        beta, eps, reinterpret_cast<const TW*>(w), w_ld, (int)M, (int)d, (int)V, seen, banned, bits_ld, penalty, (int)tb, fired,
+        counters, part);
+  });
+}
+extern "C" int tmi_lm_head_timestamp_gate(const void* x, int64_t x_ld, int32_t x_dtype, const float* gamma, const float* beta,
+                                          float eps, const void* w, int64_t w_ld, int32_t w_dtype, int64_t M, int64_t d,
+                                          int64_t V, const uint32_t* seen, uint32_t* banned, int64_t bits_ld, float penalty,
+                                          int64_t tb, int32_t* fired, void* workspace, int64_t workspace_bytes, void* stream) {
+  return tmi_plan_run<tmi_lm_head_timestamp_gate_impl>(x, x_ld, x_dtype, gamma, beta, eps, w, w_ld, w_dtype, M, d, V, seen,
+                                                       banned, bits_ld, penalty, tb, fired, workspace, workspace_bytes, stream);
+}

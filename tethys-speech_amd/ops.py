@@ -897,6 +897,43 @@ def lm_head_sample_c(x, x_ld, w, w_ld, M, d, V, ids, ids_ld, finished, n_finishe
                     temperature, top_k, top_p, seed, suppress_id, eos_id, pad_id, logprob, gamma, beta, eps)
 
 
+def timestamp_rules(prefix, ld, M, t, P, V, tb, banned, no_timestamps_id=-1, eos_id=-1, max_initial=-1, max_ts=1500):
+    """Rules a - f of the timestamp grammar (tmi_timestamp_rules; include/tethys_mi.h, "Timestamp rules") OR-ed into
+    ``banned`` int32 [M, >= constraint_words(V)] for M rows: ``prefix`` int32 with row stride ``ld``, columns [0, t) read, P
+    prompt tokens behind the start token; ``tb`` the first timestamp id; ``max_initial`` (< 0: no cap) and ``max_ts`` in
+    timestamp units."""
+    _, bp, bits_ld = _cons_args(None, banned, M, V)
+    if bp is None:
+        raise ValueError("timestamp_rules writes banned")
+    check(lib().tmi_timestamp_rules(prefix.data_ptr(), ld, M, t, P, V, tb, int(no_timestamps_id), int(eos_id), int(max_initial),
+                                    int(max_ts), bp, bits_ld, stream()), "tmi_timestamp_rules")
+
+
+def lm_head_timestamp_gate_workspace_elems(M, V):
+    """int64 elements of tmi_lm_head_timestamp_gate's workspace (tmi_lm_head_timestamp_gate_workspace_bytes / 8)."""
+    n = lib().tmi_lm_head_timestamp_gate_workspace_bytes(M, V)
+    if n < 0:
+        raise ValueError(f"tmi_lm_head_timestamp_gate takes no M {M}, V {V}")
+    return n // 8
+
+
+def lm_head_timestamp_gate(x, x_ld, w, w_ld, M, d, V, tb, fired, workspace, seen=None, banned=None, penalty=1.0, gamma=None,
+                           beta=None, eps=1e-5):
+    """Rule g of the timestamp grammar (tmi_lm_head_timestamp_gate): over the constrained logits z' of ``lm_head_argmax_c``,
+    fired[r] = logsumexp(z' over the timestamp columns [tb, V)) > max(z' over the columns [0, tb)), banned columns left out;
+    where it fired the columns [0, tb) are OR-ed into ``banned[r]``.  ``fired`` int32 [M]; ``workspace``: an int64 tensor
+    of at least ``lm_head_timestamp_gate_workspace_elems(M, V)`` elements, 16-byte aligned, zero before the first call (left
+    zero by every call)."""
+    sp, bp, bits_ld = _cons_args(seen, banned, M, V)
+    if bp is None:
+        raise ValueError("lm_head_timestamp_gate writes banned")
+    with _probe("lm_head_timestamp_gate", float(d) * w_ld * w.element_size()):
+        check(lib().tmi_lm_head_timestamp_gate(
+            x.data_ptr(), x_ld, dt(x), ptr(gamma), ptr(beta), eps, w.data_ptr(), w_ld, dt(w), M, d, V, sp, bp, bits_ld,
+            float(penalty), tb, fired.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), stream()),
+            "tmi_lm_head_timestamp_gate")
+
+
 def beam_step(cand_ids, cand_lp, N, B, K, sums, cur, nxt, ld, t, eos_id, len_pow, early_stopping, pool_ids, pool_scores,
               pool_len, pool_cnt, done, done_count, finalize=False):
     """One step of beam search's bookkeeping on the device (tmi_beam_step; the rule is whisper.generate's): candidates

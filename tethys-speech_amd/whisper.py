@@ -1018,7 +1018,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
                  top_p=None, repetition_penalty=None, attention_mask=None, eos_token_id=None, length_penalty=1.0,
                  early_stopping=False, num_return_sequences=1, return_dict_in_generate=False, do_sample=False, seed=0,
                  return_token_timestamps=False, no_repeat_ngram_size=None, suppress_tokens=None, begin_suppress_tokens=None,
-                 prompt_ids=None):
+                 prompt_ids=None, segment_timestamps=None, max_initial_timestamp=1.0, timestamp_begin=None,
+                 no_timestamps_token_id=None):
         """Greedy decoding (W:636-709) -> int32 ids [B, 1 + n] on the device, the start token first.  ``num_beams`` of 2 to
         8: beam search (``_generate_beam``; the reference accepts num_beams at W:637 and leaves it as a ``pass`` at
         W:696-698); None or 1: greedy (``_generate_greedy``).  Every mode runs the one step loop of ``_decode_steps``.
@@ -1055,14 +1056,34 @@ class WhisperForConditionalGeneration(KernelBlocks):
         ``min_length`` count generated tokens only, with P + max_length <= max_target_positions.  Per step there is one
         tmi_decode_constraints launch on the step's prefixes (so beams may reorder freely) and the _c form of the mode's
         LM head.  With every one of these at its default the call takes the path it took without them: the same kernels
-        and launches, no other buffer."""
+        and launches, no other buffer.
+
+        ``segment_timestamps=True`` (every mode; None or False: nothing changes, the same kernels, launches and bits):
+        the row is decoded under Whisper's timestamp grammar ``<|t0|> text <|t1|><|t1|> text <|t2|> ..`` - include/
+        tethys_mi.h's "Timestamp rules" a - g, acting on the logits before the temperature.  The timestamp ids are
+        [``timestamp_begin``, vocab_size) (None: vocab_size - 1501), id timestamp_begin + u standing for u * 0.02 s;
+        ``no_timestamps_token_id`` (None: timestamp_begin - 1; -1: none) is never emitted; the first timestamp is at most
+        ``max_initial_timestamp`` seconds (None: no cap) and no timestamp is past the features' encoder frame count
+        (at most 1500).  Per step two more launches follow tmi_decode_constraints - tmi_timestamp_rules and
+        tmi_lm_head_timestamp_gate, which streams the LM head once more - and the mode's _c head runs on the resulting
+        set.  The result is then the dict form with "segments": per returned row the list ``parse_timestamp_segments``
+        gives for its generated tokens (times in units of 0.02 s), and "advance" [rows] (units).  ``min_length`` must be
+        unset; ``check_timestamp_rule_args`` states the bounds.  Independent of ``return_token_timestamps``."""
         cfg = self.config
+        ts = check_timestamp_rule_args(cfg, segment_timestamps, max_initial_timestamp, timestamp_begin, no_timestamps_token_id,
+                                       suppress_tokens=suppress_tokens, min_length=min_length, eos_token_id=eos_token_id)
         cons = check_constraint_args(cfg, max_length, num_beams, repetition_penalty=repetition_penalty,
                                      no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens,
                                      begin_suppress_tokens=begin_suppress_tokens, prompt_ids=prompt_ids,
                                      eos_token_id=eos_token_id, return_token_timestamps=return_token_timestamps)
+        if ts is not None and cons is None:  # (the grammar alone: an active constraint with nothing else in it)
+            cons = {"penalty": 1.0, "ngram": 0, "suppress": [], "begin": [], "prompt": None, "P": 0, "active": True,
+                    "max_length": check_timestamp_length(cfg, max_length) if return_token_timestamps else
+                    check_generate_args(cfg, max_length, None, 1.0)}
         if cons is not None:
             max_length = cons["max_length"]
+        ts_args = dict(segment_timestamps=segment_timestamps, max_initial_timestamp=max_initial_timestamp,
+                       timestamp_begin=timestamp_begin, no_timestamps_token_id=no_timestamps_token_id)
         if return_token_timestamps:
             max_length = check_timestamp_length(cfg, max_length)
             out = self.generate(input_features, max_length=max_length, min_length=min_length, num_beams=num_beams,
@@ -1071,7 +1092,7 @@ class WhisperForConditionalGeneration(KernelBlocks):
                                 early_stopping=early_stopping, num_return_sequences=num_return_sequences,
                                 return_dict_in_generate=True, do_sample=do_sample, seed=seed,
                                 no_repeat_ngram_size=no_repeat_ngram_size, suppress_tokens=suppress_tokens,
-                                begin_suppress_tokens=begin_suppress_tokens, prompt_ids=prompt_ids)
+                                begin_suppress_tokens=begin_suppress_tokens, prompt_ids=prompt_ids, **ts_args)
             if not isinstance(out, dict):  # (the greedy path has no dict form of its own)
                 out = {"sequences": out}
             out.update(self.align(input_features, out["sequences"], out.get("lengths")))
@@ -1085,20 +1106,38 @@ class WhisperForConditionalGeneration(KernelBlocks):
             max_length = check_generate_args(cfg, max_length, num_beams, temperature)
         eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
         features = self._check_features(input_features)
+        if ts is not None:
+            ts = dict(ts, eos=eos, max_ts=min(TIMESTAMP_MAX_UNITS, self._stem_geometry(features.shape[2])["T"]))
+            cons = dict(cons, active=True, ts=ts)
+            return_dict_in_generate = True
         if do_sample:
-            return self._generate_sample(features, max_length, float(temperature), top_k, top_p, min_length, eos, int(seed),
-                                         bool(return_dict_in_generate), cons)
-        if beam:
-            return self._generate_beam(features, max_length, int(num_beams), float(temperature), eos, float(length_penalty),
-                                       bool(early_stopping), int(num_return_sequences), bool(return_dict_in_generate), cons)
-        return self._generate_greedy(features, max_length, eos, cons)
+            out = self._generate_sample(features, max_length, float(temperature), top_k, top_p, min_length, eos, int(seed),
+                                        bool(return_dict_in_generate), cons)
+        elif beam:
+            out = self._generate_beam(features, max_length, int(num_beams), float(temperature), eos, float(length_penalty),
+                                      bool(early_stopping), int(num_return_sequences), bool(return_dict_in_generate), cons)
+        else:
+            out = self._generate_greedy(features, max_length, eos, cons)
+        if ts is None:
+            return out
+        if not isinstance(out, dict):  # (the greedy path has no dict form of its own)
+            out = {"sequences": out}
+        seq, P = out["sequences"].cpu().numpy(), cons["P"]
+        lens = out["lengths"].cpu().numpy() if "lengths" in out else np.full(seq.shape[0], seq.shape[1] - 1)
+        parsed = [parse_timestamp_segments(seq[r, 1 + P:1 + int(lens[r])], ts["tb"], ts["max_ts"], eos)
+                  for r in range(seq.shape[0])]
+        out["segments"], out["advance"] = [p[0] for p in parsed], [p[1] for p in parsed]
+        return out
 
     def _constraint_state(self, cons, rows: int, K: int = 1):
         """The device side of ``cons`` (check_constraint_args; None: nothing, -> (0, None, None)) for ``rows`` decoded rows, K
         rows per batch item: the prompt's length P, the prompt as int32 [rows, P] (or None), and ``apply(prefix, ld, t,
-        first)`` -> the keyword arguments of the step's _c LM head, after one tmi_decode_constraints launch on the rows'
-        prefixes of length t (``first``: the first generated step, where begin_suppress_tokens are banned too).  Without an
-        active constraint (a prompt alone) ``apply`` is None and the mode keeps its unconstrained LM head."""
+        first, shared, ln)`` -> the keyword arguments of the step's _c LM head, after one tmi_decode_constraints launch on the
+        rows' prefixes of length t (``first``: the first generated step, where begin_suppress_tokens are banned too).
+        ``shared`` and ``ln`` are the step's hidden-state arguments (``_decode_steps``: what every head takes); they are
+        read only under the timestamp grammar (``cons["ts"]``, generate's ``segment_timestamps``), whose two launches -
+        tmi_timestamp_rules and tmi_lm_head_timestamp_gate - then follow on the banned set.  Without an active constraint
+        (a prompt alone) ``apply`` is None and the mode keeps its unconstrained LM head."""
         if cons is None:
             return 0, None, None
         dev, V = self.device, self.config.vocab_size
@@ -1117,10 +1156,19 @@ class WhisperForConditionalGeneration(KernelBlocks):
         words = lambda ids: torch.from_numpy(token_bitset(ids, V)).to(dev) if ids else None  # noqa: E731
         static, static_first = words(cons["suppress"]), words(sorted(set(cons["suppress"]) | set(cons["begin"])))
         penalty, ngram = cons["penalty"], cons["ngram"]
+        ts, P = cons.get("ts"), cons["P"]
+        if ts is not None:  # the timestamp grammar: the rule launch's scratch and the gate's workspace (left zero by every call)
+            fired = torch.zeros(rows, dtype=torch.int32, device=dev)
+            gate_ws = torch.zeros(ops.lm_head_timestamp_gate_workspace_elems(rows, V), dtype=torch.int64, device=dev)
 
-        def apply(prefix, ld, t, first):
+        def apply(prefix, ld, t, first, shared=None, ln=None):
             ops.decode_constraints(prefix, ld, rows, t, V, sets[0], sets[1], ngram=ngram,
                                    static_banned=static_first if first else static)
+            if ts is not None:  # rules a - f, then rule g over the step's own hidden states: ``shared`` is the head's
+                ops.timestamp_rules(prefix, ld, rows, t, P, V, ts["tb"], sets[1], no_timestamps_id=ts["no_ts"],
+                                    eos_id=ts["eos"], max_initial=ts["max_initial"], max_ts=ts["max_ts"])
+                ops.lm_head_timestamp_gate(*shared, ts["tb"], fired, gate_ws, seen=sets[0], banned=sets[1], penalty=penalty,
+                                           **ln)
             return dict(seen=sets[0], banned=sets[1], penalty=penalty)
 
         return cons["P"], prompt, apply
@@ -1171,8 +1219,9 @@ class WhisperForConditionalGeneration(KernelBlocks):
                 if tp > 1:
                     lab[:, :tp - 1].copy_(cur[:, 1:tp])  # (index relayout only: the embedding shift reads rows of stride tp)
                 h = self._decode_infer(lab, rows, tp, T)
-                kw = ln if apply is None else dict(ln, **apply(cur, L1, tp, t == 1))
-                count = head(t, tp, cur, lm_head, (h[tp - 1:], tp * d, wl, ldw, rows, d, V), kw)
+                shared = (h[tp - 1:], tp * d, wl, ldw, rows, d, V)
+                kw = ln if apply is None else dict(ln, **apply(cur, L1, tp, t == 1, shared, ln))
+                count = head(t, tp, cur, lm_head, shared, kw)
                 host[t:t + 1].copy_(count, non_blocking=True)
                 events[t & 1].record(main)
 
@@ -1912,6 +1961,94 @@ def check_constraint_args(cfg: WhisperConfig, max_length=None, num_beams=None, r
             "max_length": max_length, "active": active}
 
 
+TIMESTAMP_TOKENS = 1501      # <|0.00|> .. <|30.00|>: the top ids of Whisper's vocabulary
+TIMESTAMP_MAX_UNITS = 1500   # a 30 s window in timestamp units
+TIMESTAMP_UNIT_S = 0.02      # seconds per unit: one encoder frame
+TIMESTAMP_UNIT_SAMPLES = 320  # samples per unit at 16 kHz
+WINDOW_SAMPLES = 480000      # 30 s at 16 kHz
+
+
+def check_timestamp_rule_args(cfg: WhisperConfig, segment_timestamps=None, max_initial_timestamp=1.0, timestamp_begin=None,
+                              no_timestamps_token_id=None, suppress_tokens=None, min_length=None, eos_token_id=None):
+    """``generate``'s timestamp grammar (include/tethys_mi.h, "Timestamp rules"), checked on the host before the encoder
+    runs.  -> None when ``segment_timestamps`` is None or False (nothing else is then looked at), else {"tb", "no_ts" (-1:
+    none), "max_initial" (timestamp units; -1: no cap)}.  Raises ValueError unless
+      - vocab_size <= 65536 (tmi_timestamp_rules');
+      - timestamp_begin (None: vocab_size - 1501, which then has to be >= 1) is in [1, vocab_size);
+      - no_timestamps_token_id (None: timestamp_begin - 1) is -1 or in [0, timestamp_begin);
+      - max_initial_timestamp is None or finite and >= 0 (seconds; rounded to units of 0.02 s);
+      - the EOS id in force (eos_token_id, else the config's) is -1 or below timestamp_begin;
+    and no row can run out of columns:
+      - suppress_tokens holds no timestamp id (rules d and e leave a row the timestamps from the last one on) and, with
+        the no-timestamps id, does not cover every id below timestamp_begin (rule c leaves a row exactly those);
+      - min_length is None or 0 (it bans EOS, which after a closing timestamp at the window's end is all rule d leaves).
+    What remains, by cases: n == 0 leaves the timestamps up to the cap (at least timestamp_begin itself); after text
+    (rule f) every below column stays; after an opening timestamp or a pair (c) every below column stays; after a closing
+    timestamp (d, e) that timestamp itself stays, and EOS."""
+    if not segment_timestamps:
+        return None
+    V = cfg.vocab_size
+    if V > CONSTRAINT_MAX_VOCAB:
+        raise ValueError(f"segment_timestamps takes vocab_size <= {CONSTRAINT_MAX_VOCAB}")
+    tb = V - TIMESTAMP_TOKENS if timestamp_begin is None else int(timestamp_begin)
+    if isinstance(timestamp_begin, bool) or (timestamp_begin is not None and tb != timestamp_begin) or not 1 <= tb < V:
+        raise ValueError(f"timestamp_begin must be an integer in [1, {V}) (None: vocab_size - {TIMESTAMP_TOKENS})")
+    no_ts = tb - 1 if no_timestamps_token_id is None else int(no_timestamps_token_id)
+    if isinstance(no_timestamps_token_id, bool) or not -1 <= no_ts < tb:
+        raise ValueError(f"no_timestamps_token_id must be -1 (none) or in [0, timestamp_begin = {tb})")
+    if max_initial_timestamp is None:
+        max_initial = -1
+    else:
+        mi = float(max_initial_timestamp)
+        if not (math.isfinite(mi) and mi >= 0.0):
+            raise ValueError("max_initial_timestamp must be finite and >= 0 seconds (None: no cap)")
+        max_initial = min(int(round(mi / TIMESTAMP_UNIT_S)), CONSTRAINT_MAX_VOCAB)
+    eos = cfg.eos_token_id if eos_token_id is None else int(eos_token_id)
+    if eos >= tb:
+        raise ValueError(f"eos_token_id {eos} is a timestamp id (timestamp_begin = {tb})")
+    if min_length is not None and int(min_length) != 0:
+        raise ValueError("segment_timestamps does not take min_length: after a closing timestamp at the window's end EOS "
+                         "is the one column left")
+    if suppress_tokens is not None:
+        sup = np.asarray(suppress_tokens.cpu() if isinstance(suppress_tokens, torch.Tensor) else suppress_tokens).reshape(-1)
+        if sup.size and sup.dtype.kind in "iu":
+            if int(sup.max()) >= tb:
+                raise ValueError(f"suppress_tokens holds a timestamp id (>= {tb}): the grammar needs every one of them")
+            if len(set(int(v) for v in sup if v >= 0) | ({no_ts} if no_ts >= 0 else set())) >= tb:
+                raise ValueError("suppress_tokens covers every id below timestamp_begin: no text column is left")
+    return {"tb": tb, "no_ts": no_ts, "max_initial": max_initial}
+
+
+def parse_timestamp_segments(g, tb: int, window_units: int, eos_id=None):
+    """The segments of one decoded window -> (segments, advance_units).  ``g``: the generated tokens of a row (behind the
+    start token and the prompt), cut here before the first ``eos_id`` (None: nothing to cut); a timestamp is an id >= tb,
+    id tb + u standing for u units of 0.02 s; ``window_units``: the window's length in units.
+      - Two timestamps in a row close one segment and open the next: the slices of g end behind the first of each such
+        pair, and at the end of g as well when g ends in a single timestamp behind text.  A slice is the segment {"start":
+        first id - tb, "end": last id - tb, "tokens": its ids below tb}.  g ending in that single timestamp: the window
+        is done, advance = window_units; otherwise what follows the last pair is unfinished and is decoded again by the
+        next window: advance = the last slice's closing time.
+      - No pair: one segment from 0 to d with every id below tb, d = the last timestamp - tb when there is one and it is
+        not tb, else window_units; advance = window_units."""
+    g = [int(v) for v in g]
+    if eos_id is not None and eos_id in g:
+        g = g[:g.index(eos_id)]
+    n, is_t = len(g), lambda x: x >= tb  # noqa: E731
+    single_ending = n >= 2 and not is_t(g[-2]) and is_t(g[-1])
+    cons = [i + 1 for i in range(n - 1) if is_t(g[i]) and is_t(g[i + 1])]
+    if cons:
+        ends = cons + ([n] if single_ending else [])
+        segments, lo = [], 0
+        for hi in ends:
+            sl = g[lo:hi]
+            segments.append({"start": sl[0] - tb, "end": sl[-1] - tb, "tokens": [x for x in sl if not is_t(x)]})
+            lo = hi
+        return segments, (int(window_units) if single_ending else g[ends[-1] - 1] - tb)
+    stamps = [x for x in g if is_t(x)]
+    d = stamps[-1] - tb if stamps and stamps[-1] != tb else int(window_units)
+    return [{"start": 0, "end": d, "tokens": [x for x in g if not is_t(x)]}], int(window_units)
+
+
 SAMPLE_MAX_TOP_K = 64  # tmi_lm_head_sample's
 
 
@@ -2056,3 +2193,69 @@ def transcribe_audio(model, audio=None, tokenizer=None, max_length=448, num_beam
     if tokenizer is not None:
         return tokenizer.decode(ids)
     return ids
+
+
+def transcribe_long(model, audio=None, tokenizer=None, condition_on_previous_text=True, max_initial_timestamp=1.0,
+                    max_length=448, num_beams=1, length_penalty=1.0, do_sample=False, temperature=1.0, top_k=None, top_p=None,
+                    seed=0, repetition_penalty=None, no_repeat_ngram_size=None, suppress_tokens=None,
+                    begin_suppress_tokens=None, prompt_ids=None, timestamp_begin=None, no_timestamps_token_id=None):
+    """Long-form transcription of ONE audio (``transcribe_audio``'s forms of ``audio``; any length): Whisper's own walk
+    through the waveform by its timestamp tokens.  A sample position ``seek`` starts at 0; each window is wav[seek : seek +
+    480000] (30 s; the last one shorter) through the front end, decoded by ``model.generate(..., segment_timestamps=True)``
+    under the timestamp grammar with the window's own length in timestamp units (its encoder frames) as the largest
+    timestamp; the row's generated tokens go through ``parse_timestamp_segments``, the segments are offset by the seek, and
+    seek advances by advance * 320 samples: to the end of the last closed segment, or over the whole window when it closed
+    nothing or ended on a single timestamp.  The walk ends when less than one front-end frame is left.
+    ``condition_on_previous_text``: the text tokens of the windows so far - the last max_target_positions // 2 - 1 of
+    them - follow the start token as ``prompt_ids`` (the caller's ``prompt_ids`` serve while there are none, and every
+    window otherwise).  The decode arguments are ``transcribe_audio``'s; ``max_length`` is capped per window so that prompt
+    and transcript fit the decoder's positions.  -> {"segments": [{"start", "end" (seconds from the start of the audio),
+    "text" (with a tokenizer) or "ids"}], "ids" (every text token in order, a list), "n_windows"}."""
+    from .frontend import LogMelFrontend
+    if audio is None:
+        wav = dummy_waveform()
+    elif isinstance(audio, (str, os.PathLike)):
+        wav = read_wav(os.fspath(audio))
+    else:
+        wav = audio
+    wav = torch.as_tensor(wav).to(device=model.device, dtype=torch.float32)
+    if wav.dim() != 1:
+        raise ValueError("transcribe_long takes one waveform, [samples]")
+    cfg = model.config
+    fe = model.__dict__.get("_frontend")
+    if fe is None:
+        fe = model._frontend = LogMelFrontend(device=model.device, n_mels=cfg.n_mels)
+    eos = cfg.eos_token_id
+    tb = cfg.vocab_size - TIMESTAMP_TOKENS if timestamp_begin is None else int(timestamp_begin)
+    keep = cfg.max_target_positions // 2 - 1
+    mode = dict(do_sample=True, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed) if do_sample else \
+        dict(num_beams=num_beams, length_penalty=length_penalty) if num_beams is not None and int(num_beams) > 1 else {}
+    cons = {k: v for k, v in (("repetition_penalty", repetition_penalty), ("no_repeat_ngram_size", no_repeat_ngram_size),
+                              ("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens))
+            if v is not None}
+    segments, text, seek, n_windows = [], [], 0, 0
+    while wav.numel() - seek >= fe.n_fft:
+        win = wav[seek:seek + WINDOW_SAMPLES].contiguous()
+        feats = fe(win)
+        units = min(TIMESTAMP_MAX_UNITS, (fe.num_frames(win.numel()) + 1) // 2)  # the window's encoder frames
+        prompt = text[-keep:] if condition_on_previous_text and text and keep > 0 else prompt_ids
+        P = 0 if prompt is None else int(np.asarray(prompt).shape[-1])
+        out = model.generate(feats, max_length=max(0, min(int(max_length), cfg.max_target_positions - P)),
+                             return_dict_in_generate=True, segment_timestamps=True,
+                             max_initial_timestamp=max_initial_timestamp, timestamp_begin=timestamp_begin,
+                             no_timestamps_token_id=no_timestamps_token_id,
+                             **({} if prompt is None else {"prompt_ids": prompt}), **mode, **cons)
+        row = out["sequences"][0].cpu().numpy()
+        n = int(out["lengths"][0]) if "lengths" in out else len(row) - 1
+        segs, advance = parse_timestamp_segments(row[1 + P:1 + n], tb, units, eos)
+        assert advance > 0, ("the timestamp grammar gives a positive advance", row.tolist())
+        t0 = seek / 16000.0
+        for sg in segs:
+            item = {"start": t0 + sg["start"] * TIMESTAMP_UNIT_S, "end": t0 + sg["end"] * TIMESTAMP_UNIT_S}
+            item["text" if tokenizer is not None else "ids"] = tokenizer.decode(sg["tokens"]) if tokenizer is not None \
+                else list(sg["tokens"])
+            segments.append(item)
+            text.extend(sg["tokens"])
+        seek += advance * TIMESTAMP_UNIT_SAMPLES
+        n_windows += 1
+    return {"segments": segments, "ids": text, "n_windows": n_windows}

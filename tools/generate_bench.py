@@ -17,8 +17,13 @@ equal M, original and constrained alternating, every pair repeated (median, and 
 tmi_decode_constraints alone; and greedy, beam-4 and sampled ``generate`` with and without no_repeat_ngram_size 3,
 repetition_penalty 1.2 and 90 suppressed ids, alternating too.
 
+--segment_timestamps: the timestamp grammar, all in ONE run (a JSON file, --out): tmi_lm_head_timestamp_gate beside
+tmi_lm_head_argmax at equal M, alternating (device time); tmi_timestamp_rules alone; and greedy, beam-4 and sampled
+``generate`` with and without ``segment_timestamps=True``, alternating too.
+
 usage: python tools/generate_bench.py [--steps 448] [--batch 8] [--reps 2] [--num_beams 1] [--do_sample [--top_k K] [--top_p P]]
-       python tools/generate_bench.py --constrained [--steps 448] [--batch 8] [--reps 3] [--out profiles/r19_generate_constrained.json]"""
+       python tools/generate_bench.py --constrained [--steps 448] [--batch 8] [--reps 3] [--out profiles/r19_generate_constrained.json]
+       python tools/generate_bench.py --segment_timestamps [--steps 448] [--batch 8] [--reps 3] [--out profiles/r22_generate_timestamps.json]"""
 import argparse
 import json
 import os
@@ -174,11 +179,83 @@ def constrained_report(args):
                       "lm_head": {k: v["constrained_over_original"] for k, v in heads.items()}}), flush=True)
 
 
+def gate_alone(dev, d, M=8, V=51865, Vp=51904, tb=50364):
+    """tmi_lm_head_timestamp_gate alone on M rows (``constraint_sets``, penalty 1.2): device time per launch.  The banned
+    set is restored by nothing between launches: a row that fired keeps its below columns banned, which changes no work."""
+    g = torch.Generator(device=dev).manual_seed(d)
+    x = torch.randn(M, d, device=dev, generator=g).to(torch.bfloat16)
+    w = (torch.randn(d, Vp, device=dev, generator=g) * 0.03).to(torch.bfloat16)
+    gamma, beta = torch.ones(d, device=dev), torch.zeros(d, device=dev)
+    seen, banned = constraint_sets(dev, M, V)
+    fired = torch.zeros(M, dtype=torch.int32, device=dev)
+    ws = torch.zeros(ops.lm_head_timestamp_gate_workspace_elems(M, V), dtype=torch.int64, device=dev)
+    call = lambda: ops.lm_head_timestamp_gate(x, d, w, Vp, M, d, V, tb, fired, ws, seen=seen, banned=banned,  # noqa: E731
+                                              penalty=1.2, gamma=gamma, beta=beta)
+    us = graph_us(call)
+    return {"us": round(us, 2), "GBps": round(d * Vp * 2 / (us * 1e-6) / 1e9, 1)}
+
+
+def timestamps_report(args):
+    """The --segment_timestamps run: see the module docstring."""
+    dev, B, reps = "cuda:0", args.batch, max(3, args.reps)
+    out = {"what": "tools/generate_bench.py --segment_timestamps on one MI355X, one process: the two forms alternating, "
+                   "every figure the median of the repeats with their min, max and (max - min) / median",
+           "batch": B, "steps": args.steps, "reps": reps, "precision": "bf16"}
+    heads = {}
+    for M in (B, 4 * B):
+        runs = {"argmax": [], "gate": []}
+        for _ in range(reps):
+            runs["argmax"].append(argmax_alone(dev, 768, M)["us"])
+            runs["gate"].append(gate_alone(dev, 768, M)["us"])
+        a, g = _stats(runs["argmax"]), _stats(runs["gate"])
+        heads[f"M{M}_d768"] = {"argmax_us": a, "timestamp_gate_us": g, "gate_over_argmax": round(g["median"] / a["median"], 4)}
+    out["lm_head"] = heads
+    V, tb = 51865, 50364
+    rules = {}
+    for M in (B, 4 * B):
+        for t in (1, 224, 448):
+            prefix = torch.randint(0, V, (M, 449), dtype=torch.int32, device=dev)
+            banned = torch.zeros(M, ops.constraint_words(V), dtype=torch.int32, device=dev)
+            call = lambda: ops.timestamp_rules(prefix, 449, M, t, 0, V, tb, banned, no_timestamps_id=tb - 1, eos_id=2,  # noqa: E731
+                                               max_initial=50, max_ts=1500)
+            rules[f"M{M}_t{t}"] = _stats([graph_us(call) for _ in range(reps)])
+    out["timestamp_rules_us"] = rules
+    model = whisper.create_whisper_model("small", device=dev, precision="bf16")
+    feats = torch.randn(B, 80, 3000, generator=torch.Generator().manual_seed(0)).to(dev)
+    ts = dict(segment_timestamps=True)
+    gen = {}
+    for name, mode in (("greedy", {}), ("beam_K4", dict(num_beams=4)),
+                       ("sample_k50_p0.9", dict(do_sample=True, top_k=50, top_p=0.9, temperature=0.8, seed=1))):
+        runs = {"plain": [], "timestamps": []}
+        for kw in ({}, ts):
+            model.generate(feats, max_length=4, eos_token_id=-1, **mode, **kw)  # warm-up: workspace, kernels
+        torch.cuda.synchronize()
+        for _ in range(reps):
+            for which, kw in (("plain", {}), ("timestamps", ts)):
+                t0 = time.perf_counter()
+                ids = model.generate(feats, max_length=args.steps, eos_token_id=-1, **mode, **kw)
+                torch.cuda.synchronize()
+                runs[which].append((time.perf_counter() - t0) * 1e3 / args.steps)
+                ids = ids["sequences"] if isinstance(ids, dict) else ids
+                assert ids.shape[1] == 1 + args.steps, ids.shape
+        p, c = _stats(runs["plain"]), _stats(runs["timestamps"])
+        gen[name] = {"plain_per_step_ms": p, "timestamps_per_step_ms": c,
+                     "timestamps_over_plain": round(c["median"] / p["median"], 4),
+                     "added_per_step_us": round((c["median"] - p["median"]) * 1e3, 1)}
+    out["generate"] = gen
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps({"wrote": args.out, "generate": {k: v["timestamps_over_plain"] for k, v in gen.items()},
+                      "lm_head": {k: v["gate_over_argmax"] for k, v in heads.items()}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--constrained", action="store_true")
-    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                  "r19_generate_constrained.json"))
+    ap.add_argument("--segment_timestamps", action="store_true")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=448)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--reps", type=int, default=2)
@@ -187,6 +264,11 @@ def main():
     ap.add_argument("--top_k", type=int, default=50)
     ap.add_argument("--top_p", type=float, default=0.9)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                "r22_generate_timestamps.json" if args.segment_timestamps else "r19_generate_constrained.json")
+    if args.segment_timestamps:
+        return timestamps_report(args)
     if args.constrained:
         return constrained_report(args)
     K = args.num_beams
