@@ -370,6 +370,40 @@ int tmi_dtw(const float* cost, int64_t c_sn, int64_t c_ss, const int32_t* rows, 
             int32_t* path_len, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Error-rate evaluation: tmi_edit_distance, the batched Levenshtein distance with operation counts between token rows that
+ * are already on the device (Whisper's generated sequences against labels, CTC transcripts against labels, n-best lists
+ * against one reference).  Integers only: every output is exact.
+ *
+ * hyp int32, element (i, c) at hyp[i*hyp_ld + c], N rows of which the first hyp_cols columns are read; hyp_len int32 [N]
+ * or NULL (every row is hyp_cols long).  ref int32, element (b, c) at ref[b*ref_ld + c], N / R rows, ref_cols columns
+ * read; ref_len int32 [N / R] or NULL.  R >= 1 divides N: pair i is hypothesis i against reference i / R (the layout of
+ * num_return_sequences).  out int32, pair i at out[i*out_ld .. i*out_ld + 6), out_ld >= 6.
+ * Normalisation, of both sides alike, in the kernel:
+ *   a row is its first min(len, cols) tokens (a negative len counts as 0);
+ *   it is cut before the first occurrence of stop_id (stop_id == -1: no cut);
+ *   every token x with skip_lo <= x < skip_hi is dropped (skip_lo >= skip_hi: none is).
+ * A token is only compared, never used as an index: any int32 value, and anything past the length, is harmless.
+ * The rule.  h[1..n], r[1..m] the kept tokens; a cell is the tuple (d, sub, del, ins):
+ *   C[0][0] = (0, 0, 0, 0),  C[i][0] = (i, 0, 0, i),  C[0][j] = (j, 0, j, 0)
+ *   C[i][j] = the first of these candidates whose d is smallest (a later one replaces an earlier one only when its d is
+ *             strictly smaller):
+ *               1. diagonal  C[i-1][j-1], with d + 1, sub + 1 when h[i] != r[j]
+ *               2. up        C[i-1][j]    with d + 1, ins + 1   (a hypothesis token with no partner)
+ *               3. left      C[i][j-1]    with d + 1, del + 1   (a reference token with no partner)
+ *   out[i] = (d, sub, del, ins, n, m) of C[n][m]
+ * so d is the Levenshtein distance, sub + del + ins == d and ins - del == n - m.
+ * One workgroup per pair; both rows are compacted into LDS in order (a ballot over the keep flags), the table is swept by
+ * anti-diagonals with three rotating diagonals of packed cells in LDS and one barrier per diagonal (csrc/edit.hip).
+ * Limits: 0 <= hyp_cols, ref_cols <= 4096, 1 <= N <= 65535, hyp_ld >= hyp_cols, ref_ld >= ref_cols, strides <= 2^30.
+ * TMI_ERR_INVALID, before anything is launched and with nothing written: hyp, ref or out NULL, a pointer that is not
+ * 4-byte aligned, a size outside those limits, R < 1 or not dividing N, a stride too small.
+ * No atomics, no workspace: the same call gives the same bits.
+ * Not built: a backtrace - no per-token operations and no alignment come out, only the counts. */
+int tmi_edit_distance(const int32_t* hyp, int64_t hyp_ld, int64_t hyp_cols, const int32_t* hyp_len, const int32_t* ref,
+                      int64_t ref_ld, int64_t ref_cols, const int32_t* ref_len, int64_t N, int64_t R, int32_t stop_id,
+                      int32_t skip_lo, int32_t skip_hi, int32_t* out, int64_t out_ld, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * CTC inference (wav2vec2.py Wav2Vec2ForCTC: V:940-1001, forward only): the head's log-softmax, the greedy collapse, the
  * loss and the forced alignment.  All arithmetic is fp32; `blank` is an argument; -inf is the additive zero, and a
  * log-sum-exp LSE whose inputs are all -inf is -inf, never NaN.  No atomics, no allocation, no synchronisation: the same

@@ -20,6 +20,8 @@ builds such a table from a file of label lines (``wav2vec2.ngram_lm_table``, add
 no model is created and no GPU is needed.
 Prints one JSON line per clip: the token ids, with ``--timestamps`` their start and end times in seconds, the best path's
 log-probability, and with labels the nll, the edit distance of the transcript and the aligned times; then one summary line.
+``--edit_ops`` (with ``--labels``): the error counts come from the device kernel (``evaluate(edit_ops=True)``) and the
+summary line adds the substitutions, deletions and insertions and, with ``--num_beams``, the n-best oracle error rate.
 There is no tokenizer: ids in, ids out.
 """
 import argparse
@@ -59,6 +61,8 @@ def main(argv=None):
     parser.add_argument("--lm", default=None, help="with --num_beams: .npy n-gram table [vocab_size] * order fused into the search")
     parser.add_argument("--lm_alpha", type=float, default=0.5, help="weight of the table's log-probabilities")
     parser.add_argument("--lm_beta", type=float, default=0.0, help="bonus per token")
+    parser.add_argument("--edit_ops", action="store_true",
+                        help="with --labels: count substitutions / deletions / insertions on the device (and the n-best oracle)")
     parser.add_argument("--build_lm", default=None, help="file of token ids, one line per sequence: build a table and exit")
     parser.add_argument("--lm_order", type=int, default=2, help="with --build_lm: the order of the table (1..4)")
     parser.add_argument("--lm_out", default=None, help="with --build_lm: where the .npy table goes")
@@ -130,7 +134,7 @@ def main(argv=None):
             labels[i, :len(r)] = torch.tensor(r, dtype=torch.int64)
         lens = [len(r) for r in rows]
         ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True,
-                            num_beams=args.num_beams if beam else None, **lm_kw)
+                            num_beams=args.num_beams if beam else None, edit_ops=args.edit_ops, **lm_kw)
         al = model.align(audio, labels, lens, attention_mask=mask)
         if args.posteriors:
             post = model.posteriors(audio, labels, lens, attention_mask=mask)
@@ -174,6 +178,9 @@ def main(argv=None):
     summary = {"clips": len(clips), "samples": T_in, "seconds": round(dt, 4)}
     if ev is not None:
         summary.update({k: ev[k] for k in ("loss", "nll_sum", "n_infeasible", "n_edits", "n_ref_tokens", "token_error_rate")})
+        if args.edit_ops:
+            summary.update({k: ev[k] for k in ("n_sub", "n_del", "n_ins", "n_hyp_tokens", "n_oracle_edits", "oracle_error_rate")
+                            if k in ev})
     print(json.dumps(summary), flush=True)
 
 

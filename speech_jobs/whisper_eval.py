@@ -6,6 +6,10 @@ Loads ``--weights`` (a ``save_checkpoint`` or ``save_weights`` file, through ``t
 model keeps its seeded initialisation) and evaluates ``--num_batches`` batches of ``--batch_size`` items of the dummy
 pool drawn with ``--seed`` (the training pool's seed is 1234: any other seed is held-out data; the project ships no real
 dataset).  Prints loss, accuracy and perplexity = exp(loss) and writes them as one JSON file (``--out``).
+``--generate`` also runs ``generate`` on the same batches (``--num_beams K``, ``--max_length n``, ``--nbest R`` returned
+sequences per item) and compares what it emits with the labels (``train.evaluate_generate_whisper``,
+``model.evaluate_generate``): the result file gains the error counts, ``token_error_rate`` and the n-best
+``oracle_error_rate``.  Without the flag nothing changes.
 """
 import argparse
 import json
@@ -32,7 +36,13 @@ def main(argv=None):
     parser.add_argument("--out", default="whisper_eval.json", help="result file")
     parser.add_argument("--mask_padding", action="store_true",
                         help="score with decoder_attention_mask = (labels != 0), the objective of a --mask_padding training run")
+    parser.add_argument("--generate", action="store_true", help="also generate and report the token error rate")
+    parser.add_argument("--num_beams", type=int, default=None, help="with --generate: beam search with this many beams")
+    parser.add_argument("--max_length", type=int, default=None, help="with --generate: generated tokens per item at most")
+    parser.add_argument("--nbest", type=int, default=1, help="with --generate --num_beams: returned sequences per item")
     args = parser.parse_args(argv)
+    if not args.generate and (args.num_beams is not None or args.max_length is not None or args.nbest != 1):
+        parser.error("--num_beams, --max_length and --nbest come with --generate")
     if args.batch_size < 1 or args.num_batches < 1:
         parser.error("--batch_size and --num_batches must be at least 1")
 
@@ -53,13 +63,22 @@ def main(argv=None):
                                    with_mask=args.mask_padding))
     torch.cuda.synchronize()
     t0 = time.time()
-    res = train.evaluate_whisper(None, model, (next(ds) for _ in range(args.num_batches)))
+    batches = [next(ds) for _ in range(args.num_batches)] if args.generate else (next(ds) for _ in range(args.num_batches))
+    res = train.evaluate_whisper(None, model, batches)
     dt = time.time() - t0
     out = {"model_type": args.model_type, "precision": args.precision, "weights": args.weights, "batch_size": args.batch_size,
            "num_batches": args.num_batches, "loss": res["loss"], "accuracy": res["accuracy"],
            "perplexity": math.exp(res["loss"]) if res["loss"] < 700 else float("inf"), "n_tokens": res["n_tokens"],
            "n_correct": res["n_correct"], "loss_sum": res["loss_sum"], "seconds": round(dt, 4)}
     print(f"Loss: {out['loss']:.4f}, Accuracy: {out['accuracy']:.4f}, Perplexity: {out['perplexity']:.4f}", flush=True)
+    if args.generate:
+        kw = {k: v for k, v in (("num_beams", args.num_beams), ("max_length", args.max_length)) if v is not None}
+        if args.nbest != 1:
+            kw["num_return_sequences"] = args.nbest
+        t0 = time.time()
+        gen = train.evaluate_generate_whisper(None, model, batches, log=print, **kw)
+        out.update(gen)
+        out.update(generate=kw, generate_seconds=round(time.time() - t0, 4))
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
     print(json.dumps(out), flush=True)

@@ -190,6 +190,8 @@ SIGNATURES = {
                              c_vp]),
     "tmi_ctc_beam_lm": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_vp, c_vp, c_vp,
                                 c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
+    "tmi_edit_distance": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
+                                  c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

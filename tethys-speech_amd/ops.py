@@ -2,7 +2,8 @@
 
 Each function resolves pointers / element strides from torch tensors (device memory is
 PyTorch's caching allocator: plumbing) and launches the HIP kernel on torch's current
-stream.  Nothing here computes on the host or falls back to torch ops.
+stream.  Nothing here computes on the host or falls back to torch ops (``edit_counts`` alone sums the integer table of
+``edit_distance`` with torch reductions on the device, ahead of its one read-back).
 """
 from __future__ import annotations
 
@@ -487,6 +488,82 @@ def dtw(cost, rows, cols, tok_start, tok_end, total, workspace, path=None, path_
         check(lib().tmi_dtw(cost.data_ptr(), cost.stride(0), cost.stride(1), rows.data_ptr(), cols.data_ptr(), N, S, T,
                             tok_start.data_ptr(), tok_end.data_ptr(), total.data_ptr(), ptr(path), ptr(path_len),
                             workspace.data_ptr(), workspace.numel() * 4, stream()), "tmi_dtw")
+
+
+EDIT_MAX_COLS = 4096  # tmi_edit_distance: columns read of either side
+
+
+def _edit_rows(t, what):
+    if not isinstance(t, torch.Tensor) or t.device.type == "cpu" or t.dtype != torch.int32 or t.dim() != 2:
+        raise ValueError(f"edit_distance: {what} must be an int32 [rows, cols] tensor on the device")
+    rows, cols = t.shape
+    if cols > EDIT_MAX_COLS:
+        raise ValueError(f"edit_distance: {what} has {cols} columns, at most {EDIT_MAX_COLS} are read")
+    if cols > 1 and t.stride(1) != 1:
+        raise ValueError(f"edit_distance: {what} must have unit column stride")
+    ld = t.stride(0) if rows > 1 else max(cols, 1)
+    if ld < cols:
+        raise ValueError(f"edit_distance: the rows of {what} overlap")
+    return rows, cols, ld
+
+
+def edit_distance(hyp, ref, hyp_len=None, ref_len=None, R=1, stop_id=-1, skip=(0, 0), out=None):
+    """Levenshtein distance with operation counts of every (hypothesis, reference) pair, on the device (tmi_edit_distance in
+    include/tethys_mi.h states the rule).  ``hyp`` int32 [N, n_cols], ``ref`` int32 [N / R, m_cols]: pair i is hypothesis i
+    against reference i // R.  Both may be strided views with unit column stride (``sequences[:, 1 + P:]`` needs no copy).
+    ``hyp_len`` [N], ``ref_len`` [N / R] int32 or None (the whole row).  Both sides are cut before ``stop_id`` (-1: no cut)
+    and lose every token in [skip[0], skip[1]).  -> ``out`` int32 [N, 6] = (d, sub, del, ins, n, m) per pair (``out``: write
+    there instead, int32 [N, >= 6] with unit column stride)."""
+    N, hc, h_ld = _edit_rows(hyp, "hyp")
+    Nr, rc, r_ld = _edit_rows(ref, "ref")
+    R = int(R)
+    if ref.device != hyp.device:
+        raise ValueError("edit_distance: hyp and ref are on different devices")
+    if N < 1 or N > 65535 or R < 1 or Nr * R != N:
+        raise ValueError(f"edit_distance: 1 <= N <= 65535 hypotheses, R >= 1 per reference; got {N} against {Nr} with R = {R}")
+    for t, n, w in ((hyp_len, N, "hyp_len"), (ref_len, Nr, "ref_len")):
+        if t is not None:
+            _i32_dev(t, n, "edit_distance: " + w)
+            if t.device != hyp.device or t.numel() != n:
+                raise ValueError(f"edit_distance: {w} must hold {n} entries on the device of hyp")
+    if out is None:
+        out = torch.empty(N, 6, dtype=torch.int32, device=hyp.device)
+    elif (out.dtype != torch.int32 or out.device != hyp.device or out.dim() != 2 or out.shape[0] != N or out.shape[1] < 6 or
+          out.stride(1) != 1 or (N > 1 and out.stride(0) < 6)):
+        raise ValueError("edit_distance: out must be int32 [N, >= 6] with unit column stride on the device of hyp")
+    with _probe("edit_distance", 8.0 * N * max(hc, 1) * max(rc, 1)):
+        check(lib().tmi_edit_distance(hyp.data_ptr(), h_ld, hc, ptr(hyp_len), ref.data_ptr(), r_ld, rc, ptr(ref_len), N, R,
+                                      int(stop_id), int(skip[0]), int(skip[1]), out.data_ptr(),
+                                      out.stride(0) if N > 1 else max(out.shape[1], 6), stream()), "tmi_edit_distance")
+    return out
+
+
+def edit_counts(out, R=1, valid=None):
+    """The sums of an ``edit_distance`` result as Python floats (fp64: shards can be added) - torch reductions on the device,
+    then ONE read-back.  The error counts are over the first of every item's ``R`` rows; "n_oracle_edits" is the sum of the
+    per-item minimum of d over its rows (``valid`` bool [items, R]: over these rows only; the first row always counts)."""
+    o = out[:, :6].reshape(-1, R, 6)
+    first = o[:, 0, :].long()
+    d_all = o[:, :, 0].long()
+    if valid is not None:
+        keep = valid.clone()
+        keep[:, 0] = True
+        d_all = torch.where(keep, d_all, torch.full_like(d_all, 1 << 40))
+    sums = torch.cat([first.sum(0), (first[:, 0] == 0).sum().view(1), d_all.min(1).values.sum().view(1)])
+    d, s, dl, ins, nh, nr, ex, orc = (float(x) for x in sums.cpu().tolist())
+    return finish_edit_counts({"n_edits": d, "n_sub": s, "n_del": dl, "n_ins": ins, "n_ref_tokens": nr, "n_hyp_tokens": nh,
+                               "n_exact": ex, "n_items": float(o.shape[0]), "n_oracle_edits": orc})
+
+
+EDIT_COUNT_KEYS = ("n_edits", "n_sub", "n_del", "n_ins", "n_ref_tokens", "n_hyp_tokens", "n_exact", "n_items", "n_oracle_edits")
+
+
+def finish_edit_counts(c):
+    """Adds the two rates to a dictionary of ``EDIT_COUNT_KEYS`` sums (NaN where there is no reference token)."""
+    n = c["n_ref_tokens"]
+    c["token_error_rate"] = c["n_edits"] / n if n > 0 else float("nan")
+    c["oracle_error_rate"] = c["n_oracle_edits"] / n if n > 0 else float("nan")
+    return c
 
 
 def _ctc_logp(logp, what):

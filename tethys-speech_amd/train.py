@@ -6,6 +6,7 @@ import time
 
 import torch
 
+from . import ops
 from .data import create_dummy_dataset
 from .dist import DataParallelStrategy
 from .optim import Adam
@@ -222,8 +223,11 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
                   num_batches=40, precision="bf16", device="cuda:0", checkpoint_dir=None, log=print, seed=1234,
                   model_overrides=None, seq_len=3000, max_target_length=100, tensor_log_dir=None,
                   resume_from=None, dropout=None, loss_fetch_depth=2, eval_every=0, eval_batches=0, eval_seed=4321,
-                  mask_padding=False):
+                  mask_padding=False, eval_generate=None):
     """W:894-958: model + Adam(1e-4), dummy dataset, per-step log line, checkpoint at epoch end.
+    ``eval_generate`` (a dict of ``generate`` arguments, {} for greedy; None: off): every held-out evaluation is followed
+    by ``evaluate_generate_whisper`` on the same batches, logged as "Eval step N, TER: ..., Sub: ..., Del: ..., Ins: ..."
+    and kept in ``model.eval_generate_history``.
     ``mask_padding``: train on the reference's weighted loss (W:596-598) with decoder_attention_mask = (labels != 0), the pad
     id of the dummy pool (W:784-815), instead of the plain mean that spends 30-45 % of its positions on pad after pad; the
     evaluation batches then carry the same mask, so the "Eval step" lines report the objective being trained.
@@ -266,7 +270,7 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
             if report is not None:
                 report.log_step(i)
     do_eval = eval_every > 0 and eval_batches > 0
-    eval_history = []
+    eval_history, gen_history = [], []
     if do_eval:
         if eval_seed == seed:
             raise ValueError("eval_seed must differ from seed: the evaluation pool is held-out data")
@@ -280,6 +284,9 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
         def run_eval(at_step):
             emit(fetch.drain())  # (the step lines first, in order)
             eval_history.append((at_step, evaluate_whisper(strategy, model, eval_set, log=log, step=at_step)))
+            if eval_generate is not None:
+                gen_history.append((at_step, evaluate_generate_whisper(strategy, model, eval_set, log=log, step=at_step,
+                                                                       **eval_generate)))
     # (one replica on a GPU: the step is recorded once per batch shape and replayed from a launch plan, planned_step)
     train_step = planned_step(strategy, model, optimizer, "whisper", pipelined=True)
     last_eval = -1
@@ -304,6 +311,8 @@ def train_whisper(strategy, model_type="small", num_epochs=1, learning_rate=1e-4
         if last_eval != step:
             run_eval(step)
         model.eval_history = eval_history
+        if eval_generate is not None:
+            model.eval_generate_history = gen_history
     if report is not None:
         summ = report.save_final_results()
         report.close()
@@ -345,6 +354,39 @@ def evaluate_whisper(strategy, model, batches, log=None, step=None):
            "n_tokens": sums[2]}
     if log is not None:
         log(_eval_line(0 if step is None else step, out["loss"], out["accuracy"]))
+    return out
+
+
+def _ter_line(step, r):
+    return (f"Eval step {step}, TER: {r['token_error_rate']:.4f}, Sub: {int(r['n_sub'])}, Del: {int(r['n_del'])}, "
+            f"Ins: {int(r['n_ins'])}")
+
+
+def evaluate_generate_whisper(strategy, model, batches, log=None, step=None, **generate_kwargs):
+    """Held-out error rate of what the model GENERATES: ``model.evaluate_generate`` (which states what is compared with
+    what) over the iterable ``batches`` of (features, labels[, anything]), this replica's shard, with ``generate_kwargs``
+    passed on.  The counts (``ops.EDIT_COUNT_KEYS``; fp64) are added up on the host and, with replicas, reduced ONCE after
+    the loop with the strategy's sum reduction; an empty shard (no batches, or batches of zero rows) contributes zeros.
+    -> the dictionary of ``evaluate_generate``; ``log``: also print "Eval step {step}, TER: ..., Sub: ..., Del: ...,
+    Ins: ..." (on every rank, as the step lines)."""
+    keys = ops.EDIT_COUNT_KEYS
+    sums = [0.0] * len(keys)
+    for batch in batches:
+        features, labels = batch[0], batch[1]
+        if features.shape[0] == 0:
+            continue
+        r = model.evaluate_generate(features, labels, **generate_kwargs)
+        for i, k in enumerate(keys):
+            sums[i] += r[k]
+    if strategy is not None and (strategy.world > 1 or strategy.force_collectives):
+        t = torch.tensor(sums, dtype=torch.float64, device=model.device)
+        sums = [float(v) for v in strategy.reduce_sum(t).cpu()]
+    out = dict(zip(keys, sums))
+    if not out["n_ref_tokens"] > 0.0:
+        raise ValueError("evaluate_generate_whisper: no reference token in any batch")
+    ops.finish_edit_counts(out)
+    if log is not None:
+        log(_ter_line(0 if step is None else step, out))
     return out
 
 

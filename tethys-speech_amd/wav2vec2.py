@@ -1381,7 +1381,7 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
 
     @torch.no_grad()
     def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False, num_beams=None,
-                 lm=None, lm_alpha=0.5, lm_beta=0.0):
+                 lm=None, lm_alpha=0.5, lm_beta=0.0, edit_ops=False):
         """The CTC loss of one batch and the error rate of its greedy transcript, forward only.  ``labels`` integer
         [B, L_max] with ``label_lengths`` [B] (see ``check_ctc_args``).  Returns Python numbers, float64 on the host, so
         that shards add up: ``nll_sum`` over the feasible items, ``n_items``, ``n_infeasible`` (items with fewer frames than
@@ -1393,7 +1393,15 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         ``sequences`` / ``lengths`` of the greedy transcript.  ``num_beams`` in [2, 16]: ``n_edits`` / ``token_error_rate`` are
         those of the best sequence of the prefix beam search (``decode(num_beams=...)``) instead of the greedy transcript,
         and ``return_items`` adds its ``beam_sequences`` / ``beam_lengths``; everything else is as without it.  ``lm`` /
-        ``lm_alpha`` / ``lm_beta`` (with ``num_beams`` >= 2) as in ``decode``: the best sequence is the fused search's."""
+        ``lm_alpha`` / ``lm_beta`` (with ``num_beams`` >= 2) as in ``decode``: the best sequence is the fused search's.
+
+        ``edit_ops=True``: the error counts come from ONE tmi_edit_distance launch (include/tethys_mi.h states the rule)
+        on the device tensors the pass holds - the greedy tokens and lengths, or the beams' - so the B * T transcript
+        tokens are not copied to the host, and the result gains ``n_sub`` / ``n_del`` / ``n_ins`` (which add up to
+        ``n_edits``) and ``n_hyp_tokens``.  With ``num_beams`` it also gains ``n_oracle_edits`` / ``oracle_error_rate``: the
+        per-item minimum of the distance over the ranks the search filled (``n_beams``), the error rate a perfect
+        rescoring of the n-best list would reach.  At most 4096 frames.  False: the function as it was, the same path
+        and the same keys."""
         cfg = self.config
         K, _ = check_ctc_beam_args(cfg, num_beams)
         lm = check_ctc_lm_args(cfg, lm, lm_alpha, lm_beta, num_beams)
@@ -1404,12 +1412,14 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             nll, bad = torch.zeros(B, **c["f32"]), torch.zeros(B, **c["i32"])
             ops.ctc_forward(c["logp"], c["labels"], c["label_lens"], c["frame_lens"], cfg.ctc_blank_id, nll, bad, False)
             g = self._greedy(c)
-            # one copy of what the host needs: the tokens and lengths of the transcript, nll and the flags
-            host = torch.cat([g["tokens"].reshape(-1), g["len"], bad, nll.view(torch.int32)]).cpu()
+            # one copy of what the host needs: the tokens and lengths of the transcript, nll and the flags (with edit_ops
+            # the tokens stay on the device)
             T = c["T"]
-            tok = host[:B * T].view(B, T).numpy()
-            hl, hbad = host[B * T:B * T + B].numpy(), host[B * T + B:B * T + 2 * B].numpy()
-            hnll = host[B * T + 2 * B:].view(torch.float32).double().numpy()
+            o = 0 if edit_ops else B * T
+            host = torch.cat(([] if edit_ops else [g["tokens"].reshape(-1)]) + [g["len"], bad, nll.view(torch.int32)]).cpu()
+            tok = None if edit_ops else host[:o].view(B, T).numpy()
+            hl, hbad = host[o:o + B].numpy(), host[o + B:o + 2 * B].numpy()
+            hnll = host[o + 2 * B:].view(torch.float32).double().numpy()
             ok = hbad == 0
             lens, lab = c["label_lens_host"], c["labels_host"]
             nll_sum = float(hnll[ok].sum())
@@ -1418,16 +1428,28 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                 loss = float((item / np.maximum(lens, 1)).mean())
             else:
                 loss = float(item.sum())
-            hyp_tok, hyp_len = tok, hl
+            result = {"nll_sum": nll_sum, "n_items": float(B), "n_infeasible": float((~ok).sum()), "loss": loss}
             if K > 1:
                 bm = self._beam(c, K, lm)
-                bhost = torch.cat([bm["tokens"][:, 0].reshape(-1), bm["len"][:, 0]]).cpu()
-                hyp_tok, hyp_len = bhost[:B * T].view(B, T).numpy(), bhost[B * T:].numpy()
-            n_edits = sum(edit_distance(hyp_tok[b, :hyp_len[b]], lab[b, :lens[b]]) for b in range(B))
-            n_ref = int(lens.sum())
-            result = {"nll_sum": nll_sum, "n_items": float(B), "n_infeasible": float((~ok).sum()), "loss": loss,
-                      "n_edits": float(n_edits), "n_ref_tokens": float(n_ref),
-                      "token_error_rate": n_edits / n_ref if n_ref else float("nan")}
+            if edit_ops:
+                if K > 1:
+                    ranks = torch.arange(K, device=self.device)[None, :] < bm["n"][:, None]
+                    edits = ops.edit_distance(bm["tokens"].view(B * K, T), c["labels"], bm["len"].view(-1), c["label_lens"], R=K)
+                    counts = ops.edit_counts(edits, K, valid=ranks)
+                else:
+                    counts = ops.edit_counts(ops.edit_distance(g["tokens"], c["labels"], g["len"], c["label_lens"]))
+                keys = ("n_edits", "n_ref_tokens", "token_error_rate", "n_sub", "n_del", "n_ins", "n_hyp_tokens")
+                result.update({k: counts[k] for k in keys + (("n_oracle_edits", "oracle_error_rate") if K > 1 else ())})
+                hyp_len = bm["len"][:, 0] if K > 1 else None
+            else:
+                hyp_tok, hyp_len = tok, hl
+                if K > 1:
+                    bhost = torch.cat([bm["tokens"][:, 0].reshape(-1), bm["len"][:, 0]]).cpu()
+                    hyp_tok, hyp_len = bhost[:B * T].view(B, T).numpy(), bhost[B * T:].numpy()
+                n_edits = sum(edit_distance(hyp_tok[b, :hyp_len[b]], lab[b, :lens[b]]) for b in range(B))
+                n_ref = int(lens.sum())
+                result.update({"n_edits": float(n_edits), "n_ref_tokens": float(n_ref),
+                               "token_error_rate": n_edits / n_ref if n_ref else float("nan")})
             if return_items:
                 n = max(int(hl.max()), 0)
                 result.update(nll=nll, infeasible=bad, sequences=g["tokens"][:, :n].clone(), lengths=g["len"])

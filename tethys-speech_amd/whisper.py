@@ -1473,6 +1473,60 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return out
 
     @torch.no_grad()
+    def evaluate_generate(self, features, labels, label_lengths=None, return_items=False, **generate_kwargs):
+        """The token error rate of what ``generate`` emits for one batch against ``labels``: ``generate`` in any mode
+        (greedy, beam with ``num_return_sequences=R``, sampled, constrained, prompted, ``segment_timestamps``; every
+        keyword but ``return_token_timestamps`` and ``return_dict_in_generate`` is passed on), then ONE tmi_edit_distance
+        launch on the device tensors (include/tethys_mi.h states the rule) and one read-back of its sums.
+
+        NOT THE TRAINING SHIFT.  The labels are compared AS GIVEN with the generated tokens: no column is shifted or
+        dropped, unlike ``evaluate``'s double shift.  Which labels to pass (with or without a leading start token or
+        prompt) is the caller's business.
+
+        Hypothesis of returned row r: columns [1 + P, ..) of "sequences" (P: the prompt's length), lengths[r] - P of them
+        where the mode reports "lengths", otherwise every generated column; cut before the first EOS (``eos_token_id``,
+        else the config's; -1: no cut).  Reference of item b: labels[b, :label_lengths[b]] (int32 [B, S]; lengths None: S),
+        cut before EOS in the same way.  Under ``segment_timestamps`` the ids [timestamp_begin, vocab_size) are dropped
+        from both sides.  Row r belongs to item r // R.
+        -> Python floats (fp64 sums: add them over batches or shards and divide once): "n_edits", "n_sub", "n_del",
+        "n_ins", "n_ref_tokens", "n_hyp_tokens", "n_exact" (items with d == 0), "n_items" and "token_error_rate" =
+        n_edits / n_ref_tokens, all over the FIRST returned sequence of every item; "n_oracle_edits" and
+        "oracle_error_rate": the per-item minimum of d over its R sequences (the same as the above when R == 1).
+        ``return_items`` adds the device tensors "edits" int32 [B * R, 6] = (d, sub, del, ins, n, m) per row,
+        "sequences" and "lengths" (None where the mode reports none).  No backtrace: which token was substituted is not
+        known, only the counts; no text normalisation."""
+        cfg = self.config
+        labels = torch.as_tensor(labels)
+        lens_host = None
+        if label_lengths is not None:
+            ll = torch.as_tensor(label_lengths)
+            lens_host = ll.cpu().numpy()
+        P = check_evaluate_generate_args(cfg, tuple(labels.shape), labels.dtype, lens_host, generate_kwargs)
+        labels = labels.to(self.device)
+        B, S = labels.shape
+        eos = generate_kwargs.get("eos_token_id")
+        eos = cfg.eos_token_id if eos is None else int(eos)
+        ref_len = None if label_lengths is None else torch.as_tensor(label_lengths).to(device=self.device, dtype=torch.int32).contiguous()
+        out = self.generate(features, return_dict_in_generate=True, **generate_kwargs)
+        if not isinstance(out, dict):  # (the greedy path has no dict form of its own)
+            out = {"sequences": out}
+        seq, lengths = out["sequences"], out.get("lengths")
+        if seq.shape[0] % B:
+            raise ValueError("features and labels disagree on the batch size")
+        R = seq.shape[0] // B
+        hyp_len = None if lengths is None else (lengths.to(torch.int32) - P).contiguous()
+        skip = (0, 0)
+        if generate_kwargs.get("segment_timestamps"):
+            tb = generate_kwargs.get("timestamp_begin")
+            skip = (cfg.vocab_size - TIMESTAMP_TOKENS if tb is None else int(tb), cfg.vocab_size)
+        edits = ops.edit_distance(seq[:, 1 + P:], labels, hyp_len, ref_len, R=R, stop_id=eos, skip=skip)
+        res = ops.edit_counts(edits, R)
+        check_evaluate_generate_args(cfg, (B, S), labels.dtype, lens_host, generate_kwargs, n_ref_tokens=res["n_ref_tokens"])
+        if return_items:
+            res.update(edits=edits, sequences=seq, lengths=lengths)
+        return res
+
+    @torch.no_grad()
     def score(self, features, sequences, lengths=None, chunk_cols=None):
         """Log-probability of given token sequences under the model, as ``generate`` would have scored them.
 
@@ -1814,6 +1868,72 @@ def check_evaluate_args(cfg: WhisperConfig, labels_shape, mask_shape=None, mask_
     if mask_sum is not None and not (float(mask_sum) > 0.0 and math.isfinite(float(mask_sum))):
         raise ValueError("decoder_attention_mask[:, :-1] must have a positive, finite sum (W:598 divides by it)")
     return B, S
+
+
+def check_evaluate_generate_args(cfg: WhisperConfig, labels_shape, labels_dtype, label_lengths=None, generate_kwargs=None,
+                                 n_ref_tokens=None) -> int:
+    """The arguments of ``evaluate_generate``, checked on the host -> P, the prompt's length (0 without ``prompt_ids``).
+    labels int32 [B, S] with B >= 1 and 1 <= S <= 4096 (tmi_edit_distance's columns); ``label_lengths`` (a host array or
+    None) [B] integers in [0, S]; ``generate_kwargs`` without ``return_token_timestamps`` (the alignment pass has nothing
+    to compare) and without ``return_dict_in_generate`` (the method sets it).  ``n_ref_tokens``: the number of reference
+    tokens where the caller has it - the error rate divides by it, so it must be >= 1."""
+    if len(labels_shape) != 2:
+        raise ValueError("labels must be [B, S]")
+    B, S = int(labels_shape[0]), int(labels_shape[1])
+    if labels_dtype != torch.int32:
+        raise TypeError("labels must be int32")
+    if B < 1:
+        raise ValueError("empty batch")
+    if not 1 <= S <= ops.EDIT_MAX_COLS:
+        raise ValueError(f"the label length must be in [1, {ops.EDIT_MAX_COLS}]")
+    if label_lengths is not None:
+        ll = np.asarray(label_lengths)
+        if ll.shape != (B,) or ll.dtype.kind not in "iu":
+            raise ValueError("label_lengths must be [B] integers")
+        if int(ll.min()) < 0 or int(ll.max()) > S:
+            raise ValueError(f"label_lengths must be in [0, {S}]")
+        if int(ll.sum()) < 1:
+            raise ValueError("the labels hold no reference token: the error rate has nothing to divide by")
+    kw = generate_kwargs or {}
+    if kw.get("return_token_timestamps"):
+        raise ValueError("evaluate_generate does not take return_token_timestamps")
+    if "return_dict_in_generate" in kw:
+        raise ValueError("evaluate_generate sets return_dict_in_generate itself")
+    if n_ref_tokens is not None and not float(n_ref_tokens) >= 1.0:
+        raise ValueError("the labels hold no reference token: the error rate has nothing to divide by")
+    prompt = kw.get("prompt_ids")
+    if prompt is None:
+        return 0
+    shape = tuple(prompt.shape) if hasattr(prompt, "shape") else np.asarray(prompt).shape
+    if len(shape) not in (1, 2) or shape[-1] < 1:
+        raise ValueError("prompt_ids must be [P] or [B, P], P >= 1")
+    return int(shape[-1])
+
+
+def word_error_rate(hyp_texts, ref_texts, device="cuda:0"):
+    """Word-level error counts of hypothesis strings against reference strings, by the kernel of ``evaluate_generate``:
+    every text is split on whitespace (no other normalisation: case and punctuation count), the words of both lists are
+    numbered through one dictionary, the rows are padded and ONE tmi_edit_distance call compares pair i.  -> the
+    dictionary of ``evaluate_generate`` (R == 1), "token_error_rate" being the word error rate."""
+    hyp_texts, ref_texts = list(hyp_texts), list(ref_texts)
+    if len(hyp_texts) != len(ref_texts) or not hyp_texts:
+        raise ValueError("word_error_rate takes as many hypotheses as references, at least one")
+    ids: Dict[str, int] = {}
+    rows = [[[ids.setdefault(w, len(ids)) for w in str(t).split()] for t in texts] for texts in (hyp_texts, ref_texts)]
+    if sum(len(r) for r in rows[1]) < 1:
+        raise ValueError("the references hold no word: the error rate has nothing to divide by")
+    dev_rows = []
+    for side in rows:
+        width = max(1, max(len(r) for r in side))
+        if width > ops.EDIT_MAX_COLS:
+            raise ValueError(f"a text has more than {ops.EDIT_MAX_COLS} words")
+        pad = np.full((len(side), width), -1, np.int32)
+        for i, r in enumerate(side):
+            pad[i, :len(r)] = r
+        lens = np.asarray([len(r) for r in side], np.int32)
+        dev_rows.append((torch.from_numpy(pad).to(device), torch.from_numpy(lens).to(device)))
+    (h, hl), (r, rl) = dev_rows
+    return ops.edit_counts(ops.edit_distance(h, r, hl, rl))
 
 
 def prepare_loss_mask(cfg: WhisperConfig, labels_shape, mask, device) -> torch.Tensor:
