@@ -403,6 +403,52 @@ int tmi_edit_distance(const int32_t* hyp, int64_t hyp_ld, int64_t hyp_cols, cons
                       int64_t ref_ld, int64_t ref_cols, const int32_t* ref_len, int64_t N, int64_t R, int32_t stop_id,
                       int32_t skip_lo, int32_t skip_hi, int32_t* out, int64_t out_ld, void* stream);
 
+/* tmi_edit_align: the same table, and the alignment itself.  The inputs, the normalisation, the rule, the limits and out
+ * are those of tmi_edit_distance (out[i] holds the same six numbers as that call on the same arguments).  In addition
+ * every cell with i >= 1 and j >= 1 records which candidate won - diagonal, up or left; row 0 moves left and column 0
+ * moves up - and the path is traced from (n, m) to (0, 0).  The tie rule makes that path unique.
+ *   n_steps[i]  the length of pair i's path, = m + ins = n + del
+ *   steps       int32, element (i, k, f) at steps[i*steps_ld + 3*k + f], k < n_steps[i], in forward order (from the start
+ *               of both rows):
+ *     f = 0  the operation: 0 match, 1 substitution, 2 deletion (a reference token with no partner, a left move),
+ *            3 insertion (a hypothesis token with no partner, an up move)
+ *     f = 1  the hypothesis token's column in the caller's row as passed in - before the cut and before skipped tokens
+ *            were dropped; -1 for a deletion
+ *     f = 2  the reference token's column in the caller's row, likewise; -1 for an insertion
+ * so hyp[i*hyp_ld + steps[..1]] and ref[(i/R)*ref_ld + steps[..2]] are the tokens a step names, and the same columns
+ * index whatever else the caller keeps per token (timestamps, frames).  Entries at or past n_steps[i] are not written.
+ * A pair with an empty side is m deletions, n insertions, or no step at all.  The numbers of steps with op 1, 2, 3 are
+ * out[1], out[2], out[3].
+ * steps_ld >= 3 (hyp_cols + ref_cols), <= 2^30.  workspace: tmi_edit_align_workspace_bytes (-1 outside the limits on N and
+ * the columns), any contents; it holds the moves, two bits a cell, as the two 64-bit ballots of every 64 neighbouring
+ * cells of an anti-diagonal: 16 (hyp_cols + ref_cols + 1) ((min(hyp_cols, ref_cols) + 64) / 64) bytes a pair (csrc/edit.hip
+ * has the layout).  LDS: tmi_edit_distance's plus 2 (hyp_cols + ref_cols) bytes for the columns, 147480 at the limits.
+ * TMI_ERR_INVALID, before anything is launched and with nothing written: what tmi_edit_distance refuses; steps, n_steps or
+ * workspace NULL or not 4-byte aligned; steps_ld too small; workspace_bytes below the size function's value.
+ * The sweep is parallel; the trace is one lane's walk of at most n + m steps.
+ * No atomics, no allocation, no synchronisation: the same call gives the same bits.
+ *
+ * tmi_edit_confusion folds the steps of many pairs into a confusion table.  steps, steps_ld, n_steps as tmi_edit_align
+ * wrote them, hyp / ref with the strides, columns, N and R of that call.  first_only = 1 counts only the pairs i with
+ * i % R == 0.  1 <= V <= 1024.  counts int32 [(V + 1) (V + 1) + 1]: element (row, col) at counts[row*(V + 1) + col], the
+ * row is the reference token and the column the hypothesis token of a step, index V stands for "none" - a deletion lands
+ * in column V, an insertion in row V, a match on the diagonal.  This is the one place where a token becomes an index: a
+ * step with a token outside [0, V) (or with an op or a column that tmi_edit_align cannot have written) is not indexed
+ * but counted in the trailing element counts[(V + 1) (V + 1)].  accumulate = 0 zeroes counts first, 1 adds to what it
+ * holds.  One workgroup per pair, one global integer atomic add per step: integer adds commute, so the same call gives
+ * the same bits.  TMI_ERR_INVALID: a NULL or misaligned pointer, sizes or strides that tmi_edit_align refuses, V outside
+ * 1..1024, a flag that is not 0 or 1.
+ * Not built: text normalisation (case, punctuation, numerals), and mapping an error to a time - the columns index the
+ * caller's per-token times directly. */
+int64_t tmi_edit_align_workspace_bytes(int64_t N, int64_t hyp_cols, int64_t ref_cols);
+int tmi_edit_align(const int32_t* hyp, int64_t hyp_ld, int64_t hyp_cols, const int32_t* hyp_len, const int32_t* ref,
+                   int64_t ref_ld, int64_t ref_cols, const int32_t* ref_len, int64_t N, int64_t R, int32_t stop_id,
+                   int32_t skip_lo, int32_t skip_hi, int32_t* out, int64_t out_ld, int32_t* steps, int64_t steps_ld,
+                   int32_t* n_steps, void* workspace, int64_t workspace_bytes, void* stream);
+int tmi_edit_confusion(const int32_t* steps, int64_t steps_ld, const int32_t* n_steps, const int32_t* hyp, int64_t hyp_ld,
+                       int64_t hyp_cols, const int32_t* ref, int64_t ref_ld, int64_t ref_cols, int64_t N, int64_t R,
+                       int32_t first_only, int64_t V, int32_t* counts, int32_t accumulate, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * CTC inference (wav2vec2.py Wav2Vec2ForCTC: V:940-1001, forward only): the head's log-softmax, the greedy collapse, the
  * loss and the forced alignment.  All arithmetic is fp32; `blank` is an argument; -inf is the additive zero, and a

@@ -22,6 +22,9 @@ Prints one JSON line per clip: the token ids, with ``--timestamps`` their start 
 log-probability, and with labels the nll, the edit distance of the transcript and the aligned times; then one summary line.
 ``--edit_ops`` (with ``--labels``): the error counts come from the device kernel (``evaluate(edit_ops=True)``) and the
 summary line adds the substitutions, deletions and insertions and, with ``--num_beams``, the n-best oracle error rate.
+``--confusion PATH.npy`` (with ``--edit_ops``): the confusion table of the transcripts against the labels, int64
+[vocab_size + 1, vocab_size + 1] (row = the label, column = the transcript's token, the last index = none), is folded on the
+device (``evaluate(confusion=True)``) and saved.
 There is no tokenizer: ids in, ids out.
 """
 import argparse
@@ -63,10 +66,13 @@ def main(argv=None):
     parser.add_argument("--lm_beta", type=float, default=0.0, help="bonus per token")
     parser.add_argument("--edit_ops", action="store_true",
                         help="with --labels: count substitutions / deletions / insertions on the device (and the n-best oracle)")
+    parser.add_argument("--confusion", default=None, help="with --labels --edit_ops: save the confusion table as this .npy file")
     parser.add_argument("--build_lm", default=None, help="file of token ids, one line per sequence: build a table and exit")
     parser.add_argument("--lm_order", type=int, default=2, help="with --build_lm: the order of the table (1..4)")
     parser.add_argument("--lm_out", default=None, help="with --build_lm: where the .npy table goes")
     args = parser.parse_args(argv)
+    if args.confusion and not (args.edit_ops and args.labels):
+        parser.error("--confusion comes with --labels and --edit_ops")
 
     import numpy as np
     if args.build_lm:
@@ -134,7 +140,8 @@ def main(argv=None):
             labels[i, :len(r)] = torch.tensor(r, dtype=torch.int64)
         lens = [len(r) for r in rows]
         ev = model.evaluate(audio, labels, lens, attention_mask=mask, return_items=True,
-                            num_beams=args.num_beams if beam else None, edit_ops=args.edit_ops, **lm_kw)
+                            num_beams=args.num_beams if beam else None, edit_ops=args.edit_ops, confusion=bool(args.confusion),
+                            **lm_kw)
         al = model.align(audio, labels, lens, attention_mask=mask)
         if args.posteriors:
             post = model.posteriors(audio, labels, lens, attention_mask=mask)
@@ -181,6 +188,9 @@ def main(argv=None):
         if args.edit_ops:
             summary.update({k: ev[k] for k in ("n_sub", "n_del", "n_ins", "n_hyp_tokens", "n_oracle_edits", "oracle_error_rate")
                             if k in ev})
+        if args.confusion:
+            np.save(args.confusion, ev["confusion"].cpu().numpy())
+            summary["confusion"] = args.confusion
     print(json.dumps(summary), flush=True)
 
 

@@ -9,7 +9,9 @@ dataset).  Prints loss, accuracy and perplexity = exp(loss) and writes them as o
 ``--generate`` also runs ``generate`` on the same batches (``--num_beams K``, ``--max_length n``, ``--nbest R`` returned
 sequences per item) and compares what it emits with the labels (``train.evaluate_generate_whisper``,
 ``model.evaluate_generate``): the result file gains the error counts, ``token_error_rate`` and the n-best
-``oracle_error_rate``.  Without the flag nothing changes.
+``oracle_error_rate``.  Without the flag nothing changes.  ``--alignments PATH`` (with ``--generate``) also writes one JSON
+line per item to PATH: which tokens were matched, substituted, deleted and inserted, with their positions
+(``whisper.alignment_record``; the launch is tmi_edit_align instead of tmi_edit_distance, the counts are the same).
 """
 import argparse
 import json
@@ -40,9 +42,10 @@ def main(argv=None):
     parser.add_argument("--num_beams", type=int, default=None, help="with --generate: beam search with this many beams")
     parser.add_argument("--max_length", type=int, default=None, help="with --generate: generated tokens per item at most")
     parser.add_argument("--nbest", type=int, default=1, help="with --generate --num_beams: returned sequences per item")
+    parser.add_argument("--alignments", default=None, help="with --generate: write one JSON line per item with its aligned tokens")
     args = parser.parse_args(argv)
-    if not args.generate and (args.num_beams is not None or args.max_length is not None or args.nbest != 1):
-        parser.error("--num_beams, --max_length and --nbest come with --generate")
+    if not args.generate and (args.num_beams is not None or args.max_length is not None or args.nbest != 1 or args.alignments):
+        parser.error("--num_beams, --max_length, --nbest and --alignments come with --generate")
     if args.batch_size < 1 or args.num_batches < 1:
         parser.error("--batch_size and --num_batches must be at least 1")
 
@@ -76,8 +79,13 @@ def main(argv=None):
         if args.nbest != 1:
             kw["num_return_sequences"] = args.nbest
         t0 = time.time()
-        gen = train.evaluate_generate_whisper(None, model, batches, log=print, **kw)
+        items = [] if args.alignments else None
+        gen = train.evaluate_generate_whisper(None, model, batches, log=print, alignments=items, **kw)
         out.update(gen)
+        if args.alignments:
+            with open(args.alignments, "w") as f:
+                f.writelines(whisper.alignment_record(i, al) + "\n" for i, al in enumerate(items))
+            out.update(alignments=args.alignments)
         out.update(generate=kw, generate_seconds=round(time.time() - t0, 4))
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)

@@ -192,6 +192,11 @@ SIGNATURES = {
                                 c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     "tmi_edit_distance": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
                                   c_i64, c_vp]),
+    "tmi_edit_align_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "tmi_edit_align": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp,
+                               c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
+    "tmi_edit_confusion": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_vp,
+                                   c_i32, c_vp]),
 }
 
 ABI_VERSION = 31

@@ -3,7 +3,8 @@
 Each function resolves pointers / element strides from torch tensors (device memory is
 PyTorch's caching allocator: plumbing) and launches the HIP kernel on torch's current
 stream.  Nothing here computes on the host or falls back to torch ops (``edit_counts`` alone sums the integer table of
-``edit_distance`` with torch reductions on the device, ahead of its one read-back).
+``edit_distance`` with torch reductions on the device, ahead of its one read-back, and ``edit_alignment_items`` gathers the
+tokens that ``edit_align``'s steps name ahead of its one).
 """
 from __future__ import annotations
 
@@ -536,6 +537,132 @@ def edit_distance(hyp, ref, hyp_len=None, ref_len=None, R=1, stop_id=-1, skip=(0
                                       int(stop_id), int(skip[0]), int(skip[1]), out.data_ptr(),
                                       out.stride(0) if N > 1 else max(out.shape[1], 6), stream()), "tmi_edit_distance")
     return out
+
+
+EDIT_ALIGN_WORKSPACE_CAP = 256 << 20  # bytes of workspace ``edit_align`` allocates at most, when more than one chunk would need more
+
+
+def edit_align_workspace_elems(N: int, hyp_cols: int, ref_cols: int) -> int:
+    """int32 elements of tmi_edit_align's workspace (tmi_edit_align_workspace_bytes / 4)."""
+    n = int(lib().tmi_edit_align_workspace_bytes(N, hyp_cols, ref_cols))
+    if n < 0:
+        raise ValueError(f"tmi_edit_align takes 1 <= N <= 65535 pairs of at most {EDIT_MAX_COLS} columns a side, got {N} x "
+                         f"{hyp_cols} x {ref_cols}")
+    return n // 4
+
+
+def edit_align_chunks(N: int, R: int, pair_bytes: int, cap: int = EDIT_ALIGN_WORKSPACE_CAP):
+    """The (first pair, pairs) pieces in which ``edit_align`` runs N pairs so that pairs * pair_bytes stays under ``cap``:
+    every piece is a multiple of R (the R hypotheses of a reference stay together) and at least R, whatever the cap."""
+    per = max(R, cap // max(pair_bytes, 1) // R * R)
+    return [(s, min(per, N - s)) for s in range(0, N, per)]
+
+
+def _edit_align_args(hyp, ref, hyp_len, ref_len, R, what):
+    N, hc, h_ld = _edit_rows(hyp, "hyp")
+    Nr, rc, r_ld = _edit_rows(ref, "ref")
+    R = int(R)
+    if ref.device != hyp.device:
+        raise ValueError(f"{what}: hyp and ref are on different devices")
+    if N < 1 or N > 65535 or R < 1 or Nr * R != N:
+        raise ValueError(f"{what}: 1 <= N <= 65535 hypotheses, R >= 1 per reference; got {N} against {Nr} with R = {R}")
+    for t, n, w in ((hyp_len, N, "hyp_len"), (ref_len, Nr, "ref_len")):
+        if t is not None:
+            _i32_dev(t, n, f"{what}: {w}")
+            if t.device != hyp.device or t.numel() != n:
+                raise ValueError(f"{what}: {w} must hold {n} entries on the device of hyp")
+    return N, hc, h_ld, rc, r_ld, R
+
+
+def edit_align(hyp, ref, hyp_len=None, ref_len=None, R=1, stop_id=-1, skip=(0, 0), workspace=None):
+    """``edit_distance`` with the alignment (tmi_edit_align in include/tethys_mi.h): the same arguments and host checks, ->
+    ``(out, steps, n_steps)``: ``out`` int32 [N, 6] as ``edit_distance`` gives it, ``steps`` int32 [N, hyp_cols + ref_cols, 3]
+    of which the first ``n_steps[i]`` rows of pair i are written - (op, column in hyp, column in ref), op 0 match,
+    1 substitution, 2 deletion, 3 insertion, the columns those of the tensors as passed in, -1 for the missing side -
+    and ``n_steps`` int32 [N].  ``workspace``: int32, ``edit_align_workspace_elems(N, hyp_cols, ref_cols)`` entries, any
+    contents, for ONE launch; None: allocated here, and the pairs run in the pieces of ``edit_align_chunks`` so that it
+    stays under ``EDIT_ALIGN_WORKSPACE_CAP`` (pairs are independent: the pieces cannot change a result)."""
+    N, hc, h_ld, rc, r_ld, R = _edit_align_args(hyp, ref, hyp_len, ref_len, R, "edit_align")
+    dev = hyp.device
+    out = torch.empty(N, 6, dtype=torch.int32, device=dev)
+    steps = torch.empty(N, max(hc + rc, 1), 3, dtype=torch.int32, device=dev)
+    n_steps = torch.empty(N, dtype=torch.int32, device=dev)
+    if workspace is None:
+        pieces = edit_align_chunks(N, R, 4 * edit_align_workspace_elems(1, hc, rc))
+        workspace = torch.empty(edit_align_workspace_elems(pieces[0][1], hc, rc), dtype=torch.int32, device=dev)
+    else:
+        pieces = [(0, N)]
+        _i32_dev(workspace, edit_align_workspace_elems(N, hc, rc), "edit_align: workspace")
+        if workspace.device != dev:
+            raise ValueError("edit_align: workspace must be on the device of hyp")
+    for s, c in pieces:
+        with _probe("edit_align", 8.0 * c * max(hc, 1) * max(rc, 1)):
+            check(lib().tmi_edit_align(hyp[s:s + c].data_ptr(), h_ld, hc, ptr(None if hyp_len is None else hyp_len[s:s + c]),
+                                       ref[s // R:(s + c) // R].data_ptr(), r_ld, rc,
+                                       ptr(None if ref_len is None else ref_len[s // R:(s + c) // R]), c, R, int(stop_id),
+                                       int(skip[0]), int(skip[1]), out[s:s + c].data_ptr(), 6, steps[s:s + c].data_ptr(),
+                                       steps.stride(0), n_steps[s:s + c].data_ptr(), workspace.data_ptr(), workspace.numel() * 4,
+                                       stream()), "tmi_edit_align")
+    return out, steps[:, :hc + rc], n_steps
+
+
+def edit_confusion(steps, n_steps, hyp, ref, V, R=1, first_only=True, counts=None):
+    """The confusion table of the alignments ``edit_align`` returned for ``hyp`` and ``ref`` (tmi_edit_confusion in
+    include/tethys_mi.h): ``counts`` int32 [(V + 1) * (V + 1) + 1] on the device - row = the reference token, column = the
+    hypothesis token, index V = none, the trailing element = the steps whose tokens lie outside [0, V).  ``counts`` None:
+    a fresh, zeroed table; given: the steps are ADDED to it (batches sum on the device).  ``first_only``: only the first of
+    every reference's R hypotheses counts.  -> counts (``counts[:-1].view(V + 1, V + 1)`` is the table)."""
+    N, hc, h_ld, rc, r_ld, R = _edit_align_args(hyp, ref, None, None, R, "edit_confusion")
+    V = int(V)
+    if V < 1 or V > 1024:
+        raise ValueError(f"edit_confusion: 1 <= V <= 1024, got {V}")
+    if (not isinstance(steps, torch.Tensor) or steps.dtype != torch.int32 or steps.device != hyp.device or steps.dim() != 3 or
+            tuple(steps.shape) != (N, hc + rc, 3) or (hc + rc > 0 and (steps.stride(2) != 1 or steps.stride(1) != 3)) or
+            (N > 1 and steps.stride(0) < 3 * (hc + rc))):
+        raise ValueError(f"edit_confusion: steps must be int32 [{N}, {hc + rc}, 3] with dense rows on the device of hyp")
+    _i32_dev(n_steps, N, "edit_confusion: n_steps")
+    size = (V + 1) * (V + 1) + 1
+    accumulate = counts is not None
+    if counts is None:
+        counts = torch.empty(size, dtype=torch.int32, device=hyp.device)
+    else:
+        _i32_dev(counts, size, "edit_confusion: counts")
+    if n_steps.device != hyp.device or n_steps.numel() != N or counts.device != hyp.device or counts.numel() != size:
+        raise ValueError(f"edit_confusion: n_steps [{N}] and counts [{size}] must be on the device of hyp")
+    steps_ld = steps.stride(0) if N > 1 else max(3 * (hc + rc), steps.stride(0) if hc + rc > 0 else 3)
+    with _probe("edit_confusion", 12.0 * N * max(hc + rc, 1)):
+        check(lib().tmi_edit_confusion(steps.data_ptr(), steps_ld, n_steps.data_ptr(), hyp.data_ptr(), h_ld, hc, ref.data_ptr(),
+                                       r_ld, rc, N, R, 1 if first_only else 0, V, counts.data_ptr(), 1 if accumulate else 0,
+                                       stream()), "tmi_edit_confusion")
+    return counts
+
+
+EDIT_OPS = ("match", "substitution", "deletion", "insertion")  # the op codes 0..3 of tmi_edit_align's steps
+
+
+def edit_alignment_items(steps, n_steps, hyp, ref, R=1):
+    """The alignments of ``edit_align`` on the host, for the FIRST of every reference's R hypotheses: per item the list of
+    (op, hyp_token, ref_token, hyp_column, ref_column) in order, None for the missing side.  The tokens are gathered by
+    the steps' columns with torch on the device, then everything comes over in ONE read-back."""
+    st, ns, h = steps[::R], n_steps[::R], hyp[::R]
+    B, S = st.shape[0], st.shape[1]
+    if S == 0:
+        return [[] for _ in range(B)]
+    live = torch.arange(S, device=st.device)[None, :] < ns[:, None]
+
+    def tokens(rows, col):
+        if rows.shape[1] == 0:
+            return torch.zeros(B, S, dtype=torch.int32, device=st.device)
+        return torch.gather(rows, 1, torch.where(live & (col >= 0), col, torch.zeros_like(col)).long().clamp_(max=rows.shape[1] - 1))
+
+    host = torch.cat([st.reshape(B, 3 * S), tokens(h, st[:, :, 1]), tokens(ref, st[:, :, 2]), ns[:, None]], 1).cpu().numpy()
+    items = []
+    for b in range(B):
+        row, n = host[b], int(host[b, 5 * S])
+        items.append([(int(row[3 * k]), None if row[3 * k + 1] < 0 else int(row[3 * S + k]), None if row[3 * k + 2] < 0 else int(row[4 * S + k]),
+                       None if row[3 * k + 1] < 0 else int(row[3 * k + 1]), None if row[3 * k + 2] < 0 else int(row[3 * k + 2]))
+                      for k in range(n)])
+    return items
 
 
 def edit_counts(out, R=1, valid=None):

@@ -362,13 +362,16 @@ def _ter_line(step, r):
             f"Ins: {int(r['n_ins'])}")
 
 
-def evaluate_generate_whisper(strategy, model, batches, log=None, step=None, **generate_kwargs):
+def evaluate_generate_whisper(strategy, model, batches, log=None, step=None, alignments=None, **generate_kwargs):
     """Held-out error rate of what the model GENERATES: ``model.evaluate_generate`` (which states what is compared with
     what) over the iterable ``batches`` of (features, labels[, anything]), this replica's shard, with ``generate_kwargs``
     passed on.  The counts (``ops.EDIT_COUNT_KEYS``; fp64) are added up on the host and, with replicas, reduced ONCE after
     the loop with the strategy's sum reduction; an empty shard (no batches, or batches of zero rows) contributes zeros.
     -> the dictionary of ``evaluate_generate``; ``log``: also print "Eval step {step}, TER: ..., Sub: ..., Del: ...,
-    Ins: ..." (on every rank, as the step lines)."""
+    Ins: ..." (on every rank, as the step lines).  ``alignments``: a list that receives every item's "alignment" of
+    ``evaluate_generate(return_alignment=True)`` in order (this replica's items; None: the call as it was)."""
+    if alignments is not None:
+        generate_kwargs = dict(generate_kwargs, return_alignment=True)
     keys = ops.EDIT_COUNT_KEYS
     sums = [0.0] * len(keys)
     for batch in batches:
@@ -378,6 +381,8 @@ def evaluate_generate_whisper(strategy, model, batches, log=None, step=None, **g
         r = model.evaluate_generate(features, labels, **generate_kwargs)
         for i, k in enumerate(keys):
             sums[i] += r[k]
+        if alignments is not None:
+            alignments.extend(r["alignment"])
     if strategy is not None and (strategy.world > 1 or strategy.force_collectives):
         t = torch.tensor(sums, dtype=torch.float64, device=model.device)
         sums = [float(v) for v in strategy.reduce_sum(t).cpu()]

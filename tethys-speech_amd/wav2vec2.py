@@ -1107,6 +1107,16 @@ def check_ctc_beam_args(cfg: Wav2Vec2Config, num_beams=None, num_return_sequence
     return int(K), int(num_return_sequences)
 
 
+def check_ctc_confusion_args(cfg: Wav2Vec2Config, confusion=False, edit_ops=False) -> bool:
+    """Host validation of ``Wav2Vec2ForCTC.evaluate``'s ``confusion`` (no GPU needed): a bool; True only together with
+    ``edit_ops=True`` - the table is folded from the alignment of the kernel path, the host loop has none.  -> the flag."""
+    if not isinstance(confusion, (bool, np.bool_)):
+        raise TypeError("confusion must be a bool (the CLI's path is not the flag)")
+    if confusion and not edit_ops:
+        raise ValueError("confusion=True needs edit_ops=True (the table comes from tmi_edit_align's steps)")
+    return bool(confusion)
+
+
 CTC_LM_MAX_ORDER = 4          # tmi_ctc_beam_lm: a dense table of V^order entries ...
 CTC_LM_MAX_ENTRIES = 1 << 24  # ... of at most this many
 
@@ -1381,7 +1391,7 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
 
     @torch.no_grad()
     def evaluate(self, inputs, labels, label_lengths=None, attention_mask=None, return_items=False, num_beams=None,
-                 lm=None, lm_alpha=0.5, lm_beta=0.0, edit_ops=False):
+                 lm=None, lm_alpha=0.5, lm_beta=0.0, edit_ops=False, confusion=False):
         """The CTC loss of one batch and the error rate of its greedy transcript, forward only.  ``labels`` integer
         [B, L_max] with ``label_lengths`` [B] (see ``check_ctc_args``).  Returns Python numbers, float64 on the host, so
         that shards add up: ``nll_sum`` over the feasible items, ``n_items``, ``n_infeasible`` (items with fewer frames than
@@ -1401,8 +1411,15 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         ``n_edits``) and ``n_hyp_tokens``.  With ``num_beams`` it also gains ``n_oracle_edits`` / ``oracle_error_rate``: the
         per-item minimum of the distance over the ranks the search filled (``n_beams``), the error rate a perfect
         rescoring of the n-best list would reach.  At most 4096 frames.  False: the function as it was, the same path
-        and the same keys."""
+        and the same keys.
+
+        ``confusion=True`` (with ``edit_ops=True``): the launch is tmi_edit_align instead, with the same counts, and
+        tmi_edit_confusion folds its steps on the device; the result gains ``confusion``, an int64 tensor [V + 1, V + 1] on
+        the device - row = the label, column = the transcript's token, index V = none (deletions in column V, insertions
+        in row V) - of every item's transcript, with ``num_beams`` of its best beam only.  The transcript tokens still do
+        not go to the host.  Tables of batches add."""
         cfg = self.config
+        confusion = check_ctc_confusion_args(cfg, confusion, edit_ops)
         K, _ = check_ctc_beam_args(cfg, num_beams)
         lm = check_ctc_lm_args(cfg, lm, lm_alpha, lm_beta, num_beams)
         if K > 1:
@@ -1432,12 +1449,18 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             if K > 1:
                 bm = self._beam(c, K, lm)
             if edit_ops:
+                hyp, hyp_lens = (bm["tokens"].view(B * K, T), bm["len"].view(-1)) if K > 1 else (g["tokens"], g["len"])
+                if confusion:
+                    edits, steps, n_steps = ops.edit_align(hyp, c["labels"], hyp_lens, c["label_lens"], R=K)
+                    table = ops.edit_confusion(steps, n_steps, hyp, c["labels"], cfg.vocab_size, R=K, first_only=True)
+                    result["confusion"] = table[:-1].view(cfg.vocab_size + 1, cfg.vocab_size + 1).long()
+                else:
+                    edits = ops.edit_distance(hyp, c["labels"], hyp_lens, c["label_lens"], R=K)
                 if K > 1:
                     ranks = torch.arange(K, device=self.device)[None, :] < bm["n"][:, None]
-                    edits = ops.edit_distance(bm["tokens"].view(B * K, T), c["labels"], bm["len"].view(-1), c["label_lens"], R=K)
                     counts = ops.edit_counts(edits, K, valid=ranks)
                 else:
-                    counts = ops.edit_counts(ops.edit_distance(g["tokens"], c["labels"], g["len"], c["label_lens"]))
+                    counts = ops.edit_counts(edits)
                 keys = ("n_edits", "n_ref_tokens", "token_error_rate", "n_sub", "n_del", "n_ins", "n_hyp_tokens")
                 result.update({k: counts[k] for k in keys + (("n_oracle_edits", "oracle_error_rate") if K > 1 else ())})
                 hyp_len = bm["len"][:, 0] if K > 1 else None

@@ -43,6 +43,7 @@ add per candidate and correctly rounded divisions.
 """
 from __future__ import annotations
 
+import json
 import math
 import os
 from dataclasses import dataclass
@@ -1473,7 +1474,8 @@ class WhisperForConditionalGeneration(KernelBlocks):
         return out
 
     @torch.no_grad()
-    def evaluate_generate(self, features, labels, label_lengths=None, return_items=False, **generate_kwargs):
+    def evaluate_generate(self, features, labels, label_lengths=None, return_items=False, return_alignment=False,
+                          **generate_kwargs):
         """The token error rate of what ``generate`` emits for one batch against ``labels``: ``generate`` in any mode
         (greedy, beam with ``num_return_sequences=R``, sampled, constrained, prompted, ``segment_timestamps``; every
         keyword but ``return_token_timestamps`` and ``return_dict_in_generate`` is passed on), then ONE tmi_edit_distance
@@ -1493,15 +1495,24 @@ class WhisperForConditionalGeneration(KernelBlocks):
         n_edits / n_ref_tokens, all over the FIRST returned sequence of every item; "n_oracle_edits" and
         "oracle_error_rate": the per-item minimum of d over its R sequences (the same as the above when R == 1).
         ``return_items`` adds the device tensors "edits" int32 [B * R, 6] = (d, sub, del, ins, n, m) per row,
-        "sequences" and "lengths" (None where the mode reports none).  No backtrace: which token was substituted is not
-        known, only the counts; no text normalisation."""
+        "sequences" and "lengths" (None where the mode reports none).  No text normalisation.
+
+        ``return_alignment=True``: ONE tmi_edit_align launch takes the place of the tmi_edit_distance launch (the same
+        counts) and, after one more read-back, the result gains "alignment": per item, for its FIRST returned sequence,
+        a dictionary "steps": [(op, hyp_token, ref_token)] in order - op 0 match, 1 substitution, 2 deletion, 3 insertion
+        (``ops.EDIT_OPS`` names them), None for the missing side -, "hyp_positions": the column of every step's
+        hypothesis token in that row of "sequences" (None for a deletion) and "ref_positions": the column of its
+        reference token in ``labels`` (None for an insertion).  The positions index whatever else is kept per token
+        (``token_timestamps`` of a later ``generate`` call on the same row).  With ``return_items`` also the device tensors
+        "steps" int32 [B * R, n_cols + S, 3] (columns relative to sequences[:, 1 + P:]) and "n_steps" int32 [B * R]."""
         cfg = self.config
         labels = torch.as_tensor(labels)
         lens_host = None
         if label_lengths is not None:
             ll = torch.as_tensor(label_lengths)
             lens_host = ll.cpu().numpy()
-        P = check_evaluate_generate_args(cfg, tuple(labels.shape), labels.dtype, lens_host, generate_kwargs)
+        P = check_evaluate_generate_args(cfg, tuple(labels.shape), labels.dtype, lens_host, generate_kwargs,
+                                         return_alignment=return_alignment)
         labels = labels.to(self.device)
         B, S = labels.shape
         eos = generate_kwargs.get("eos_token_id")
@@ -1519,11 +1530,21 @@ class WhisperForConditionalGeneration(KernelBlocks):
         if generate_kwargs.get("segment_timestamps"):
             tb = generate_kwargs.get("timestamp_begin")
             skip = (cfg.vocab_size - TIMESTAMP_TOKENS if tb is None else int(tb), cfg.vocab_size)
-        edits = ops.edit_distance(seq[:, 1 + P:], labels, hyp_len, ref_len, R=R, stop_id=eos, skip=skip)
+        if return_alignment:
+            edits, steps, n_steps = ops.edit_align(seq[:, 1 + P:], labels, hyp_len, ref_len, R=R, stop_id=eos, skip=skip)
+        else:
+            edits = ops.edit_distance(seq[:, 1 + P:], labels, hyp_len, ref_len, R=R, stop_id=eos, skip=skip)
         res = ops.edit_counts(edits, R)
         check_evaluate_generate_args(cfg, (B, S), labels.dtype, lens_host, generate_kwargs, n_ref_tokens=res["n_ref_tokens"])
+        if return_alignment:
+            items = ops.edit_alignment_items(steps, n_steps, seq[:, 1 + P:], labels, R)
+            res["alignment"] = [{"steps": [(op, h, r) for op, h, r, _, _ in it],
+                                 "hyp_positions": [None if hc is None else hc + 1 + P for _, _, _, hc, _ in it],
+                                 "ref_positions": [rc for _, _, _, _, rc in it]} for it in items]
         if return_items:
             res.update(edits=edits, sequences=seq, lengths=lengths)
+            if return_alignment:
+                res.update(steps=steps, n_steps=n_steps)
         return res
 
     @torch.no_grad()
@@ -1871,12 +1892,15 @@ def check_evaluate_args(cfg: WhisperConfig, labels_shape, mask_shape=None, mask_
 
 
 def check_evaluate_generate_args(cfg: WhisperConfig, labels_shape, labels_dtype, label_lengths=None, generate_kwargs=None,
-                                 n_ref_tokens=None) -> int:
+                                 n_ref_tokens=None, return_alignment=False) -> int:
     """The arguments of ``evaluate_generate``, checked on the host -> P, the prompt's length (0 without ``prompt_ids``).
     labels int32 [B, S] with B >= 1 and 1 <= S <= 4096 (tmi_edit_distance's columns); ``label_lengths`` (a host array or
     None) [B] integers in [0, S]; ``generate_kwargs`` without ``return_token_timestamps`` (the alignment pass has nothing
     to compare) and without ``return_dict_in_generate`` (the method sets it).  ``n_ref_tokens``: the number of reference
-    tokens where the caller has it - the error rate divides by it, so it must be >= 1."""
+    tokens where the caller has it - the error rate divides by it, so it must be >= 1.  ``return_alignment``: a bool (a
+    path or a count passed by mistake is refused, not taken for True)."""
+    if not isinstance(return_alignment, (bool, np.bool_)):
+        raise TypeError("return_alignment must be a bool")
     if len(labels_shape) != 2:
         raise ValueError("labels must be [B, S]")
     B, S = int(labels_shape[0]), int(labels_shape[1])
@@ -1910,11 +1934,15 @@ def check_evaluate_generate_args(cfg: WhisperConfig, labels_shape, labels_dtype,
     return int(shape[-1])
 
 
-def word_error_rate(hyp_texts, ref_texts, device="cuda:0"):
+def word_error_rate(hyp_texts, ref_texts, device="cuda:0", return_alignment=False):
     """Word-level error counts of hypothesis strings against reference strings, by the kernel of ``evaluate_generate``:
     every text is split on whitespace (no other normalisation: case and punctuation count), the words of both lists are
     numbered through one dictionary, the rows are padded and ONE tmi_edit_distance call compares pair i.  -> the
-    dictionary of ``evaluate_generate`` (R == 1), "token_error_rate" being the word error rate."""
+    dictionary of ``evaluate_generate`` (R == 1), "token_error_rate" being the word error rate.  ``return_alignment=True``:
+    the call is tmi_edit_align instead and the result gains "alignment": per pair the list of (op, hyp_word, ref_word) in
+    order, op as in ``ops.EDIT_OPS``, None for the missing side."""
+    if not isinstance(return_alignment, (bool, np.bool_)):
+        raise TypeError("return_alignment must be a bool")
     hyp_texts, ref_texts = list(hyp_texts), list(ref_texts)
     if len(hyp_texts) != len(ref_texts) or not hyp_texts:
         raise ValueError("word_error_rate takes as many hypotheses as references, at least one")
@@ -1933,7 +1961,24 @@ def word_error_rate(hyp_texts, ref_texts, device="cuda:0"):
         lens = np.asarray([len(r) for r in side], np.int32)
         dev_rows.append((torch.from_numpy(pad).to(device), torch.from_numpy(lens).to(device)))
     (h, hl), (r, rl) = dev_rows
-    return ops.edit_counts(ops.edit_distance(h, r, hl, rl))
+    if not return_alignment:
+        return ops.edit_counts(ops.edit_distance(h, r, hl, rl))
+    edits, steps, n_steps = ops.edit_align(h, r, hl, rl)
+    res = ops.edit_counts(edits)
+    words = list(ids)
+    res["alignment"] = [[(op, None if a is None else words[a], None if b is None else words[b]) for op, a, b, _, _ in it]
+                        for it in ops.edit_alignment_items(steps, n_steps, h, r)]
+    return res
+
+
+def alignment_record(item: int, alignment) -> str:
+    """One JSON line for one item's "alignment" of ``evaluate_generate(return_alignment=True)``: {"item", "n_steps",
+    "n_errors", "steps": [[op name, hyp_token, ref_token, hyp_position, ref_position], ...]} with null for the missing
+    side (``speech_jobs/whisper_eval.py --alignments`` writes these)."""
+    steps = [[ops.EDIT_OPS[op], h, r, hp, rp] for (op, h, r), hp, rp in
+             zip(alignment["steps"], alignment["hyp_positions"], alignment["ref_positions"])]
+    return json.dumps({"item": int(item), "n_steps": len(steps), "n_errors": sum(1 for s in steps if s[0] != ops.EDIT_OPS[0]),
+                       "steps": steps})
 
 
 def prepare_loss_mask(cfg: WhisperConfig, labels_shape, mask, device) -> torch.Tensor:
