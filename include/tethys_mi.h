@@ -1130,6 +1130,64 @@ int tmi_masked_mean_pool(const void* x, int32_t x_dtype, const float* mask, floa
                          void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The sequence-classification head (Wav2Vec2ForSequenceClassification, V:1045-1056) on pooled features, fp32 throughout.
+ * N rows; row r of the call reads pooled[s * ld_x .. + H) with s = row_index ? row_index[r] : r (row_index int32 [N] or
+ * NULL; n_src = the rows `pooled` holds: an index outside [0, n_src) reads as a row of zeros).  Wp [H, P], bp [P],
+ * Wc [P, C], bc [C] contiguous.
+ *
+ * tmi_cls_head_fwd, per row r:
+ *   pre[c]    = (fmaf(x[h], Wp[h][c], .) over h = 0 .. H-1 in that order, from 0) + bp[c]
+ *   z[c]      = tanhf(pre[c])
+ *   y[c]      = keep(seed, r, c) ? z[c] * 65536/(65536-thr) : 0    tmi_dropout's generator exactly: stream 0, row = r (the
+ *               position in THIS call, not the source row), column = c, 16-bit draws, thr = round(p * 65536); p == 0: y = z
+ *               and nothing is hashed (the seed is ignored)
+ *   logits[k] = (fmaf(y[c], Wc[c][k], .) over c = 0 .. P-1 in that order, from 0) + bc[k]
+ *   m = max_k logits[k];  s = sum_k expf(logits[k] - m): lane l of a wave adds its classes l, l + 64, .. in ascending
+ *               order from 0, then the xor butterfly 32, 16, .., 1 folds the 64 lanes;  lse = m + logf(s)
+ *   log_probs[k] = logits[k] - lse
+ *   pred      = the lowest k with logits[k] == m (numeric comparison: -0 ties with +0)
+ *   labelled rows (labels non-NULL and 0 <= labels[r] < C):
+ *     nll        = -(logits[label] - lse)       (= -log_probs[label], bit for bit)
+ *     label_rank = #{k : logits[k] > logits[label]} + #{k < label : logits[k] == logits[label]}
+ *                  so label_rank < n means "the label is in the top n", and label_rank == 0 exactly when pred == label
+ *     confusion[label * ld_conf + pred] += 1    (int64, global integer atomics: order cannot change the result; the
+ *                  caller zeroes the table, or passes the previous one in to accumulate)
+ *   unlabelled rows: nll = 0, label_rank = -1, no table update.
+ * logits [N, ld_logits] and pred [N] are always written; z [N, ld_z] (the tanh output BEFORE dropout: what the backward
+ * takes), log_probs [N, ld_lp], nll [N], label_rank [N] and confusion may be NULL.  Nothing else is written; no
+ * floating-point atomic: the same call gives the same bits.
+ *
+ * tmi_cls_head_bwd: the gradients of loss = (sum over labelled rows of nll) / n_valid, from the z and log_probs the
+ * forward saved and the same (p, seed); no mask is stored, y is recomputed.
+ *   n_valid   = the number of labelled rows, counted on the device (integer)
+ *   loss[0]   = (thread t of 256 adds -log_probs[r][label] of rows t, t + 256, .. ascending; wave butterflies; the four wave
+ *               sums in order) / n_valid; 0 when n_valid == 0
+ *   dlogits[r][k] = (expf(log_probs[r][k]) - (k == label)) * (1 / n_valid) on labelled rows, 0 elsewhere
+ *   gbc[k]    = sum_r dlogits[r][k]               gWc[c][k] = fmaf(y[r][c], dlogits[r][k], .)  both over r ascending (*)
+ *   dy[r][c]  = fmaf(dlogits[r][k], Wc[c][k], .) over k ascending
+ *   dpre[r][c] = (keep(seed, r, c) ? dy * scale : 0) * fmaf(-z, z, 1)     (a saturated tanh, z = +-1, gives exactly 0)
+ *   gbp[c]    = sum_r dpre[r][c]                  gWp[h][c] = fmaf(x[r][h], dpre[r][c], .)     both over r ascending (*)
+ *   (*) N <= 256: one chain from 0 over r = 0 .. N-1.  N > 256: one such chain per chunk of 256 consecutive rows, then the
+ *       chunks' sums added in ascending order.  The order depends on N alone.
+ * Gradients (gWp [H, P], gbp [P], gWc [P, C], gbc [C], contiguous) are written, not accumulated; with n_valid == 0 all are
+ * zero.  workspace: tmi_cls_head_workspace_bytes(N, H, P, C) bytes, 16-byte aligned, any contents; afterwards a 256-byte
+ * header (int32 n_valid first), dpre [N, P] behind it and, for N > 256, the chunks' partial sums behind that.
+ *
+ * Limits, both calls: 1 <= N <= 65535; 4 <= H <= 4096, a multiple of 4; 2 <= P <= 1024, even; 1 <= C <= 1024; 0 <= p < 1;
+ * row strides >= the row and <= 2^30; without a row_index n_src >= N.  Anything else: TMI_ERR_INVALID, nothing is launched
+ * and nothing written.  tmi_cls_head_workspace_bytes returns -1 outside the limits. */
+int64_t tmi_cls_head_workspace_bytes(int64_t N, int64_t H, int64_t P, int64_t C);
+int tmi_cls_head_fwd(const float* pooled, int64_t ld_x, int64_t n_src, const int32_t* row_index, const float* Wp,
+                     const float* bp, const float* Wc, const float* bc, const int32_t* labels, float p, uint64_t seed,
+                     float* logits, int64_t ld_logits, int32_t* pred, float* z, int64_t ld_z, float* log_probs, int64_t ld_lp,
+                     float* nll, int32_t* label_rank, int64_t* confusion, int64_t ld_conf, int64_t N, int64_t H, int64_t P,
+                     int64_t C, void* stream);
+int tmi_cls_head_bwd(const float* pooled, int64_t ld_x, int64_t n_src, const int32_t* row_index, const float* Wc,
+                     const int32_t* labels, float p, uint64_t seed, const float* z, int64_t ld_z, const float* log_probs,
+                     int64_t ld_lp, float* gWp, float* gbp, float* gWc, float* gbc, float* loss, void* workspace,
+                     int64_t workspace_bytes, int64_t N, int64_t H, int64_t P, int64_t C, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Log-mel front end (speech_jobs/whisper_dist.py:739-766, extract_fbank_features; dead in the
  * reference's training path).  The windowed DFT of the frames is a tmi_gemm
  * (frames = overlapping rows of the waveform, a_sm = hop; B = [n_fft, 2*n_bins] Hann-weighted

@@ -197,6 +197,11 @@ SIGNATURES = {
                                c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp]),
     "tmi_edit_confusion": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i32, c_i64, c_vp,
                                    c_i32, c_vp]),
+    "tmi_cls_head_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "tmi_cls_head_fwd": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, C.c_uint64, c_vp, c_i64, c_vp,
+                                 c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "tmi_cls_head_bwd": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, C.c_uint64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
+                                 c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

@@ -98,3 +98,12 @@ class W2VDummyDataset:
         s = min(self._pos + self.rank * self.batch_size, self.n)
         self._pos += self.global_batch
         return self.audio[s:min(s + self.batch_size, self.n)]
+
+
+def w2v_dummy_labels(num_samples: int, num_labels: int) -> np.ndarray:
+    """A class per clip of the W2V dummy pool, a deterministic function of the clip index alone (the reference's dummy
+    labels are unused, V:1123-1153): label(i) = (7 i + 3) mod num_labels, int32 [num_samples].  The clips are noise: the
+    labels exercise the classification path, they are not learnable from the audio."""
+    if num_samples < 0 or num_labels < 1:
+        raise ValueError("num_samples >= 0 and num_labels >= 1")
+    return ((7 * np.arange(num_samples, dtype=np.int64) + 3) % num_labels).astype(np.int32)

@@ -861,6 +861,91 @@ def masked_mean_pool(x, mask, out, B, T, C):
     check(lib().tmi_masked_mean_pool(x.data_ptr(), dt(x), ptr(mask), out.data_ptr(), B, T, C, stream()), "tmi_masked_mean_pool")
 
 
+def cls_head_workspace_elems(N: int, H: int, P: int, C: int) -> int:
+    """float32 elements of tmi_cls_head_bwd's workspace (tmi_cls_head_workspace_bytes / 4)."""
+    n = int(lib().tmi_cls_head_workspace_bytes(int(N), int(H), int(P), int(C)))
+    if n < 0:
+        raise ValueError(f"tmi_cls_head takes 1 <= N <= 65535 rows, H <= 4096 a multiple of 4, P even <= 1024 and 1 <= C <= 1024, "
+                         f"got {N} x {H} x {P} x {C}")
+    return n // 4
+
+
+def _cls_rows(t, cols, what):
+    """A float32 2-D tensor with unit column stride and at least ``cols`` columns -> its row stride."""
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < cols or (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < cols:
+        raise ValueError(f"{what} must be float32 [rows, >= {cols}] with unit column stride")
+    return t.stride(0)
+
+
+def _cls_head_args(pooled, row_index, labels, N, H, what):
+    ld_x = _cls_rows(pooled, H, what + ": pooled")
+    if row_index is not None:
+        _i32_dev(row_index, N, what + ": row_index")
+    elif pooled.shape[0] < N:
+        raise ValueError(f"{what}: pooled holds {pooled.shape[0]} rows, the call asks for {N}")
+    if labels is not None:
+        _i32_dev(labels, N, what + ": labels")
+    return ld_x, int(pooled.shape[0])
+
+
+def cls_head_fwd(pooled, Wp, bp, Wc, bc, logits, pred, N=None, row_index=None, labels=None, p=0.0, seed=0, z=None,
+                 log_probs=None, nll=None, label_rank=None, confusion=None):
+    """The classification head on ``N`` pooled rows (tmi_cls_head_fwd in include/tethys_mi.h): ``pooled`` fp32 [n_src, H]
+    (any row stride), gathered through ``row_index`` int32 [N] when given; ``Wp`` [H, P], ``bp`` [P], ``Wc`` [P, C], ``bc``
+    [C] contiguous fp32; ``logits`` fp32 [N, C] and ``pred`` int32 [N] are written, and of the optional outputs those given:
+    ``z`` fp32 [N, P] (tanh before dropout), ``log_probs`` fp32 [N, C], ``nll`` fp32 [N], ``label_rank`` int32 [N],
+    ``confusion`` int64 [C, C] (added to: the caller zeroes it).  ``labels`` int32 [N] (outside [0, C): unlabelled)."""
+    H, P = Wp.shape
+    C = Wc.shape[1]
+    N = int(pooled.shape[0] if N is None and row_index is None else (row_index.numel() if N is None else N))
+    ld_x, n_src = _cls_head_args(pooled, row_index, labels, N, H, "cls_head_fwd")
+    for t, n, w in ((Wp, H * P, "Wp"), (bp, P, "bp"), (Wc, P * C, "Wc"), (bc, C, "bc")) + \
+            (() if nll is None else ((nll, N, "nll"),)):
+        _f32_flat(t, n, "cls_head_fwd: " + w)
+    if Wc.shape[0] != P or logits.shape[0] < N:
+        raise ValueError("cls_head_fwd: Wc must be [P, C] and logits hold N rows")
+    ld_lg = _cls_rows(logits, C, "cls_head_fwd: logits")
+    ld_z = 0 if z is None else _cls_rows(z, P, "cls_head_fwd: z")
+    ld_lp = 0 if log_probs is None else _cls_rows(log_probs, C, "cls_head_fwd: log_probs")
+    _i32_dev(pred, N, "cls_head_fwd: pred")
+    if label_rank is not None:
+        _i32_dev(label_rank, N, "cls_head_fwd: label_rank")
+    ld_cf = 0
+    if confusion is not None:
+        if confusion.dtype != torch.int64 or confusion.dim() != 2 or confusion.shape[0] < C or confusion.shape[1] < C or confusion.stride(1) != 1:
+            raise ValueError("cls_head_fwd: confusion must be int64 [C, C] with unit column stride")
+        ld_cf = confusion.stride(0)
+    with _probe("cls_head_fwd", 2.0 * N * (H * P + P * C)):
+        check(lib().tmi_cls_head_fwd(pooled.data_ptr(), ld_x, n_src, ptr(row_index), Wp.data_ptr(), bp.data_ptr(), Wc.data_ptr(),
+                                     bc.data_ptr(), ptr(labels), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, logits.data_ptr(),
+                                     ld_lg, pred.data_ptr(), ptr(z), ld_z, ptr(log_probs), ld_lp, ptr(nll), ptr(label_rank),
+                                     ptr(confusion), ld_cf, N, H, P, C, stream()), "tmi_cls_head_fwd")
+
+
+def cls_head_bwd(pooled, Wc, labels, z, log_probs, gWp, gbp, gWc, gbc, loss, workspace, N=None, row_index=None, p=0.0, seed=0):
+    """The head's backward (tmi_cls_head_bwd in include/tethys_mi.h) from the ``z`` and ``log_probs`` that ``cls_head_fwd``
+    saved with the same ``row_index``, ``labels``, ``p`` and ``seed``: ``gWp`` [H, P], ``gbp`` [P], ``gWc`` [P, C], ``gbc``
+    [C] (written, not accumulated) and the mean loss over the labelled rows in ``loss`` [1].  ``workspace``: float32, of
+    ``cls_head_workspace_elems(N, H, P, C)`` elements, any contents; dpre [N, P] is left behind its 64-element header."""
+    H, P = gWp.shape
+    C = Wc.shape[1]
+    N = int(pooled.shape[0] if N is None and row_index is None else (row_index.numel() if N is None else N))
+    if labels is None:
+        raise ValueError("cls_head_bwd: labels are required")
+    ld_x, n_src = _cls_head_args(pooled, row_index, labels, N, H, "cls_head_bwd")
+    for t, n, w in ((Wc, P * C, "Wc"), (gWp, H * P, "gWp"), (gbp, P, "gbp"), (gWc, P * C, "gWc"), (gbc, C, "gbc"), (loss, 1, "loss"),
+                    (workspace, cls_head_workspace_elems(N, H, P, C), "workspace")):
+        _f32_flat(t, n, "cls_head_bwd: " + w)
+    if Wc.shape[0] != P or z.shape[0] < N or log_probs.shape[0] < N:
+        raise ValueError("cls_head_bwd: Wc must be [P, C]; z and log_probs hold N rows")
+    ld_z, ld_lp = _cls_rows(z, P, "cls_head_bwd: z"), _cls_rows(log_probs, C, "cls_head_bwd: log_probs")
+    with _probe("cls_head_bwd", 2.0 * N * (H * P + 3 * P * C)):
+        check(lib().tmi_cls_head_bwd(pooled.data_ptr(), ld_x, n_src, ptr(row_index), Wc.data_ptr(), labels.data_ptr(), float(p),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, z.data_ptr(), ld_z, log_probs.data_ptr(), ld_lp,
+                                     gWp.data_ptr(), gbp.data_ptr(), gWc.data_ptr(), gbc.data_ptr(), loss.data_ptr(),
+                                     workspace.data_ptr(), workspace.numel() * 4, N, H, P, C, stream()), "tmi_cls_head_bwd")
+
+
 def fill_zero(t):
     """t[...] = 0 on the launch stream through the library (tmi_memset_async / tmi_memset2d_async), so that the fill is part
     of a recorded launch plan: a torch ``zero_()`` between two recorded launches would be missing from every replay.

@@ -57,11 +57,14 @@ class Wav2Vec2Config:  # V:24-128 (fields read by the pre-training path)
     ctc_blank_id: int = 0
     ctc_loss_reduction: str = "sum"   # V:94-95
     ctc_zero_infinity: bool = False
+    classifier_proj_size: int = 256   # V:108-114; the classification head's projection (Wav2Vec2ForSequenceClassification)
+    num_labels: int = 2               # V:1015 reads it, V:24-128 never sets it: a default of this build
 
 
 # dropout site ids (KernelBlocks._site_seed; restated in oracle/dropout.py): V:296, V:779, V:560 (x2), then per
 # layer V:359 (attention probabilities), V:431 (attention output), V:393 (FFN intermediate), V:396 (FFN output)
 SITE_FE, SITE_FP, SITE_PH, SITE_PQ = 1, 2, 3, 4
+SITE_CLS = 5  # V:1046: the classification head's Dropout between its two Dense layers (tmi_cls_head_fwd / _bwd)
 SITE_ATTN, SITE_ATTN_OUT, SITE_FFN_MID, SITE_FFN_OUT = 100, 200, 300, 400
 
 
@@ -70,12 +73,12 @@ def make_config(model_size: str = "small", **overrides) -> Wav2Vec2Config:
         kw = dict(hidden_size=512, num_hidden_layers=6, num_attention_heads=8, intermediate_size=2048,
                   conv_dim=(256,) * 5, conv_stride=(5, 2, 2, 2, 2), conv_kernel=(10, 3, 3, 3, 2),
                   num_conv_pos_embeddings=64, num_conv_pos_embedding_groups=8,
-                  num_codevectors_per_group=160, codevector_dim=128, proj_codevector_dim=128)
+                  num_codevectors_per_group=160, codevector_dim=128, proj_codevector_dim=128, classifier_proj_size=128)
     elif model_size == "tiny":
         kw = dict(hidden_size=256, num_hidden_layers=4, num_attention_heads=4, intermediate_size=1024,
                   conv_dim=(128,) * 4, conv_stride=(5, 2, 2, 2), conv_kernel=(10, 3, 3, 2),
                   num_conv_pos_embeddings=32, num_conv_pos_embedding_groups=4,
-                  num_codevectors_per_group=80, codevector_dim=64, proj_codevector_dim=64)
+                  num_codevectors_per_group=80, codevector_dim=64, proj_codevector_dim=64, classifier_proj_size=64)
     else:
         kw = {}
     kw.update(overrides)
@@ -179,11 +182,13 @@ def check_evaluate_args(cfg: Wav2Vec2Config, audio, neg_indices, attention_mask=
 
 class W2VArena(Arena):
     """``head="pretraining"``: the base model, the quantiser and the two projection heads (V:826-865).  ``head="ctc"``: the
-    base model's parameters under the same names, then ``lm_head`` (V:940-975) - no quantiser, project_q or project_hid."""
+    base model's parameters under the same names, then ``lm_head`` (V:940-975) - no quantiser, project_q or project_hid.
+    ``head="classification"``: the base model likewise, then ``classifier_proj`` and ``classifier`` (V:1013-1015), the
+    contiguous tail of the arena."""
 
     def __init__(self, cfg: Wav2Vec2Config, device, head: str = "pretraining"):
-        if head not in ("pretraining", "ctc"):
-            raise ValueError('head must be "pretraining" or "ctc"')
+        if head not in ("pretraining", "ctc", "classification"):
+            raise ValueError('head must be "pretraining", "ctc" or "classification"')
         pre = head == "pretraining"
         H, I = cfg.hidden_size, cfg.intermediate_size
         C, G = cfg.conv_dim[-1], cfg.num_conv_pos_embedding_groups
@@ -220,8 +225,12 @@ class W2VArena(Arena):
         if pre:
             spec.extend([("project_hid.dense.kernel", (H, cfg.proj_codevector_dim)), ("project_hid.dense.bias", (cfg.proj_codevector_dim,))])
             ln("project_hid.layer_norm", cfg.proj_codevector_dim)
-        else:
+        elif head == "ctc":
             spec.extend([("lm_head.kernel", (H, cfg.vocab_size)), ("lm_head.bias", (cfg.vocab_size,))])
+        else:
+            P, Cl = cfg.classifier_proj_size, cfg.num_labels
+            spec.extend([("classifier_proj.kernel", (H, P)), ("classifier_proj.bias", (P,)),
+                         ("classifier.kernel", (P, Cl)), ("classifier.bias", (Cl,))])
         super().__init__(spec, device)
 
 
@@ -1544,22 +1553,371 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         return result
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Sequence classification (V:1004-1067): masked-mean pooling, Dense + tanh, Dropout, Dense.  Inference and evaluation on
+# padded batches, and training of the HEAD alone on pooled features of the frozen encoder (a linear probe).  Encoder
+# fine-tuning is not built.
+CLS_MAX_ROWS = 65535    # tmi_cls_head_fwd / _bwd: rows per call
+CLS_MAX_HIDDEN = 4096   # H, a multiple of 4
+CLS_MAX_PROJ = 1024     # classifier_proj_size, even
+CLS_MAX_LABELS = 1024   # num_labels
+
+
+def check_classification_args(cfg: Wav2Vec2Config, inputs_shape, labels=None, attention_mask=None, top_k=(1,)):
+    """Host validation of ``Wav2Vec2ForSequenceClassification``'s calls (no GPU needed; the kernels cannot see values in
+    device memory).  ``inputs_shape`` (B, T_in) of the audio - or (N, H) of pooled features, ``T_in`` then unused by the
+    caller; 1 <= B <= 65535; the config inside the head kernels' limits (hidden_size a multiple of 4 and <= 4096,
+    classifier_proj_size even and <= 1024, 1 <= num_labels <= 1024); ``labels`` None or B integers (tensor, array or list) -
+    when they are on the host every one in [-1, num_labels), -1 meaning "unlabelled"; ``attention_mask`` None or [B, T]
+    over frames (``frame_attention_mask``); ``top_k`` integers in [1, num_labels], no duplicates.
+    -> (B, T, labels as a contiguous int32 tensor on the device they came from or None, top_k as a tuple)."""
+    def integer(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    H, P, C = cfg.hidden_size, cfg.classifier_proj_size, cfg.num_labels
+    if not (integer(C) and 1 <= C <= CLS_MAX_LABELS):
+        raise ValueError(f"num_labels must be an integer in [1, {CLS_MAX_LABELS}] (tmi_cls_head_fwd)")
+    if not (integer(P) and 2 <= P <= CLS_MAX_PROJ and P % 2 == 0):
+        raise ValueError(f"classifier_proj_size must be even and in [2, {CLS_MAX_PROJ}] (the dropout generator draws per column pair)")
+    if not (4 <= H <= CLS_MAX_HIDDEN and H % 4 == 0):
+        raise ValueError(f"hidden_size must be a multiple of 4 and <= {CLS_MAX_HIDDEN} (tmi_cls_head_fwd)")
+    if len(inputs_shape) != 2 or int(inputs_shape[0]) < 1 or int(inputs_shape[1]) < 1:
+        raise ValueError("inputs must be [B, T_in]")
+    B, T_in = int(inputs_shape[0]), int(inputs_shape[1])
+    if B > CLS_MAX_ROWS:
+        raise ValueError(f"at most {CLS_MAX_ROWS} rows per call (tmi_cls_head_fwd)")
+    T = frame_lengths(cfg, [T_in])[0]
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask)
+        if m.dim() != 2 or tuple(m.shape) != (B, T):
+            raise ValueError(f"attention_mask must be [B, T] over frames = [{B}, {T}] (frame_attention_mask), got {list(m.shape)}")
+    lab = None
+    if labels is not None:
+        lab = labels if torch.is_tensor(labels) else torch.as_tensor(np.asarray(labels))
+        if lab.dtype not in (torch.int32, torch.int64) or lab.dim() != 1 or lab.shape[0] != B:
+            raise ValueError(f"labels must be B = {B} integers (int32 or int64)")
+        if lab.device.type == "cpu" and B and (int(lab.min()) < -1 or int(lab.max()) >= C):
+            raise ValueError(f"labels must be in [-1, {C}): a class, or -1 for an unlabelled item")
+        lab = lab.detach().to(torch.int32).contiguous()
+    ks = tuple(top_k) if isinstance(top_k, (tuple, list)) else (top_k,)
+    if not ks or any(not integer(k) or not 1 <= k <= C for k in ks) or len(set(ks)) != len(ks):
+        raise ValueError(f"top_k must be distinct integers in [1, num_labels = {C}]")
+    return B, T, lab, tuple(int(k) for k in ks)
+
+
+class Wav2Vec2ForSequenceClassification(Wav2Vec2ForPreTraining):
+    """V:1004-1067: the base model (the blocks and the inference workspace of ``Wav2Vec2ForPreTraining``), the masked mean
+    over time (tmi_masked_mean_pool) and the head classifier_proj (Dense + tanh) -> Dropout -> classifier (Dense) on the
+    kernels of csrc/cls_head.hip.  The head runs in fp32 from the arena's master weights in both precisions: the pooled
+    vector is fp32 already.  Inference and ``evaluate`` run under ``torch.no_grad()`` on the inference workspace with
+    dropout off; ``head_step`` / ``fit_head`` train the HEAD on pooled features of the frozen encoder and touch nothing of
+    the arena outside the head's slice.  Encoder fine-tuning is not built: the training entry points raise.  Not built
+    either: ``use_weighted_layer_sum``, class weights, the x-vector model."""
+
+    _arena_head = "classification"
+
+    def __init__(self, config: Wav2Vec2Config, device="cuda:0", precision: str = "bf16", seed: int = 1234):
+        check_classification_args(config, (1, 1))
+        super().__init__(config, device=device, precision=precision, seed=seed)
+        a = self.arena
+        self.head_lo, self.head_hi = a.offsets["classifier_proj.kernel"], a.numel  # the head: the arena's contiguous tail
+        self._head_call = None
+        self._head_sets: Dict[int, Dict[str, torch.Tensor]] = {}
+
+    def forward_backward(self, *a, **k):
+        raise NotImplementedError("encoder fine-tuning is not built")
+
+    def __call__(self, inputs, attention_mask=None, labels=None, output_hidden_states=False, output_attentions=False,
+                 training=False, **kw):
+        """``model(inputs, attention_mask=None, labels=None, ...)`` is ``forward_infer``; ``training=True`` raises (the head
+        alone is trained, on pooled features: ``head_step``)."""
+        if training:
+            raise NotImplementedError("encoder fine-tuning is not built")
+        return self.forward_infer(inputs, attention_mask=attention_mask, labels=labels, output_hidden_states=output_hidden_states,
+                                  output_attentions=output_attentions, **kw)
+
+    # -- the head ----------------------------------------------------------------------------------------------------
+    def _head_params(self):
+        a = self.arena
+        return (a.param("classifier_proj.kernel"), a.param("classifier_proj.bias"), a.param("classifier.kernel"),
+                a.param("classifier.bias"))
+
+    def _head_buffers(self, N, store=None):
+        """The head's outputs for ``N`` rows: in the inference workspace (``store`` None) or in a set of their own."""
+        cfg = self.config
+        if store is None:
+            saved = None
+            ws = self.ws
+        else:
+            saved, self.ws = self.ws, store
+            ws = store
+        try:
+            if "cls_logits" not in ws or ws["cls_logits"].shape[0] != N:
+                f32, i32 = torch.float32, torch.int32
+                self._buf("cls_logits", (N, cfg.num_labels), f32)
+                self._buf("cls_logp", (N, cfg.num_labels), f32)
+                self._buf("cls_pred", (N,), i32)
+                self._buf("cls_nll", (N,), f32)
+                self._buf("cls_rank", (N,), i32)
+        finally:
+            if saved is not None:
+                self.ws = saved
+        return ws
+
+    def _head_fwd(self, pooled, N, ws, labels=None, confusion=None, row_index=None, p=0.0, seed=0, z=None):
+        Wp, bp, Wc, bc = self._head_params()
+        ops.cls_head_fwd(pooled, Wp, bp, Wc, bc, ws["cls_logits"], ws["cls_pred"], N=N, row_index=row_index, labels=labels,
+                         p=p, seed=seed, z=z, log_probs=ws["cls_logp"], nll=ws["cls_nll"], label_rank=ws["cls_rank"],
+                         confusion=confusion)
+
+    def _infer_head(self, x, inf, result):
+        call = self._head_call
+        if call is None or call.get("skip"):
+            return
+        B = inf["key"][0]
+        ws = self._head_buffers(B)
+        labels = call.get("labels")
+        self._head_fwd(result["pooled_output"], B, ws, labels=labels, confusion=call.get("confusion"))
+        result["logits"] = ws["cls_logits"].clone()
+        result["log_probs"] = ws["cls_logp"].clone()
+        result["predictions"] = ws["cls_pred"].clone()
+        if labels is not None:
+            result["nll"] = ws["cls_nll"].clone()
+            result["label_rank"] = ws["cls_rank"].clone()
+
+    @torch.no_grad()
+    def forward_infer(self, inputs, attention_mask=None, labels=None, output_hidden_states=False, output_attentions=False,
+                      attentions_dtype=None, pool="mean", _confusion=None):
+        """V:1017-1067 with training=False: the base model's outputs (``Wav2Vec2ForPreTraining.forward_infer``, always with
+        ``pool="mean"``: ``pooled_output`` fp32 [B, H] is bit for bit what that call gives) plus ``logits`` fp32 [B, C],
+        ``log_probs`` fp32 [B, C], ``predictions`` int32 [B] (the argmax, the lowest index on ties).  ``attention_mask`` is
+        the frame mask of ``frame_attention_mask``.  With ``labels`` (B integers in [0, C), or -1: unlabelled) also ``nll``
+        fp32 [B] and ``label_rank`` int32 [B] per item, and ``loss``: the mean of the sparse categorical cross-entropy
+        over the labelled items, a one-element device tensor (V:1053-1056).  The reference computes the loss only in
+        training; here it is computed whenever labels are given.  No dropout."""
+        if pool != "mean":
+            raise ValueError('the classification model pools with "mean"')
+        if not torch.is_tensor(inputs) or inputs.dim() != 2:
+            raise TypeError("inputs must be float32 [B, T_in]")
+        B, _, lab, _ = check_classification_args(self.config, tuple(inputs.shape), labels, attention_mask)
+        lab_dev = None if lab is None else lab.to(self.device)
+        self._head_call = {"labels": lab_dev, "confusion": _confusion}
+        try:
+            result = super().forward_infer(inputs, attention_mask=attention_mask, output_hidden_states=output_hidden_states,
+                                           pool="mean", output_attentions=output_attentions, attentions_dtype=attentions_dtype)
+        finally:
+            self._head_call = None
+        if lab_dev is not None:
+            n = ((lab_dev >= 0) & (lab_dev < self.config.num_labels)).sum().clamp(min=1).to(torch.float32).view(1)
+            loss = torch.empty(1, dtype=torch.float32, device=self.device)
+            ops.sum_scale_dev(result["nll"], loss, B, 1.0 / n)  # (unlabelled items hold 0)
+            result["loss"] = loss
+        return result
+
+    @torch.no_grad()
+    def pool_features(self, inputs, attention_mask=None):
+        """The frozen encoder's pooled output fp32 [B, H] (``forward_infer``'s ``pooled_output``, the head not run): what
+        ``head_step`` / ``fit_head`` train on.  Cache it: the encoder does not change while the head is trained."""
+        self._head_call = {"skip": True}
+        try:
+            return super().forward_infer(inputs, attention_mask=attention_mask, pool="mean")["pooled_output"]
+        finally:
+            self._head_call = None
+
+    @staticmethod
+    def _score_sums(nll, rank, top_k):
+        """-> [nll_sum, n_items, n_correct, topk_correct per k] as one float64 device vector (a few torch reductions over
+        [B] ahead of the call's one read-back, as ``ops.edit_counts``)."""
+        valid = rank >= 0
+        parts = [nll.double().sum(), valid.sum().double(), (rank == 0).sum().double()]
+        parts += [(valid & (rank < k)).sum().double() for k in top_k]
+        return torch.stack(parts)
+
+    @staticmethod
+    def _finish_scores(sums, top_k):
+        s = [float(v) for v in sums.cpu().tolist()]
+        n = s[1]
+        out = {"n_items": int(n), "nll_sum": s[0], "loss": s[0] / n if n else 0.0, "n_correct": int(s[2]),
+               "accuracy": s[2] / n if n else 0.0, "topk_correct": {k: int(v) for k, v in zip(top_k, s[3:])}}
+        out["topk_accuracy"] = {k: (v / n if n else 0.0) for k, v in out["topk_correct"].items()}
+        return out
+
+    def _confusion_arg(self, confusion):
+        C = self.config.num_labels
+        if confusion is None or confusion is False:
+            return None
+        if confusion is True:
+            return torch.zeros((C, C), dtype=torch.int64, device=self.device)
+        if not torch.is_tensor(confusion) or confusion.dtype != torch.int64 or tuple(confusion.shape) != (C, C) or \
+                confusion.device != self.device or not confusion.is_contiguous():
+            raise ValueError(f"confusion must be a bool or the previous int64 [{C}, {C}] table on the model's device")
+        return confusion
+
+    @torch.no_grad()
+    def evaluate(self, inputs, labels, attention_mask=None, top_k=(1,), return_items=False, confusion=False):
+        """Classification metrics of one batch, forward only (``forward_infer``: inference workspace, dropout off).
+        ``labels`` B integers in [0, C), or -1 for an unlabelled item: it is scored 0 and counted nowhere.  Returns Python
+        numbers from ONE read-back of the sums: ``n_items`` (labelled), ``nll_sum``, ``loss`` = nll_sum / n_items,
+        ``n_correct``, ``accuracy``, ``topk_correct`` / ``topk_accuracy`` {k: ...} for every k of ``top_k`` - an item is in
+        the top k when its ``label_rank`` (tmi_cls_head_fwd: the classes that beat the label) is < k, so no sort runs.
+        ``confusion`` True: also ``confusion``, an int64 [C, C] device table, label by prediction; pass the previous
+        call's table instead of True and this batch is ADDED to it on the device.  ``return_items``: the device tensors
+        ``nll`` fp32, ``predictions`` and ``label_rank`` int32 [B]."""
+        if labels is None:
+            raise ValueError("evaluate takes labels")
+        if not torch.is_tensor(inputs) or inputs.dim() != 2:
+            raise TypeError("inputs must be float32 [B, T_in]")
+        _, _, _, ks = check_classification_args(self.config, tuple(inputs.shape), labels, attention_mask, top_k)
+        table = self._confusion_arg(confusion)
+        r = self.forward_infer(inputs, attention_mask=attention_mask, labels=labels, _confusion=table)
+        out = self._finish_scores(self._score_sums(r["nll"], r["label_rank"], ks), ks)
+        if table is not None:
+            out["confusion"] = table
+        if return_items:
+            out.update(nll=r["nll"], predictions=r["predictions"], label_rank=r["label_rank"])
+        return out
+
+    @torch.no_grad()
+    def evaluate_features(self, pooled, labels, top_k=(1,), confusion=False):
+        """``evaluate`` on cached pooled features fp32 [N, H] (``pool_features``): the head alone, dropout off, in pieces of
+        at most 65535 rows.  Same result keys, without the per-item tensors."""
+        pooled = self._check_pooled(pooled)
+        N = pooled.shape[0]
+        _, _, lab, ks = check_classification_args(self.config, (min(N, CLS_MAX_ROWS), 1), None, None, top_k)
+        lab = torch.as_tensor(labels) if not torch.is_tensor(labels) else labels
+        if lab.dim() != 1 or lab.shape[0] != N or lab.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"labels must be N = {N} integers")
+        lab = lab.to(self.device, torch.int32).contiguous()
+        table = self._confusion_arg(confusion)
+        total = None
+        for s in range(0, N, CLS_MAX_ROWS):
+            n = min(CLS_MAX_ROWS, N - s)
+            ws = self._head_buffers(n, self._head_sets.setdefault(("eval", n), {}))
+            self._head_fwd(pooled[s:s + n], n, ws, labels=lab[s:s + n], confusion=table)
+            sums = self._score_sums(ws["cls_nll"], ws["cls_rank"], ks)
+            total = sums if total is None else total + sums
+        out = self._finish_scores(total, ks)
+        if table is not None:
+            out["confusion"] = table
+        return out
+
+    def _check_pooled(self, pooled):
+        H = self.config.hidden_size
+        if not torch.is_tensor(pooled) or pooled.dtype != torch.float32 or pooled.dim() != 2 or pooled.shape[1] != H or \
+                pooled.shape[0] < 1 or pooled.stride(1) != 1:
+            raise TypeError(f"pooled features must be float32 [N, {H}] with unit column stride")
+        return pooled if pooled.device == self.device else pooled.to(self.device)
+
+    # -- training of the head on cached features (the linear probe) --------------------------------------------------
+    def head_step(self, pooled, labels, optimizer, row_index=None, dropout=None, seed=0, step=0):
+        """One training step of the HEAD on pooled features ``pooled`` fp32 [N_src, H] of the frozen encoder: forward with
+        Dropout (V:1046; rate ``dropout``, None: ``config.hidden_dropout``), backward into the head's slice of ``arena.g``
+        (tmi_cls_head_fwd / _bwd), then ``optimizer``'s Adam (tmi_adam_step; ``optim.Adam`` defaults to the Keras
+        epsilon) over that slice ONLY.  The encoder's parameters, their moments and the bf16 mirror outside the head are
+        not touched.  ``row_index`` int32 device tensor [N]: row r of the step is ``pooled[row_index[r]]`` (the minibatch
+        gather costs nothing extra); ``labels`` int32 device tensor [N] BY POSITION in the step (-1: unlabelled).  The
+        mask of the step is that of dropout site SITE_CLS under (``seed``, ``step``), as every site of this project.
+        -> the mean loss over the labelled rows before the update, a one-element device tensor (no read-back)."""
+        cfg = self.config
+        pooled = self._check_pooled(pooled)
+        N = int(pooled.shape[0] if row_index is None else row_index.numel())
+        if not 1 <= N <= CLS_MAX_ROWS:
+            raise ValueError(f"head_step takes 1 <= N <= {CLS_MAX_ROWS} rows")
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.numel() != N or labels.device != self.device:
+            raise TypeError("labels must be an int32 tensor [N] on the model's device (by position in the step)")
+        if row_index is not None and (row_index.dtype != torch.int32 or row_index.device != self.device):
+            raise TypeError("row_index must be an int32 tensor on the model's device")
+        p = float(cfg.hidden_dropout if dropout is None else dropout)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        P, C = cfg.classifier_proj_size, cfg.num_labels
+        ws = self._head_buffers(N, self._head_sets.setdefault(("step", N), {}))
+        if "cls_z" not in ws:
+            saved, self.ws = self.ws, ws
+            try:
+                self._buf("cls_z", (N, P), torch.float32)
+                self._buf("cls_bwd_ws", (ops.cls_head_workspace_elems(N, cfg.hidden_size, P, C),), torch.float32)
+            finally:
+                self.ws = saved
+        while len(self._head_sets) > 8:
+            self._head_sets.pop(next(k for k in self._head_sets if self._head_sets[k] is not ws))
+        site = (int(seed) + int(step) * 0x9E3779B97F4A7C15 + SITE_CLS * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+        a = self.arena
+        self._head_fwd(pooled, N, ws, labels=labels, row_index=row_index, p=p, seed=site, z=ws["cls_z"])
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        ops.cls_head_bwd(pooled, a.param("classifier.kernel"), labels, ws["cls_z"], ws["cls_logp"],
+                         a.grad("classifier_proj.kernel"), a.grad("classifier_proj.bias"), a.grad("classifier.kernel"),
+                         a.grad("classifier.bias"), loss, ws["cls_bwd_ws"], N=N, row_index=row_index, p=p, seed=site)
+        optimizer.iterations += 1
+        optimizer._update(self, self.head_lo, self.head_hi, 1.0, False, 0)
+        return loss
+
+
+def fit_head(model, features, labels, epochs, batch_size, learning_rate=1e-3, seed=0, eval_features=None, eval_labels=None):
+    """Train ``model``'s head (a linear probe) on cached pooled features ``features`` fp32 [N, H] with ``labels`` [N]
+    integers (-1: unlabelled).  Every epoch draws one permutation from a host generator seeded with ``seed``, uploads it
+    (and the labels in that order) once, and runs one ``head_step`` per minibatch with a slice of it as ``row_index``; the
+    last batch may be short.  Adam with ``learning_rate`` and the Keras epsilon.  -> the history: one dict per epoch with
+    ``epoch``, ``loss`` (the mean of the steps' losses weighted by their rows; one read-back per epoch) and, with
+    ``eval_features`` / ``eval_labels``, ``eval_loss`` and ``eval_accuracy`` (``evaluate_features``)."""
+    from . import optim
+    feats = model._check_pooled(features)
+    N = feats.shape[0]
+    lab = np.asarray(torch.as_tensor(labels).detach().cpu().numpy()).astype(np.int64).reshape(-1)
+    C = model.config.num_labels
+    if lab.shape[0] != N or (lab < -1).any() or (lab >= C).any():
+        raise ValueError(f"labels must be N = {N} integers in [-1, {C})")
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or not 1 <= batch_size <= CLS_MAX_ROWS:
+        raise ValueError(f"epochs >= 0 and 1 <= batch_size <= {CLS_MAX_ROWS}")
+    if (eval_features is None) != (eval_labels is None):
+        raise ValueError("eval_features and eval_labels come together")
+    opt = optim.Adam(learning_rate)
+    rng = np.random.default_rng(seed)
+    history, step = [], 0
+    for epoch in range(epochs):
+        perm = rng.permutation(N)
+        idx = torch.from_numpy(perm.astype(np.int32)).to(model.device)
+        lab_dev = torch.from_numpy(lab[perm].astype(np.int32)).to(model.device)
+        losses, rows = [], []
+        for s in range(0, N, batch_size):
+            e = min(N, s + batch_size)
+            losses.append(model.head_step(feats, lab_dev[s:e], opt, row_index=idx[s:e], seed=seed, step=step))
+            rows.append(e - s)
+            step += 1
+        w = torch.tensor(rows, dtype=torch.float64, device=model.device)
+        rec = {"epoch": epoch, "loss": float((torch.cat(losses).double() * w).sum() / w.sum())}
+        if eval_features is not None:
+            ev = model.evaluate_features(eval_features, eval_labels)
+            rec.update(eval_loss=ev["loss"], eval_accuracy=ev["accuracy"])
+        history.append(rec)
+    return history
+
+
+def create_classification_model(model_size: str = "small", num_labels: int = 2, device="cuda:0", precision: str = "bf16",
+                                seed: int = 1234, **overrides):
+    """Wav2Vec2ForSequenceClassification (V:1004-1067) of ``model_size`` with ``num_labels`` classes.  A factory of its own:
+    ``create_full_model`` keeps the two types it has (a test pins its refusal of the others)."""
+    cfg = make_config(model_size, num_labels=num_labels, **overrides)
+    return Wav2Vec2ForSequenceClassification(cfg, device=device, precision=precision, seed=seed)
+
+
 def load_pretrained_encoder(model, path):
-    """Copy into ``model`` (a Wav2Vec2ForCTC) every reference-keyed tensor of a ``train.save_weights`` file of a pre-training
-    model that the CTC model also has: the whole base model.  The head keeps its initialisation, the file's quantiser and
+    """Copy into ``model`` (a Wav2Vec2ForCTC or a Wav2Vec2ForSequenceClassification) every reference-keyed tensor of a
+    ``train.save_weights`` file of a pre-training model that the model also has: the whole base model.  The head keeps its initialisation, the file's quantiser and
     projection heads are ignored, the bf16 mirror is re-derived.  Raises if a shared name has another shape or the file
     shares nothing.  -> the names copied."""
     ck = torch.load(path, map_location="cpu")
     if not isinstance(ck, dict) or "p" in ck:
         raise ValueError("load_pretrained_encoder takes a save_weights file (reference-keyed tensors)")
     views = model.arena.ref_views(model.arena.p)
-    shared = [k for k in views if k in ck and not k.startswith("lm_head.")]
+    heads = ("lm_head.", "classifier_proj.", "classifier.")  # a head of the model's own: absent from a pre-training file
+    shared = [k for k in views if k in ck and not k.startswith(heads)]
     if not shared:
         raise ValueError("the file shares no parameter with the model")
     for k in shared:
         if tuple(ck[k].shape) != tuple(views[k].shape):
             raise ValueError(f"{k}: the file has shape {tuple(ck[k].shape)}, the model {tuple(views[k].shape)}")
-    missing = [k for k in views if k not in ck and not k.startswith("lm_head.")]
+    missing = [k for k in views if k not in ck and not k.startswith(heads)]
     if missing:
         raise ValueError(f"the file lacks base-model parameters: {missing[:4]} ...")
     if hasattr(model, "finish_late"):
