@@ -1188,6 +1188,63 @@ int tmi_cls_head_bwd(const float* pooled, int64_t ld_x, int64_t n_src, const int
                      int64_t workspace_bytes, int64_t N, int64_t H, int64_t P, int64_t C, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The CTC head on cached encoder features (Wav2Vec2ForCTC, V:972-975: Dropout, then Dense), for training the head with
+ * the encoder frozen (csrc/ctc_head.hip).  fp32 throughout, from fp32 W [H, V] and b [V] (contiguous).  `hidden` holds the
+ * encoder's output in x_dtype (TMI_BF16 or TMI_F32): element (s, t, h) at hidden[s*x_sn + t*x_st + h].  N items per call,
+ * T_max frames each; item n reads source item s = row_index ? row_index[n] : n (row_index int32 [N] or NULL; n_src = the
+ * items `hidden` holds: an index outside [0, n_src) reads as zeros).  frame_lens, label_lens, nll, infeasible are BY
+ * POSITION n in the call, as tmi_ctc_posteriors takes and writes them; only `hidden` is gathered.  T = min(frame_lens[n],
+ * T_max); row r = n*T_max + t is LIVE when t < T.  Frames t >= T, and every frame of an item with frame_lens[n] < 1, are
+ * neither read nor written by these calls.
+ *
+ * tmi_ctc_head_fwd, per live row:
+ *   xd[h]     = keep(seed, r, h) ? x[h] * 65536/(65536-thr) : 0    tmi_dropout's generator exactly: stream 0, row = r =
+ *               n*T_max + t (the position in THIS call, not the source row), column = h, 16-bit draws, thr = round(p * 65536),
+ *               the scale formed in fp32 as tmi_cls_head_fwd forms it; p == 0: xd = x, nothing is hashed, the seed is ignored
+ *   logits[v] = (fmaf(xd[h], W[h][v], .) over h = 0 .. H-1 in that order, from 0) + b[v]
+ *   m = max_v logits[v];  s = sum_v expf(logits[v] - m): column v on lane v of a wave, the lanes past V hold 0, folded by the
+ *               xor butterfly 32, 16, .., 1;  lse = m + logf(s);  logp[v] = logits[v] - lse   (tmi_ctc_logsoftmax's form)
+ *   argmax    = the smallest column among equal maxima of the logits (tmi_ctc_logsoftmax's rule)
+ * logp (element (n, t, v) at logp[n*lp_sn + t*lp_st + v]) is always written; logits (the same layout under lg_sn / lg_st)
+ * and argmax (int32 [N][T_max], dense) may be NULL.  Columns past V are not written.
+ *
+ * tmi_ctc_head_bwd: the gradients of loss = sum_n w_n nll[n] with respect to W and b, from `grad` as tmi_ctc_posteriors
+ * wrote it (d nll[n] / d logits, element (n, t, v) at grad[n*gr_sn + t*gr_st + v]), its nll [N] and infeasible [N], and the
+ * same hidden, row_index, frame_lens and (p, seed) as the forward; no mask is stored, xd is recomputed.
+ *   w_n       = 0 when infeasible[n] != 0; else 1 (reduction 0, "sum") or 1 / ((float) max(min(label_lens[n], L_max), 1) *
+ *               (float) N) (reduction 1, "mean": torch's ctc_loss(reduction="mean", zero_infinity=True))
+ *   gs[r][v]  = grad[r][v] * w_n on a live row; a row that is not live counts as zeros and is not read
+ *   gW[h][v]  = fmaf(xd[r][h], gs[r][v], .)       gb[v] = sum of gs[r][v]       both over the rows r ascending (*)
+ *   (*) the rows 0 .. N*T_max - 1 are cut into chunks of rc = 256 * ceil(N*T_max / 16384) consecutive rows (256 rows up to
+ *       N*T_max = 16384; at most 64 chunks).  Per chunk one chain from 0 over its rows in ascending order; then the chunks'
+ *       sums are added in ascending chunk order, starting from chunk 0's.  The order depends on N*T_max alone.
+ *   loss[0]   = sum over the feasible items of w_n * nll[n] (one product, then added): thread t of 256 adds its items t,
+ *               t + 256, .. in ascending order from 0, the 64 lanes of a wave meet in the xor butterfly 32, 16, .., 1, the four
+ *               wave sums are added ((w0 + w1) + w2) + w3.  An infeasible item's nll is not read into the sum.
+ *   n_infeasible[0] = the number of items with infeasible[n] != 0 (int32)
+ * gW [H, V], gb [V] (contiguous), loss and n_infeasible are written, not accumulated; with no live row gW and gb are zero.
+ * No floating-point atomic anywhere: the same call gives the same bits.  workspace: tmi_ctc_head_workspace_bytes(N, T_max,
+ * H, V) bytes (the chunks' partial sums, chunks * (H*V + V) floats), 16-byte aligned, any contents.
+ *
+ * Limits, both calls: 1 <= N <= 65535; 1 <= T_max <= 4096; N*T_max <= 2^22; 8 <= H <= 4096, a multiple of 8; 2 <= V <= 64;
+ * 0 <= p < 1; frame strides >= the row (x_st >= H; lp_st, lg_st, gr_st >= V), item strides >= T_max * the frame stride, all
+ * <= 2^30; 1 <= n_src <= 2^30, and >= N without a row_index; hidden and W 16-byte aligned; 1 <= L_max <= 511; reduction 0 or
+ * 1.  Anything else: TMI_ERR_INVALID, nothing is launched and nothing written; tmi_last_error names the function and the
+ * limits.  tmi_ctc_head_workspace_bytes returns -1 outside the limits.  Values in device memory are never trusted: lengths
+ * are clamped and indices checked before use.
+ * Not built: a gradient with respect to hidden (the encoder stays frozen), label smoothing. */
+int64_t tmi_ctc_head_workspace_bytes(int64_t N, int64_t T_max, int64_t H, int64_t V);
+int tmi_ctc_head_fwd(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src, const int32_t* row_index,
+                     const int32_t* frame_lens, const float* W, const float* b, float p, uint64_t seed, float* logits,
+                     int64_t lg_sn, int64_t lg_st, float* logp, int64_t lp_sn, int64_t lp_st, int32_t* argmax, int64_t N,
+                     int64_t T_max, int64_t H, int64_t V, void* stream);
+int tmi_ctc_head_bwd(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src, const int32_t* row_index,
+                     const int32_t* frame_lens, const int32_t* label_lens, const float* grad, int64_t gr_sn, int64_t gr_st,
+                     const float* nll, const int32_t* infeasible, float p, uint64_t seed, int32_t reduction, float* gW,
+                     float* gb, float* loss, int32_t* n_infeasible, void* workspace, int64_t workspace_bytes, int64_t N,
+                     int64_t T_max, int64_t L_max, int64_t H, int64_t V, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Log-mel front end (speech_jobs/whisper_dist.py:739-766, extract_fbank_features; dead in the
  * reference's training path).  The windowed DFT of the frames is a tmi_gemm
  * (frames = overlapping rows of the waveform, a_sm = hop; B = [n_fft, 2*n_bins] Hann-weighted

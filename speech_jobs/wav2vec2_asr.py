@@ -25,6 +25,11 @@ summary line adds the substitutions, deletions and insertions and, with ``--num_
 ``--confusion PATH.npy`` (with ``--edit_ops``): the confusion table of the transcripts against the labels, int64
 [vocab_size + 1, vocab_size + 1] (row = the label, column = the transcript's token, the last index = none), is folded on the
 device (``evaluate(confusion=True)``) and saved.
+``--fit_head`` (with ``--labels``; ``--epochs``, ``--train_batch_size``, ``--learning_rate``, ``--save FILE``): before anything
+is decoded the CTC head is trained on the clips with the encoder frozen - the clips are encoded once
+(``encode_features``), ``wav2vec2.fit_ctc_head`` runs the epochs and prints one JSON line per epoch, then the line of
+``evaluate_features`` on the same clips; ``--save`` writes the model with ``train.save_weights``.  The rest of the job then
+reports the trained head.  Clips without labels (an empty line) train as an empty transcript.
 There is no tokenizer: ids in, ids out.
 """
 import argparse
@@ -67,12 +72,21 @@ def main(argv=None):
     parser.add_argument("--edit_ops", action="store_true",
                         help="with --labels: count substitutions / deletions / insertions on the device (and the n-best oracle)")
     parser.add_argument("--confusion", default=None, help="with --labels --edit_ops: save the confusion table as this .npy file")
+    parser.add_argument("--fit_head", action="store_true", help="with --labels: train the CTC head on the clips, the encoder frozen")
+    parser.add_argument("--epochs", type=int, default=10, help="with --fit_head")
+    parser.add_argument("--train_batch_size", type=int, default=8, help="with --fit_head: clips per head step")
+    parser.add_argument("--learning_rate", type=float, default=1e-3, help="with --fit_head: Adam's")
+    parser.add_argument("--save", default=None, help="with --fit_head: write the trained model here (train.save_weights)")
     parser.add_argument("--build_lm", default=None, help="file of token ids, one line per sequence: build a table and exit")
     parser.add_argument("--lm_order", type=int, default=2, help="with --build_lm: the order of the table (1..4)")
     parser.add_argument("--lm_out", default=None, help="with --build_lm: where the .npy table goes")
     args = parser.parse_args(argv)
     if args.confusion and not (args.edit_ops and args.labels):
         parser.error("--confusion comes with --labels and --edit_ops")
+    if args.fit_head and not args.labels:
+        parser.error("--fit_head comes with --labels")
+    if args.save and not args.fit_head:
+        parser.error("--save comes with --fit_head")
 
     import numpy as np
     if args.build_lm:
@@ -116,6 +130,22 @@ def main(argv=None):
     mask = wav2vec2.frame_attention_mask(model.config, lengths, T_in)
     audio = torch.from_numpy(batch).to(device)
     rows = read_labels(args.labels, len(clips)) if args.labels else None
+    if args.fit_head:
+        L = max([len(r) for r in rows] + [1])
+        fit_labels = np.zeros((len(rows), L), dtype=np.int64)
+        for i, r in enumerate(rows):
+            fit_labels[i, :len(r)] = r
+        fit_lens = [len(r) for r in rows]
+        feats = model.encode_features(audio, attention_mask=mask)
+        hist = wav2vec2.fit_ctc_head(model, feats["hidden"], feats["frame_lengths"], fit_labels, fit_lens, args.epochs,
+                                     args.train_batch_size, learning_rate=args.learning_rate)
+        for rec in hist:
+            print(json.dumps({"fit_head_epoch": rec["epoch"] + 1, "loss": rec["loss"], "n_infeasible": rec["n_infeasible"]}), flush=True)
+        fit = model.evaluate_features(feats["hidden"], feats["frame_lengths"], fit_labels, fit_lens)
+        print(json.dumps({"fit_head": {k: fit[k] for k in ("loss", "nll_sum", "n_infeasible", "n_edits", "n_ref_tokens",
+                                                           "token_error_rate")}, "epochs": len(hist)}), flush=True)
+        if args.save:
+            train.save_weights(model, args.save)
     torch.cuda.synchronize()
     t0 = time.time()
     beam = args.num_beams is not None and args.num_beams > 1

@@ -202,6 +202,11 @@ SIGNATURES = {
                                  c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "tmi_cls_head_bwd": (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_f32, C.c_uint64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp,
                                  c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "tmi_ctc_head_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    "tmi_ctc_head_fwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, C.c_uint64, c_vp, c_i64, c_i64,
+                                 c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "tmi_ctc_head_bwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_f32,
+                                 C.c_uint64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

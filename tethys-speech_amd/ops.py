@@ -946,6 +946,79 @@ def cls_head_bwd(pooled, Wc, labels, z, log_probs, gWp, gbp, gWc, gbc, loss, wor
                                      workspace.data_ptr(), workspace.numel() * 4, N, H, P, C, stream()), "tmi_cls_head_bwd")
 
 
+def ctc_head_workspace_elems(N: int, T_max: int, H: int, V: int) -> int:
+    """float32 elements of tmi_ctc_head_bwd's workspace (tmi_ctc_head_workspace_bytes / 4)."""
+    n = int(lib().tmi_ctc_head_workspace_bytes(int(N), int(T_max), int(H), int(V)))
+    if n < 0:
+        raise ValueError(f"tmi_ctc_head takes 1 <= N <= 65535 items of 1 <= T_max <= 4096 frames, N * T_max <= 2^22, 8 <= H <= 4096 a "
+                         f"multiple of 8 and 2 <= V <= 64, got {N} x {T_max} x {H} x {V}")
+    return n // 4
+
+
+def _ctc_head_args(hidden, row_index, frame_lens, N, T_max, H, what):
+    """``hidden`` bf16 / fp32 [n_src, >= T_max, >= H] with unit column stride -> (x_sn, x_st, n_src)."""
+    if hidden.dtype not in (torch.float32, torch.bfloat16) or hidden.dim() != 3 or hidden.shape[1] < T_max or hidden.shape[2] < H or \
+            hidden.stride(2) != 1 or hidden.stride(1) < H or hidden.stride(0) < T_max * hidden.stride(1):
+        raise ValueError(f"{what}: hidden must be bfloat16 or float32 [n_src, >= {T_max}, >= {H}] with unit column stride")
+    if row_index is not None:
+        _i32_dev(row_index, N, what + ": row_index")
+    elif hidden.shape[0] < N:
+        raise ValueError(f"{what}: hidden holds {hidden.shape[0]} items, the call asks for {N}")
+    _i32_dev(frame_lens, N, what + ": frame_lens")
+    return hidden.stride(0), hidden.stride(1), int(hidden.shape[0])
+
+
+def ctc_head_fwd(hidden, W, b, frame_lens, logp, row_index=None, p=0.0, seed=0, logits=None, argmax=None):
+    """Dropout, the Dense head and the log-softmax over cached encoder features (tmi_ctc_head_fwd in include/tethys_mi.h):
+    ``hidden`` bf16 / fp32 [n_src, >= T_max, H], gathered per item through ``row_index`` int32 [N] when given; ``W`` [H, V],
+    ``b`` [V] contiguous fp32; ``frame_lens`` int32 [N] by position; ``logp`` fp32 [N, T_max, V] is written on the frames
+    inside each length, and so are ``logits`` (the same shape) and ``argmax`` int32 [N, T_max] when given."""
+    N, T_max, V = _ctc_logp(logp, "ctc_head_fwd")
+    H = W.shape[0]
+    x_sn, x_st, n_src = _ctc_head_args(hidden, row_index, frame_lens, N, T_max, H, "ctc_head_fwd")
+    if W.dim() != 2 or W.shape[1] != V:
+        raise ValueError("ctc_head_fwd: W must be [H, V] with V the columns of logp")
+    _f32_flat(W, H * V, "ctc_head_fwd: W")
+    _f32_flat(b, V, "ctc_head_fwd: b")
+    if logits is not None and tuple(_ctc_logp(logits, "ctc_head_fwd: logits")) != (N, T_max, V):
+        raise ValueError("ctc_head_fwd: logits must be float32 [N, T, V] as logp")
+    if argmax is not None:
+        _i32_dev(argmax, N * T_max, "ctc_head_fwd: argmax")
+    with _probe("ctc_head_fwd", 2.0 * N * T_max * H * V):
+        check(lib().tmi_ctc_head_fwd(hidden.data_ptr(), dt(hidden), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(),
+                                     W.data_ptr(), b.data_ptr(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(logits),
+                                     0 if logits is None else logits.stride(0), 0 if logits is None else logits.stride(1),
+                                     logp.data_ptr(), logp.stride(0), logp.stride(1), ptr(argmax), N, T_max, H, V, stream()),
+              "tmi_ctc_head_fwd")
+
+
+def ctc_head_bwd(hidden, frame_lens, label_lens, grad, nll, infeasible, gW, gb, loss, n_infeasible, workspace, L_max,
+                 row_index=None, p=0.0, seed=0, reduction="mean"):
+    """The head's weight and bias gradients (tmi_ctc_head_bwd in include/tethys_mi.h) from the ``grad`` fp32 [N, T_max, V],
+    ``nll`` and ``infeasible`` that ``ctc_posteriors`` wrote for the log-probs of ``ctc_head_fwd`` with the same ``hidden``,
+    ``row_index``, ``frame_lens``, ``p`` and ``seed``: ``gW`` [H, V], ``gb`` [V], ``loss`` [1] fp32 and ``n_infeasible`` [1] int32
+    are written, not accumulated.  ``workspace``: float32, ``ctc_head_workspace_elems(N, T_max, H, V)`` elements, any contents."""
+    N, T_max, V = _ctc_logp(grad, "ctc_head_bwd")
+    H = gW.shape[0]
+    if reduction not in ("sum", "mean"):
+        raise ValueError('ctc_head_bwd: reduction must be "sum" or "mean"')
+    x_sn, x_st, n_src = _ctc_head_args(hidden, row_index, frame_lens, N, T_max, H, "ctc_head_bwd")
+    for t, n, w in ((label_lens, N, "label_lens"), (infeasible, N, "infeasible"), (n_infeasible, 1, "n_infeasible")):
+        _i32_dev(t, n, "ctc_head_bwd: " + w)
+    for t, n, w in ((nll, N, "nll"), (gW, H * V, "gW"), (gb, V, "gb"), (loss, 1, "loss"),
+                    (workspace, ctc_head_workspace_elems(N, T_max, H, V), "workspace")):
+        _f32_flat(t, n, "ctc_head_bwd: " + w)
+    if gW.dim() != 2 or gW.shape[1] != V:
+        raise ValueError("ctc_head_bwd: gW must be [H, V] with V the columns of grad")
+    with _probe("ctc_head_bwd", 2.0 * N * T_max * H * V):
+        check(lib().tmi_ctc_head_bwd(hidden.data_ptr(), dt(hidden), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(),
+                                     label_lens.data_ptr(), grad.data_ptr(), grad.stride(0), grad.stride(1), nll.data_ptr(),
+                                     infeasible.data_ptr(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     1 if reduction == "mean" else 0, gW.data_ptr(), gb.data_ptr(), loss.data_ptr(),
+                                     n_infeasible.data_ptr(), workspace.data_ptr(), workspace.numel() * 4, N, T_max, int(L_max),
+                                     H, V, stream()), "tmi_ctc_head_bwd")
+
+
 def fill_zero(t):
     """t[...] = 0 on the launch stream through the library (tmi_memset_async / tmi_memset2d_async), so that the fill is part
     of a recorded launch plan: a torch ``zero_()`` between two recorded launches would be missing from every replay.

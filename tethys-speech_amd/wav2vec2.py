@@ -65,6 +65,7 @@ class Wav2Vec2Config:  # V:24-128 (fields read by the pre-training path)
 # layer V:359 (attention probabilities), V:431 (attention output), V:393 (FFN intermediate), V:396 (FFN output)
 SITE_FE, SITE_FP, SITE_PH, SITE_PQ = 1, 2, 3, 4
 SITE_CLS = 5  # V:1046: the classification head's Dropout between its two Dense layers (tmi_cls_head_fwd / _bwd)
+SITE_CTC = 6  # V:972: the CTC model's Dropout in front of lm_head (tmi_ctc_head_fwd / _bwd)
 SITE_ATTN, SITE_ATTN_OUT, SITE_FFN_MID, SITE_FFN_OUT = 100, 200, 300, 400
 
 
@@ -1027,8 +1028,8 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# CTC inference (V:940-1001): the head, greedy decoding, the loss and forced alignment.  Forward only - CTC gradients and
-# fine-tuning are not built.
+# CTC (V:940-1001): the head, greedy decoding, the loss and forced alignment, and training of the HEAD alone on cached
+# features of the frozen encoder.  The head trains, the encoder does not: encoder fine-tuning is not built.
 CTC_MAX_LABELS = 511   # tmi_ctc_forward: one thread per extended state, 2 L + 1 <= 1023
 CTC_MAX_FRAMES = 4096  # tmi_ctc_viterbi: the moves of a walk-back piece are staged in LDS
 CTC_MAX_BEAMS = 16     # tmi_ctc_beam: one wave per beam
@@ -1070,6 +1071,14 @@ def check_ctc_args(cfg: Wav2Vec2Config, inputs_shape, labels=None, label_lengths
             raise ValueError("attention_mask must be a prefix per row: ones on the clip's frames, zeros behind them")
         if int(frame_lens.min()) < 1:
             raise ValueError("attention_mask leaves a row without a frame")
+    lab, lens = _check_ctc_labels(cfg, B, labels, label_lengths)
+    return B, T, frame_lens, mask, lab, lens
+
+
+def _check_ctc_labels(cfg: Wav2Vec2Config, B: int, labels, label_lengths):
+    """The label rules of ``check_ctc_args`` for ``B`` items -> (labels int32 [B, max(L_max, 1)], lengths int32 [B]), or
+    (None, None) without labels."""
+    V, blank = cfg.vocab_size, cfg.ctc_blank_id
     lab = lens = None
     if labels is None:
         if label_lengths is not None:
@@ -1097,7 +1106,48 @@ def check_ctc_args(cfg: Wav2Vec2Config, inputs_shape, labels=None, label_lengths
         if L_max == 0:
             lab = np.zeros((B, 1), dtype=np.int32)  # (the kernels take L_max >= 1; every length is 0)
         lab = np.ascontiguousarray(lab)
-    return B, T, frame_lens, mask, lab, lens
+    return lab, lens
+
+
+CTC_HEAD_MAX_ITEMS = 65535    # tmi_ctc_head_fwd / _bwd: items per call
+CTC_HEAD_MAX_ROWS = 1 << 22   # items x frames per call
+CTC_HEAD_MAX_HIDDEN = 4096    # H, a multiple of 8
+
+
+def check_ctc_head_args(cfg: Wav2Vec2Config, hidden_shape, hidden_dtype, frame_lengths, labels, label_lengths=None):
+    """Host validation of the cached-feature calls of ``Wav2Vec2ForCTC`` (``head_step`` through ``fit_ctc_head``,
+    ``evaluate_features``; no GPU needed).  ``hidden_shape`` (N, T_max, H) with H the model's hidden size, a multiple of 8
+    and <= 4096, 1 <= T_max <= 4096; ``hidden_dtype`` torch.float32 or torch.bfloat16; ``frame_lengths`` N integers in
+    [1, T_max]; ``labels`` / ``label_lengths`` under the rules of ``check_ctc_args``; 2 <= vocab_size <= 64.  N itself is not
+    limited: the calls cut it into pieces of at most 65535 items and 2^22 frames (``ctc_head_batch_limit``).
+    -> (N, T_max, frame_lens int32 [N], labels int32 [N, max(L_max, 1)], label_lengths int32 [N]) on the host."""
+    if len(hidden_shape) != 3 or any(int(s) < 1 for s in hidden_shape):
+        raise ValueError("hidden must be [N, T_max, H]")
+    N, T_max, H = (int(s) for s in hidden_shape)
+    if H != cfg.hidden_size or H % 8 or not 8 <= H <= CTC_HEAD_MAX_HIDDEN:
+        raise ValueError(f"hidden must be [N, T_max, hidden_size = {cfg.hidden_size}], a multiple of 8 in [8, {CTC_HEAD_MAX_HIDDEN}]")
+    if T_max > CTC_MAX_FRAMES:
+        raise ValueError(f"at most {CTC_MAX_FRAMES} frames per item (tmi_ctc_posteriors), got {T_max}")
+    if hidden_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("hidden must be float32 or bfloat16")
+    if not 2 <= cfg.vocab_size <= 64:
+        raise ValueError("the CTC head takes 2 <= vocab_size <= 64 (tmi_ctc_logsoftmax: one lane per column)")
+    if not 0 <= cfg.ctc_blank_id < cfg.vocab_size:
+        raise ValueError("ctc_blank_id must be in [0, vocab_size)")
+    fl = np.asarray(torch.as_tensor(frame_lengths).detach().to("cpu").numpy())
+    if fl.dtype.kind not in "iu" or fl.reshape(-1).shape[0] != N or fl.ndim != 1:
+        raise ValueError(f"frame_lengths must be N = {N} integers")
+    if (fl < 1).any() or (fl > T_max).any():
+        raise ValueError(f"frame_lengths must lie in [1, T_max = {T_max}]")
+    if labels is None:
+        raise ValueError("labels are required")
+    lab, lens = _check_ctc_labels(cfg, N, labels, label_lengths)
+    return N, T_max, fl.astype(np.int32), lab, lens
+
+
+def ctc_head_batch_limit(T_max: int) -> int:
+    """The most items one tmi_ctc_head call takes at ``T_max`` frames: 65535, and 2^22 frames in all."""
+    return max(1, min(CTC_HEAD_MAX_ITEMS, CTC_HEAD_MAX_ROWS // int(T_max)))
 
 
 def check_ctc_beam_args(cfg: Wav2Vec2Config, num_beams=None, num_return_sequences=1):
@@ -1219,9 +1269,13 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
     """V:940-1001 at inference: the base model (stem, positional conv, projection, encoder - the blocks and the inference
     workspace of ``Wav2Vec2ForPreTraining``) and a Dense head (V:972-975) over ``vocab_size`` symbols, with greedy CTC
     decoding, the CTC loss and forced alignment on the kernels of csrc/ctc.hip, and the forward-backward posteriors of
-    csrc/ctc_post.hip.  Every public method runs under
+    csrc/ctc_post.hip.  Every inference method runs under
     ``torch.no_grad()`` on the inference workspace with dropout off, and reads or writes nothing of the training state.
-    The training entry points raise: CTC gradients are not built."""
+    The head trains, the encoder does not: ``encode_features`` caches the frozen encoder's output, ``head_step`` /
+    ``fit_ctc_head`` train ``lm_head`` on it (csrc/ctc_head.hip around tmi_ctc_posteriors) and touch nothing of the arena
+    outside the head's slice, ``evaluate_features`` scores it.  The whole-model training entry points raise.  Not built:
+    encoder fine-tuning, a gradient with respect to the features, a weighted sum over layers, SpecAugment on the cached
+    features, label smoothing."""
 
     _arena_head = "ctc"
 
@@ -1233,6 +1287,9 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         if config.ctc_loss_reduction not in ("sum", "mean"):
             raise ValueError('ctc_loss_reduction must be "sum" or "mean"')
         super().__init__(config, device=device, precision=precision, seed=seed)
+        a = self.arena
+        self.head_lo, self.head_hi = a.offsets["lm_head.kernel"], a.numel  # the head: the arena's contiguous tail
+        self._head_sets: Dict[tuple, Dict[str, torch.Tensor]] = {}
 
     def forward_backward(self, *a, **k):
         raise NotImplementedError("CTC fine-tuning is not built")
@@ -1551,6 +1608,206 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             if return_states:
                 result["state_posteriors"] = gamma[:, :, :2 * c["L_max"] + 1]
         return result
+
+    # -- the head on cached features of the frozen encoder (the CTC probe) -------------------------------------------
+    @torch.no_grad()
+    def encode_features(self, inputs, attention_mask=None):
+        """The frozen encoder's output for ``head_step`` / ``fit_ctc_head`` / ``evaluate_features``: ``hidden`` [B, T, H] in
+        the model's dtype, bit for bit ``forward_infer``'s ``last_hidden_state`` (the head is not run), and
+        ``frame_lengths`` int32 [B] on the device (the row sums of ``attention_mask``, a binary prefix mask over frames as
+        ``check_ctc_args`` takes it; T without one).  Cache it: the encoder does not change while the head is trained."""
+        if not torch.is_tensor(inputs) or inputs.dim() != 2 or inputs.dtype != torch.float32:
+            raise TypeError("inputs must be float32 [B, T_in]")
+        B, T, frame_lens, mask, _, _ = check_ctc_args(self.config, tuple(inputs.shape), None, None, attention_mask)
+        audio = inputs.to(self.device).contiguous()
+        inf = self._infer_prepare(B, inputs.shape[1])
+        with self._inference(inf):
+            key_bias = None if mask is None else ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, as forward_infer
+            x, _ = self._infer_body(audio, inf, key_bias)
+            hidden = x.view(B, T, self.config.hidden_size).clone()
+        return {"hidden": hidden, "frame_lengths": torch.from_numpy(frame_lens).to(self.device)}
+
+    def _check_hidden(self, hidden):
+        H = self.config.hidden_size
+        if not torch.is_tensor(hidden) or hidden.dtype != self.dtype or hidden.dim() != 3 or hidden.shape[2] != H or \
+                hidden.shape[0] < 1 or hidden.shape[1] < 1 or hidden.stride(2) != 1:
+            raise TypeError(f"hidden must be {self.dtype} [N, T, {H}] with unit column stride (encode_features)")
+        if hidden.shape[1] > CTC_MAX_FRAMES:
+            raise ValueError(f"at most {CTC_MAX_FRAMES} frames per item (tmi_ctc_posteriors), got {hidden.shape[1]}")
+        return hidden if hidden.device == self.device else hidden.to(self.device)
+
+    def _ctc_head_buffers(self, kind, N, T, L):
+        """The buffers of one cached-feature call, kept per (kind, N, T_max, L_max); at most 8 sets live."""
+        key = (kind, N, T, L)
+        ws = self._head_sets.get(key)
+        if ws is None:
+            V, H = self.config.vocab_size, self.config.hidden_size
+            f32, i32 = dict(dtype=torch.float32, device=self.device), dict(dtype=torch.int32, device=self.device)
+            # (what the kernels leave unwritten - frames past a clip - is zero from here on)
+            ws = {"logp": torch.zeros((N, T, V), **f32), "nll": torch.zeros(N, **f32), "bad": torch.zeros(N, **i32)}
+            if kind == "step":
+                ws.update(grad=torch.zeros((N, T, V), **f32), occ=torch.zeros((N, T, V), **f32),
+                          gamma=torch.zeros((N, T, 2 * L + 1), **f32), tok_frames=torch.zeros((N, L), **f32),
+                          tok_center=torch.zeros((N, L), **f32),
+                          bwd_ws=torch.empty(ops.ctc_head_workspace_elems(N, T, H, V), **f32))
+            else:
+                ws.update(argmax=torch.zeros((N, T), **i32), tokens=torch.zeros((N, T), **i32), start=torch.zeros((N, T), **i32),
+                          end=torch.zeros((N, T), **i32), len=torch.zeros(N, **i32), best=torch.zeros(N, **f32))
+            self._head_sets[key] = ws
+            while len(self._head_sets) > 8:
+                self._head_sets.pop(next(k for k in self._head_sets if k != key))
+        return ws
+
+    def _check_step_args(self, hidden, frame_lengths, labels, label_lengths, row_index):
+        hidden = self._check_hidden(hidden)
+        N = int(hidden.shape[0] if row_index is None else row_index.numel())
+        T = int(hidden.shape[1])
+        if not 1 <= N <= ctc_head_batch_limit(T):
+            raise ValueError(f"one call takes 1 <= N <= {ctc_head_batch_limit(T)} items of {T} frames (65535 items, 2^22 frames)")
+        for t, shape, w in ((frame_lengths, (N,), "frame_lengths"), (label_lengths, (N,), "label_lengths"), (row_index, (N,), "row_index")):
+            if t is None and w == "row_index":
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.int32 or tuple(t.shape) != shape or t.device != self.device or \
+                    not t.is_contiguous():
+                raise TypeError(f"{w} must be a contiguous int32 tensor [N = {N}] on the model's device (by position in the call)")
+        if not torch.is_tensor(labels) or labels.dtype != torch.int32 or labels.dim() != 2 or labels.shape[0] != N or \
+                not 1 <= labels.shape[1] <= CTC_MAX_LABELS or labels.device != self.device or not labels.is_contiguous():
+            raise TypeError(f"labels must be a contiguous int32 tensor [N = {N}, 1 <= L_max <= {CTC_MAX_LABELS}] on the model's device")
+        return hidden, N, T, int(labels.shape[1])
+
+    def head_step(self, hidden, frame_lengths, labels, label_lengths, optimizer, row_index=None, dropout=None, seed=0, step=0,
+                  return_intermediates=False):
+        """One training step of the HEAD (``lm_head``) on cached features ``hidden`` [N_src, T, H] of the frozen encoder
+        (``encode_features``), in this order: tmi_ctc_head_fwd with the reference's Dropout (V:972; rate ``dropout``, None:
+        ``config.hidden_dropout``) in front of the Dense layer; tmi_ctc_posteriors with zero_infinity on, so an infeasible
+        item costs 0 and gives no gradient; tmi_ctc_head_bwd into the head's slice of ``arena.g`` with
+        ``config.ctc_loss_reduction``; then ``optimizer``'s Adam (``optim.Adam`` defaults to the Keras epsilon) over that
+        slice ONLY.  The encoder's parameters, their moments and the bf16 mirror outside the head are not touched; the
+        mirror inside it is refreshed, so ``decode`` / ``evaluate`` see the trained head at once.  ``row_index`` int32
+        device tensor [N]: item n of the step is ``hidden[row_index[n]]`` (the minibatch gather costs nothing extra);
+        ``frame_lengths`` [N], ``labels`` [N, L_max] and ``label_lengths`` [N], int32 device tensors, are BY POSITION in
+        the step.  Their values are not read back here (``check_ctc_head_args`` validates them on the host; the kernels
+        clamp lengths and never dereference a symbol outside the row).  The mask of the step is that of dropout site
+        SITE_CTC under (``seed``, ``step``), as every site of this project, keyed by the position n * T + t in the step.
+        -> ``loss`` (before the update: the sum of the items' nll, or with "mean" the mean of nll / max(L, 1)) and
+        ``n_infeasible`` as one-element device tensors, no read-back.  ``return_intermediates`` adds clones of the step's
+        ``log_probs`` and ``logit_grad`` fp32 [N, T, V] (zeros past a clip's frames)."""
+        cfg = self.config
+        hidden, N, T, L = self._check_step_args(hidden, frame_lengths, labels, label_lengths, row_index)
+        p = float(cfg.hidden_dropout if dropout is None else dropout)
+        if not 0.0 <= p < 1.0:
+            raise ValueError("dropout must be in [0, 1)")
+        ws = self._ctc_head_buffers("step", N, T, L)
+        site = (int(seed) + int(step) * 0x9E3779B97F4A7C15 + SITE_CTC * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+        a = self.arena
+        ops.ctc_head_fwd(hidden, a.param("lm_head.kernel"), a.param("lm_head.bias"), frame_lengths, ws["logp"],
+                         row_index=row_index, p=p, seed=site)
+        ops.ctc_posteriors(ws["logp"], labels, label_lengths, frame_lengths, cfg.ctc_blank_id, ws["nll"], ws["bad"], ws["gamma"],
+                           ws["occ"], ws["tok_frames"], ws["tok_center"], ws["grad"], True)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        n_bad = torch.empty(1, dtype=torch.int32, device=self.device)
+        ops.ctc_head_bwd(hidden, frame_lengths, label_lengths, ws["grad"], ws["nll"], ws["bad"], a.grad("lm_head.kernel"),
+                         a.grad("lm_head.bias"), loss, n_bad, ws["bwd_ws"], L, row_index=row_index, p=p, seed=site,
+                         reduction=cfg.ctc_loss_reduction)
+        optimizer.iterations += 1
+        optimizer._update(self, self.head_lo, self.head_hi, 1.0, False, 0)
+        out = {"loss": loss, "n_infeasible": n_bad}
+        if return_intermediates:
+            out.update(log_probs=ws["logp"].clone(), logit_grad=ws["grad"].clone())
+        return out
+
+    @torch.no_grad()
+    def evaluate_features(self, hidden, frame_lengths, labels, label_lengths=None):
+        """``evaluate(edit_ops=True)`` on cached features ``hidden`` [N, T, H] (``encode_features``): tmi_ctc_head_fwd without
+        dropout from the fp32 master weights, then tmi_ctc_forward, tmi_ctc_greedy and tmi_edit_distance, in pieces of at
+        most 65535 items and 2^22 frames.  Arguments as ``check_ctc_head_args`` takes them.  -> Python numbers: ``nll_sum``,
+        ``n_items``, ``n_infeasible``, ``loss`` (as ``evaluate``: by ``ctc_loss_reduction``, an infeasible item +inf, or 0
+        with ``ctc_zero_infinity``), ``n_edits``, ``n_sub``, ``n_del``, ``n_ins``, ``n_ref_tokens``, ``n_hyp_tokens``,
+        ``token_error_rate``.  On a bf16 model this differs from ``evaluate(inputs, ...)`` only by the latter's bf16
+        rounding of ``lm_head`` (its GEMM reads the bf16 mirror; the head here reads the fp32 master in both precisions);
+        on an fp32 model only by the order of the sums."""
+        cfg = self.config
+        hidden = self._check_hidden(hidden)
+        N, T, fl, lab, lens = check_ctc_head_args(cfg, tuple(hidden.shape), hidden.dtype, frame_lengths, labels, label_lengths)
+        L = lab.shape[1]
+        a = self.arena
+        nll_sum = item_sum = 0.0
+        n_bad = 0
+        counts = {k: 0.0 for k in ops.EDIT_COUNT_KEYS}
+        step = ctc_head_batch_limit(T)
+        for s in range(0, N, step):
+            n = min(step, N - s)
+            ws = self._ctc_head_buffers("eval", n, T, L)
+            fl_d, lab_d = torch.from_numpy(fl[s:s + n]).to(self.device), torch.from_numpy(lab[s:s + n]).to(self.device)
+            lens_d = torch.from_numpy(lens[s:s + n]).to(self.device)
+            ops.ctc_head_fwd(hidden[s:s + n], a.param("lm_head.kernel"), a.param("lm_head.bias"), fl_d, ws["logp"], argmax=ws["argmax"])
+            ops.ctc_forward(ws["logp"], lab_d, lens_d, fl_d, cfg.ctc_blank_id, ws["nll"], ws["bad"], False)
+            ops.ctc_greedy(ws["argmax"], ws["logp"], fl_d, cfg.ctc_blank_id, ws["tokens"], ws["len"], ws["start"], ws["end"],
+                           ws["best"])
+            edits = ops.edit_distance(ws["tokens"], lab_d, ws["len"], lens_d)
+            c = ops.edit_counts(edits)
+            for k in counts:
+                counts[k] += c[k]
+            host = torch.cat([ws["bad"], ws["nll"].view(torch.int32)]).cpu()
+            hbad, hnll = host[:n].numpy(), host[n:].view(torch.float32).double().numpy()
+            ok = hbad == 0
+            nll_sum += float(hnll[ok].sum())
+            n_bad += int((~ok).sum())
+            item = np.where(ok, hnll, 0.0 if cfg.ctc_zero_infinity else np.inf)
+            item_sum += float((item / np.maximum(lens[s:s + n], 1)).sum() if cfg.ctc_loss_reduction == "mean" else item.sum())
+        counts = ops.finish_edit_counts(counts)
+        result = {"nll_sum": nll_sum, "n_items": float(N), "n_infeasible": float(n_bad),
+                  "loss": item_sum / N if cfg.ctc_loss_reduction == "mean" else item_sum}
+        result.update({k: counts[k] for k in ("n_edits", "n_ref_tokens", "token_error_rate", "n_sub", "n_del", "n_ins", "n_hyp_tokens")})
+        return result
+
+
+def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, batch_size, learning_rate=1e-3, seed=0,
+                 eval_set=None):
+    """Train ``model``'s CTC head on cached features ``hidden`` [N, T, H] (``model.encode_features``) with
+    ``frame_lengths`` [N], ``labels`` [N, L_max] and ``label_lengths`` [N] (``check_ctc_head_args``).  Every epoch draws one
+    permutation from a host generator seeded with ``seed``, gathers the labels and the two lengths in that order on the
+    host, uploads them and the permutation once, and runs one ``head_step`` per minibatch with a slice of the permutation
+    as ``row_index``: ``hidden`` stays where it is.  The last batch may be short.  Adam with ``learning_rate`` and the Keras
+    epsilon; the dropout rate is ``config.hidden_dropout``.  -> the history, one dict per epoch: ``epoch``, ``loss`` ("mean":
+    the mean of the steps' losses weighted by their items; "sum": their sum; one read-back per epoch), ``n_infeasible``
+    (over the epoch's steps) and, with ``eval_set`` = (hidden, frame_lengths, labels, label_lengths), ``eval_loss`` and
+    ``eval_token_error_rate`` (``evaluate_features``)."""
+    from . import optim
+    feats = model._check_hidden(hidden)
+    N, T, fl, lab, lens = check_ctc_head_args(model.config, tuple(feats.shape), feats.dtype, frame_lengths, labels, label_lengths)
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 0 or not 1 <= batch_size <= ctc_head_batch_limit(T):
+        raise ValueError(f"epochs >= 0 and 1 <= batch_size <= {ctc_head_batch_limit(T)}")
+    if eval_set is not None and len(eval_set) != 4:
+        raise ValueError("eval_set is (hidden, frame_lengths, labels, label_lengths)")
+    mean = model.config.ctc_loss_reduction == "mean"
+    opt = optim.Adam(learning_rate)
+    rng = np.random.default_rng(seed)
+    history, step = [], 0
+    for epoch in range(epochs):
+        perm = rng.permutation(N)
+        idx = torch.from_numpy(perm.astype(np.int32)).to(model.device)
+        fl_d = torch.from_numpy(np.ascontiguousarray(fl[perm])).to(model.device)
+        lab_d = torch.from_numpy(np.ascontiguousarray(lab[perm])).to(model.device)
+        lens_d = torch.from_numpy(np.ascontiguousarray(lens[perm])).to(model.device)
+        losses, bad, rows = [], [], []
+        for s in range(0, N, batch_size):
+            e = min(N, s + batch_size)
+            r = model.head_step(feats, fl_d[s:e], lab_d[s:e], lens_d[s:e], opt, row_index=idx[s:e], seed=seed, step=step)
+            losses.append(r["loss"])
+            bad.append(r["n_infeasible"])
+            rows.append(e - s)
+            step += 1
+        w = torch.tensor(rows if mean else [1.0] * len(rows), dtype=torch.float64, device=model.device)
+        total = (torch.cat(losses).double() * w).sum() / (w.sum() if mean else 1.0)
+        host = torch.stack([total, torch.cat(bad).sum().double()]).cpu().tolist()
+        rec = {"epoch": epoch, "loss": float(host[0]), "n_infeasible": int(host[1])}
+        if eval_set is not None:
+            ev = model.evaluate_features(*eval_set)
+            rec.update(eval_loss=ev["loss"], eval_token_error_rate=ev["token_error_rate"])
+        history.append(rec)
+    return history
 
 
 # ---------------------------------------------------------------------------------------------------------------------
