@@ -1245,6 +1245,64 @@ int tmi_ctc_head_bwd(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t 
                      int64_t T_max, int64_t L_max, int64_t H, int64_t V, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * The learned weighted sum over encoder layers in front of the CTC head (csrc/layer_mix.hip): the frozen-encoder probe of
+ * SUPERB / s3prl (`use_weighted_layer_sum`).  K layers of hidden states, all in x_dtype (TMI_BF16 or TMI_F32) and of one
+ * layout: element (s, t, h) of layer k at layers[k][s*x_sn + t*x_st + h].  `layers` is a HOST array of K device pointers; it
+ * is copied into the kernels' arguments, so no device-side pointer table exists and the layers may be separate allocations
+ * or slices of one stacked [K, n_src, T, H] tensor.  row_index, n_src, frame_lens, the live rows r = n*T_max + t and the
+ * clamping of device values are exactly those of tmi_ctc_head_fwd: a dead row is neither read nor written, a row_index entry
+ * outside [0, n_src) reads as zeros.  fp32 arithmetic throughout.
+ *
+ * Both calls form the weights w = softmax(a) from the fp32 logits a [K] in the same way in every workgroup:
+ *   m = max_k a[k];  e_k = expf(a[k] - m);  s = e_0 + e_1 + .. in ascending k, starting from e_0;  w_k = e_k / s
+ *
+ * tmi_layer_mix_fwd, per live row:
+ *   mixed[n, t, h] = fmaf(w_k, (float) x_k[s, t, h], acc) for k = 0 .. K-1 in that order, from acc = 0
+ * mixed is fp32, element (n, t, h) at mixed[n*m_sn + t*m_st + h], BY POSITION: the gather through row_index happens here, and
+ * the head kernels then run on mixed with row_index = NULL and x_dtype = TMI_F32.  w_out fp32 [K] may be NULL; when given it
+ * receives w.
+ *
+ * tmi_layer_mix_bwd: the gradient of loss = sum_n w_n nll[n] with respect to a, from `grad` as tmi_ctc_posteriors wrote it
+ * for the log-probs tmi_ctc_head_fwd formed from `mixed` with dropout (p, seed), its infeasible [N], and the head's fp32
+ * W [H, V] (contiguous):
+ *   w_n       = as tmi_ctc_head_bwd forms it (0 when infeasible[n] != 0: that item's grad is then not read)
+ *   gs[r][v]  = grad[r][v] * w_n on a live row
+ *   dx[r][h]  = keep(seed, r, h) ? (fmaf(gs[r][v], W[h][v], .) over v = 0 .. V-1 in that order, from 0) * 65536/(65536-thr) : 0
+ *               the generator and keying of tmi_ctc_head_fwd: stream 0, row = the position r, column = h, the scale formed
+ *               the same way; p == 0 hashes nothing.  dx is never stored to memory.
+ *   d_k       = sum over the live rows r and the columns h of dx[r][h] * (float) x_k[s, t, h]                         (*)
+ *   g_a[k]    = w_k * (d_k - dot),  dot = fmaf(w_j, d_j, .) over j = 0 .. K-1 in that order, from 0
+ *   (*) the rows 0 .. N*T_max - 1 are cut into tiles of tr = 8 * ceil(N*T_max / 8192) consecutive rows (8 rows up to
+ *       N*T_max = 8192; at most 1024 tiles).  H is cut into slices of hs = 256 columns (128 when V > 32), a slice into pieces
+ *       of 8 consecutive columns; rp = 2048 / hs rows of a tile are in flight at a time.  Thread (j, q) of a tile's 256,
+ *       j < rp, q < hs / 8, owns the rows j, j + rp, .. of the tile and in every slice the columns 8 q .. 8 q + 7.  Its sum is
+ *       one fmaf chain from 0: the slices in ascending order, inside a slice its rows ascending, inside a row its 8 columns
+ *       ascending (a row that is not live, an infeasible item and a piece past H add nothing).  The 64 lanes of a wave -
+ *       threads 64 w .. 64 w + 63 in the order (j, q) -> j * (hs / 8) + q - meet in the xor butterfly 32, 16, .., 1; the four
+ *       waves are added ((w0 + w1) + w2) + w3: the tile's partial sum.  d_k: lane l of a wave adds the tiles l, l + 64, .. in
+ *       ascending order from 0, and the 64 lanes meet in the same butterfly.  The order depends on (N*T_max, H, V) alone.
+ * g_a fp32 [K] and, when not NULL, d fp32 [K] (the gradient with respect to the weights themselves) are written, not
+ * accumulated; both are zero with no live row.  No floating-point atomic anywhere: the same call gives the same bits.
+ * workspace: tmi_layer_mix_workspace_bytes(N, T_max, H, V, K) bytes (the tiles' partial sums, tiles * K floats), 16-byte
+ * aligned, any contents.
+ *
+ * Limits: 1 <= K <= 64; N, T_max, N*T_max, H, V, L_max, p, reduction, the strides (m_st >= H) and n_src as for
+ * tmi_ctc_head_*; every layer, mixed and W 16-byte aligned, the other pointers 4.  Anything else, a NULL `layers` or a NULL
+ * entry among its first K included: TMI_ERR_INVALID, nothing is launched and nothing written; tmi_last_error names the
+ * function and the limits.  tmi_layer_mix_workspace_bytes returns -1 outside the limits.
+ * Not built: a LayerNorm per layer before the mix, the same mix in front of the classification head (it needs a gradient with
+ * respect to `pooled` that tmi_cls_head_bwd does not form). */
+int64_t tmi_layer_mix_workspace_bytes(int64_t N, int64_t T_max, int64_t H, int64_t V, int64_t K);
+int tmi_layer_mix_fwd(const void* const* layers, int64_t K, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
+                      const int32_t* row_index, const int32_t* frame_lens, const float* a, float* w_out, float* mixed,
+                      int64_t m_sn, int64_t m_st, int64_t N, int64_t T_max, int64_t H, void* stream);
+int tmi_layer_mix_bwd(const void* const* layers, int64_t K, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
+                      const int32_t* row_index, const int32_t* frame_lens, const int32_t* label_lens, const float* grad,
+                      int64_t gr_sn, int64_t gr_st, const int32_t* infeasible, float p, uint64_t seed, int32_t reduction,
+                      const float* W, const float* a, float* g_a, float* d, void* workspace, int64_t workspace_bytes, int64_t N,
+                      int64_t T_max, int64_t L_max, int64_t H, int64_t V, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Log-mel front end (speech_jobs/whisper_dist.py:739-766, extract_fbank_features; dead in the
  * reference's training path).  The windowed DFT of the frames is a tmi_gemm
  * (frames = overlapping rows of the waveform, a_sm = hop; B = [n_fft, 2*n_bins] Hann-weighted

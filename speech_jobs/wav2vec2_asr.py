@@ -30,6 +30,11 @@ is decoded the CTC head is trained on the clips with the encoder frozen - the cl
 (``encode_features``), ``wav2vec2.fit_ctc_head`` runs the epochs and prints one JSON line per epoch, then the line of
 ``evaluate_features`` on the same clips; ``--save`` writes the model with ``train.save_weights``.  The rest of the job then
 reports the trained head.  Clips without labels (an empty line) train as an empty transcript.
+``--layer_mix`` (with ``--fit_head``): the probe reads a learned softmax-weighted sum of ALL encoder layers instead of the last
+one (``encode_features(layers="all")``, ``fit_ctc_head(layer_mix=...)``): every epoch's line adds the layer weights,
+``--save FILE`` also writes ``FILE.layermix.npy`` (the K logits), and the mix stays attached (``set_layer_mix``) so the rest of
+the job decodes through it.  ``--layer_mix_file F.npy`` attaches a saved mix for the rest of the job (without ``--fit_head``:
+to a model loaded with ``--weights``; with ``--fit_head --layer_mix``: the logits the fit starts from).
 There is no tokenizer: ids in, ids out.
 """
 import argparse
@@ -77,6 +82,9 @@ def main(argv=None):
     parser.add_argument("--train_batch_size", type=int, default=8, help="with --fit_head: clips per head step")
     parser.add_argument("--learning_rate", type=float, default=1e-3, help="with --fit_head: Adam's")
     parser.add_argument("--save", default=None, help="with --fit_head: write the trained model here (train.save_weights)")
+    parser.add_argument("--layer_mix", action="store_true",
+                        help="with --fit_head: train a softmax-weighted sum over all encoder layers in front of the head")
+    parser.add_argument("--layer_mix_file", default=None, help=".npy of K mixing logits: attach this layer mix for the rest of the job")
     parser.add_argument("--build_lm", default=None, help="file of token ids, one line per sequence: build a table and exit")
     parser.add_argument("--lm_order", type=int, default=2, help="with --build_lm: the order of the table (1..4)")
     parser.add_argument("--lm_out", default=None, help="with --build_lm: where the .npy table goes")
@@ -87,6 +95,8 @@ def main(argv=None):
         parser.error("--fit_head comes with --labels")
     if args.save and not args.fit_head:
         parser.error("--save comes with --fit_head")
+    if args.layer_mix and not args.fit_head:
+        parser.error("--layer_mix comes with --fit_head")
 
     import numpy as np
     if args.build_lm:
@@ -130,7 +140,31 @@ def main(argv=None):
     mask = wav2vec2.frame_attention_mask(model.config, lengths, T_in)
     audio = torch.from_numpy(batch).to(device)
     rows = read_labels(args.labels, len(clips)) if args.labels else None
-    if args.fit_head:
+    mix = None
+    if args.layer_mix or args.layer_mix_file:
+        mix = wav2vec2.LayerMix(model.config.num_hidden_layers + 1, device)
+        if args.layer_mix_file:
+            mix.load_state_dict({"logits": np.load(args.layer_mix_file)})
+    if args.fit_head and mix is not None and args.layer_mix:
+        L = max([len(r) for r in rows] + [1])
+        fit_labels = np.zeros((len(rows), L), dtype=np.int64)
+        for i, r in enumerate(rows):
+            fit_labels[i, :len(r)] = r
+        fit_lens = [len(r) for r in rows]
+        feats = model.encode_features(audio, attention_mask=mask, layers="all")
+        hist = wav2vec2.fit_ctc_head(model, feats["hidden_layers"], feats["frame_lengths"], fit_labels, fit_lens, args.epochs,
+                                     args.train_batch_size, learning_rate=args.learning_rate, layer_mix=mix)
+        for rec in hist:
+            print(json.dumps({"fit_head_epoch": rec["epoch"] + 1, "loss": rec["loss"], "n_infeasible": rec["n_infeasible"],
+                              "layer_weights": rec["layer_weights"]}), flush=True)
+        fit = model.evaluate_features(feats["hidden_layers"], feats["frame_lengths"], fit_labels, fit_lens, layer_mix=mix)
+        print(json.dumps({"fit_head": {k: fit[k] for k in ("loss", "nll_sum", "n_infeasible", "n_edits", "n_ref_tokens",
+                                                           "token_error_rate")}, "epochs": len(hist),
+                          "layer_weights": mix.weights().cpu().tolist()}), flush=True)
+        if args.save:
+            train.save_weights(model, args.save)
+            np.save(args.save + ".layermix.npy", mix.state_dict()["logits"].numpy())
+    elif args.fit_head:
         L = max([len(r) for r in rows] + [1])
         fit_labels = np.zeros((len(rows), L), dtype=np.int64)
         for i, r in enumerate(rows):
@@ -146,6 +180,8 @@ def main(argv=None):
                                                            "token_error_rate")}, "epochs": len(hist)}), flush=True)
         if args.save:
             train.save_weights(model, args.save)
+    if mix is not None:
+        model.set_layer_mix(mix)
     torch.cuda.synchronize()
     t0 = time.time()
     beam = args.num_beams is not None and args.num_beams > 1

@@ -206,7 +206,11 @@ SIGNATURES = {
     "tmi_ctc_head_fwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_f32, C.c_uint64, c_vp, c_i64, c_i64,
                                  c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_vp]),
     "tmi_ctc_head_bwd": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_f32,
-                                 C.c_uint64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+                                 C.c_uint64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),    "tmi_layer_mix_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i64, c_i64]),
+    "tmi_layer_mix_fwd": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64,
+                                  c_i64, c_vp]),
+    "tmi_layer_mix_bwd": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_f32,
+                                  C.c_uint64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
 }
 
 ABI_VERSION = 31

@@ -1019,6 +1019,81 @@ def ctc_head_bwd(hidden, frame_lens, label_lens, grad, nll, infeasible, gW, gb, 
                                      H, V, stream()), "tmi_ctc_head_bwd")
 
 
+def layer_mix_workspace_elems(N: int, T_max: int, H: int, V: int, K: int) -> int:
+    """float32 elements of tmi_layer_mix_bwd's workspace (tmi_layer_mix_workspace_bytes / 4)."""
+    n = int(lib().tmi_layer_mix_workspace_bytes(int(N), int(T_max), int(H), int(V), int(K)))
+    if n < 0:
+        raise ValueError(f"tmi_layer_mix takes 1 <= K <= 64 layers and the sizes of tmi_ctc_head (1 <= N <= 65535, 1 <= T_max <= "
+                         f"4096, N * T_max <= 2^22, 8 <= H <= 4096 a multiple of 8, 2 <= V <= 64), got K {K}, {N} x {T_max} x {H} x {V}")
+    return n // 4
+
+
+def _layer_mix_args(layers, row_index, frame_lens, N, T_max, H, what):
+    """``layers``: one stacked tensor [K, n_src, >= T_max, >= H] or a sequence of K tensors [n_src, >= T_max, >= H] of one
+    dtype, shape and strides -> (host array of K device pointers, K, a layer, x_sn, x_st, n_src)."""
+    if torch.is_tensor(layers):
+        if layers.dim() != 4:
+            raise ValueError(f"{what}: stacked layers must be [K, n_src, T, H]")
+        layers = layers.unbind(0)
+    layers = list(layers)
+    K = len(layers)
+    if not 1 <= K <= 64:
+        raise ValueError(f"{what}: 1 <= K <= 64 layers, got {K}")
+    x0 = layers[0]
+    for x in layers:
+        if not torch.is_tensor(x) or x.dtype != x0.dtype or x.shape != x0.shape or x.stride() != x0.stride() or x.device != x0.device:
+            raise ValueError(f"{what}: every layer must have the dtype, shape, strides and device of the first")
+    x_sn, x_st, n_src = _ctc_head_args(x0, row_index, frame_lens, N, T_max, H, what)
+    table = (C.c_void_p * K)(*[x.data_ptr() for x in layers])
+    return table, K, x0, x_sn, x_st, n_src
+
+
+def layer_mix_fwd(layers, a, frame_lens, mixed, row_index=None, w_out=None):
+    """The softmax-weighted sum of K layers of hidden states (tmi_layer_mix_fwd in include/tethys_mi.h): ``layers`` one
+    stacked bf16 / fp32 tensor [K, n_src, >= T_max, H] or a sequence of K tensors [n_src, >= T_max, H] of one layout, gathered
+    per item through ``row_index`` int32 [N] when given; ``a`` fp32 with at least K entries, the mixing logits;
+    ``frame_lens`` int32 [N] by position; ``mixed`` fp32 [N, T_max, H] is written on the frames inside each length, by
+    position; ``w_out`` fp32 (at least K entries) receives softmax(a) when given."""
+    if mixed.dtype != torch.float32 or mixed.dim() != 3 or mixed.stride(2) != 1:
+        raise ValueError("layer_mix_fwd: mixed must be float32 [N, T_max, H] with unit column stride")
+    N, T_max, H = mixed.shape
+    table, K, x0, x_sn, x_st, n_src = _layer_mix_args(layers, row_index, frame_lens, N, T_max, H, "layer_mix_fwd")
+    _f32_flat(a, K, "layer_mix_fwd: a")
+    if w_out is not None:
+        _f32_flat(w_out, K, "layer_mix_fwd: w_out")
+    with _probe("layer_mix_fwd", 2.0 * N * T_max * H * K):
+        check(lib().tmi_layer_mix_fwd(table, K, dt(x0), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(), a.data_ptr(),
+                                      ptr(w_out), mixed.data_ptr(), mixed.stride(0), mixed.stride(1), N, T_max, H, stream()),
+              "tmi_layer_mix_fwd")
+
+
+def layer_mix_bwd(layers, a, frame_lens, label_lens, grad, infeasible, W, g_a, workspace, L_max, row_index=None, p=0.0, seed=0,
+                  reduction="mean", d=None):
+    """The gradient of the head's loss with respect to the mixing logits (tmi_layer_mix_bwd in include/tethys_mi.h) from the
+    ``grad`` fp32 [N, T_max, V] and ``infeasible`` that ``ctc_posteriors`` wrote for the log-probs ``ctc_head_fwd`` formed
+    from ``layer_mix_fwd``'s output with dropout (``p``, ``seed``) and the head's ``W`` fp32 [H, V]: ``g_a`` fp32 (at least K
+    entries) and, when given, ``d`` (the gradient with respect to the weights) are written, not accumulated.  ``workspace``:
+    float32, ``layer_mix_workspace_elems(N, T_max, H, V, K)`` elements, any contents."""
+    N, T_max, V = _ctc_logp(grad, "layer_mix_bwd")
+    H = W.shape[0]
+    if reduction not in ("sum", "mean"):
+        raise ValueError('layer_mix_bwd: reduction must be "sum" or "mean"')
+    table, K, x0, x_sn, x_st, n_src = _layer_mix_args(layers, row_index, frame_lens, N, T_max, H, "layer_mix_bwd")
+    if W.dim() != 2 or W.shape[1] != V:
+        raise ValueError("layer_mix_bwd: W must be [H, V] with V the columns of grad")
+    for t, n, w in ((label_lens, N, "label_lens"), (infeasible, N, "infeasible")):
+        _i32_dev(t, n, "layer_mix_bwd: " + w)
+    for t, n, w in ((W, H * V, "W"), (a, K, "a"), (g_a, K, "g_a"),
+                    (workspace, layer_mix_workspace_elems(N, T_max, H, V, K), "workspace")) + (() if d is None else ((d, K, "d"),)):
+        _f32_flat(t, n, "layer_mix_bwd: " + w)
+    with _probe("layer_mix_bwd", 2.0 * N * T_max * H * (V + K)):
+        check(lib().tmi_layer_mix_bwd(table, K, dt(x0), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(),
+                                      label_lens.data_ptr(), grad.data_ptr(), grad.stride(0), grad.stride(1), infeasible.data_ptr(),
+                                      float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if reduction == "mean" else 0, W.data_ptr(),
+                                      a.data_ptr(), g_a.data_ptr(), ptr(d), workspace.data_ptr(), workspace.numel() * 4, N, T_max,
+                                      int(L_max), H, V, stream()), "tmi_layer_mix_bwd")
+
+
 def fill_zero(t):
     """t[...] = 0 on the launch stream through the library (tmi_memset_async / tmi_memset2d_async), so that the fill is part
     of a recorded launch plan: a torch ``zero_()`` between two recorded launches would be missing from every replay.

@@ -21,7 +21,7 @@ import contextlib
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -925,8 +925,8 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                 mask_dev = mask.to(self.device)
                 key_bias = ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, on the host, once per call
             attentions = [] if output_attentions else None
-            x, hidden = self._infer_body(audio, inf, key_bias, output_hidden_states, attentions=attentions,
-                                         attentions_dtype=attentions_dtype)
+            x, hidden = self._infer_body(audio, inf, key_bias, output_hidden_states or self._head_reads_layers(),
+                                         attentions=attentions, attentions_dtype=attentions_dtype)
             last = x.view(B, T, H).clone()
             result = {"last_hidden_state": last, "extract_features": ws["feats"].view(B, T, C).clone()}
             if output_hidden_states:
@@ -937,8 +937,17 @@ class Wav2Vec2ForPreTraining(KernelBlocks):
                 pooled = torch.empty(B, H, dtype=torch.float32, device=self.device)
                 ops.masked_mean_pool(x, mask_dev, pooled, B, T, H)
                 result["pooled_output"] = pooled
-            self._infer_head(x, inf, result)
+            inf["layer_inputs"] = hidden
+            try:
+                self._infer_head(x, inf, result)
+            finally:
+                del inf["layer_inputs"]
         return result
+
+    def _head_reads_layers(self) -> bool:
+        """Whether ``_infer_head`` reads the inputs of the layers (``inf["layer_inputs"]``) beside the last hidden state:
+        Wav2Vec2ForCTC with a layer mix attached.  The base model's does not."""
+        return False
 
     def _infer_head(self, x, inf, result):
         """What a model with a head of its own adds to ``forward_infer``'s outputs from the last hidden state ``x`` [B*T, H],
@@ -1145,6 +1154,80 @@ def check_ctc_head_args(cfg: Wav2Vec2Config, hidden_shape, hidden_dtype, frame_l
     return N, T_max, fl.astype(np.int32), lab, lens
 
 
+LAYER_MIX_MAX_LAYERS = 64   # tmi_layer_mix_fwd / _bwd: K
+
+
+class LayerMix:
+    """The learned mixing logits of a weighted sum over K layers of hidden states (``use_weighted_layer_sum``, the
+    frozen-encoder protocol of SUPERB / s3prl) and their Adam state: fp32 ``logits`` (zeros: uniform weights), ``grad`` and
+    the moments ``m``, ``v``, K entries each.  It lives OUTSIDE the model's arena - the arena's layout and the files of
+    ``train.save_weights`` are what they were - and is updated by ``head_step`` with ``ops.adam_step`` on its own four
+    buffers under the optimizer's hyper-parameters and iteration count (``learning_rate``: its own rate; None: the
+    optimizer's).  The allocations are padded to a multiple of 4 entries, the 16-byte granularity of tmi_adam_step; the pad
+    stays zero and the mixing kernels read K entries only."""
+
+    def __init__(self, num_layers, device="cuda:0", learning_rate=None):
+        K = int(num_layers)
+        if not 1 <= K <= LAYER_MIX_MAX_LAYERS:
+            raise ValueError(f"1 <= num_layers <= {LAYER_MIX_MAX_LAYERS}, got {num_layers}")
+        self.num_layers, self.device = K, torch.device(device)
+        self.learning_rate = None if learning_rate is None else float(learning_rate)
+        self._n = -(-K // 4) * 4
+        self._p, self._g, self._m, self._v = (torch.zeros(self._n, dtype=torch.float32, device=self.device) for _ in range(4))
+
+    logits = property(lambda self: self._p[:self.num_layers])
+    grad = property(lambda self: self._g[:self.num_layers])
+    m = property(lambda self: self._m[:self.num_layers])
+    v = property(lambda self: self._v[:self.num_layers])
+
+    def weights(self):
+        """softmax(logits), fp32 [K] on the mix's device (what tmi_layer_mix_fwd forms, to its rounding)."""
+        return torch.softmax(self.logits.double(), 0).float()
+
+    def state_dict(self):
+        return {k: getattr(self, k).detach().cpu().clone() for k in ("logits", "m", "v")}
+
+    def load_state_dict(self, state):
+        """``logits`` [K] is required; ``m`` and ``v`` are zeroed when absent (a mix saved as its logits alone)."""
+        if "logits" not in state:
+            raise ValueError("a LayerMix state holds logits")
+        for k, buf in (("logits", self._p), ("m", self._m), ("v", self._v)):
+            if k in state:
+                t = torch.as_tensor(np.asarray(state[k], dtype=np.float32) if not torch.is_tensor(state[k]) else state[k])
+                if tuple(t.shape) != (self.num_layers,):
+                    raise ValueError(f"{k} must hold num_layers = {self.num_layers} entries, got {list(t.shape)}")
+                buf[:self.num_layers].copy_(t.to(torch.float32))
+            else:
+                buf.zero_()
+        self._g.zero_()
+
+    def adam_step(self, optimizer):
+        """Adam over the K logits from ``grad`` with ``optimizer``'s hyper-parameters and its CURRENT iteration count."""
+        lr = optimizer.learning_rate if self.learning_rate is None else self.learning_rate
+        ops.adam_step(self._p, self._g, self._m, self._v, self._n, lr, optimizer.beta_1, optimizer.beta_2, optimizer.epsilon,
+                      optimizer.iterations, optimizer.eps_mode, optimizer.weight_decay, 1.0)
+
+
+def check_layer_mix_args(cfg: Wav2Vec2Config, layers_shape, layers_dtype, mix):
+    """Host validation of a stacked-layers argument of the CTC probe (no GPU needed): ``layers_shape`` (K, N, T_max, H) with
+    K = ``mix.num_layers`` in [1, 64], H the model's hidden size (a multiple of 8, <= 4096), 1 <= T_max <= 4096;
+    ``layers_dtype`` torch.float32 or torch.bfloat16; ``mix`` a ``LayerMix``.  -> (K, N, T_max)."""
+    if not isinstance(mix, LayerMix):
+        raise TypeError("layer_mix must be a wav2vec2.LayerMix")
+    if len(layers_shape) != 4 or any(int(s) < 1 for s in layers_shape):
+        raise ValueError("with a layer mix hidden must be the stacked layers [K, N, T_max, H] (encode_features(layers=\"all\"))")
+    K, N, T_max, H = (int(s) for s in layers_shape)
+    if K != mix.num_layers or not 1 <= K <= LAYER_MIX_MAX_LAYERS:
+        raise ValueError(f"hidden stacks {K} layers, the mix weighs {mix.num_layers} (1 .. {LAYER_MIX_MAX_LAYERS})")
+    if H != cfg.hidden_size or H % 8 or not 8 <= H <= CTC_HEAD_MAX_HIDDEN:
+        raise ValueError(f"hidden must be [K, N, T_max, hidden_size = {cfg.hidden_size}], a multiple of 8 in [8, {CTC_HEAD_MAX_HIDDEN}]")
+    if T_max > CTC_MAX_FRAMES:
+        raise ValueError(f"at most {CTC_MAX_FRAMES} frames per item (tmi_ctc_posteriors), got {T_max}")
+    if layers_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("hidden must be float32 or bfloat16")
+    return K, N, T_max
+
+
 def ctc_head_batch_limit(T_max: int) -> int:
     """The most items one tmi_ctc_head call takes at ``T_max`` frames: 65535, and 2^22 frames in all."""
     return max(1, min(CTC_HEAD_MAX_ITEMS, CTC_HEAD_MAX_ROWS // int(T_max)))
@@ -1273,9 +1356,10 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
     ``torch.no_grad()`` on the inference workspace with dropout off, and reads or writes nothing of the training state.
     The head trains, the encoder does not: ``encode_features`` caches the frozen encoder's output, ``head_step`` /
     ``fit_ctc_head`` train ``lm_head`` on it (csrc/ctc_head.hip around tmi_ctc_posteriors) and touch nothing of the arena
-    outside the head's slice, ``evaluate_features`` scores it.  The whole-model training entry points raise.  Not built:
-    encoder fine-tuning, a gradient with respect to the features, a weighted sum over layers, SpecAugment on the cached
-    features, label smoothing."""
+    outside the head's slice, ``evaluate_features`` scores it.  With a ``LayerMix`` the probe reads a learned
+    softmax-weighted sum of all layers (csrc/layer_mix.hip; ``encode_features(layers="all")``, ``layer_mix=`` on the three
+    calls, ``set_layer_mix`` for inference).  The whole-model training entry points raise.  Not built: encoder fine-tuning,
+    a LayerNorm per layer before the mix, SpecAugment on the cached features, label smoothing."""
 
     _arena_head = "ctc"
 
@@ -1290,9 +1374,29 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         a = self.arena
         self.head_lo, self.head_hi = a.offsets["lm_head.kernel"], a.numel  # the head: the arena's contiguous tail
         self._head_sets: Dict[tuple, Dict[str, torch.Tensor]] = {}
+        self._layer_mix: Optional[LayerMix] = None
 
     def forward_backward(self, *a, **k):
         raise NotImplementedError("CTC fine-tuning is not built")
+
+    def set_layer_mix(self, mix):
+        """Attach (or, with None, detach) a ``LayerMix`` over the num_hidden_layers + 1 hidden states.  While one is attached
+        the head of every inference call - ``model(inputs)``, ``decode`` (greedy, beam, LM), ``evaluate``, ``align``,
+        ``posteriors`` - reads tmi_layer_mix_fwd of the layers' inputs and the last layer's output, then tmi_ctc_head_fwd
+        without dropout from the fp32 master weights (as ``evaluate_features`` does), so they follow a probe trained with
+        ``head_step(layer_mix=...)``.  ``last_hidden_state`` stays the encoder's.  With None the head is the GEMM it was."""
+        if mix is not None:
+            if not isinstance(mix, LayerMix):
+                raise TypeError("set_layer_mix takes a wav2vec2.LayerMix or None")
+            if mix.num_layers != self.config.num_hidden_layers + 1:
+                raise ValueError(f"the mix must weigh num_hidden_layers + 1 = {self.config.num_hidden_layers + 1} layers, "
+                                 f"got {mix.num_layers}")
+            if mix.device != self.device:
+                raise ValueError("the mix must live on the model's device")
+        self._layer_mix = mix
+
+    def _head_reads_layers(self) -> bool:
+        return self._layer_mix is not None
 
     def __call__(self, inputs, attention_mask=None, training=False, **kw):
         """``model(inputs, attention_mask=None, training=False)`` is ``forward_infer``."""
@@ -1315,18 +1419,41 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         finally:
             self.ws = saved
 
-    def _ctc_head(self, x, inf):
+    def _ctc_head(self, x, inf, layer_inputs=None):
         """V:972-975: logits = x . lm_head + bias as ONE tmi_gemm into fp32 (bf16 operands on the bf16 model: the logits are
         never rounded to bf16), then tmi_ctc_logsoftmax.  -> (logits, log_probs fp32 [B*T, V], argmax int32 [B*T])."""
         self._ctc_buffers(inf)
         ws = inf["ws"]
+        if self._layer_mix is not None:
+            return self._ctc_head_mixed(x, inf, layer_inputs)
         self._dense_fwd(x, "lm_head.kernel", ws["ctc_logits"])
         ops.ctc_logsoftmax(ws["ctc_logits"], self.config.vocab_size, ws["ctc_logp"], ws["ctc_argmax"])
         return ws["ctc_logits"], ws["ctc_logp"], ws["ctc_argmax"]
 
+    def _ctc_head_mixed(self, x, inf, layer_inputs):
+        """The head behind the attached layer mix: tmi_layer_mix_fwd over ``layer_inputs`` (the input of every layer, as
+        ``_infer_body`` collects them) and ``x``, then ONE tmi_ctc_head_fwd without dropout from the fp32 master weights,
+        which writes logits, log-probs and argmax.  Every frame is computed, as the GEMM path computes every frame."""
+        ws, cfg = inf["ws"], self.config
+        B, T, H, V = inf["key"][0], inf["T"], cfg.hidden_size, cfg.vocab_size
+        if layer_inputs is None or len(layer_inputs) != cfg.num_hidden_layers:
+            raise RuntimeError("the attached layer mix needs the inputs of all layers (_infer_body(output_hidden_states=True))")
+        if "ctc_mixed" not in ws:
+            saved, self.ws = self.ws, ws
+            try:
+                self._buf("ctc_mixed", (B, T, H), torch.float32)
+            finally:
+                self.ws = saved
+            ws["ctc_all_frames"] = torch.full((B,), T, dtype=torch.int32, device=self.device)
+        a = self.arena
+        ops.layer_mix_fwd(list(layer_inputs) + [x.view(B, T, H)], self._layer_mix.logits, ws["ctc_all_frames"], ws["ctc_mixed"])
+        ops.ctc_head_fwd(ws["ctc_mixed"], a.param("lm_head.kernel"), a.param("lm_head.bias"), ws["ctc_all_frames"],
+                         ws["ctc_logp"].view(B, T, V), logits=ws["ctc_logits"].view(B, T, V), argmax=ws["ctc_argmax"])
+        return ws["ctc_logits"], ws["ctc_logp"], ws["ctc_argmax"]
+
     def _infer_head(self, x, inf, result):
         B, T, V = inf["key"][0], inf["T"], self.config.vocab_size
-        logits, logp, _ = self._ctc_head(x, inf)
+        logits, logp, _ = self._ctc_head(x, inf, inf.get("layer_inputs"))
         result["logits"] = logits.view(B, T, V).clone()
         result["log_probs"] = logp.view(B, T, V).clone()
 
@@ -1342,8 +1469,8 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         inf = self._infer_prepare(B, inputs.shape[1])
         with self._inference(inf):
             key_bias = None if mask is None else ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, as forward_infer
-            x, _ = self._infer_body(audio, inf, key_bias)
-            _, logp, amax = self._ctc_head(x, inf)
+            x, layer_inputs = self._infer_body(audio, inf, key_bias, self._layer_mix is not None)
+            _, logp, amax = self._ctc_head(x, inf, layer_inputs)
             i32 = dict(dtype=torch.int32, device=self.device)
             yield {"B": B, "T": T, "V": cfg.vocab_size, "logp": logp.view(B, T, cfg.vocab_size), "argmax": amax.view(B, T),
                    "frame_lens": torch.from_numpy(frame_lens).to(self.device), "frame_lens_host": frame_lens,
@@ -1611,11 +1738,16 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
 
     # -- the head on cached features of the frozen encoder (the CTC probe) -------------------------------------------
     @torch.no_grad()
-    def encode_features(self, inputs, attention_mask=None):
+    def encode_features(self, inputs, attention_mask=None, layers=None):
         """The frozen encoder's output for ``head_step`` / ``fit_ctc_head`` / ``evaluate_features``: ``hidden`` [B, T, H] in
         the model's dtype, bit for bit ``forward_infer``'s ``last_hidden_state`` (the head is not run), and
         ``frame_lengths`` int32 [B] on the device (the row sums of ``attention_mask``, a binary prefix mask over frames as
-        ``check_ctc_args`` takes it; T without one).  Cache it: the encoder does not change while the head is trained."""
+        ``check_ctc_args`` takes it; T without one).  Cache it: the encoder does not change while the head is trained.
+        ``layers="all"`` adds ``hidden_layers`` [K, B, T, H], K = num_hidden_layers + 1, in the model's dtype: slice k is bit
+        for bit ``forward_infer(output_hidden_states=True)["hidden_states"][k]`` (the input of layer k; the last slice is
+        ``hidden``) - what the calls take with a ``LayerMix``."""
+        if layers not in (None, "all"):
+            raise ValueError('layers must be None or "all"')
         if not torch.is_tensor(inputs) or inputs.dim() != 2 or inputs.dtype != torch.float32:
             raise TypeError("inputs must be float32 [B, T_in]")
         B, T, frame_lens, mask, _, _ = check_ctc_args(self.config, tuple(inputs.shape), None, None, attention_mask)
@@ -1623,12 +1755,23 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         inf = self._infer_prepare(B, inputs.shape[1])
         with self._inference(inf):
             key_bias = None if mask is None else ((1.0 - mask) * -10000.0).to(self.device)  # V:352-355, as forward_infer
-            x, _ = self._infer_body(audio, inf, key_bias)
+            x, layer_inputs = self._infer_body(audio, inf, key_bias, layers == "all")
             hidden = x.view(B, T, self.config.hidden_size).clone()
-        return {"hidden": hidden, "frame_lengths": torch.from_numpy(frame_lens).to(self.device)}
+        result = {"hidden": hidden, "frame_lengths": torch.from_numpy(frame_lens).to(self.device)}
+        if layers == "all":
+            result["hidden_layers"] = torch.stack(layer_inputs + [hidden])
+        return result
 
-    def _check_hidden(self, hidden):
+    def _check_hidden(self, hidden, layer_mix=None):
         H = self.config.hidden_size
+        if layer_mix is not None:
+            if not torch.is_tensor(hidden) or hidden.dtype != self.dtype or hidden.dim() != 4 or hidden.stride(3) != 1:
+                raise TypeError(f"with a layer mix hidden must be {self.dtype} [K, N, T, {H}] with unit column stride "
+                                f"(encode_features(layers=\"all\"))")
+            check_layer_mix_args(self.config, tuple(hidden.shape), hidden.dtype, layer_mix)
+            if layer_mix.device != self.device:
+                raise ValueError("the mix must live on the model's device")
+            return hidden if hidden.device == self.device else hidden.to(self.device)
         if not torch.is_tensor(hidden) or hidden.dtype != self.dtype or hidden.dim() != 3 or hidden.shape[2] != H or \
                 hidden.shape[0] < 1 or hidden.shape[1] < 1 or hidden.stride(2) != 1:
             raise TypeError(f"hidden must be {self.dtype} [N, T, {H}] with unit column stride (encode_features)")
@@ -1658,10 +1801,22 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
                 self._head_sets.pop(next(k for k in self._head_sets if k != key))
         return ws
 
-    def _check_step_args(self, hidden, frame_lengths, labels, label_lengths, row_index):
-        hidden = self._check_hidden(hidden)
-        N = int(hidden.shape[0] if row_index is None else row_index.numel())
-        T = int(hidden.shape[1])
+    def _layer_mix_buffers(self, ws, kind, N, T, K):
+        """What a call with a layer mix adds to its buffer set: the fp32 ``mixed`` [N, T, H] (zeros past a clip's frames) and,
+        for a step, the weights and tmi_layer_mix_bwd's workspace."""
+        V, H = self.config.vocab_size, self.config.hidden_size
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if "mixed" not in ws:
+            ws["mixed"] = torch.zeros((N, T, H), **f32)
+        if kind == "step" and ws.get("mix_K") != K:
+            ws.update(mix_K=K, mix_w=torch.zeros(K, **f32), mix_ws=torch.empty(ops.layer_mix_workspace_elems(N, T, H, V, K), **f32))
+        return ws
+
+    def _check_step_args(self, hidden, frame_lengths, labels, label_lengths, row_index, layer_mix=None):
+        hidden = self._check_hidden(hidden, layer_mix)
+        items = hidden if layer_mix is None else hidden[0]
+        N = int(items.shape[0] if row_index is None else row_index.numel())
+        T = int(items.shape[1])
         if not 1 <= N <= ctc_head_batch_limit(T):
             raise ValueError(f"one call takes 1 <= N <= {ctc_head_batch_limit(T)} items of {T} frames (65535 items, 2^22 frames)")
         for t, shape, w in ((frame_lengths, (N,), "frame_lengths"), (label_lengths, (N,), "label_lengths"), (row_index, (N,), "row_index")):
@@ -1676,7 +1831,7 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         return hidden, N, T, int(labels.shape[1])
 
     def head_step(self, hidden, frame_lengths, labels, label_lengths, optimizer, row_index=None, dropout=None, seed=0, step=0,
-                  return_intermediates=False):
+                  return_intermediates=False, layer_mix=None):
         """One training step of the HEAD (``lm_head``) on cached features ``hidden`` [N_src, T, H] of the frozen encoder
         (``encode_features``), in this order: tmi_ctc_head_fwd with the reference's Dropout (V:972; rate ``dropout``, None:
         ``config.hidden_dropout``) in front of the Dense layer; tmi_ctc_posteriors with zero_infinity on, so an infeasible
@@ -1691,15 +1846,26 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         SITE_CTC under (``seed``, ``step``), as every site of this project, keyed by the position n * T + t in the step.
         -> ``loss`` (before the update: the sum of the items' nll, or with "mean" the mean of nll / max(L, 1)) and
         ``n_infeasible`` as one-element device tensors, no read-back.  ``return_intermediates`` adds clones of the step's
-        ``log_probs`` and ``logit_grad`` fp32 [N, T, V] (zeros past a clip's frames)."""
+        ``log_probs`` and ``logit_grad`` fp32 [N, T, V] (zeros past a clip's frames).
+
+        ``layer_mix`` (a ``LayerMix``): ``hidden`` is the stacked layers [K, N_src, T, H] (``encode_features(layers="all")``)
+        and the step trains the mix with the head: tmi_layer_mix_fwd gathers and mixes the layers into a cached fp32
+        buffer BY POSITION; tmi_ctc_head_fwd (with the dropout, keyed by position as above), tmi_ctc_posteriors and
+        tmi_ctc_head_bwd run on that buffer; tmi_layer_mix_bwd writes the gradient of the loss with respect to the mixing
+        logits; then Adam over the head's slice, then Adam over the mix (``LayerMix.adam_step``).  Nothing else of the
+        arena is written.  ``return_intermediates`` then adds ``layer_weights`` [K] (the softmax the step used),
+        ``layer_logit_grad`` [K] and ``mixed`` fp32 [N, T, H]."""
         cfg = self.config
-        hidden, N, T, L = self._check_step_args(hidden, frame_lengths, labels, label_lengths, row_index)
+        hidden, N, T, L = self._check_step_args(hidden, frame_lengths, labels, label_lengths, row_index, layer_mix)
         p = float(cfg.hidden_dropout if dropout is None else dropout)
         if not 0.0 <= p < 1.0:
             raise ValueError("dropout must be in [0, 1)")
         ws = self._ctc_head_buffers("step", N, T, L)
         site = (int(seed) + int(step) * 0x9E3779B97F4A7C15 + SITE_CTC * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
         a = self.arena
+        if layer_mix is not None:
+            return self._mixed_head_step(hidden, frame_lengths, labels, label_lengths, optimizer, row_index, p, site, ws, N, T, L,
+                                         return_intermediates, layer_mix)
         ops.ctc_head_fwd(hidden, a.param("lm_head.kernel"), a.param("lm_head.bias"), frame_lengths, ws["logp"],
                          row_index=row_index, p=p, seed=site)
         ops.ctc_posteriors(ws["logp"], labels, label_lengths, frame_lengths, cfg.ctc_blank_id, ws["nll"], ws["bad"], ws["gamma"],
@@ -1716,8 +1882,33 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             out.update(log_probs=ws["logp"].clone(), logit_grad=ws["grad"].clone())
         return out
 
+    def _mixed_head_step(self, layers, frame_lengths, labels, label_lengths, optimizer, row_index, p, site, ws, N, T, L,
+                         return_intermediates, mix):
+        """``head_step`` behind a layer mix (its docstring states the order)."""
+        cfg, a = self.config, self.arena
+        self._layer_mix_buffers(ws, "step", N, T, mix.num_layers)
+        W, b = a.param("lm_head.kernel"), a.param("lm_head.bias")
+        ops.layer_mix_fwd(layers, mix.logits, frame_lengths, ws["mixed"], row_index=row_index, w_out=ws["mix_w"])
+        ops.ctc_head_fwd(ws["mixed"], W, b, frame_lengths, ws["logp"], p=p, seed=site)
+        ops.ctc_posteriors(ws["logp"], labels, label_lengths, frame_lengths, cfg.ctc_blank_id, ws["nll"], ws["bad"], ws["gamma"],
+                           ws["occ"], ws["tok_frames"], ws["tok_center"], ws["grad"], True)
+        loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        n_bad = torch.empty(1, dtype=torch.int32, device=self.device)
+        ops.ctc_head_bwd(ws["mixed"], frame_lengths, label_lengths, ws["grad"], ws["nll"], ws["bad"], a.grad("lm_head.kernel"),
+                         a.grad("lm_head.bias"), loss, n_bad, ws["bwd_ws"], L, p=p, seed=site, reduction=cfg.ctc_loss_reduction)
+        ops.layer_mix_bwd(layers, mix.logits, frame_lengths, label_lengths, ws["grad"], ws["bad"], W, mix.grad, ws["mix_ws"], L,
+                          row_index=row_index, p=p, seed=site, reduction=cfg.ctc_loss_reduction)
+        out = {"loss": loss, "n_infeasible": n_bad}
+        if return_intermediates:
+            out.update(log_probs=ws["logp"].clone(), logit_grad=ws["grad"].clone(), layer_weights=ws["mix_w"].clone(),
+                       layer_logit_grad=mix.grad.clone(), mixed=ws["mixed"].clone())
+        optimizer.iterations += 1
+        optimizer._update(self, self.head_lo, self.head_hi, 1.0, False, 0)
+        mix.adam_step(optimizer)
+        return out
+
     @torch.no_grad()
-    def evaluate_features(self, hidden, frame_lengths, labels, label_lengths=None):
+    def evaluate_features(self, hidden, frame_lengths, labels, label_lengths=None, layer_mix=None):
         """``evaluate(edit_ops=True)`` on cached features ``hidden`` [N, T, H] (``encode_features``): tmi_ctc_head_fwd without
         dropout from the fp32 master weights, then tmi_ctc_forward, tmi_ctc_greedy and tmi_edit_distance, in pieces of at
         most 65535 items and 2^22 frames.  Arguments as ``check_ctc_head_args`` takes them.  -> Python numbers: ``nll_sum``,
@@ -1725,10 +1916,12 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         with ``ctc_zero_infinity``), ``n_edits``, ``n_sub``, ``n_del``, ``n_ins``, ``n_ref_tokens``, ``n_hyp_tokens``,
         ``token_error_rate``.  On a bf16 model this differs from ``evaluate(inputs, ...)`` only by the latter's bf16
         rounding of ``lm_head`` (its GEMM reads the bf16 mirror; the head here reads the fp32 master in both precisions);
-        on an fp32 model only by the order of the sums."""
+        on an fp32 model only by the order of the sums.  ``layer_mix``: ``hidden`` is the stacked layers [K, N, T, H] and
+        the head reads tmi_layer_mix_fwd of them (the path of ``set_layer_mix``)."""
         cfg = self.config
-        hidden = self._check_hidden(hidden)
-        N, T, fl, lab, lens = check_ctc_head_args(cfg, tuple(hidden.shape), hidden.dtype, frame_lengths, labels, label_lengths)
+        hidden = self._check_hidden(hidden, layer_mix)
+        items_shape = tuple(hidden.shape) if layer_mix is None else tuple(hidden.shape[1:])
+        N, T, fl, lab, lens = check_ctc_head_args(cfg, items_shape, hidden.dtype, frame_lengths, labels, label_lengths)
         L = lab.shape[1]
         a = self.arena
         nll_sum = item_sum = 0.0
@@ -1740,7 +1933,11 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             ws = self._ctc_head_buffers("eval", n, T, L)
             fl_d, lab_d = torch.from_numpy(fl[s:s + n]).to(self.device), torch.from_numpy(lab[s:s + n]).to(self.device)
             lens_d = torch.from_numpy(lens[s:s + n]).to(self.device)
-            ops.ctc_head_fwd(hidden[s:s + n], a.param("lm_head.kernel"), a.param("lm_head.bias"), fl_d, ws["logp"], argmax=ws["argmax"])
+            feats = hidden[s:s + n]
+            if layer_mix is not None:
+                feats = self._layer_mix_buffers(ws, "eval", n, T, layer_mix.num_layers)["mixed"]
+                ops.layer_mix_fwd(hidden[:, s:s + n], layer_mix.logits, fl_d, feats)
+            ops.ctc_head_fwd(feats, a.param("lm_head.kernel"), a.param("lm_head.bias"), fl_d, ws["logp"], argmax=ws["argmax"])
             ops.ctc_forward(ws["logp"], lab_d, lens_d, fl_d, cfg.ctc_blank_id, ws["nll"], ws["bad"], False)
             ops.ctc_greedy(ws["argmax"], ws["logp"], fl_d, cfg.ctc_blank_id, ws["tokens"], ws["len"], ws["start"], ws["end"],
                            ws["best"])
@@ -1763,7 +1960,7 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
 
 
 def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, batch_size, learning_rate=1e-3, seed=0,
-                 eval_set=None):
+                 eval_set=None, layer_mix=None, mix_learning_rate=None):
     """Train ``model``'s CTC head on cached features ``hidden`` [N, T, H] (``model.encode_features``) with
     ``frame_lengths`` [N], ``labels`` [N, L_max] and ``label_lengths`` [N] (``check_ctc_head_args``).  Every epoch draws one
     permutation from a host generator seeded with ``seed``, gathers the labels and the two lengths in that order on the
@@ -1772,10 +1969,16 @@ def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, ba
     epsilon; the dropout rate is ``config.hidden_dropout``.  -> the history, one dict per epoch: ``epoch``, ``loss`` ("mean":
     the mean of the steps' losses weighted by their items; "sum": their sum; one read-back per epoch), ``n_infeasible``
     (over the epoch's steps) and, with ``eval_set`` = (hidden, frame_lengths, labels, label_lengths), ``eval_loss`` and
-    ``eval_token_error_rate`` (``evaluate_features``)."""
+    ``eval_token_error_rate`` (``evaluate_features``).  ``layer_mix`` (a ``LayerMix``): ``hidden`` - and ``eval_set``'s - is
+    the stacked layers [K, N, T, H], every step trains the mix with the head (``mix_learning_rate``: the mix's own Adam
+    rate; None: ``learning_rate``), and every epoch's record gains ``layer_weights``, the K softmax weights after the epoch
+    (the logits come back in the epoch's one read-back, with the loss)."""
     from . import optim
-    feats = model._check_hidden(hidden)
-    N, T, fl, lab, lens = check_ctc_head_args(model.config, tuple(feats.shape), feats.dtype, frame_lengths, labels, label_lengths)
+    feats = model._check_hidden(hidden, layer_mix)
+    N, T, fl, lab, lens = check_ctc_head_args(model.config, tuple(feats.shape) if layer_mix is None else tuple(feats.shape[1:]),
+                                              feats.dtype, frame_lengths, labels, label_lengths)
+    if layer_mix is not None and mix_learning_rate is not None:
+        layer_mix.learning_rate = float(mix_learning_rate)
     epochs, batch_size = int(epochs), int(batch_size)
     if epochs < 0 or not 1 <= batch_size <= ctc_head_batch_limit(T):
         raise ValueError(f"epochs >= 0 and 1 <= batch_size <= {ctc_head_batch_limit(T)}")
@@ -1794,17 +1997,25 @@ def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, ba
         losses, bad, rows = [], [], []
         for s in range(0, N, batch_size):
             e = min(N, s + batch_size)
-            r = model.head_step(feats, fl_d[s:e], lab_d[s:e], lens_d[s:e], opt, row_index=idx[s:e], seed=seed, step=step)
+            r = model.head_step(feats, fl_d[s:e], lab_d[s:e], lens_d[s:e], opt, row_index=idx[s:e], seed=seed, step=step,
+                                layer_mix=layer_mix)
             losses.append(r["loss"])
             bad.append(r["n_infeasible"])
             rows.append(e - s)
             step += 1
         w = torch.tensor(rows if mean else [1.0] * len(rows), dtype=torch.float64, device=model.device)
         total = (torch.cat(losses).double() * w).sum() / (w.sum() if mean else 1.0)
-        host = torch.stack([total, torch.cat(bad).sum().double()]).cpu().tolist()
+        back = [total.view(1), torch.cat(bad).sum().double().view(1)]
+        if layer_mix is not None:
+            back.append(layer_mix.logits.double())
+        host = torch.cat(back).cpu().tolist()
         rec = {"epoch": epoch, "loss": float(host[0]), "n_infeasible": int(host[1])}
+        if layer_mix is not None:
+            z = np.asarray(host[2:], dtype=np.float64)
+            e = np.exp(z - z.max())
+            rec["layer_weights"] = (e / e.sum()).tolist()
         if eval_set is not None:
-            ev = model.evaluate_features(*eval_set)
+            ev = model.evaluate_features(*eval_set, layer_mix=layer_mix)
             rec.update(eval_loss=ev["loss"], eval_token_error_rate=ev["token_error_rate"])
         history.append(rec)
     return history
