@@ -95,18 +95,39 @@ constexpr float LAZY = 8.f;             // forward: rescale only when a maximum 
 #define PIN(v) asm volatile("" : "+v"(v))
 
 // LDS-DMA from inline asm (see gemm_fast.hip: keeps hipcc from draining it before LDS reads)
-__device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  const unsigned dst = (unsigned)(size_t)((__attribute__((address_space(3))) char*)lds_wave_base);
-  const unsigned dst_u = __builtin_amdgcn_readfirstlane(dst);
+// Every LDS destination below is a 32-bit LDS byte offset formed by integer arithmetic on lds_base(smem), which a kernel
+// takes once: a generic -> LDS pointer cast inside a tile loop costs its null check (five scalar instructions) per use.
+__device__ __forceinline__ unsigned lds_base(const char* smem) {
+  return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)smem);  // (an address constant: wave-uniform)
+}
+__device__ __forceinline__ void glds16(const void* src, unsigned lds_wave_base) {
+  lds_wave_base = __builtin_amdgcn_readfirstlane(lds_wave_base);  // (free where hipcc already holds it in a scalar register)
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
-               : "v"(src), "s"(dst_u)
+               : "v"(src), "s"(lds_wave_base)
                : "memory");
 }
+// the four pieces a wave stages of a tile's two images (a0, a1 -> dst, dst + 1 KiB; b0, b1 -> the same of the image behind
+// it) in one statement: m0 saved and restored once per tile (m0 is reserved, so it cannot go on the clobber list)
+__device__ __forceinline__ void glds16x4(const void* a0, const void* a1, const void* b0, const void* b1, unsigned dst) {
+  static_assert(IMG == 0x2000, "the offsets inside the statement");
+  dst = __builtin_amdgcn_readfirstlane(dst);
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\t"
+      "s_mov_b32 m0, %5\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+      "s_add_u32 m0, %5, 0x400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
+      "s_add_u32 m0, %5, 0x2000\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
+      "s_add_u32 m0, %5, 0x2400\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(a0), "v"(a1), "v"(b0), "v"(b1), "s"(dst)
+      : "memory", "scc");
+}
 
-// stage rows [row0, row0+64) of a [T][.. 64 d ..] matrix (token stride st elements) into img
-__device__ __forceinline__ void stage_img(char* img, const bf16_t* base, int64_t st, int row0, int T, int wave, int lane) {
+// stage rows [row0, row0+64) of a [T][.. 64 d ..] matrix (token stride stb BYTES) into the image at LDS offset img
+__device__ __forceinline__ void stage_img(unsigned img, const char* base, int64_t stb, int row0, int T, int wave, int lane) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int j = 2 * wave + i;
@@ -114,38 +135,55 @@ __device__ __forceinline__ void stage_img(char* img, const bf16_t* base, int64_t
     const int c = (lane & 7) ^ swz(r);
     int gr = row0 + r;
     gr = gr < T ? gr : T - 1;
-    glds16(base + (int64_t)gr * st + c * 8, img + j * 1024);
+    glds16(base + (int64_t)gr * stb + c * 16, img + j * 1024);
   }
 }
 
-// Same staging with the per-lane part of the source address computed once: lp[i] points at the
-// lane's 16 bytes of row r_i of tile 0; full tiles add a wave-uniform offset.
+// Same staging for full tiles with RUNNING per-lane source pointers: p[i] points at the lane's 16 bytes of row r_i of the
+// next tile to stage (tiles are staged in ascending order from `row0` on) and moves on by the loop-invariant `step` with
+// every full tile staged.  Everything in bytes, so that one 64-bit scalar per matrix (the step) serves both paths.
 struct LaneSrc {
-  const bf16_t* lp[2];
-  const bf16_t* base;
-  int64_t st;
+  const char* p[2];
+  const char* base;
+  int64_t step;  // one tile = TROWS token strides, in bytes
   int T;
 };
-__device__ __forceinline__ LaneSrc lane_src(const bf16_t* base, int64_t st, int T, int wave, int lane) {
+__device__ __forceinline__ LaneSrc lane_src(const bf16_t* base, int64_t st, int T, int row0, int wave, int lane) {
   LaneSrc L;
-  L.base = base;
-  L.st = st;
+  L.base = reinterpret_cast<const char*>(base);
+  L.step = st * (TROWS * 2);
   L.T = T;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r = 8 * (2 * wave + i) + (lane >> 3);
     const int c = (lane & 7) ^ swz(r);
-    L.lp[i] = base + (int64_t)r * st + c * 8;
+    L.p[i] = L.base + (int64_t)(row0 + r) * (L.step / TROWS) + c * 16;  // (only dereferenced for a full tile)
   }
   return L;
 }
-__device__ __forceinline__ void stage_tile(char* img, const LaneSrc& L, int row0, int wave, int lane) {
+// any tile: full ones from the running pointers, the ragged last one row by row
+__device__ __forceinline__ void stage_tile(unsigned img, LaneSrc& L, int row0, int wave, int lane) {
   if (row0 + TROWS <= L.T) {
-    const int64_t off = (int64_t)row0 * L.st;  // wave-uniform
 #pragma unroll
-    for (int i = 0; i < 2; ++i) glds16(L.lp[i] + off, img + (2 * wave + i) * 1024);
+    for (int i = 0; i < 2; ++i) {
+      glds16(L.p[i], img + (2 * wave + i) * 1024);
+      L.p[i] += L.step;
+    }
   } else {
-    stage_img(img, L.base, L.st, row0, L.T, wave, lane);
+    stage_img(img, L.base, L.step / TROWS, row0, L.T, wave, lane);
+  }
+}
+// a FULL tile of two matrices into the images at img and img + IMG (the caller knows the tile is full)
+__device__ __forceinline__ void stage_pair_full(unsigned img, LaneSrc& A, LaneSrc& B, int wave) {
+  glds16x4(A.p[0], A.p[1], B.p[0], B.p[1], img + 2 * wave * 1024);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    A.p[i] += A.step;
+    B.p[i] += B.step;
+    // (keeps them running pointers in vector registers: otherwise hipcc turns them back into lane pointer + a running
+    // 64-bit scalar offset per matrix, which the scalar-register-bound dK/dV pass has to spill for)
+    PIN(A.p[i]);
+    PIN(B.p[i]);
   }
 }
 
@@ -232,7 +270,36 @@ __device__ __forceinline__ void store_owner(const f32x16 (&y)[2], bf16_t* base, 
     }
   }
 }
-
+// The same values (same product, same rounding) stored as whole rows.  With the owner on the lane a store instruction of
+// store_owner touches 32 rows with 16 bytes each.  Here the wave first lays its 32 owner rows down in a private 4 KiB slice
+// of LDS (row c of the slice = the owner of lane c; 16-byte chunk ch at ch ^ ((c >> 1) & 7), so the 8-byte writes of a
+// wave spread over all banks), then eight consecutive lanes store one 128-byte row as 16-byte pieces: a store instruction
+// writes eight full rows.  row_of(r) = the output row of slice row r; rows >= T are not stored.  The caller guarantees that
+// no wave of the workgroup still reads the slice's bytes (the barrier that ends the last tile).
+template <class RowOf>
+__device__ __forceinline__ void store_owner_rows(const f32x16 (&y)[2], char* slice, bf16_t* base, int64_t st, int T, int lane,
+                                                 float scale, RowOf row_of) {
+  const int c = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int blk = 0; blk < 2; ++blk) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      bf16x4 v;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = (bf16_t)(y[blk][4 * g + i] * scale);
+      *reinterpret_cast<bf16x4*>(slice + c * 128 + (((4 * blk + g) ^ ((c >> 1) & 7)) << 4) + 8 * h) = v;
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the wave's own writes; nobody else touches the slice
+  const int j = lane & 7;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int r = 8 * k + (lane >> 3);
+    const bf16x8 v = *reinterpret_cast<const bf16x8*>(slice + r * 128 + ((j ^ ((r >> 1) & 7)) << 4));
+    const int orow = row_of(r);
+    if (orow < T) *reinterpret_cast<bf16x8*>(base + (int64_t)orow * st + j * 8) = v;
+  }
+}
 
 // the same owner-on-lane tile as fp32 into one row of 64 floats (key-split partials)
 __device__ __forceinline__ void store_owner_f32(const f32x16 (&y)[2], float* row, int h) {
@@ -407,13 +474,17 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   uint32_t* mrow = nullptr;
   if constexpr (DROP) mrow = mask_column(P, b, head, h, q);
 
-  const LaneSrc Ks = lane_src(kb, d.k_st, Tk, wave, lane);
-  const LaneSrc Vs = lane_src(vb, d.v_st, Tk, wave, lane);
   const int ntiles_all = (Tk + TROWS - 1) / TROWS;
   const int per = (ntiles_all + ks - 1) / ks;
   const int t0 = sp * per, ntiles = min(ntiles_all, t0 + per);  // this workgroup's key tiles [t0, ntiles) (host: never empty)
-  stage_tile(smem, Ks, t0 * TROWS, wave, lane);
-  stage_tile(smem + IMG, Vs, t0 * TROWS, wave, lane);
+  LaneSrc Ks = lane_src(kb, d.k_st, Tk, t0 * TROWS, wave, lane);
+  LaneSrc Vs = lane_src(vb, d.v_st, Tk, t0 * TROWS, wave, lane);
+  const unsigned lds0 = lds_base(smem);
+  stage_tile(lds0, Ks, t0 * TROWS, wave, lane);
+  stage_tile(lds0 + IMG, Vs, t0 * TROWS, wave, lane);
+  // this lane's word of the stored mask of the tile at hand: a running pointer, one tile = 2 * TQP words on
+  const uint32_t mstep = 2 * (uint32_t)P.TQP;
+  if constexpr (DROP) mrow += (int64_t)t0 * mstep;
   float* kbl = nullptr;            // BIAS: the key terms of the current / next tile in log2 units, [2][64]
   const float* kbrow = nullptr;
   if constexpr (BIAS) {
@@ -424,13 +495,17 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int cur = 0;
-  // one tile; EDGE = needs masking (causal, a key bias, or the ragged last key tile)
-  auto body = [&](int tile, auto edge_tag) {
+  // one tile; EDGE = needs masking (causal, a key bias, or the ragged last key tile); LEAN = the caller knows that the next
+  // tile exists and is full, so it is staged without a test and in one statement
+  auto body = [&](int tile, auto edge_tag, auto lean_tag) {
     constexpr bool edge = decltype(edge_tag)::value;
+    constexpr bool lean = decltype(lean_tag)::value;
     const char* Kimg = smem + cur * 2 * IMG;
     const char* Vimg = Kimg + IMG;
-    if (tile + 1 < ntiles) {
-      char* nx = smem + (cur ^ 1) * 2 * IMG;
+    const unsigned nx = lds0 + (cur ^ 1) * 2 * IMG;
+    if constexpr (lean) {
+      stage_pair_full(nx, Ks, Vs, wave);
+    } else if (tile + 1 < ntiles) {
       stage_tile(nx, Ks, (tile + 1) * TROWS, wave, lane);
       stage_tile(nx + IMG, Vs, (tile + 1) * TROWS, wave, lane);
     }
@@ -545,7 +620,8 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
         pb[rbk][0] = __builtin_bit_cast(bf16x8, u[0]);
         pb[rbk][1] = __builtin_bit_cast(bf16x8, u[1]);
       }
-      mrow[(int64_t)tile * (2 * P.TQP)] = w;
+      *mrow = w;
+      mrow += mstep;
       second_product_b(Vimg, 0, pb[0], o, lane);
       second_product_b(Vimg, 32, pb[1], o, lane);
     } else {
@@ -565,8 +641,9 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   };
   const int nfast = (causal || BIAS) ? 0 : min(Tk / TROWS, ntiles);  // full, unmasked tiles first
   int tile = t0;
-  for (; tile < nfast; ++tile) body(tile, std::false_type{});
-  for (; tile < ntiles; ++tile) body(tile, std::true_type{});
+  for (; tile + 1 < nfast; ++tile) body(tile, std::false_type{}, std::true_type{});  // ... while the next one is full too
+  if (tile < nfast) body(tile++, std::false_type{}, std::false_type{});              // the last full tile: whatever follows
+  for (; tile < ntiles; ++tile) body(tile, std::true_type{}, std::false_type{});
   l += __shfl_xor(l, 32, 64);
   if (ks > 1) {  // partial of this key range: un-normalised o, (m, l); attn_combine_kernel<true> finishes
     if (q < Tq) {
@@ -582,7 +659,12 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_kernel(const AttnP P) {
   }
   const float inv = 1.0f / l;
   bf16_t* ob = head_of(d.o, d.o_sb, b, head);
-  store_owner(o, ob, d.o_st, q, Tq, h, DROP ? inv * P.keep_scale : inv);
+  // (measured, encoder layer: whole rows 90.0 -> 87.9 us without dropout, but 116.6 -> 122.0 us with it - the dropout form
+  // keeps the per-lane stores; profiles/attn_staging_ab.txt)
+  if constexpr (DROP)
+    store_owner(o, ob, d.o_st, q, Tq, h, inv * P.keep_scale);
+  else
+    store_owner_rows(o, smem + wave * 4096, ob, d.o_st, Tq, lane, inv, [&](int r) { return qt * 128 + wave * 32 + r; });
   if (h == 0 && q < Tq) {
     float* st = d.stats + ((b * d.H + head) * Tq + q) * 2;
     st[0] = m;  // log2 units
@@ -606,7 +688,8 @@ __device__ __forceinline__ void block_coords(const AttnP& P, int& bx, int& head,
   }
 }
 
-template <bool DROP>
+// SPLIT: full tiles whose successor is full too get a loop of their own with the lean staging
+template <bool DROP, bool SPLIT>
 __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, const int head, const int64_t b) {
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K img | V img]
   const AttnD& d = P.d;
@@ -661,29 +744,47 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, c
   const uint32_t* mrow = nullptr;
   if constexpr (DROP) mrow = mask_column(P, b, head, h, q);
 
-  const LaneSrc Ks = lane_src(kb, d.k_st, Tk, wave, lane);
-  const LaneSrc Vs = lane_src(vb, d.v_st, Tk, wave, lane);
   const int ntiles_all = (Tk + TROWS - 1) / TROWS;
   const int per = (ntiles_all + ks - 1) / ks;
   const int t0 = sp * per, ntiles = min(ntiles_all, t0 + per);  // this workgroup's key tiles [t0, ntiles)
+  LaneSrc Ks = lane_src(kb, d.k_st, Tk, t0 * TROWS, wave, lane);
+  LaneSrc Vs = lane_src(vb, d.v_st, Tk, t0 * TROWS, wave, lane);
+  const unsigned lds0 = lds_base(smem);
+  // the word of the NEXT tile: a running pointer, one tile = 2 * TQP words on
+  const uint32_t mstep = 2 * (uint32_t)P.TQP;
   uint32_t wcur = 0;
-  if constexpr (DROP) wcur = mrow[(int64_t)t0 * (2 * P.TQP)];
-  stage_tile(smem, Ks, t0 * TROWS, wave, lane);
-  stage_tile(smem + IMG, Vs, t0 * TROWS, wave, lane);
+  if constexpr (DROP) {
+    mrow += (int64_t)t0 * mstep;
+    wcur = *mrow;
+    mrow += mstep;
+  }
+  stage_tile(lds0, Ks, t0 * TROWS, wave, lane);
+  stage_tile(lds0 + IMG, Vs, t0 * TROWS, wave, lane);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   PIN(wcur);
   int cur = 0;
-  auto body = [&](int tile, auto edge_tag) {
+  // (edge / lean as in the forward: lean = the next tile exists and is full)
+  auto body = [&](int tile, auto edge_tag, auto lean_tag) {
     constexpr bool edge = decltype(edge_tag)::value;
+    constexpr bool lean = decltype(lean_tag)::value;
     const char* Kimg = smem + cur * 2 * IMG;
     const char* Vimg = Kimg + IMG;
+    const unsigned nx = lds0 + (cur ^ 1) * 2 * IMG;
     uint32_t wnext = 0;
-    if (tile + 1 < ntiles) {
-      char* nx = smem + (cur ^ 1) * 2 * IMG;
+    if constexpr (lean) {
+      stage_pair_full(nx, Ks, Vs, wave);
+      if constexpr (DROP) {
+        wnext = *mrow;  // under this tile's MFMAs, like the DMA
+        mrow += mstep;
+      }
+    } else if (tile + 1 < ntiles) {
       stage_tile(nx, Ks, (tile + 1) * TROWS, wave, lane);
       stage_tile(nx + IMG, Vs, (tile + 1) * TROWS, wave, lane);
-      if constexpr (DROP) wnext = mrow[(int64_t)(tile + 1) * (2 * P.TQP)];  // under this tile's MFMAs, like the DMA
+      if constexpr (DROP) {
+        wnext = *mrow;
+        mrow += mstep;
+      }
     }
     const int key0 = tile * TROWS;
     static_for(std::make_integer_sequence<int, 2>{}, [&](auto rbk_c) {
@@ -718,14 +819,21 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnP& P, const int bx, c
   };
   const int nfast = causal ? 0 : min(Tk / TROWS, ntiles);
   int tile = t0;
-  for (; tile < nfast; ++tile) body(tile, std::false_type{});
-  for (; tile < ntiles; ++tile) body(tile, std::true_type{});
+  if constexpr (SPLIT) {
+    for (; tile + 1 < nfast; ++tile) body(tile, std::false_type{}, std::true_type{});
+    if (tile < nfast) body(tile++, std::false_type{}, std::false_type{});
+  } else {
+    for (; tile < nfast; ++tile) body(tile, std::false_type{}, std::false_type{});
+  }
+  for (; tile < ntiles; ++tile) body(tile, std::true_type{}, std::false_type{});
   if (ks > 1) {  // partial dQ of this key range (unscaled); attn_combine_kernel<false> sums and scales
     if (q < Tq) store_owner_f32(dq, P.part + ((((int64_t)b * d.H + head) * ks + sp) * Tq + q) * HD, h);
     return;
   }
   bf16_t* dqb = head_of(d.dq, d.dq_sb, b, head);
-  store_owner(dq, dqb, d.dq_st, q, Tq, h, P.dq_scale * P.sscale);
+  // (the one-launch kernel is short of scalar registers: there the row number of slice row r comes from lane r)
+  store_owner_rows(dq, smem + wave * 4096, dqb, d.dq_st, Tq, lane, P.dq_scale * P.sscale,
+                   [&](int r) { return SPLIT ? qt * 128 + wave * 32 + r : __shfl(q, r, 64); });
 }
 
 template <bool DROP, int OCC>
@@ -733,7 +841,7 @@ __global__ __launch_bounds__(256, OCC) void attn_bwd_dq_kernel(const AttnP P) {
   int bx, head;
   int64_t b;
   block_coords(P, bx, head, b);
-  attn_bwd_dq_body<DROP>(P, bx, head, b);
+  attn_bwd_dq_body<DROP, true>(P, bx, head, b);
 }
 
 // ------------------------------------------------------------------ dK/dV pass (owner = key)
@@ -799,7 +907,12 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
   // per-tile row constants: thread t carries (which = t / 64, row = t % 64)
   // (the raw loads are combined only when they are written to LDS at the end of the iteration, so
   // that nothing waits on them while the next tile's DMA is in flight)
+  // The thread's two loads walk running pointers, one tile on with every call (the calls run over the tiles in order):
+  // c0p -> delta (third wave) or m of its row, c1p -> 1/l.
   const int cwhich = threadIdx.x >> 6;
+  const int c0step = cwhich == 2 ? TROWS : 2 * TROWS;
+  const float* c0p = cwhich == 2 ? deltas + (threadIdx.x & 63) : stats + 2 * (threadIdx.x & 63);
+  const float* c1p = stats + 2 * (threadIdx.x & 63) + 1;
   auto load_consts = [&](int row0, float& x0, float& x1) {
     const int qi = row0 + (threadIdx.x & 63);
     x0 = 0.f;
@@ -821,21 +934,24 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
           }
         x0 = part[0] + part[1];
       } else {
-        x0 = cwhich == 2 ? deltas[qi] : stats[qi * 2];
+        x0 = *c0p;
       }
-      x1 = stats[qi * 2 + 1];
+      x1 = *c1p;
     }
+    c0p += c0step;
+    c1p += 2 * TROWS;
   };
   // with dropout dS = keep_scale * (P_kept * dP - P * delta / keep_scale): the factor goes to the final store of dK
   auto make_const = [&](float x0, float x1) -> float {
     return cwhich == 1 ? x1 : (cwhich == 3 ? lg2(x1) - x0 : (cwhich == 2 ? x0 * inv_ks : x0));
   };
 
-  const LaneSrc Qs = lane_src(qb, d.q_st, Tq, wave, lane);
-  const LaneSrc Os = lane_src(dob, d.do_st, Tq, wave, lane);
+  LaneSrc Qs = lane_src(qb, d.q_st, Tq, 0, wave, lane);
+  LaneSrc Os = lane_src(dob, d.do_st, Tq, 0, wave, lane);
+  const unsigned lds0 = lds_base(smem);
   const int ntiles = (Tq + TROWS - 1) / TROWS;
-  stage_tile(smem, Qs, 0, wave, lane);
-  stage_tile(smem + IMG, Os, 0, wave, lane);
+  stage_tile(lds0, Qs, 0, wave, lane);
+  stage_tile(lds0 + IMG, Os, 0, wave, lane);
   {
     float x0, x1;
     load_consts(0, x0, x1);
@@ -846,38 +962,51 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
   // destination whenever it returns, so a destination the compiler believes dead - and hands to an address computation - would
   // be overwritten behind its back)
   uint32_t warm0 = 0, warm1 = 0;
-  auto issue_masks0 = [&](int tile) {  // first half of a tile + one dword of each line of the second half (scalar-cache warm-up)
-    const uint32_t* mt = mwave + tile * 64;
+  // (mt = the wave's 64 words of the tile AT HAND, a running pointer: issue_masks0_next fetches the tile behind it through
+  // the instruction's offset field)
+  const uint32_t* mt = mwave;
+  auto issue_masks0 = [&]() {  // first half of a tile + one dword of each line of the second half (scalar-cache warm-up)
     asm volatile("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx16 %1, %4, 0x40\n\ts_load_dword %2, %4, 0x80\n\ts_load_dword %3, %4, 0xc0"
                  : "=&s"(mk0), "=&s"(mk1), "=&s"(warm0), "=&s"(warm1) : "s"(mt) : "memory");
   };
-  auto issue_masks1 = [&](int tile) {
-    const uint32_t* mt = mwave + tile * 64;
+  auto issue_masks0_next = [&]() {
+    asm volatile("s_load_dwordx16 %0, %4, 0x100\n\ts_load_dwordx16 %1, %4, 0x140\n\ts_load_dword %2, %4, 0x180\n\ts_load_dword %3, %4, 0x1c0"
+                 : "=&s"(mk0), "=&s"(mk1), "=&s"(warm0), "=&s"(warm1) : "s"(mt) : "memory");
+  };
+  auto issue_masks1 = [&]() {
     asm volatile("s_load_dwordx16 %0, %2, 0x80\n\ts_load_dwordx16 %1, %2, 0xc0" : "=&s"(mk2), "=&s"(mk3) : "s"(mt) : "memory");
   };
   auto wait_masks0 = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(mk0), "+s"(mk1), "+s"(warm0), "+s"(warm1)::"memory"); };
   auto wait_masks1 = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(mk2), "+s"(mk3)::"memory"); };
-  if constexpr (DROP) issue_masks0(0);
+  if constexpr (DROP) issue_masks0();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if constexpr (DROP) wait_masks0();
   int cur = 0;
-  auto body = [&](int tile, auto edge_tag) {
+  // (edge / lean as in the forward: lean = the next tile exists and is full)
+  auto body = [&](int tile, auto edge_tag, auto lean_tag) {
     constexpr bool edge = decltype(edge_tag)::value;
+    constexpr bool lean = decltype(lean_tag)::value;
     const char* Qimg = smem + cur * 2 * IMG;
     const char* Oimg = Qimg + IMG;
     const float* rowc = rowc_base + cur * (NCONST * 64);
+    const unsigned nx = lds0 + (cur ^ 1) * 2 * IMG;
     float cn0 = 0.f, cn1 = 1.f;
     uint32_t warm = 0;
-    const bool more = tile + 1 < ntiles;
-    if (more) {
-      char* nx = smem + (cur ^ 1) * 2 * IMG;
+    const bool more = lean || tile + 1 < ntiles;
+    if constexpr (lean) {
+      stage_pair_full(nx, Qs, Os, wave);
+      cn0 = *c0p;  // (a full tile: no row test; the small problems of LOCAL_DELTA have no lean iterations)
+      cn1 = *c1p;
+      c0p += c0step;
+      c1p += 2 * TROWS;
+    } else if (more) {
       stage_tile(nx, Qs, (tile + 1) * TROWS, wave, lane);
       stage_tile(nx + IMG, Os, (tile + 1) * TROWS, wave, lane);
       load_consts((tile + 1) * TROWS, cn0, cn1);
-      if constexpr (DROP) {
-        if (tile + 2 < ntiles) warm = mwave[(tile + 2) * 64 + lane];
-      }
+    }
+    if constexpr (DROP) {
+      if (more && tile + 2 < ntiles) warm = mt[2 * 64 + lane];
     }
     const int q0 = tile * TROWS;
     // select mask of accumulator register e of 32-row half rbk
@@ -934,7 +1063,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
       if constexpr (DROP) {
         // second half's masks: issued once the first half's are spent (same registers), a scalar-cache hit by now, in flight
         // under the 16 MFMAs below and the next 8; waited for where that half's arithmetic starts
-        if (rbk == 0) issue_masks1(tile);
+        if (rbk == 0) issue_masks1();
       }
       second_product(Oimg, 32 * rbk, s, dv, lane);   // dVt[d][key] += sum_q dO[q][d] P[q][key]
       second_product(Qimg, 32 * rbk, ds, dk, lane);  // dKt[d][key] += sum_q Q[q][d] dS[q][key]
@@ -944,7 +1073,8 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
     PIN(cn1);  // next iteration's DMA issue
     PIN(warm);
     if constexpr (DROP) {
-      if (more) issue_masks0(tile + 1);
+      if (more) issue_masks0_next();
+      mt += 64;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -953,12 +1083,27 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnP& P, const int bx, 
   };
   const int nfast = causal ? 0 : Tq / TROWS;
   int tile = 0;
-  for (; tile < nfast; ++tile) body(tile, std::false_type{});
-  for (; tile < ntiles; ++tile) body(tile, std::true_type{});
+  if constexpr (!LOCAL_DELTA) {
+    for (; tile + 1 < nfast; ++tile) body(tile, std::false_type{}, std::true_type{});
+    if (tile < nfast) body(tile++, std::false_type{}, std::false_type{});
+  } else {
+    for (; tile < nfast; ++tile) body(tile, std::false_type{}, std::false_type{});
+  }
+  for (; tile < ntiles; ++tile) body(tile, std::true_type{}, std::false_type{});
   bf16_t* dkb = head_of(d.dk, d.dk_sb, b, head);
   bf16_t* dvb = head_of(d.dv, d.dv_sb, b, head);
-  store_owner(dk, dkb, d.dk_st, key, Tk, h, DROP ? P.sscale * P.keep_scale : P.sscale);
-  store_owner(dv, dvb, d.dv_st, key, Tk, h, DROP ? P.keep_scale : 1.0f);
+  // slice row r is the key of lane r, whichever that is (with dropout the permuted ownership above): fetched from that
+  // lane, the pass is short of scalar registers
+  auto key_of = [&](int r) { return __shfl(key, r, 64); };
+  if constexpr (!LOCAL_DELTA) {
+    store_owner_rows(dk, smem + wave * 4096, dkb, d.dk_st, Tk, lane, DROP ? P.sscale * P.keep_scale : P.sscale, key_of);
+    store_owner_rows(dv, smem + 2 * IMG + wave * 4096, dvb, d.dv_st, Tk, lane, DROP ? P.keep_scale : 1.0f, key_of);
+  } else {
+    // (the one-launch kernel holds both passes' scalars: with the row form of these two stores its form without dropout
+    // spills one, and its one or two key blocks per pair are launch latency, not store issue)
+    store_owner(dk, dkb, d.dk_st, key, Tk, h, DROP ? P.sscale * P.keep_scale : P.sscale);
+    store_owner(dv, dvb, d.dv_st, key, Tk, h, DROP ? P.keep_scale : 1.0f);
+  }
 }
 
 template <bool DROP, int OCC>
@@ -976,7 +1121,7 @@ template <bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_small_kernel(const AttnP P) {
   const int bx = (int)blockIdx.x;
   if (bx < P.nq)
-    attn_bwd_dq_body<DROP>(P, bx, (int)blockIdx.y, (int64_t)blockIdx.z);
+    attn_bwd_dq_body<DROP, false>(P, bx, (int)blockIdx.y, (int64_t)blockIdx.z);
   else
     attn_bwd_dkv_body<DROP, true>(P, bx - P.nq, (int)blockIdx.y, (int64_t)blockIdx.z);
 }
@@ -1033,10 +1178,11 @@ __global__ __launch_bounds__(256, 4) void attn_probs_kernel(const AttnP P, OT* _
   };
   auto make_const = [&](float x0, float x1) -> float { return cwhich == 1 ? x1 : (cwhich == 2 ? lg2(x1) - x0 : x0); };
 
-  const LaneSrc Qs = lane_src(qb, d.q_st, Tq, wave, lane);
   const int ntiles_all = (Tq + TROWS - 1) / TROWS;
   const int t0 = qblk * PQT, ntiles = min(ntiles_all, t0 + PQT);  // this workgroup's query tiles [t0, ntiles) (host: never empty)
-  stage_tile(smem, Qs, t0 * TROWS, wave, lane);
+  LaneSrc Qs = lane_src(qb, d.q_st, Tq, t0 * TROWS, wave, lane);
+  const unsigned lds0 = lds_base(smem);
+  stage_tile(lds0, Qs, t0 * TROWS, wave, lane);
   {
     float x0, x1;
     load_consts(t0 * TROWS, x0, x1);
@@ -1052,7 +1198,7 @@ __global__ __launch_bounds__(256, 4) void attn_probs_kernel(const AttnP P, OT* _
     float cn0 = 0.f, cn1 = 1.f;
     const bool more = tile + 1 < ntiles;
     if (more) {
-      stage_tile(smem + (cur ^ 1) * IMG, Qs, (tile + 1) * TROWS, wave, lane);
+      stage_tile(lds0 + (cur ^ 1) * IMG, Qs, (tile + 1) * TROWS, wave, lane);
       load_consts((tile + 1) * TROWS, cn0, cn1);
     }
     const int q0 = tile * TROWS;
