@@ -1303,6 +1303,73 @@ int tmi_layer_mix_bwd(const void* const* layers, int64_t K, int32_t x_dtype, int
                       int64_t T_max, int64_t L_max, int64_t H, int64_t V, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * SpecAugment span masks on the probes' cached features (apply_time_mask / apply_feature_mask, V:1073-1119;
+ * csrc/spec_augment.hip, and the MASKED instantiations of csrc/ctc_head.hip and csrc/layer_mix.hip).  TensorFlow's RNG stream
+ * cannot be reproduced: as at every dropout site the draws are this build's counter-based generator (tmi_keep), the
+ * structure is the reference's.
+ *   seed      the caller passes the SITE seed: site = (seed + step * 0x9E3779B97F4A7C15 + SITE_SPEC * 0xD1B54A32D192ED03) mod
+ *             2^64 with SITE_SPEC = 7 (next to SITE_CTC = 6; the Python layer forms it)
+ *   streams   1: the time mask, 2: the feature mask (stream 0 stays the flat dropout's)
+ *   start(n, c) = NOT keep[key = the stream's key of (site, stream), row = n, col = c, thr]: tmi_dropout's keep decision and
+ *             stream key (csrc/tmi_common.h),  thr = round(prob * 65536) as tmi_dropout forms it;  n = the item's POSITION in
+ *             the call;  c = the frame t in [0, T_max) for the time mask, the column h in [0, H) for the feature mask.
+ *             prob == 0: no bit is set and nothing is hashed.
+ *   mask(n, c)  = OR over i = 0 .. length-1 of start(n, c - i), start false for c - i < 0 (V:1083-1086): a start masks itself
+ *             and the length - 1 positions after it, cut at the end of the row.  Starts are drawn over all of T_max whatever
+ *             frame_lens says: the mask of frame t does not depend on the clip's length.
+ *   effect    a masked element is +0 (V:1092 / V:1117 multiply by 1 - mask): the time mask zeroes whole frames of item n, the
+ *             feature mask whole columns of item n, of the tensor the head's Dropout sees (`hidden`, or `mixed` behind a layer
+ *             mix; Dropout of a zero is a zero, so the order does not matter).
+ *   bits      time_bits uint32 [N][ld_t], ld_t >= ceil(T_max / 32): frame t is bit t % 32 of word t / 32.  feat_bits uint32
+ *             [N][ld_f], ld_f >= ceil(H / 32), the same over h.  Bits past T_max / H in the last word are 0; words past
+ *             ceil(cols / 32) of a row are not written.
+ *
+ * tmi_spec_masks draws both bit sets in ONE launch; either pointer may be NULL (that mask is off: its prob, length and ld
+ * are not looked at), not both.  counts int32 [N][2] may be NULL; it receives the set bits of each row's time and feature
+ * mask (0 for a mask that is off).  Integers only, no atomic: the same call gives the same bits.
+ *
+ * tmi_span_mask_apply: out = masked ? +0 : x for x [N, T, H] in x_dtype (TMI_BF16 or TMI_F32; element (n, t, h) at
+ * x[n*x_sn + t*x_st + h], out the same under o_sn / o_st, in the same dtype; the elements are moved as bits).  Either mask
+ * may be NULL.  16-byte accesses when the strides and both pointers allow it, element accesses otherwise.  The probe's step
+ * does not use it: it serves apply_time_mask / apply_feature_mask and the unfused comparison.
+ *
+ * tmi_ctc_head_fwd_m, tmi_ctc_head_bwd_m, tmi_layer_mix_bwd_m take the arguments of tmi_ctc_head_fwd / _bwd /
+ * tmi_layer_mix_bwd and (time_bits, ld_t, feat_bits, ld_f), each pointer possibly NULL, BY POSITION n as frame_lens is.
+ * They compute what the plain call computes on a copy of hidden (of every layer) with the masked elements of the live rows
+ * set to +0, bit for bit: the summation orders, chunks and tiles are the plain call's.  A time-masked live row is not loaded;
+ * its xd is zeros, so its logits are b; it still adds its gs to gb, and nothing to gW or d_k.  tmi_layer_mix_bwd_m zeroes dx
+ * under the mask where the dropout mask is applied.  tmi_layer_mix_fwd has no masked form: the mix is linear, so masking
+ * `mixed` inside the head kernels is masking every layer.  With both pointers NULL each is the plain call.
+ *
+ * Limits: 1 <= length <= 64; 0 <= prob < 1; N, T_max (T), N*T_max, H as for tmi_ctc_head_*; ld <= 2^30; bit pointers 4-byte
+ * aligned.  Anything else: TMI_ERR_INVALID, nothing is launched and nothing written.
+ * Not built: HF's min_masks, span counts proportional to the length, masks keyed by the source row, a learned mask
+ * embedding, masking in the pre-training step. */
+int tmi_spec_masks(uint32_t* time_bits, int64_t ld_t, uint32_t* feat_bits, int64_t ld_f, int32_t* counts, int64_t N, int64_t T_max,
+                   int64_t H, float time_prob, int64_t time_length, float feat_prob, int64_t feat_length, uint64_t seed,
+                   void* stream);
+int tmi_span_mask_apply(const void* x, int32_t x_dtype, int64_t x_sn, int64_t x_st, const uint32_t* time_bits, int64_t ld_t,
+                        const uint32_t* feat_bits, int64_t ld_f, void* out, int64_t o_sn, int64_t o_st, int64_t N, int64_t T,
+                        int64_t H, void* stream);
+int tmi_ctc_head_fwd_m(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src, const int32_t* row_index,
+                       const int32_t* frame_lens, const float* W, const float* b, float p, uint64_t seed, float* logits,
+                       int64_t lg_sn, int64_t lg_st, float* logp, int64_t lp_sn, int64_t lp_st, int32_t* argmax, int64_t N,
+                       int64_t T_max, int64_t H, int64_t V, const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits,
+                       int64_t ld_f, void* stream);
+int tmi_ctc_head_bwd_m(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src, const int32_t* row_index,
+                       const int32_t* frame_lens, const int32_t* label_lens, const float* grad, int64_t gr_sn, int64_t gr_st,
+                       const float* nll, const int32_t* infeasible, float p, uint64_t seed, int32_t reduction, float* gW,
+                       float* gb, float* loss, int32_t* n_infeasible, void* workspace, int64_t workspace_bytes, int64_t N,
+                       int64_t T_max, int64_t L_max, int64_t H, int64_t V, const uint32_t* time_bits, int64_t ld_t,
+                       const uint32_t* feat_bits, int64_t ld_f, void* stream);
+int tmi_layer_mix_bwd_m(const void* const* layers, int64_t K, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
+                        const int32_t* row_index, const int32_t* frame_lens, const int32_t* label_lens, const float* grad,
+                        int64_t gr_sn, int64_t gr_st, const int32_t* infeasible, float p, uint64_t seed, int32_t reduction,
+                        const float* W, const float* a, float* g_a, float* d, void* workspace, int64_t workspace_bytes, int64_t N,
+                        int64_t T_max, int64_t L_max, int64_t H, int64_t V, const uint32_t* time_bits, int64_t ld_t,
+                        const uint32_t* feat_bits, int64_t ld_f, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Log-mel front end (speech_jobs/whisper_dist.py:739-766, extract_fbank_features; dead in the
  * reference's training path).  The windowed DFT of the frames is a tmi_gemm
  * (frames = overlapping rows of the waveform, a_sm = hop; B = [n_fft, 2*n_bins] Hann-weighted

@@ -35,6 +35,11 @@ one (``encode_features(layers="all")``, ``fit_ctc_head(layer_mix=...)``): every 
 ``--save FILE`` also writes ``FILE.layermix.npy`` (the K logits), and the mix stays attached (``set_layer_mix``) so the rest of
 the job decodes through it.  ``--layer_mix_file F.npy`` attaches a saved mix for the rest of the job (without ``--fit_head``:
 to a model loaded with ``--weights``; with ``--fit_head --layer_mix``: the logits the fit starts from).
+``--mask_time_prob P --mask_time_length L --mask_feature_prob P --mask_feature_length L`` (with ``--fit_head``, with or without
+``--layer_mix``): SpecAugment on the cached features - every step of the fit zeroes spans of frames and of columns inside the
+head kernels (``fit_ctc_head(spec_augment=wav2vec2.SpecAugment(...))``; a flag that is not given keeps ``SpecAugment``'s
+default: 0.05 / 10 for the time mask, 0 / 10 for the feature mask) and every epoch's line adds ``masked_frame_fraction``.
+The evaluation and the rest of the job never mask.
 There is no tokenizer: ids in, ids out.
 """
 import argparse
@@ -85,6 +90,12 @@ def main(argv=None):
     parser.add_argument("--layer_mix", action="store_true",
                         help="with --fit_head: train a softmax-weighted sum over all encoder layers in front of the head")
     parser.add_argument("--layer_mix_file", default=None, help=".npy of K mixing logits: attach this layer mix for the rest of the job")
+    parser.add_argument("--mask_time_prob", type=float, default=None,
+                        help="with --fit_head: SpecAugment, the probability that a frame starts a masked span (default 0.05)")
+    parser.add_argument("--mask_time_length", type=int, default=None, help="with --fit_head: frames per span, 1..64 (default 10)")
+    parser.add_argument("--mask_feature_prob", type=float, default=None,
+                        help="with --fit_head: SpecAugment, the probability that a column starts a masked span (default 0)")
+    parser.add_argument("--mask_feature_length", type=int, default=None, help="with --fit_head: columns per span, 1..64 (default 10)")
     parser.add_argument("--build_lm", default=None, help="file of token ids, one line per sequence: build a table and exit")
     parser.add_argument("--lm_order", type=int, default=2, help="with --build_lm: the order of the table (1..4)")
     parser.add_argument("--lm_out", default=None, help="with --build_lm: where the .npy table goes")
@@ -97,6 +108,19 @@ def main(argv=None):
         parser.error("--save comes with --fit_head")
     if args.layer_mix and not args.fit_head:
         parser.error("--layer_mix comes with --fit_head")
+    spec_flags = {k: getattr(args, k) for k in ("mask_time_prob", "mask_time_length", "mask_feature_prob", "mask_feature_length")
+                  if getattr(args, k) is not None}
+    if spec_flags and not args.fit_head:
+        parser.error("--" + sorted(spec_flags)[0] + " comes with --fit_head")
+    spec = None
+    if spec_flags:
+        import tethys_speech_amd  # noqa: F401
+        from tethys_speech_amd import wav2vec2 as w2v
+        spec = w2v.SpecAugment(**spec_flags)
+        try:
+            w2v.check_spec_augment_args(spec, 1, 8)  # the probabilities and lengths; T and H are checked by the fit
+        except ValueError as e:
+            parser.error(str(e))
 
     import numpy as np
     if args.build_lm:
@@ -145,6 +169,10 @@ def main(argv=None):
         mix = wav2vec2.LayerMix(model.config.num_hidden_layers + 1, device)
         if args.layer_mix_file:
             mix.load_state_dict({"logits": np.load(args.layer_mix_file)})
+
+    def masked(rec):  # the epoch line's share of SpecAugment
+        return {"masked_frame_fraction": rec["masked_frame_fraction"]} if "masked_frame_fraction" in rec else {}
+
     if args.fit_head and mix is not None and args.layer_mix:
         L = max([len(r) for r in rows] + [1])
         fit_labels = np.zeros((len(rows), L), dtype=np.int64)
@@ -153,10 +181,10 @@ def main(argv=None):
         fit_lens = [len(r) for r in rows]
         feats = model.encode_features(audio, attention_mask=mask, layers="all")
         hist = wav2vec2.fit_ctc_head(model, feats["hidden_layers"], feats["frame_lengths"], fit_labels, fit_lens, args.epochs,
-                                     args.train_batch_size, learning_rate=args.learning_rate, layer_mix=mix)
+                                     args.train_batch_size, learning_rate=args.learning_rate, layer_mix=mix, spec_augment=spec)
         for rec in hist:
             print(json.dumps({"fit_head_epoch": rec["epoch"] + 1, "loss": rec["loss"], "n_infeasible": rec["n_infeasible"],
-                              "layer_weights": rec["layer_weights"]}), flush=True)
+                              "layer_weights": rec["layer_weights"], **masked(rec)}), flush=True)
         fit = model.evaluate_features(feats["hidden_layers"], feats["frame_lengths"], fit_labels, fit_lens, layer_mix=mix)
         print(json.dumps({"fit_head": {k: fit[k] for k in ("loss", "nll_sum", "n_infeasible", "n_edits", "n_ref_tokens",
                                                            "token_error_rate")}, "epochs": len(hist),
@@ -172,9 +200,10 @@ def main(argv=None):
         fit_lens = [len(r) for r in rows]
         feats = model.encode_features(audio, attention_mask=mask)
         hist = wav2vec2.fit_ctc_head(model, feats["hidden"], feats["frame_lengths"], fit_labels, fit_lens, args.epochs,
-                                     args.train_batch_size, learning_rate=args.learning_rate)
+                                     args.train_batch_size, learning_rate=args.learning_rate, spec_augment=spec)
         for rec in hist:
-            print(json.dumps({"fit_head_epoch": rec["epoch"] + 1, "loss": rec["loss"], "n_infeasible": rec["n_infeasible"]}), flush=True)
+            print(json.dumps({"fit_head_epoch": rec["epoch"] + 1, "loss": rec["loss"], "n_infeasible": rec["n_infeasible"],
+                              **masked(rec)}), flush=True)
         fit = model.evaluate_features(feats["hidden"], feats["frame_lengths"], fit_labels, fit_lens)
         print(json.dumps({"fit_head": {k: fit[k] for k in ("loss", "nll_sum", "n_infeasible", "n_edits", "n_ref_tokens",
                                                            "token_error_rate")}, "epochs": len(hist)}), flush=True)

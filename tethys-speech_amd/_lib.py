@@ -211,7 +211,14 @@ SIGNATURES = {
                                   c_i64, c_vp]),
     "tmi_layer_mix_bwd": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_f32,
                                   C.c_uint64, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_vp]),
+    "tmi_spec_masks": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_f32, c_i64, c_f32, c_i64, C.c_uint64, c_vp]),
+    "tmi_span_mask_apply": (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                    c_vp]),
 }
+# the masked forms: the plain call's arguments, then (time_bits, ld_t, feat_bits, ld_f) in front of the stream
+for _name in ("tmi_ctc_head_fwd", "tmi_ctc_head_bwd", "tmi_layer_mix_bwd"):
+    _res, _args = SIGNATURES[_name]
+    SIGNATURES[_name + "_m"] = (_res, _args[:-1] + [c_vp, c_i64, c_vp, c_i64] + _args[-1:])
 
 ABI_VERSION = 31
 _lib = None

@@ -23,8 +23,14 @@
 //   counts the infeasible items (integers).
 //   rc = 256 * ceil(N * T_max / 16384): at most 64 chunks, so the workspace stays at 64 (H V + V) floats however long the
 //   batch is; up to 16384 rows a chunk is 256 rows.
+//
+// SpecAugment (tmi_ctc_head_fwd_m / _bwd_m; the bits of tmi_spec_masks): the forward and the outer kernel are templates on
+//   MASKED, and the existing entry points launch the instantiation without it.  With it, a thread that stages a piece reads
+//   the time bit of its row (a masked row is not loaded: its xd is zeros) and the byte of the feature word that covers its
+//   8 columns, and zeroes xd under it.  Nothing else differs: the sums and their orders are the same.
 #include "tmi_common.h"
 #include <math.h>
+#include <string>
 
 namespace {
 
@@ -43,6 +49,23 @@ struct drop_t {
   float scale;
   bool on;
 };
+
+struct mask_t {  // span masks by position n (tmi_spec_masks' layout); a NULL pointer: that mask is off
+  const uint32_t* time_bits;
+  const uint32_t* feat_bits;
+  int64_t ld_t, ld_f;
+};
+__device__ __forceinline__ bool ct_time_masked(const mask_t& mk, int n, int t) {
+  return mk.time_bits != nullptr && ((mk.time_bits[(int64_t)n * mk.ld_t + (t >> 5)] >> (t & 31)) & 1u) != 0;
+}
+// v[0..8) of item n, columns c .. c + 7 (c a multiple of 8: one byte of a word), zeroed under the feature mask
+__device__ __forceinline__ void ct_feat_mask8(const mask_t& mk, int n, int c, float (&v)[8]) {
+  if (mk.feat_bits == nullptr) return;
+  const uint32_t m = (mk.feat_bits[(int64_t)n * mk.ld_f + (c >> 5)] >> (c & 31)) & 0xffu;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if ((m >> k) & 1u) v[k] = 0.f;
+}
 
 struct rows_t {  // what locates a row: the same in every kernel
   int64_t x_sn, x_st, n_src;
@@ -90,23 +113,27 @@ __device__ __forceinline__ void ct_load8(const T* __restrict__ hidden, const row
   if (d.on) tmi_drop8(v, r, c, d.key, d.thr, d.scale);
 }
 
-template <typename T>
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(CT_THREADS) void ctc_head_fwd_kernel(const T* __restrict__ hidden, rows_t g,
                                                                  const float* __restrict__ W, const float* __restrict__ b,
                                                                  drop_t drop, float* __restrict__ logits, int64_t lg_sn,
                                                                  int64_t lg_st, float* __restrict__ logp, int64_t lp_sn,
-                                                                 int64_t lp_st, int32_t* __restrict__ amax, int H, int V) {
+                                                                 int64_t lp_st, int32_t* __restrict__ amax, int H, int V, mask_t mk) {
   __shared__ __attribute__((aligned(16))) float xs[CT_FR][CT_HC];
   __shared__ __attribute__((aligned(16))) float Ws[CT_HC * 64];  // the slice's rows of W, [hl][V] as in memory
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int R = g.N * g.T_max, r0 = blockIdx.x * CT_FR;
   // the 8-element piece this thread stages per slice: row tid / 16, columns (tid % 16) * 8
   const int sr = tid >> 4, sc = (tid & 15) * 8;
-  int st_t = 0;
+  int st_t = 0, st_n = 0;
   int64_t st_s = -1;
   if (r0 + sr < R) {
     const int r = r0 + sr, n = r / g.T_max, t = r - n * g.T_max;
     if (t < ct_frames(g, n)) st_s = ct_src(g, n), st_t = t;
+    if constexpr (MASKED) {
+      st_n = n;
+      if (st_s >= 0 && ct_time_masked(mk, n, t)) st_s = -1;  // a time-masked row is not loaded
+    }
   }
   // the four rows of this wave (uniform over it)
   bool live[4], any = false;
@@ -127,7 +154,10 @@ __global__ __launch_bounds__(CT_THREADS) void ctc_head_fwd_kernel(const T* __res
     __syncthreads();
     if (sc < hl) {
       float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      if (st_s >= 0) ct_load8(hidden, g, drop, st_s, st_t, r0 + sr, h0 + sc, v);
+      if (st_s >= 0) {
+        ct_load8(hidden, g, drop, st_s, st_t, r0 + sr, h0 + sc, v);
+        if constexpr (MASKED) ct_feat_mask8(mk, st_n, h0 + sc, v);
+      }
       *reinterpret_cast<f32x4*>(&xs[sr][sc]) = f32x4{v[0], v[1], v[2], v[3]};
       *reinterpret_cast<f32x4*>(&xs[sr][sc + 4]) = f32x4{v[4], v[5], v[6], v[7]};
     }
@@ -175,13 +205,13 @@ __device__ __forceinline__ float ct_weight(const int32_t* __restrict__ label_len
   return 1.0f / ((float)L * (float)N);
 }
 
-template <typename T>
+template <typename T, bool MASKED>
 __global__ __launch_bounds__(CT_THREADS) void ctc_head_outer_kernel(const T* __restrict__ hidden, rows_t g,
                                                                    const int32_t* __restrict__ label_lens,
                                                                    const float* __restrict__ grad, int64_t gr_sn, int64_t gr_st,
                                                                    const int32_t* __restrict__ infeasible, drop_t drop,
                                                                    int reduction, float* __restrict__ part, int L_max, int H,
-                                                                   int V, int rc) {
+                                                                   int V, int rc, mask_t mk) {
   __shared__ __attribute__((aligned(16))) float As[CT_RS][CT_T];
   __shared__ __attribute__((aligned(16))) float Bs[CT_RS][CT_T];
   const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
@@ -206,7 +236,14 @@ __global__ __launch_bounds__(CT_THREADS) void ctc_head_outer_kernel(const T* __r
         const int n = r / g.T_max, t = r - n * g.T_max;
         if (t < ct_frames(g, n)) {
           const int64_t s = ct_src(g, n);
-          if (s >= 0 && i0 + c8 < H) ct_load8(hidden, g, drop, s, t, r, i0 + c8, av);
+          if constexpr (MASKED) {
+            if (s >= 0 && i0 + c8 < H && !ct_time_masked(mk, n, t)) {
+              ct_load8(hidden, g, drop, s, t, r, i0 + c8, av);
+              ct_feat_mask8(mk, n, i0 + c8, av);
+            }
+          } else {
+            if (s >= 0 && i0 + c8 < H) ct_load8(hidden, g, drop, s, t, r, i0 + c8, av);
+          }
           const float w = infeasible[n] != 0 ? 0.f : ct_weight(label_lens, n, g.N, L_max, reduction);
           const float* __restrict__ gp = grad + (int64_t)n * gr_sn + (int64_t)t * gr_st;
 #pragma unroll
@@ -320,6 +357,14 @@ drop_t ct_drop_of(float p, uint64_t seed) {
   d.scale = tmi_keep_scale(d.thr);
   return d;
 }
+// (NULL: that mask is off and its ld is not looked at)
+bool ct_mask_ok(const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, int64_t T_max, int64_t H) {
+  const int64_t lim = (int64_t)1 << 30;
+  return (time_bits == nullptr || (tmi_aligned(time_bits, 4) && ld_t >= (T_max + 31) / 32 && ld_t <= lim)) &&
+         (feat_bits == nullptr || (tmi_aligned(feat_bits, 4) && ld_f >= (H + 31) / 32 && ld_f <= lim));
+}
+const char* const ct_mask_msg = ": bad mask (time_bits / feat_bits NULL or 4-byte aligned uint32 [N][ld], ld_t >= ceil(T_max / 32), "
+                                "ld_f >= ceil(H / 32), both <= 2^30)";
 inline bool f4(const void* p) { return p != nullptr && tmi_aligned(p, 4); }
 inline bool f4n(const void* p) { return tmi_aligned(p, 4); }  // (may be NULL)
 
@@ -333,7 +378,8 @@ extern "C" int64_t tmi_ctc_head_workspace_bytes(int64_t N, int64_t T_max, int64_
 static int tmi_ctc_head_fwd_impl(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
                                  const int32_t* row_index, const int32_t* frame_lens, const float* W, const float* b, float p,
                                  uint64_t seed, float* logits, int64_t lg_sn, int64_t lg_st, float* logp, int64_t lp_sn,
-                                 int64_t lp_st, int32_t* argmax, int64_t N, int64_t T_max, int64_t H, int64_t V, void* stream) {
+                                 int64_t lp_st, int32_t* argmax, int64_t N, int64_t T_max, int64_t H, int64_t V,
+                                 const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, void* stream) {
   const bool ok = ct_sizes_ok(N, T_max, H, V) && ct_p_ok(p) &&
                   ct_rows_ok(hidden, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, N, T_max, H) && W != nullptr &&
                   tmi_aligned(W, 16) && f4(b) && f4(logp) && ct_stride_ok(lp_sn, lp_st, T_max, V) && f4n(logits) &&
@@ -345,15 +391,28 @@ static int tmi_ctc_head_fwd_impl(const void* hidden, int32_t x_dtype, int64_t x_
                   "W non-NULL and 16-byte aligned; frame_lens, b, logp non-NULL; pointers 4-byte aligned)");
     return TMI_ERR_INVALID;
   }
+  if (!ct_mask_ok(time_bits, ld_t, feat_bits, ld_f, T_max, H)) {
+    tmi_set_error((std::string("tmi_ctc_head_fwd_m") + ct_mask_msg).c_str());
+    return TMI_ERR_INVALID;
+  }
   const rows_t g = ct_rows_of(x_dtype, x_sn, x_st, n_src, row_index, frame_lens, N, T_max);
+  const mask_t mk{time_bits, feat_bits, ld_t, ld_f};
+  const bool masked = time_bits != nullptr || feat_bits != nullptr;
   const dim3 grid((unsigned)((N * T_max + CT_FR - 1) / CT_FR));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (x_dtype == TMI_BF16)
-    hipLaunchKernelGGL(ctc_head_fwd_kernel<bf16_t>, grid, dim3(CT_THREADS), 0, st, reinterpret_cast<const bf16_t*>(hidden), g, W, b,
-                       ct_drop_of(p, seed), logits, lg_sn, lg_st, logp, lp_sn, lp_st, argmax, (int)H, (int)V);
-  else
-    hipLaunchKernelGGL(ctc_head_fwd_kernel<float>, grid, dim3(CT_THREADS), 0, st, reinterpret_cast<const float*>(hidden), g, W, b,
-                       ct_drop_of(p, seed), logits, lg_sn, lg_st, logp, lp_sn, lp_st, argmax, (int)H, (int)V);
+  const auto launch = [&](auto kernel, auto* x) {
+    hipLaunchKernelGGL(kernel, grid, dim3(CT_THREADS), 0, st, x, g, W, b, ct_drop_of(p, seed), logits, lg_sn, lg_st, logp, lp_sn,
+                       lp_st, argmax, (int)H, (int)V, mk);
+  };
+  if (x_dtype == TMI_BF16) {
+    const bf16_t* x = reinterpret_cast<const bf16_t*>(hidden);
+    if (masked) launch(ctc_head_fwd_kernel<bf16_t, true>, x);
+    else launch(ctc_head_fwd_kernel<bf16_t, false>, x);
+  } else {
+    const float* x = reinterpret_cast<const float*>(hidden);
+    if (masked) launch(ctc_head_fwd_kernel<float, true>, x);
+    else launch(ctc_head_fwd_kernel<float, false>, x);
+  }
   return tmi_check_launch("tmi_ctc_head_fwd");
 }
 
@@ -362,7 +421,18 @@ extern "C" int tmi_ctc_head_fwd(const void* hidden, int32_t x_dtype, int64_t x_s
                                 uint64_t seed, float* logits, int64_t lg_sn, int64_t lg_st, float* logp, int64_t lp_sn,
                                 int64_t lp_st, int32_t* argmax, int64_t N, int64_t T_max, int64_t H, int64_t V, void* stream) {
   return tmi_plan_run<tmi_ctc_head_fwd_impl>(hidden, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, W, b, p, tmi_plan_seed{seed},
-                                             logits, lg_sn, lg_st, logp, lp_sn, lp_st, argmax, N, T_max, H, V, stream);
+                                             logits, lg_sn, lg_st, logp, lp_sn, lp_st, argmax, N, T_max, H, V,
+                                             (const uint32_t*)nullptr, (int64_t)0, (const uint32_t*)nullptr, (int64_t)0, stream);
+}
+
+extern "C" int tmi_ctc_head_fwd_m(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
+                                  const int32_t* row_index, const int32_t* frame_lens, const float* W, const float* b, float p,
+                                  uint64_t seed, float* logits, int64_t lg_sn, int64_t lg_st, float* logp, int64_t lp_sn,
+                                  int64_t lp_st, int32_t* argmax, int64_t N, int64_t T_max, int64_t H, int64_t V,
+                                  const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, void* stream) {
+  return tmi_plan_run<tmi_ctc_head_fwd_impl>(hidden, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, W, b, p, tmi_plan_seed{seed},
+                                             logits, lg_sn, lg_st, logp, lp_sn, lp_st, argmax, N, T_max, H, V, time_bits, ld_t,
+                                             feat_bits, ld_f, stream);
 }
 
 static int tmi_ctc_head_bwd_impl(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
@@ -370,7 +440,7 @@ static int tmi_ctc_head_bwd_impl(const void* hidden, int32_t x_dtype, int64_t x_
                                  int64_t gr_sn, int64_t gr_st, const float* nll, const int32_t* infeasible, float p, uint64_t seed,
                                  int32_t reduction, float* gW, float* gb, float* loss, int32_t* n_infeasible, void* workspace,
                                  int64_t workspace_bytes, int64_t N, int64_t T_max, int64_t L_max, int64_t H, int64_t V,
-                                 void* stream) {
+                                 const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, void* stream) {
   const bool ok = ct_sizes_ok(N, T_max, H, V) && ct_p_ok(p) &&
                   ct_rows_ok(hidden, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, N, T_max, H) && f4(label_lens) && f4(grad) &&
                   ct_stride_ok(gr_sn, gr_st, T_max, V) && f4(nll) && f4(infeasible) && (reduction == 0 || reduction == 1) &&
@@ -383,18 +453,31 @@ static int tmi_ctc_head_bwd_impl(const void* hidden, int32_t x_dtype, int64_t x_
                   "V) bytes)");
     return TMI_ERR_INVALID;
   }
+  if (!ct_mask_ok(time_bits, ld_t, feat_bits, ld_f, T_max, H)) {
+    tmi_set_error((std::string("tmi_ctc_head_bwd_m") + ct_mask_msg).c_str());
+    return TMI_ERR_INVALID;
+  }
   const rows_t g = ct_rows_of(x_dtype, x_sn, x_st, n_src, row_index, frame_lens, N, T_max);
   const drop_t drop = ct_drop_of(p, seed);
+  const mask_t mk{time_bits, feat_bits, ld_t, ld_f};
+  const bool masked = time_bits != nullptr || feat_bits != nullptr;
   const int64_t R = N * T_max, rc = ct_chunk_rows(R), nchunk = ct_chunks(R);
   float* part = reinterpret_cast<float*>(workspace);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((H + CT_T - 1) / CT_T), (unsigned)nchunk);
-  if (x_dtype == TMI_BF16)
-    hipLaunchKernelGGL(ctc_head_outer_kernel<bf16_t>, grid, dim3(CT_THREADS), 0, st, reinterpret_cast<const bf16_t*>(hidden), g,
-                       label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction, part, (int)L_max, (int)H, (int)V, (int)rc);
-  else
-    hipLaunchKernelGGL(ctc_head_outer_kernel<float>, grid, dim3(CT_THREADS), 0, st, reinterpret_cast<const float*>(hidden), g,
-                       label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction, part, (int)L_max, (int)H, (int)V, (int)rc);
+  const auto launch = [&](auto kernel, auto* x) {
+    hipLaunchKernelGGL(kernel, grid, dim3(CT_THREADS), 0, st, x, g, label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction,
+                       part, (int)L_max, (int)H, (int)V, (int)rc, mk);
+  };
+  if (x_dtype == TMI_BF16) {
+    const bf16_t* x = reinterpret_cast<const bf16_t*>(hidden);
+    if (masked) launch(ctc_head_outer_kernel<bf16_t, true>, x);
+    else launch(ctc_head_outer_kernel<bf16_t, false>, x);
+  } else {
+    const float* x = reinterpret_cast<const float*>(hidden);
+    if (masked) launch(ctc_head_outer_kernel<float, true>, x);
+    else launch(ctc_head_outer_kernel<float, false>, x);
+  }
   int rc_launch = tmi_check_launch("tmi_ctc_head_bwd");
   if (rc_launch != 0) return rc_launch;
   const int64_t n_out = H * V + V;
@@ -412,5 +495,18 @@ extern "C" int tmi_ctc_head_bwd(const void* hidden, int32_t x_dtype, int64_t x_s
                                 void* stream) {
   return tmi_plan_run<tmi_ctc_head_bwd_impl>(hidden, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, label_lens, grad, gr_sn,
                                              gr_st, nll, infeasible, p, tmi_plan_seed{seed}, reduction, gW, gb, loss, n_infeasible,
-                                             workspace, workspace_bytes, N, T_max, L_max, H, V, stream);
+                                             workspace, workspace_bytes, N, T_max, L_max, H, V, (const uint32_t*)nullptr,
+                                             (int64_t)0, (const uint32_t*)nullptr, (int64_t)0, stream);
+}
+
+extern "C" int tmi_ctc_head_bwd_m(const void* hidden, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
+                                  const int32_t* row_index, const int32_t* frame_lens, const int32_t* label_lens, const float* grad,
+                                  int64_t gr_sn, int64_t gr_st, const float* nll, const int32_t* infeasible, float p, uint64_t seed,
+                                  int32_t reduction, float* gW, float* gb, float* loss, int32_t* n_infeasible, void* workspace,
+                                  int64_t workspace_bytes, int64_t N, int64_t T_max, int64_t L_max, int64_t H, int64_t V,
+                                  const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, void* stream) {
+  return tmi_plan_run<tmi_ctc_head_bwd_impl>(hidden, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, label_lens, grad, gr_sn,
+                                             gr_st, nll, infeasible, p, tmi_plan_seed{seed}, reduction, gW, gb, loss, n_infeasible,
+                                             workspace, workspace_bytes, N, T_max, L_max, H, V, time_bits, ld_t, feat_bits, ld_f,
+                                             stream);
 }

@@ -25,6 +25,9 @@
 // layer_mix_fold_kernel - one workgroup; wave w takes the layers w, w + 4, ..: lane l adds the tiles l, l + 64, .. ascending
 //   from 0, the lanes meet in the same butterfly: d_k.  Then g_a[k] = w_k * (d_k - sum_j w_j d_j), the inner sum a chain of
 //   fmaf over j ascending from 0.
+// SpecAugment (tmi_layer_mix_bwd_m; the bits of tmi_spec_masks): the backward kernel is a template on MASKED, and the existing
+//   entry point launches the instantiation without it.  With it a time-masked row is skipped like a dead one, and dx is
+//   zeroed under the byte of the feature word that covers the thread's 8 columns, right after the dropout mask.
 #include "tmi_common.h"
 #include <math.h>
 
@@ -165,13 +168,20 @@ struct drop_t {
   bool on;
 };
 
-template <typename T, int KM>
+struct mask_t {  // span masks by position n (tmi_spec_masks' layout); a NULL pointer: that mask is off
+  const uint32_t* time_bits;
+  const uint32_t* feat_bits;
+  int64_t ld_t, ld_f;
+};
+
+template <typename T, int KM, bool MASKED>
 __global__ __launch_bounds__(LM_THREADS) void layer_mix_bwd_kernel(layers_t L, int K, rows_t g,
                                                                   const int32_t* __restrict__ label_lens,
                                                                   const float* __restrict__ grad, int64_t gr_sn, int64_t gr_st,
                                                                   const int32_t* __restrict__ infeasible, drop_t drop,
                                                                   int reduction, const float* __restrict__ W,
-                                                                  float* __restrict__ part, int L_max, int H, int V, int tr) {
+                                                                  float* __restrict__ part, int L_max, int H, int V, int tr,
+                                                                  mask_t mk) {
   __shared__ __attribute__((aligned(16))) float Wt[LM_WT];
   __shared__ float gss[16 * LM_MAXV];
   __shared__ float red[4][KM];
@@ -210,6 +220,10 @@ __global__ __launch_bounds__(LM_THREADS) void layer_mix_bwd_kernel(layers_t L, i
       if (t >= lm_frames(g, n) || infeasible[n] != 0) continue;
       const int64_t s = lm_src(g, n);
       if (s < 0) continue;  // every layer reads as zeros
+      if constexpr (MASKED) {
+        if (mk.time_bits != nullptr && ((mk.time_bits[(int64_t)n * mk.ld_t + (t >> 5)] >> (t & 31)) & 1u) != 0)
+          continue;  // a time-masked row: `mixed` was zeros under the head, so dx meets zeros
+      }
       float dx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       for (int v = 0; v < V; ++v) {
         const float gv = gss[slot * V + v];
@@ -219,6 +233,14 @@ __global__ __launch_bounds__(LM_THREADS) void layer_mix_bwd_kernel(layers_t L, i
         for (int i = 0; i < 4; ++i) dx[i] = fmaf(gv, wa[i], dx[i]), dx[4 + i] = fmaf(gv, wb[i], dx[4 + i]);
       }
       if (drop.on) tmi_drop8(dx, r, h0 + c, drop.key, drop.thr, drop.scale);
+      if constexpr (MASKED) {
+        if (mk.feat_bits != nullptr) {  // the 8 columns are one byte of a word
+          const uint32_t m = (mk.feat_bits[(int64_t)n * mk.ld_f + ((h0 + c) >> 5)] >> ((h0 + c) & 31)) & 0xffu;
+#pragma unroll
+          for (int i = 0; i < 8; ++i)
+            if ((m >> i) & 1u) dx[i] = 0.f;
+        }
+      }
       const int64_t off = s * g.x_sn + (int64_t)t * g.x_st + h0 + c;
 #pragma unroll
       for (int kb = 0; kb < KM; kb += LM_LB) {
@@ -346,15 +368,16 @@ extern "C" int tmi_layer_mix_fwd(const void* const* layers, int64_t K, int32_t x
 }
 
 template <typename T, int KM, typename... A>
-static void lm_launch_bwd(dim3 grid, hipStream_t st, A... a) {
-  hipLaunchKernelGGL((layer_mix_bwd_kernel<T, KM>), grid, dim3(LM_THREADS), 0, st, a...);
+static void lm_launch_bwd(bool masked, dim3 grid, hipStream_t st, A... a) {
+  if (masked) hipLaunchKernelGGL((layer_mix_bwd_kernel<T, KM, true>), grid, dim3(LM_THREADS), 0, st, a...);
+  else hipLaunchKernelGGL((layer_mix_bwd_kernel<T, KM, false>), grid, dim3(LM_THREADS), 0, st, a...);
 }
 template <typename T, typename... A>
-static void lm_launch_bwd_k(int64_t K, dim3 grid, hipStream_t st, A... a) {
-  if (K <= 8) lm_launch_bwd<T, 8>(grid, st, a...);
-  else if (K <= 16) lm_launch_bwd<T, 16>(grid, st, a...);
-  else if (K <= 32) lm_launch_bwd<T, 32>(grid, st, a...);
-  else lm_launch_bwd<T, 64>(grid, st, a...);
+static void lm_launch_bwd_k(int64_t K, bool masked, dim3 grid, hipStream_t st, A... a) {
+  if (K <= 8) lm_launch_bwd<T, 8>(masked, grid, st, a...);
+  else if (K <= 16) lm_launch_bwd<T, 16>(masked, grid, st, a...);
+  else if (K <= 32) lm_launch_bwd<T, 32>(masked, grid, st, a...);
+  else lm_launch_bwd<T, 64>(masked, grid, st, a...);
 }
 
 static int tmi_layer_mix_bwd_impl(layers_t L, bool have_layers, int64_t K, int32_t x_dtype, int64_t x_sn, int64_t x_st,
@@ -362,7 +385,7 @@ static int tmi_layer_mix_bwd_impl(layers_t L, bool have_layers, int64_t K, int32
                                   const float* grad, int64_t gr_sn, int64_t gr_st, const int32_t* infeasible, float p, uint64_t seed,
                                   int32_t reduction, const float* W, const float* a, float* g_a, float* d, void* workspace,
                                   int64_t workspace_bytes, int64_t N, int64_t T_max, int64_t L_max, int64_t H, int64_t V,
-                                  void* stream) {
+                                  const uint32_t* time_bits, int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, void* stream) {
   const bool ok = have_layers && lm_sizes_ok(N, T_max, H, K) && lm_v_ok(V) && lm_p_ok(p) &&
                   lm_rows_ok(L, K, x_dtype, x_sn, x_st, n_src, row_index, frame_lens, N, T_max, H) && f4(label_lens) && f4(grad) &&
                   lm_stride_ok(gr_sn, gr_st, T_max, V) && f4(infeasible) && (reduction == 0 || reduction == 1) && W != nullptr &&
@@ -375,6 +398,15 @@ static int tmi_layer_mix_bwd_impl(layers_t L, bool have_layers, int64_t K, int32
                   "of tmi_layer_mix_workspace_bytes(N, T_max, H, V, K) bytes)");
     return TMI_ERR_INVALID;
   }
+  const int64_t lim = (int64_t)1 << 30;
+  if (!((time_bits == nullptr || (tmi_aligned(time_bits, 4) && ld_t >= (T_max + 31) / 32 && ld_t <= lim)) &&
+        (feat_bits == nullptr || (tmi_aligned(feat_bits, 4) && ld_f >= (H + 31) / 32 && ld_f <= lim)))) {
+    tmi_set_error("tmi_layer_mix_bwd_m: bad mask (time_bits / feat_bits NULL or 4-byte aligned uint32 [N][ld], ld_t >= ceil(T_max / "
+                  "32), ld_f >= ceil(H / 32), both <= 2^30)");
+    return TMI_ERR_INVALID;
+  }
+  const mask_t mk{time_bits, feat_bits, ld_t, ld_f};
+  const bool masked = time_bits != nullptr || feat_bits != nullptr;
   const rows_t g = lm_rows_of(x_dtype, x_sn, x_st, n_src, row_index, frame_lens, N, T_max);
   drop_t drop;
   drop.on = p > 0.f;
@@ -386,11 +418,11 @@ static int tmi_layer_mix_bwd_impl(layers_t L, bool have_layers, int64_t K, int32
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)ntiles);
   if (x_dtype == TMI_BF16)
-    lm_launch_bwd_k<bf16_t>(K, grid, st, L, (int)K, g, label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction, W, part,
-                            (int)L_max, (int)H, (int)V, (int)tr);
+    lm_launch_bwd_k<bf16_t>(K, masked, grid, st, L, (int)K, g, label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction, W,
+                            part, (int)L_max, (int)H, (int)V, (int)tr, mk);
   else
-    lm_launch_bwd_k<float>(K, grid, st, L, (int)K, g, label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction, W, part,
-                           (int)L_max, (int)H, (int)V, (int)tr);
+    lm_launch_bwd_k<float>(K, masked, grid, st, L, (int)K, g, label_lens, grad, gr_sn, gr_st, infeasible, drop, (int)reduction, W,
+                           part, (int)L_max, (int)H, (int)V, (int)tr, mk);
   const int rc = tmi_check_launch("tmi_layer_mix_bwd");
   if (rc != 0) return rc;
   hipLaunchKernelGGL(layer_mix_fold_kernel, dim3(1), dim3(LM_THREADS), 0, st, part, (int)ntiles, (int)K, a, g_a, d);
@@ -404,5 +436,18 @@ extern "C" int tmi_layer_mix_bwd(const void* const* layers, int64_t K, int32_t x
                                  int64_t N, int64_t T_max, int64_t L_max, int64_t H, int64_t V, void* stream) {
   return tmi_plan_run<tmi_layer_mix_bwd_impl>(lm_layers_of(layers, K), layers != nullptr, K, x_dtype, x_sn, x_st, n_src, row_index,
                                               frame_lens, label_lens, grad, gr_sn, gr_st, infeasible, p, tmi_plan_seed{seed},
-                                              reduction, W, a, g_a, d, workspace, workspace_bytes, N, T_max, L_max, H, V, stream);
+                                              reduction, W, a, g_a, d, workspace, workspace_bytes, N, T_max, L_max, H, V,
+                                              (const uint32_t*)nullptr, (int64_t)0, (const uint32_t*)nullptr, (int64_t)0, stream);
+}
+
+extern "C" int tmi_layer_mix_bwd_m(const void* const* layers, int64_t K, int32_t x_dtype, int64_t x_sn, int64_t x_st, int64_t n_src,
+                                   const int32_t* row_index, const int32_t* frame_lens, const int32_t* label_lens, const float* grad,
+                                   int64_t gr_sn, int64_t gr_st, const int32_t* infeasible, float p, uint64_t seed, int32_t reduction,
+                                   const float* W, const float* a, float* g_a, float* d, void* workspace, int64_t workspace_bytes,
+                                   int64_t N, int64_t T_max, int64_t L_max, int64_t H, int64_t V, const uint32_t* time_bits,
+                                   int64_t ld_t, const uint32_t* feat_bits, int64_t ld_f, void* stream) {
+  return tmi_plan_run<tmi_layer_mix_bwd_impl>(lm_layers_of(layers, K), layers != nullptr, K, x_dtype, x_sn, x_st, n_src, row_index,
+                                              frame_lens, label_lens, grad, gr_sn, gr_st, infeasible, p, tmi_plan_seed{seed},
+                                              reduction, W, a, g_a, d, workspace, workspace_bytes, N, T_max, L_max, H, V, time_bits,
+                                              ld_t, feat_bits, ld_f, stream);
 }

@@ -968,11 +968,56 @@ def _ctc_head_args(hidden, row_index, frame_lens, N, T_max, H, what):
     return hidden.stride(0), hidden.stride(1), int(hidden.shape[0])
 
 
-def ctc_head_fwd(hidden, W, b, frame_lens, logp, row_index=None, p=0.0, seed=0, logits=None, argmax=None):
+def _mask_bits(bits, N, cols, what):
+    """A span mask of ``spec_masks`` (or None) -> (pointer, ld): uint32 bits held in an int32 tensor [>= N, ld], unit column
+    stride, ld >= ceil(cols / 32)."""
+    if bits is None:
+        return None, 0
+    if bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[0] < N or bits.shape[1] < (cols + 31) // 32 or \
+            bits.stride(1) != 1 or bits.stride(0) < bits.shape[1]:
+        raise ValueError(f"{what} must be an int32 tensor [>= {N}, >= {(cols + 31) // 32}] with unit column stride (spec_masks)")
+    return bits.data_ptr(), bits.stride(0)
+
+
+def spec_masks_words(cols: int) -> int:
+    """uint32 words per row of a span mask over ``cols`` columns."""
+    return (int(cols) + 31) // 32
+
+
+def spec_masks(N, T_max, H, time_bits=None, feat_bits=None, counts=None, time_prob=0.05, time_length=10, feat_prob=0.05,
+               feat_length=10, seed=0):
+    """The SpecAugment span masks of one call as bits (tmi_spec_masks in include/tethys_mi.h), both from one launch:
+    ``time_bits`` int32 [N, >= ceil(T_max / 32)] (frame t is bit t % 32 of word t / 32) and ``feat_bits`` int32
+    [N, >= ceil(H / 32)], either None (that mask is off), and ``counts`` int32 [N, 2] (or None): the set bits per row.
+    ``seed`` is the site seed."""
+    tb, ld_t = _mask_bits(time_bits, N, T_max, "spec_masks: time_bits")
+    fb, ld_f = _mask_bits(feat_bits, N, H, "spec_masks: feat_bits")
+    if counts is not None:
+        _i32_dev(counts, 2 * N, "spec_masks: counts")
+    check(lib().tmi_spec_masks(tb, ld_t, fb, ld_f, ptr(counts), int(N), int(T_max), int(H), float(time_prob), int(time_length),
+                               float(feat_prob), int(feat_length), int(seed) & 0xFFFFFFFFFFFFFFFF, stream()), "tmi_spec_masks")
+
+
+def span_mask_apply(x, out, time_bits=None, feat_bits=None):
+    """``out`` = ``x`` with the masked elements set to +0 (tmi_span_mask_apply in include/tethys_mi.h): ``x`` and ``out``
+    bf16 / fp32 [N, T, H] of one dtype with unit column stride; ``time_bits`` / ``feat_bits`` as ``spec_masks`` writes them."""
+    if x.dtype not in (torch.float32, torch.bfloat16) or out.dtype != x.dtype or x.dim() != 3 or out.shape != x.shape or \
+            x.stride(2) != 1 or out.stride(2) != 1:
+        raise ValueError("span_mask_apply: x and out must be bfloat16 or float32 [N, T, H] of one dtype with unit column stride")
+    N, T, H = x.shape
+    tb, ld_t = _mask_bits(time_bits, N, T, "span_mask_apply: time_bits")
+    fb, ld_f = _mask_bits(feat_bits, N, H, "span_mask_apply: feat_bits")
+    check(lib().tmi_span_mask_apply(x.data_ptr(), dt(x), x.stride(0), x.stride(1), tb, ld_t, fb, ld_f, out.data_ptr(),
+                                    out.stride(0), out.stride(1), N, T, H, stream()), "tmi_span_mask_apply")
+
+
+def ctc_head_fwd(hidden, W, b, frame_lens, logp, row_index=None, p=0.0, seed=0, logits=None, argmax=None, time_bits=None,
+                 feat_bits=None):
     """Dropout, the Dense head and the log-softmax over cached encoder features (tmi_ctc_head_fwd in include/tethys_mi.h):
     ``hidden`` bf16 / fp32 [n_src, >= T_max, H], gathered per item through ``row_index`` int32 [N] when given; ``W`` [H, V],
     ``b`` [V] contiguous fp32; ``frame_lens`` int32 [N] by position; ``logp`` fp32 [N, T_max, V] is written on the frames
-    inside each length, and so are ``logits`` (the same shape) and ``argmax`` int32 [N, T_max] when given."""
+    inside each length, and so are ``logits`` (the same shape) and ``argmax`` int32 [N, T_max] when given.  ``time_bits`` /
+    ``feat_bits`` (``spec_masks``, by position): tmi_ctc_head_fwd_m zeroes the features under them; both None: the plain call."""
     N, T_max, V = _ctc_logp(logp, "ctc_head_fwd")
     H = W.shape[0]
     x_sn, x_st, n_src = _ctc_head_args(hidden, row_index, frame_lens, N, T_max, H, "ctc_head_fwd")
@@ -984,20 +1029,24 @@ def ctc_head_fwd(hidden, W, b, frame_lens, logp, row_index=None, p=0.0, seed=0, 
         raise ValueError("ctc_head_fwd: logits must be float32 [N, T, V] as logp")
     if argmax is not None:
         _i32_dev(argmax, N * T_max, "ctc_head_fwd: argmax")
+    args = (hidden.data_ptr(), dt(hidden), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(), W.data_ptr(), b.data_ptr(),
+            float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(logits), 0 if logits is None else logits.stride(0),
+            0 if logits is None else logits.stride(1), logp.data_ptr(), logp.stride(0), logp.stride(1), ptr(argmax), N, T_max, H, V)
+    masks = _mask_bits(time_bits, N, T_max, "ctc_head_fwd: time_bits") + _mask_bits(feat_bits, N, H, "ctc_head_fwd: feat_bits")
     with _probe("ctc_head_fwd", 2.0 * N * T_max * H * V):
-        check(lib().tmi_ctc_head_fwd(hidden.data_ptr(), dt(hidden), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(),
-                                     W.data_ptr(), b.data_ptr(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(logits),
-                                     0 if logits is None else logits.stride(0), 0 if logits is None else logits.stride(1),
-                                     logp.data_ptr(), logp.stride(0), logp.stride(1), ptr(argmax), N, T_max, H, V, stream()),
-              "tmi_ctc_head_fwd")
+        if time_bits is None and feat_bits is None:
+            check(lib().tmi_ctc_head_fwd(*args, stream()), "tmi_ctc_head_fwd")
+        else:
+            check(lib().tmi_ctc_head_fwd_m(*args, *masks, stream()), "tmi_ctc_head_fwd_m")
 
 
 def ctc_head_bwd(hidden, frame_lens, label_lens, grad, nll, infeasible, gW, gb, loss, n_infeasible, workspace, L_max,
-                 row_index=None, p=0.0, seed=0, reduction="mean"):
+                 row_index=None, p=0.0, seed=0, reduction="mean", time_bits=None, feat_bits=None):
     """The head's weight and bias gradients (tmi_ctc_head_bwd in include/tethys_mi.h) from the ``grad`` fp32 [N, T_max, V],
     ``nll`` and ``infeasible`` that ``ctc_posteriors`` wrote for the log-probs of ``ctc_head_fwd`` with the same ``hidden``,
     ``row_index``, ``frame_lens``, ``p`` and ``seed``: ``gW`` [H, V], ``gb`` [V], ``loss`` [1] fp32 and ``n_infeasible`` [1] int32
-    are written, not accumulated.  ``workspace``: float32, ``ctc_head_workspace_elems(N, T_max, H, V)`` elements, any contents."""
+    are written, not accumulated.  ``workspace``: float32, ``ctc_head_workspace_elems(N, T_max, H, V)`` elements, any contents.
+    ``time_bits`` / ``feat_bits``: the masks of the forward (tmi_ctc_head_bwd_m); both None: the plain call."""
     N, T_max, V = _ctc_logp(grad, "ctc_head_bwd")
     H = gW.shape[0]
     if reduction not in ("sum", "mean"):
@@ -1010,13 +1059,16 @@ def ctc_head_bwd(hidden, frame_lens, label_lens, grad, nll, infeasible, gW, gb, 
         _f32_flat(t, n, "ctc_head_bwd: " + w)
     if gW.dim() != 2 or gW.shape[1] != V:
         raise ValueError("ctc_head_bwd: gW must be [H, V] with V the columns of grad")
+    args = (hidden.data_ptr(), dt(hidden), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(), label_lens.data_ptr(),
+            grad.data_ptr(), grad.stride(0), grad.stride(1), nll.data_ptr(), infeasible.data_ptr(), float(p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if reduction == "mean" else 0, gW.data_ptr(), gb.data_ptr(), loss.data_ptr(),
+            n_infeasible.data_ptr(), workspace.data_ptr(), workspace.numel() * 4, N, T_max, int(L_max), H, V)
+    masks = _mask_bits(time_bits, N, T_max, "ctc_head_bwd: time_bits") + _mask_bits(feat_bits, N, H, "ctc_head_bwd: feat_bits")
     with _probe("ctc_head_bwd", 2.0 * N * T_max * H * V):
-        check(lib().tmi_ctc_head_bwd(hidden.data_ptr(), dt(hidden), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(),
-                                     label_lens.data_ptr(), grad.data_ptr(), grad.stride(0), grad.stride(1), nll.data_ptr(),
-                                     infeasible.data_ptr(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                     1 if reduction == "mean" else 0, gW.data_ptr(), gb.data_ptr(), loss.data_ptr(),
-                                     n_infeasible.data_ptr(), workspace.data_ptr(), workspace.numel() * 4, N, T_max, int(L_max),
-                                     H, V, stream()), "tmi_ctc_head_bwd")
+        if time_bits is None and feat_bits is None:
+            check(lib().tmi_ctc_head_bwd(*args, stream()), "tmi_ctc_head_bwd")
+        else:
+            check(lib().tmi_ctc_head_bwd_m(*args, *masks, stream()), "tmi_ctc_head_bwd_m")
 
 
 def layer_mix_workspace_elems(N: int, T_max: int, H: int, V: int, K: int) -> int:
@@ -1068,12 +1120,13 @@ def layer_mix_fwd(layers, a, frame_lens, mixed, row_index=None, w_out=None):
 
 
 def layer_mix_bwd(layers, a, frame_lens, label_lens, grad, infeasible, W, g_a, workspace, L_max, row_index=None, p=0.0, seed=0,
-                  reduction="mean", d=None):
+                  reduction="mean", d=None, time_bits=None, feat_bits=None):
     """The gradient of the head's loss with respect to the mixing logits (tmi_layer_mix_bwd in include/tethys_mi.h) from the
     ``grad`` fp32 [N, T_max, V] and ``infeasible`` that ``ctc_posteriors`` wrote for the log-probs ``ctc_head_fwd`` formed
     from ``layer_mix_fwd``'s output with dropout (``p``, ``seed``) and the head's ``W`` fp32 [H, V]: ``g_a`` fp32 (at least K
     entries) and, when given, ``d`` (the gradient with respect to the weights) are written, not accumulated.  ``workspace``:
-    float32, ``layer_mix_workspace_elems(N, T_max, H, V, K)`` elements, any contents."""
+    float32, ``layer_mix_workspace_elems(N, T_max, H, V, K)`` elements, any contents.  ``time_bits`` / ``feat_bits``: the masks
+    the head's forward applied to the mixed features (tmi_layer_mix_bwd_m); both None: the plain call."""
     N, T_max, V = _ctc_logp(grad, "layer_mix_bwd")
     H = W.shape[0]
     if reduction not in ("sum", "mean"):
@@ -1086,12 +1139,16 @@ def layer_mix_bwd(layers, a, frame_lens, label_lens, grad, infeasible, W, g_a, w
     for t, n, w in ((W, H * V, "W"), (a, K, "a"), (g_a, K, "g_a"),
                     (workspace, layer_mix_workspace_elems(N, T_max, H, V, K), "workspace")) + (() if d is None else ((d, K, "d"),)):
         _f32_flat(t, n, "layer_mix_bwd: " + w)
+    args = (table, K, dt(x0), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(), label_lens.data_ptr(), grad.data_ptr(),
+            grad.stride(0), grad.stride(1), infeasible.data_ptr(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            1 if reduction == "mean" else 0, W.data_ptr(), a.data_ptr(), g_a.data_ptr(), ptr(d), workspace.data_ptr(),
+            workspace.numel() * 4, N, T_max, int(L_max), H, V)
+    masks = _mask_bits(time_bits, N, T_max, "layer_mix_bwd: time_bits") + _mask_bits(feat_bits, N, H, "layer_mix_bwd: feat_bits")
     with _probe("layer_mix_bwd", 2.0 * N * T_max * H * (V + K)):
-        check(lib().tmi_layer_mix_bwd(table, K, dt(x0), x_sn, x_st, n_src, ptr(row_index), frame_lens.data_ptr(),
-                                      label_lens.data_ptr(), grad.data_ptr(), grad.stride(0), grad.stride(1), infeasible.data_ptr(),
-                                      float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, 1 if reduction == "mean" else 0, W.data_ptr(),
-                                      a.data_ptr(), g_a.data_ptr(), ptr(d), workspace.data_ptr(), workspace.numel() * 4, N, T_max,
-                                      int(L_max), H, V, stream()), "tmi_layer_mix_bwd")
+        if time_bits is None and feat_bits is None:
+            check(lib().tmi_layer_mix_bwd(*args, stream()), "tmi_layer_mix_bwd")
+        else:
+            check(lib().tmi_layer_mix_bwd_m(*args, *masks, stream()), "tmi_layer_mix_bwd_m")
 
 
 def fill_zero(t):

@@ -1228,6 +1228,114 @@ def check_layer_mix_args(cfg: Wav2Vec2Config, layers_shape, layers_dtype, mix):
     return K, N, T_max
 
 
+SITE_SPEC = 7  # V:1073-1119: the SpecAugment span masks on the probes' cached features (tmi_spec_masks)
+SPEC_MAX_LENGTH = 64   # tmi_spec_masks: columns one start can mask
+
+
+@dataclass
+class SpecAugment:
+    """The span masks of ``apply_time_mask`` / ``apply_feature_mask`` (V:1073-1119) for ``head_step`` / ``fit_ctc_head``:
+    every frame (column) of an item starts a span of ``mask_time_length`` frames (``mask_feature_length`` columns) with
+    probability ``mask_time_prob`` (``mask_feature_prob``); a probability of 0 turns that mask off.  The defaults are the
+    reference's time mask (and HF's ``mask_time_prob`` / ``mask_time_length``)."""
+    mask_time_prob: float = 0.05
+    mask_time_length: int = 10
+    mask_feature_prob: float = 0.0
+    mask_feature_length: int = 10
+
+
+def spec_site_seed(seed: int, step: int) -> int:
+    """The seed tmi_spec_masks takes in step ``step`` of a run seeded with ``seed`` (site SITE_SPEC)."""
+    return (int(seed) + int(step) * 0x9E3779B97F4A7C15 + SITE_SPEC * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+
+
+def check_spec_augment_args(spec, T, H):
+    """Host validation of a ``SpecAugment`` for items of ``T`` frames and ``H`` columns (no GPU needed): both probabilities
+    in [0, 1) - and below 1 - 2^-17, where the 16-bit threshold would round to 65536 -, both lengths integers in [1, 64],
+    1 <= T <= 4096, H a multiple of 8 in [8, 4096].  -> (time on, feature on)."""
+    if not isinstance(spec, SpecAugment):
+        raise TypeError("spec_augment must be a wav2vec2.SpecAugment")
+    T, H = int(T), int(H)
+    if not 1 <= T <= CTC_MAX_FRAMES:
+        raise ValueError(f"1 <= T <= {CTC_MAX_FRAMES} frames per item, got {T}")
+    if H % 8 or not 8 <= H <= CTC_HEAD_MAX_HIDDEN:
+        raise ValueError(f"H must be a multiple of 8 in [8, {CTC_HEAD_MAX_HIDDEN}], got {H}")
+    for name in ("mask_time", "mask_feature"):
+        prob, length = getattr(spec, name + "_prob"), getattr(spec, name + "_length")
+        if isinstance(prob, bool) or not isinstance(prob, (int, float, np.floating, np.integer)) or not 0.0 <= float(prob) < 1.0 \
+                or int(np.float32(prob) * np.float32(65536.0) + np.float32(0.5)) > 65535:
+            raise ValueError(f"{name}_prob must be in [0, 1), got {prob!r}")
+        if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or not 1 <= int(length) <= SPEC_MAX_LENGTH:
+            raise ValueError(f"1 <= {name}_length <= {SPEC_MAX_LENGTH} (an integer), got {length!r}")
+    return float(spec.mask_time_prob) > 0.0, float(spec.mask_feature_prob) > 0.0
+
+
+def _spec_mask_buffers(N, T, H, time_on, feat_on, device):
+    i32 = dict(dtype=torch.int32, device=device)
+    return (torch.zeros((N, ops.spec_masks_words(T)), **i32) if time_on else None,
+            torch.zeros((N, ops.spec_masks_words(H)), **i32) if feat_on else None, torch.zeros((N, 2), **i32))
+
+
+def spec_augment_masks(spec, N, T, H, seed=0, step=0, device="cuda:0"):
+    """The masks ``head_step(spec_augment=spec, seed=seed, step=step)`` applies to a step of ``N`` items (by position), ``T``
+    frames and ``H`` columns, from one tmi_spec_masks launch -> (``time_bits`` int32 [N, ceil(T / 32)], ``feature_bits`` int32
+    [N, ceil(H / 32)], ``counts`` int32 [N, 2]: the set bits per item).  A mask whose probability is 0 is None, its count 0."""
+    time_on, feat_on = check_spec_augment_args(spec, T, H)
+    N = int(N)
+    if not 1 <= N <= ctc_head_batch_limit(T):
+        raise ValueError(f"1 <= N <= {ctc_head_batch_limit(T)} items of {T} frames")
+    tb, fb, counts = _spec_mask_buffers(N, int(T), int(H), time_on, feat_on, torch.device(device))
+    if time_on or feat_on:
+        ops.spec_masks(N, T, H, tb, fb, counts, spec.mask_time_prob, spec.mask_time_length, spec.mask_feature_prob,
+                       spec.mask_feature_length, spec_site_seed(seed, step))
+    return tb, fb, counts
+
+
+def unpack_mask_bits(bits, cols):
+    """``bits`` int32 [N, >= ceil(cols / 32)] as tmi_spec_masks writes them -> bool [N, cols] on the same device."""
+    cols = int(cols)
+    words = (cols + 31) // 32
+    if not torch.is_tensor(bits) or bits.dtype != torch.int32 or bits.dim() != 2 or bits.shape[1] < words:
+        raise ValueError(f"bits must be int32 [N, >= {words}]")
+    w = bits[:, :words].to(torch.int64).unsqueeze(-1) >> torch.arange(32, device=bits.device)
+    return (w & 1).bool().reshape(bits.shape[0], words * 32)[:, :cols]
+
+
+def _apply_span_mask(hidden_states, mask_prob, mask_length, seed, step, time):
+    x = hidden_states
+    if not torch.is_tensor(x) or x.dim() != 3 or x.dtype not in (torch.float32, torch.bfloat16) or not x.is_cuda:
+        raise TypeError("hidden_states must be a float32 or bfloat16 device tensor [B, T, H]")
+    B, T, H = (int(s) for s in x.shape)
+    spec = SpecAugment(mask_prob if time else 0.0, mask_length if time else 1, 0.0 if time else mask_prob, 1 if time else mask_length)
+    check_spec_augment_args(spec, T, H)
+    if not 1 <= B <= ctc_head_batch_limit(T):
+        raise ValueError(f"1 <= B <= {ctc_head_batch_limit(T)} items of {T} frames")
+    if x.stride(2) != 1 or x.stride(1) < H or x.stride(0) < T * x.stride(1):
+        x = x.contiguous()
+    bits = torch.zeros((B, ops.spec_masks_words(T if time else H)), dtype=torch.int32, device=x.device)
+    with torch.cuda.device(x.device):
+        ops.spec_masks(B, T, H, bits if time else None, None if time else bits, None, mask_prob, mask_length, mask_prob, mask_length,
+                       spec_site_seed(seed, step))
+        out = torch.empty((B, T, H), dtype=x.dtype, device=x.device)
+        ops.span_mask_apply(x, out, bits if time else None, None if time else bits)
+    mask = unpack_mask_bits(bits, T if time else H).to(torch.float32)
+    return out, mask.unsqueeze(-1) if time else mask.unsqueeze(1)
+
+
+def apply_time_mask(hidden_states, mask_prob=0.05, mask_length=10, seed=0, step=0):
+    """V:1073-1094 on the device: every frame of every item starts, with probability ``mask_prob``, a span of ``mask_length``
+    frames that is set to zero (tmi_spec_masks' time mask under (``seed``, ``step``) in place of TF's global stream, then
+    tmi_span_mask_apply).  ``hidden_states`` bf16 / fp32 [B, T, H], H a multiple of 8 -> (``masked_hidden_states`` in the
+    input's dtype, ``expanded_mask`` fp32 [B, T, 1], 1 where masked)."""
+    return _apply_span_mask(hidden_states, mask_prob, mask_length, seed, step, True)
+
+
+def apply_feature_mask(hidden_states, mask_prob=0.05, mask_length=10, seed=0, step=0):
+    """V:1098-1119 on the device: the same over the columns of every item (the feature mask) -> (``masked_hidden_states``,
+    ``expanded_mask`` fp32 [B, 1, H])."""
+    return _apply_span_mask(hidden_states, mask_prob, mask_length, seed, step, False)
+
+
 def ctc_head_batch_limit(T_max: int) -> int:
     """The most items one tmi_ctc_head call takes at ``T_max`` frames: 65535, and 2^22 frames in all."""
     return max(1, min(CTC_HEAD_MAX_ITEMS, CTC_HEAD_MAX_ROWS // int(T_max)))
@@ -1358,8 +1466,10 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
     ``fit_ctc_head`` train ``lm_head`` on it (csrc/ctc_head.hip around tmi_ctc_posteriors) and touch nothing of the arena
     outside the head's slice, ``evaluate_features`` scores it.  With a ``LayerMix`` the probe reads a learned
     softmax-weighted sum of all layers (csrc/layer_mix.hip; ``encode_features(layers="all")``, ``layer_mix=`` on the three
-    calls, ``set_layer_mix`` for inference).  The whole-model training entry points raise.  Not built: encoder fine-tuning,
-    a LayerNorm per layer before the mix, SpecAugment on the cached features, label smoothing."""
+    calls, ``set_layer_mix`` for inference).  ``spec_augment=`` (a ``SpecAugment``) on ``head_step`` / ``fit_ctc_head`` zeroes
+    spans of frames and of columns of the features inside the head kernels (csrc/spec_augment.hip draws the masks as bits);
+    no inference or evaluation call masks.  The whole-model training entry points raise.  Not built: encoder fine-tuning,
+    a LayerNorm per layer before the mix, label smoothing."""
 
     _arena_head = "ctc"
 
@@ -1830,8 +1940,29 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
             raise TypeError(f"labels must be a contiguous int32 tensor [N = {N}, 1 <= L_max <= {CTC_MAX_LABELS}] on the model's device")
         return hidden, N, T, int(labels.shape[1])
 
+    def _spec_masks(self, spec, ws, N, T, seed, step, counts=None):
+        """The step's span masks, drawn into the buffer set by ONE tmi_spec_masks launch -> (time_bits, feat_bits), None
+        where that mask is off.  ``counts`` int32 [N, 2]: where the set bits per item go (default: the set's own)."""
+        H = self.config.hidden_size
+        time_on, feat_on = check_spec_augment_args(spec, T, H)
+        if "spec_counts" not in ws:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            ws.update(spec_tb=torch.zeros((N, ops.spec_masks_words(T)), **i32), spec_fb=torch.zeros((N, ops.spec_masks_words(H)), **i32),
+                      spec_counts=torch.zeros((N, 2), **i32))
+        tb, fb = ws["spec_tb"] if time_on else None, ws["spec_fb"] if feat_on else None
+        if time_on or feat_on:
+            ops.spec_masks(N, T, H, tb, fb, ws["spec_counts"] if counts is None else counts, spec.mask_time_prob,
+                           spec.mask_time_length, spec.mask_feature_prob, spec.mask_feature_length, spec_site_seed(seed, step))
+        return tb, fb
+
+    def _spec_intermediates(self, tb, fb, N, T):
+        H = self.config.hidden_size
+        off = lambda cols: torch.zeros((N, cols), dtype=torch.bool, device=self.device)
+        return dict(time_mask=off(T) if tb is None else unpack_mask_bits(tb, T),
+                    feature_mask=off(H) if fb is None else unpack_mask_bits(fb, H))
+
     def head_step(self, hidden, frame_lengths, labels, label_lengths, optimizer, row_index=None, dropout=None, seed=0, step=0,
-                  return_intermediates=False, layer_mix=None):
+                  return_intermediates=False, layer_mix=None, spec_augment=None, _spec_counts=None):
         """One training step of the HEAD (``lm_head``) on cached features ``hidden`` [N_src, T, H] of the frozen encoder
         (``encode_features``), in this order: tmi_ctc_head_fwd with the reference's Dropout (V:972; rate ``dropout``, None:
         ``config.hidden_dropout``) in front of the Dense layer; tmi_ctc_posteriors with zero_infinity on, so an infeasible
@@ -1854,7 +1985,15 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         tmi_ctc_head_bwd run on that buffer; tmi_layer_mix_bwd writes the gradient of the loss with respect to the mixing
         logits; then Adam over the head's slice, then Adam over the mix (``LayerMix.adam_step``).  Nothing else of the
         arena is written.  ``return_intermediates`` then adds ``layer_weights`` [K] (the softmax the step used),
-        ``layer_logit_grad`` [K] and ``mixed`` fp32 [N, T, H]."""
+        ``layer_logit_grad`` [K] and ``mixed`` fp32 [N, T, H].
+
+        ``spec_augment`` (a ``SpecAugment``): the step first draws its span masks with ONE tmi_spec_masks launch (site
+        SITE_SPEC under (``seed``, ``step``), keyed by the item's POSITION n in the step; drawn over all T frames whatever
+        ``frame_lengths`` says) into bit buffers of the cached buffer set, and the three calls that read the features run in
+        their masked forms (tmi_ctc_head_fwd_m, tmi_ctc_head_bwd_m and, with a mix, tmi_layer_mix_bwd_m): a masked frame or
+        column of ``hidden`` - of ``mixed`` behind a mix, which masks every layer - is +0 in front of the Dropout.  No masked
+        copy of the features is written.  ``return_intermediates`` then adds ``time_mask`` bool [N, T] and ``feature_mask``
+        bool [N, H] (``spec_augment_masks`` gives the same bits).  With None every call and launch is the one it was."""
         cfg = self.config
         hidden, N, T, L = self._check_step_args(hidden, frame_lengths, labels, label_lengths, row_index, layer_mix)
         p = float(cfg.hidden_dropout if dropout is None else dropout)
@@ -1863,41 +2002,50 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
         ws = self._ctc_head_buffers("step", N, T, L)
         site = (int(seed) + int(step) * 0x9E3779B97F4A7C15 + SITE_CTC * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
         a = self.arena
+        tb = fb = None
+        if spec_augment is not None:
+            tb, fb = self._spec_masks(spec_augment, ws, N, T, seed, step, _spec_counts)
         if layer_mix is not None:
-            return self._mixed_head_step(hidden, frame_lengths, labels, label_lengths, optimizer, row_index, p, site, ws, N, T, L,
-                                         return_intermediates, layer_mix)
+            out = self._mixed_head_step(hidden, frame_lengths, labels, label_lengths, optimizer, row_index, p, site, ws, N, T, L,
+                                        return_intermediates, layer_mix, tb, fb)
+            if return_intermediates and spec_augment is not None:
+                out.update(self._spec_intermediates(tb, fb, N, T))
+            return out
         ops.ctc_head_fwd(hidden, a.param("lm_head.kernel"), a.param("lm_head.bias"), frame_lengths, ws["logp"],
-                         row_index=row_index, p=p, seed=site)
+                         row_index=row_index, p=p, seed=site, time_bits=tb, feat_bits=fb)
         ops.ctc_posteriors(ws["logp"], labels, label_lengths, frame_lengths, cfg.ctc_blank_id, ws["nll"], ws["bad"], ws["gamma"],
                            ws["occ"], ws["tok_frames"], ws["tok_center"], ws["grad"], True)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         n_bad = torch.empty(1, dtype=torch.int32, device=self.device)
         ops.ctc_head_bwd(hidden, frame_lengths, label_lengths, ws["grad"], ws["nll"], ws["bad"], a.grad("lm_head.kernel"),
                          a.grad("lm_head.bias"), loss, n_bad, ws["bwd_ws"], L, row_index=row_index, p=p, seed=site,
-                         reduction=cfg.ctc_loss_reduction)
+                         reduction=cfg.ctc_loss_reduction, time_bits=tb, feat_bits=fb)
         optimizer.iterations += 1
         optimizer._update(self, self.head_lo, self.head_hi, 1.0, False, 0)
         out = {"loss": loss, "n_infeasible": n_bad}
         if return_intermediates:
             out.update(log_probs=ws["logp"].clone(), logit_grad=ws["grad"].clone())
+            if spec_augment is not None:
+                out.update(self._spec_intermediates(tb, fb, N, T))
         return out
 
     def _mixed_head_step(self, layers, frame_lengths, labels, label_lengths, optimizer, row_index, p, site, ws, N, T, L,
-                         return_intermediates, mix):
+                         return_intermediates, mix, tb=None, fb=None):
         """``head_step`` behind a layer mix (its docstring states the order)."""
         cfg, a = self.config, self.arena
         self._layer_mix_buffers(ws, "step", N, T, mix.num_layers)
         W, b = a.param("lm_head.kernel"), a.param("lm_head.bias")
         ops.layer_mix_fwd(layers, mix.logits, frame_lengths, ws["mixed"], row_index=row_index, w_out=ws["mix_w"])
-        ops.ctc_head_fwd(ws["mixed"], W, b, frame_lengths, ws["logp"], p=p, seed=site)
+        ops.ctc_head_fwd(ws["mixed"], W, b, frame_lengths, ws["logp"], p=p, seed=site, time_bits=tb, feat_bits=fb)
         ops.ctc_posteriors(ws["logp"], labels, label_lengths, frame_lengths, cfg.ctc_blank_id, ws["nll"], ws["bad"], ws["gamma"],
                            ws["occ"], ws["tok_frames"], ws["tok_center"], ws["grad"], True)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
         n_bad = torch.empty(1, dtype=torch.int32, device=self.device)
         ops.ctc_head_bwd(ws["mixed"], frame_lengths, label_lengths, ws["grad"], ws["nll"], ws["bad"], a.grad("lm_head.kernel"),
-                         a.grad("lm_head.bias"), loss, n_bad, ws["bwd_ws"], L, p=p, seed=site, reduction=cfg.ctc_loss_reduction)
+                         a.grad("lm_head.bias"), loss, n_bad, ws["bwd_ws"], L, p=p, seed=site, reduction=cfg.ctc_loss_reduction,
+                         time_bits=tb, feat_bits=fb)
         ops.layer_mix_bwd(layers, mix.logits, frame_lengths, label_lengths, ws["grad"], ws["bad"], W, mix.grad, ws["mix_ws"], L,
-                          row_index=row_index, p=p, seed=site, reduction=cfg.ctc_loss_reduction)
+                          row_index=row_index, p=p, seed=site, reduction=cfg.ctc_loss_reduction, time_bits=tb, feat_bits=fb)
         out = {"loss": loss, "n_infeasible": n_bad}
         if return_intermediates:
             out.update(log_probs=ws["logp"].clone(), logit_grad=ws["grad"].clone(), layer_weights=ws["mix_w"].clone(),
@@ -1960,7 +2108,7 @@ class Wav2Vec2ForCTC(Wav2Vec2ForPreTraining):
 
 
 def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, batch_size, learning_rate=1e-3, seed=0,
-                 eval_set=None, layer_mix=None, mix_learning_rate=None):
+                 eval_set=None, layer_mix=None, mix_learning_rate=None, spec_augment=None):
     """Train ``model``'s CTC head on cached features ``hidden`` [N, T, H] (``model.encode_features``) with
     ``frame_lengths`` [N], ``labels`` [N, L_max] and ``label_lengths`` [N] (``check_ctc_head_args``).  Every epoch draws one
     permutation from a host generator seeded with ``seed``, gathers the labels and the two lengths in that order on the
@@ -1972,7 +2120,10 @@ def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, ba
     ``eval_token_error_rate`` (``evaluate_features``).  ``layer_mix`` (a ``LayerMix``): ``hidden`` - and ``eval_set``'s - is
     the stacked layers [K, N, T, H], every step trains the mix with the head (``mix_learning_rate``: the mix's own Adam
     rate; None: ``learning_rate``), and every epoch's record gains ``layer_weights``, the K softmax weights after the epoch
-    (the logits come back in the epoch's one read-back, with the loss)."""
+    (the logits come back in the epoch's one read-back, with the loss).  ``spec_augment`` (a ``SpecAugment``): every step
+    masks its features (``head_step``; the evaluation never does) and every epoch's record gains ``masked_frame_fraction``:
+    the time mask's set bits over the epoch's items, divided by items x T (the masks are drawn over all T frames of an item,
+    whatever its length); the steps' counts come back in the epoch's one read-back."""
     from . import optim
     feats = model._check_hidden(hidden, layer_mix)
     N, T, fl, lab, lens = check_ctc_head_args(model.config, tuple(feats.shape) if layer_mix is None else tuple(feats.shape[1:]),
@@ -1984,6 +2135,8 @@ def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, ba
         raise ValueError(f"epochs >= 0 and 1 <= batch_size <= {ctc_head_batch_limit(T)}")
     if eval_set is not None and len(eval_set) != 4:
         raise ValueError("eval_set is (hidden, frame_lengths, labels, label_lengths)")
+    if spec_augment is not None:
+        check_spec_augment_args(spec_augment, T, model.config.hidden_size)
     mean = model.config.ctc_loss_reduction == "mean"
     opt = optim.Adam(learning_rate)
     rng = np.random.default_rng(seed)
@@ -1995,10 +2148,15 @@ def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, ba
         lab_d = torch.from_numpy(np.ascontiguousarray(lab[perm])).to(model.device)
         lens_d = torch.from_numpy(np.ascontiguousarray(lens[perm])).to(model.device)
         losses, bad, rows = [], [], []
+        counts = None if spec_augment is None else torch.zeros((N, 2), dtype=torch.int32, device=model.device)
         for s in range(0, N, batch_size):
             e = min(N, s + batch_size)
-            r = model.head_step(feats, fl_d[s:e], lab_d[s:e], lens_d[s:e], opt, row_index=idx[s:e], seed=seed, step=step,
-                                layer_mix=layer_mix)
+            if spec_augment is None:
+                r = model.head_step(feats, fl_d[s:e], lab_d[s:e], lens_d[s:e], opt, row_index=idx[s:e], seed=seed, step=step,
+                                    layer_mix=layer_mix)
+            else:
+                r = model.head_step(feats, fl_d[s:e], lab_d[s:e], lens_d[s:e], opt, row_index=idx[s:e], seed=seed, step=step,
+                                    layer_mix=layer_mix, spec_augment=spec_augment, _spec_counts=counts[s:e])
             losses.append(r["loss"])
             bad.append(r["n_infeasible"])
             rows.append(e - s)
@@ -2006,10 +2164,14 @@ def fit_ctc_head(model, hidden, frame_lengths, labels, label_lengths, epochs, ba
         w = torch.tensor(rows if mean else [1.0] * len(rows), dtype=torch.float64, device=model.device)
         total = (torch.cat(losses).double() * w).sum() / (w.sum() if mean else 1.0)
         back = [total.view(1), torch.cat(bad).sum().double().view(1)]
+        if spec_augment is not None:
+            back.append(counts[:, 0].sum().double().view(1))
         if layer_mix is not None:
             back.append(layer_mix.logits.double())
         host = torch.cat(back).cpu().tolist()
         rec = {"epoch": epoch, "loss": float(host[0]), "n_infeasible": int(host[1])}
+        if spec_augment is not None:
+            rec["masked_frame_fraction"] = float(host.pop(2)) / float(N * T)
         if layer_mix is not None:
             z = np.asarray(host[2:], dtype=np.float64)
             e = np.exp(z - z.max())
